@@ -11,9 +11,18 @@ data path) and value = total steps/s over all ranks.  Launched under torchrun th
 from the environment; launched plainly (`python bench.py --gpus N`) the script starts its N
 ranks itself, before anything in the parent touches a GPU.
 
-Prints ONE JSON line (rank 0).  Besides the contract keys: `roofline` (the P-update GEMM: one launch per step since round 6, a pair before),
-`roofline_step` (the whole step), `cpu_baseline` (fp32 oracle, 1 core), `full_loop` (frames/s of
-ekfvio_step_image: image in, KLT supplies z, update, replenishment), `klt` and `klt_cpu_baseline`.
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times --steps steps, writes the outputs if
+--dump-outputs DIR is given, and prints the line: the contract keys and the timed region's own checks.
+With --full the line also holds the extras, each measured in runs of its own after the headline: `roofline`
+(the P-update GEMM: one launch per step since round 6, a pair before), `roofline_step` (the whole step),
+`stage_us_per_step`, `pcie_inclusive_steps_per_s`, other sizes and predict modes, `cpu_baseline` (fp32 oracle,
+1 core), `full_loop` (frames/s of ekfvio_step_image: image in, KLT supplies z, update, replenishment), `klt`
+and `klt_cpu_baseline`.
+
+--dump-outputs DIR: the state the timed path left after its last timed step, which is what a caller of
+ekfvio_run_uploaded reads back (base_mu, feat_mu, last_klt, del_flag, Sigma), as DIR/<name>.npy in float32.
+The inputs depend on the arguments only (seeded synthetic sequence), so two builds can be compared output
+for output.
 """
 import argparse
 import json
@@ -31,6 +40,62 @@ if ROOT not in sys.path:
 
 PEAK_F32_MFMA_TFLOPS = 157.3  # MI355X_MICROARCH.md: v_mfma_f32_32x32x2_f32 / 16x16x4_f32, dense
 PEAK_HBM_GBS = 8000.0         # MI355X_MICROARCH.md: HBM3E spec peak
+# The synthetic config-2 camera reaches its landmarks near frame 580 of the sequence, where every filter -- the fp64 oracle
+# included -- leaves the rails.  Every timed step, and the profiled and per-call steps of --full behind
+# them, lies before this frame.
+VALID_FRAMES = 448
+DUMP_LIMIT_BYTES = 64 << 20   # --dump-outputs: everything written stays under this
+DUMP_SIGMA_SAMPLE = 1 << 22   # entries of Sigma kept when the whole matrix would not fit
+
+
+def load_native(hooks=False):
+    """Loads the HIP library that build() left in the tree, before any handle is created (capi caches it per build).
+    capi.load() decides staleness under the build lock, a file it opens for writing next to the library; the benchmark
+    may run as a user who cannot write there (a tree built by someone else, or read-only), and then the built library
+    is loaded as it is.  A library that is missing is still an error."""
+    import errno
+    from ekf_vio_amd import capi
+    try:
+        return capi.load(hooks=hooks)
+    except OSError as ex:
+        if ex.errno not in (errno.EACCES, errno.EPERM, errno.EROFS):
+            raise
+        return capi.load(build_if_missing=False, hooks=hooks)
+
+
+def _pieces(count, seg):
+    return [seg] * (count // seg) + ([count % seg] if count % seg else [])
+
+
+def timed_segments(warmup, steps, valid=VALID_FRAMES):
+    """How --warmup W and --steps K map onto the valid part of the sequence: the first `start` = min(W, valid / 2) warm-up
+    steps run from the initial state, and every later step runs from the state reached there (the snapshot), in segments
+    of at most valid - start steps over frames start, start + 1, ...: the timed K steps in `timed`, the remaining W - start
+    warm-up steps in `warm`.  Runs that fit (W + K <= valid, W <= valid / 2: the default run) are ONE segment over the same
+    frames as one uninterrupted run.  Returns (start, timed, warm)."""
+    start = min(warmup, valid // 2)
+    seg = valid - start
+    return start, _pieces(steps, seg), _pieces(warmup - start, seg)
+
+
+def dump_outputs(dirname, state):
+    """Writes the filter state (TightlyCoupledEKF.get_state()) as dirname/<name>.npy, float32.  Sigma goes whole while
+    everything fits in DUMP_LIMIT_BYTES (up to N ~ 1300 landmarks); beyond that its diagonal goes whole (Sigma_diag) and
+    DUMP_SIGMA_SAMPLE of its entries at fixed, seeded row-major positions (Sigma_sample).  Returns the names written."""
+    os.makedirs(dirname, exist_ok=True)
+    arrays = {k: np.asarray(state[k], np.float32) for k in ("base_mu", "feat_mu", "last_klt", "del_flag")}
+    sig = np.asarray(state["Sigma"], np.float32)
+    rest = sum(a.nbytes for a in arrays.values())
+    if rest + sig.nbytes <= DUMP_LIMIT_BYTES:
+        arrays["Sigma"] = sig
+    else:
+        idx = np.sort(np.random.default_rng(0).choice(sig.size, size=min(DUMP_SIGMA_SAMPLE, sig.size), replace=False))
+        arrays["Sigma_diag"] = np.ascontiguousarray(np.diagonal(sig))
+        arrays["Sigma_sample"] = sig.reshape(-1)[idx]
+    assert sum(a.nbytes for a in arrays.values()) <= DUMP_LIMIT_BYTES
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, name + ".npy"), a)
+    return sorted(arrays)
 
 
 def dist_setup(n_gpus, backend="gloo"):
@@ -431,13 +496,19 @@ def main():
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--landmarks", type=int, default=256)
     ap.add_argument("--predict", choices=["structured", "dense"], default="structured")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-full-loop", action="store_true")
-    ap.add_argument("--cpu-steps", type=int, default=0, help="oracle steps to time (0 = auto ~10-30 s)")
-    ap.add_argument("--profile-steps", type=int, default=20)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure the extras: per-stage device times, the GEMM rooflines, the PCIe-inclusive per-call rate, "
+                         "concurrent sequences, other sizes and predict modes, the image loop and the CPU baselines")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the state the timed path left after its last timed step as DIR/<name>.npy (float32, at most 64 MB)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out the CPU baselines")
+    ap.add_argument("--no-full-loop", action="store_true", help="with --full: leave out the other sizes, predict modes, concurrent sequences and image loop")
+    ap.add_argument("--cpu-steps", type=int, default=0, help="with --full: oracle steps to time (0 = auto ~10-30 s)")
+    ap.add_argument("--profile-steps", type=int, default=20, help="with --full: steps of the per-stage profiled pass")
     ap.add_argument("--replay-only", action="store_true",
                     help="for rocprofv3 --kernel-trace --stats: nothing but warm-up and the timed region's graph replays runs (no eager per-stage pass, no "
-                         "per-call loop, no GEMM micro-replay), so the per-kernel means are those of replayed steps and sum to ms_per_step")
+                         "per-call loop, no GEMM micro-replay), so the per-kernel means are those of replayed steps and sum to ms_per_step; "
+                         "a plain run (no --full) does the same")
     ap.add_argument("--selftest-dist", action="store_true")
     args = ap.parse_args()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -452,59 +523,80 @@ def main():
         raise SystemExit("bench.py needs an MI355X: there is no CPU fallback for the product path")
     world, rank, local = dist_setup(args.gpus)
     torch.cuda.set_device(local)
+    load_native()
     N = args.landmarks
     sc = Scenario(N, seed=rank)
     mode = capi.PREDICT_DENSE if args.predict == "dense" else capi.PREDICT_STRUCTURED
     g = TightlyCoupledEKF(max_features=N, device=local, predict_mode=mode)
     g.addNewFeatures(sc.initial_features())
-    total = args.warmup + args.steps
-    extra_frames = args.profile_steps + 100  # the profiled steps and the per-call (PCIe-inclusive) loop continue the sequence
-    n_frames = min(total, 4096) + extra_frames  # longer runs wrap around the uploaded sequence
+    start, segments, warm_segments = timed_segments(args.warmup, args.steps)
+    end = start + segments[-1]  # the frame the last timed step leaves the filter at
+    nh = 100  # steps of the per-call (PCIe-inclusive) loop of --full, which continues the sequence behind the profiled steps
+    n_frames = max(start + max(segments + warm_segments), end + args.profile_steps + nh)  # every segment's frames, and what follows `end`
     fr = list(sc.frames(n_frames))
     g.upload_measurements(np.stack([f[0] for f in fr]), np.stack([f[1] for f in fr]), np.stack([f[2] for f in fr]))
     dt = sc.dt
     g.run_uploaded(0, 0, dt)  # captures the launch graphs (nothing runs)
-    g.run_uploaded(0, args.warmup, dt)
+    g.run_uploaded(0, start, dt)
     g.synchronize()
     # an odd warm-up ends with one eager step, which flips the mean / covariance ping-pong the graphs were captured
     # for: prepare again (count = 0 recaptures if needed) so that no capture ever lands inside the timed region
-    g.run_uploaded(args.warmup, 0, dt)
+    g.run_uploaded(start, 0, dt)
     g.synchronize()
-    # The timed region is EXACTLY args.steps steps between barrier + synchronize on both sides.  When it is shorter than
-    # 50 ms (20 steps are 2.5 ms) a single reading is at the mercy of one scheduling hiccup: the region is then repeated
-    # on the SAME steps from the SAME state (restored outside the timed region) and `value` is the median repetition.
+    # The timed region is EXACTLY args.steps steps, each segment between barrier + synchronize on both sides.  Every segment
+    # starts from the SAME state (restored outside the clock) at frame `start`, so that no step runs past the sequence's valid
+    # part (VALID_FRAMES); the default run is one segment.  When the region is shorter than 50 ms (20 steps are 2 ms) a single
+    # reading is at the mercy of one scheduling hiccup: the region is then repeated on the SAME steps from the SAME state and
+    # `value` is the median repetition.
     snap = g.get_state()
     times, numeric = [], capi.OK
 
-    def timed_region():
-        # barrier + synchronize on both sides; every rank's own clock runs over its K steps only (enqueue, device work, the
-        # handle's and the device's synchronise): the barrier in front lines the ranks up BEFORE t0, the one behind and the
-        # max-over-ranks exchange come AFTER the clock has stopped
-        torch.cuda.synchronize()
-        barrier(world)
-        t0 = time.perf_counter()
-        g.run_uploaded(args.warmup, args.steps, dt)
-        rc = g.synchronize()
-        torch.cuda.synchronize()
-        mine = time.perf_counter() - t0
-        barrier(world)
-        return max_over_ranks(mine, world), rc
+    def restore():
+        g.set_state(snap)
+        g.run_uploaded(start, 0, dt)  # graphs re-prepared for the restored ping-pong orientation: no capture in the region
+        g.synchronize()
 
-    el, numeric = timed_region()
+    for n in warm_segments:  # warm-up steps beyond `start`: segments from the snapshot, as the timed ones
+        restore()
+        g.run_uploaded(start, n, dt)
+        g.synchronize()
+
+    def timed_region(restored):
+        # barrier + synchronize on both sides of each segment; every rank's own clock runs over its K steps only (enqueue,
+        # device work, the handle's and the device's synchronise): the barrier in front lines the ranks up BEFORE t0, the one
+        # behind and the max-over-ranks exchange come AFTER the clock has stopped
+        mine, rc_region = 0.0, capi.OK
+        for n in segments:
+            if not restored:
+                restore()
+            restored = False
+            torch.cuda.synchronize()
+            barrier(world)
+            t0 = time.perf_counter()
+            g.run_uploaded(start, n, dt)
+            rc = g.synchronize()
+            torch.cuda.synchronize()
+            mine += time.perf_counter() - t0
+            barrier(world)
+            if rc == capi.ENUMERIC:
+                rc_region = rc
+        return max_over_ranks(mine, world), rc_region
+
+    el, numeric = timed_region(restored=not warm_segments)
     times.append(el)
     repeats = 1
     if el < 0.050:
         repeats = 9
     repeats = int(max_over_ranks(float(repeats), world))  # every rank repeats as often as the slowest decision says
     for _ in range(repeats - 1):
-        g.set_state(snap)
-        g.run_uploaded(args.warmup, 0, dt)  # graphs re-prepared for the restored ping-pong orientation: no capture in the region
-        g.synchronize()
-        el, rc = timed_region()
+        el, rc = timed_region(restored=False)
         times.append(el)
         if rc == capi.ENUMERIC:
             numeric = rc
     elapsed = float(np.median(times))
+    dumped = None
+    if args.dump_outputs and rank == 0:  # every repetition ran the same steps from the same state: this is the last timed step's result
+        dumped = dump_outputs(args.dump_outputs, g.get_state())
     md, ma = g.checkSigma()
     st_ok = bool(np.isfinite(g.base_mu).all() and md >= 0)
 
@@ -512,18 +604,23 @@ def main():
              "timed_region": {"repeats": repeats, "value_is": "median" if repeats > 1 else "single reading",
                               "steps_per_s_min": world * args.steps / max(times), "steps_per_s_max": world * args.steps / min(times),
                               "region_ms": [1e3 * t for t in times],
-                              "note": "each repetition times exactly --steps steps from the same restored state, barrier + synchronize on both sides; ranks meet over gloo "
+                              "start_frame": start, "segments": len(segments), "segment_steps": segments[0],
+                              "note": "each repetition times exactly --steps steps from the same restored state, in segments of at most segment_steps steps over "
+                                      "frames start_frame, start_frame + 1, ... (the synthetic sequence's valid part), each restarted from that state outside the "
+                                      "clock, barrier + synchronize on both sides; ranks meet over gloo "
                                       "(no RCCL), each rank's clock spans its own steps only, max over ranks taken after the clocks stop"},
              "parity": "oracle unpinned against the reference binary (the reference holds one KAT, test/test_ekf.cpp:44-63; "
                        "no Eigen/ROS/OpenCV in the image to build it): HIP vs own fp32/fp64 CPU restatement, tests/ -m gpu",
              "cpu_baseline_eigen_sparse": "unavailable: no Eigen3 on this box (BASELINE.md B3)"}
+    if dumped is not None:
+        extra["dumped_outputs"] = dumped
     if rank == 0 and args.replay_only:
         extra["replay_only"] = True
         extra["t2_updates"] = g.counters()["t2_updates"]
-    elif rank == 0:
+    elif rank == 0 and args.full:
         # per-kernel-class device time with HIP events on the handle's stream
         g.profile(True)
-        g.run_uploaded(total, args.profile_steps, dt)
+        g.run_uploaded(end, args.profile_steps, dt)
         g.synchronize()
         rep = g.profile_report()
         g.profile(False)
@@ -576,13 +673,12 @@ def main():
                                           "(4n^3 predict + Joseph expansion) is listed for reference and is NOT what runs: the predict exploits F's sparsity"}
         # PCIe-inclusive rate (never `value`): the per-call boundary with host-resident measurements,
         # one ekfvio_process + one synchronising ekfvio_update per step
-        nh = 100
         import gc
         gc.collect()
         gc.disable()  # (with torch imported a generation-2 collection is a 40-70 ms pause: seen as one outlier call in some runs)
         th = time.perf_counter()
         per_call = []
-        for z_h, R_h, p_h in fr[-nh:]:
+        for z_h, R_h, p_h in fr[end + args.profile_steps:end + args.profile_steps + nh]:
             t1 = time.perf_counter()
             g.process(dt)
             g.updateWithFeaturePositions(z_h, R_h, p_h)
@@ -598,6 +694,7 @@ def main():
         try:
             import ctypes as C
             us = C.c_double(0)
+            load_native(hooks=True)
             gh = TightlyCoupledEKF(max_features=4, device=local, hooks=True)  # (a test hook: lives in the hooks build of the library, not in the product)
             rc_h = gh.lib.ekfvio_test_gemm_bench(gh.h, 1, 0, 3094, 3094, 2048, 20, 0, C.byref(us))
             gh.close()
@@ -628,13 +725,13 @@ def main():
                                                "since round 4 the stage is ONE launch that also holds the measurement gather, the first diagonal tile and the gain's tiles, "
                                                "since round 6 also T2 = Sigma (I - K H)^T, G' and K y (chol_persist_kernel, fused); in-kernel stamps: profiles/r06_persistent_t2.txt"}
     g.close()
-    if rank == 0 and world == 1 and not args.no_full_loop and not args.replay_only:
+    if rank == 0 and world == 1 and args.full and not args.no_full_loop and not args.replay_only:
         try:
             extra["concurrent_sequences_one_gpu"] = [concurrent_sequences(N, local, b, min(args.steps, 200)) for b in (2, 4, 8)]
         except Exception as ex:  # an extra, never fatal
             extra["concurrent_sequences_one_gpu"] = {"error": repr(ex)}
     if rank == 0:
-        if world == 1 and not args.no_full_loop:
+        if world == 1 and args.full and not args.no_full_loop:
             try:  # extras, never fatal: the author's deployment sizes (params/test.yaml 30, the node default 100, fast_with_insight.yaml 400
                   # with its depth variance 1000) and the north-star dense predict beside the structured one (report both)
                 extra["other_sizes"] = [device_resident_rate(30, local, depth_var=1000.0), device_resident_rate(100, local),
@@ -678,7 +775,7 @@ def main():
                 extra["full_loop"]["node_defaults_with_outputs"].pop("klt")
             except Exception as ex:  # reported, never fatal for the headline metric
                 extra["full_loop"] = {"error": repr(ex)}
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             steps = args.cpu_steps or max(3, int(round(60.0 * (256.0 / N) ** 3)))
             extra["cpu_baseline"] = cpu_baseline(N, dt, steps)
             ncpu = len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1)

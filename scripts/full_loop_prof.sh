@@ -6,7 +6,7 @@ TAG=${1:-fl}
 R=${GRAFT_REPO_ROOT:-/root/repo}
 cd /tmp && export TMPDIR=/tmp
 rm -rf /tmp/flp_$TAG
-timeout -k 10 300 rocprofv3 --kernel-trace --stats -d /tmp/flp_$TAG -o x --output-format csv -- python3 $R/bench.py --steps 30 --warmup 5 --no-cpu-baseline > $R/gpurun_out/flp_$TAG.log 2>&1
+timeout -k 10 300 rocprofv3 --kernel-trace --stats -d /tmp/flp_$TAG -o x --output-format csv -- python3 $R/bench.py --full --steps 30 --warmup 5 --no-cpu-baseline > /tmp/flp_$TAG.log 2>&1
 F=$(find /tmp/flp_$TAG -name "*kernel_stats.csv" | head -1)
 cp $F $R/gpurun_out/flp_${TAG}_kernel_stats.csv
 python3 - "$F" <<'PY'

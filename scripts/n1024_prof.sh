@@ -5,7 +5,7 @@ TAG=${1:-n1024}
 R=${GRAFT_REPO_ROOT:-/root/repo}
 cd /tmp && export TMPDIR=/tmp
 rm -rf /tmp/np_$TAG
-timeout -k 10 500 rocprofv3 --kernel-trace --stats -d /tmp/np_$TAG -o x --output-format csv -- python3 $R/bench.py --landmarks 1024 --steps 12 --warmup 3 --no-cpu-baseline --no-full-loop --profile-steps 2 > $R/gpurun_out/np_$TAG.log 2>&1
+timeout -k 10 500 rocprofv3 --kernel-trace --stats -d /tmp/np_$TAG -o x --output-format csv -- python3 $R/bench.py --full --landmarks 1024 --steps 12 --warmup 3 --no-cpu-baseline --no-full-loop --profile-steps 2 > /tmp/np_$TAG.log 2>&1
 S=$(find /tmp/np_$TAG -name "*kernel_stats.csv" | head -1); T=$(find /tmp/np_$TAG -name "*kernel_trace.csv" | head -1)
 cp $S $R/gpurun_out/np_${TAG}_kernel_stats.csv
 python3 - "$S" "$T" <<'PY'

@@ -23,7 +23,7 @@ for r in cc:
     if t is not None and r["Counter_Name"] == "SQ_BUSY_CYCLES":
         per[k]["duration_ns"].append(float(t["End_Timestamp"]) - float(t["Start_Timestamp"]))
 out = {"source": "rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES SQ_INSTS_VALU_MFMA_MOPS_F32 SQ_WAVE_CYCLES SQ_WAVES GRBM_GUI_ACTIVE "
-                 "--kernel-trace -- python3 bench.py --steps 40 --warmup 10 --no-cpu-baseline --no-full-loop, N=256, MI355X",
+                 "--kernel-trace -- python3 bench.py --full --steps 40 --warmup 10 --no-cpu-baseline --no-full-loop, N=256, MI355X",
        "notes": "means per launch.  mfma_busy_frac_of_simd_time = SQ_VALU_MFMA_BUSY_CYCLES / (1024 SIMDs x clock x duration), "
                 "clock = GRBM_GUI_ACTIVE / 8 / duration (the guide's effective-clock formula; reads high on launches this short, "
                 "so the fraction is a lower bound).  mfma_mops_f32 counts fp32 MFMA ops in units of 512 flops (MOPS) where the counter is populated.",

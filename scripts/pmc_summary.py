@@ -9,7 +9,7 @@ import sys
 tag = sys.argv[1]                                   # gpurun_out tag of the two passes
 name = sys.argv[2] if len(sys.argv) > 2 else tag      # profiles/<name>_pmc_traffic_n256.json
 root = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
-out = {"source": "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes) --kernel-trace -- python3 bench.py --steps 40 "
+out = {"source": "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes) --kernel-trace -- python3 bench.py --full --steps 40 "
                  "--warmup 10 --no-cpu-baseline, N=256, MI355X",
        "units": "FETCH_SIZE/WRITE_SIZE are reported in KiB; on gfx950 FETCH_SIZE counts half of the bytes of 16-B/lane streaming "
                 "reads (MI355X_MICROARCH.md, HBM section), hence fetch_bytes_corrected = 2*1024*FETCH_SIZE; WRITE_SIZE is exact "

@@ -9,7 +9,7 @@ cd /tmp && export TMPDIR=/tmp
 for v in $A $B; do
   export $NAME=$v
   rm -rf $OUT/prof_${NAME}_$v
-  timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_${NAME}_$v -o p -- python3 $ROOT/bench.py --steps 100 --warmup 10 --landmarks $N --no-cpu-baseline --no-full-loop > $OUT/prof_${NAME}_$v.log 2>&1 || { tail -5 $OUT/prof_${NAME}_$v.log; exit 1; }
+  timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_${NAME}_$v -o p -- python3 $ROOT/bench.py --full --steps 100 --warmup 10 --landmarks $N --no-cpu-baseline --no-full-loop > $OUT/prof_${NAME}_$v.log 2>&1 || { tail -5 $OUT/prof_${NAME}_$v.log; exit 1; }
   f=$(find $OUT/prof_${NAME}_$v -name "*kernel_stats.csv" | head -1)
   python3 - "$f" "$NAME=$v" <<'PY'
 import csv, sys

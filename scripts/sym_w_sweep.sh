@@ -19,7 +19,7 @@ print("sym_w $w", {k: ("%.0f MB" % (2 * 1024 * sum(v) / len(v) / 1e6), "%.1f us"
 PY
 done
 cd $ROOT
-for rep in 1 2; do for w in $1; do EKFVIO_SYM_W=$w python bench.py --steps 64 --warmup 10 --landmarks 1024 --no-cpu-baseline --no-full-loop 2>/dev/null | python -c "
+for rep in 1 2; do for w in $1; do EKFVIO_SYM_W=$w python bench.py --full --steps 64 --warmup 10 --landmarks 1024 --no-cpu-baseline --no-full-loop 2>/dev/null | python -c "
 import json,sys
 r=json.loads(sys.stdin.readline())
 print('sym_w $w steps/s %.1f' % r['value'], 'gemm_update %.1f' % r['stage_us_per_step']['gemm_update'])"; done; done
