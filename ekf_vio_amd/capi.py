@@ -24,7 +24,8 @@ class Config(C.Structure):
                 ("use_principal_point", C.c_int32), ("inverse_image_scale", C.c_int32), ("fast_threshold", C.c_int32),
                 ("min_new_feature_dist", C.c_int32), ("fast_blur_sigma", C.c_float), ("replenish", C.c_int32),
                 ("sample_based_uncertainty", C.c_int32), ("use_imu", C.c_int32), ("imu_gyro_variance", C.c_float),
-                ("imu_accel_variance", C.c_float), ("gravity", C.c_float * 3)]
+                ("imu_accel_variance", C.c_float), ("gravity", C.c_float * 3),
+                ("remove_lost", C.c_int32)]
 
 
 class EkfvioError(RuntimeError):
@@ -39,7 +40,7 @@ SYMBOLS = ["ekfvio_default_config", "ekfvio_create", "ekfvio_destroy", "ekfvio_r
            "ekfvio_num_features", "ekfvio_dim", "ekfvio_get_base_mu", "ekfvio_get_features", "ekfvio_get_sigma",
            "ekfvio_get_feature_cov", "ekfvio_get_depth_variance", "ekfvio_set_feature_cov", "ekfvio_metric2pixel_map",
            "ekfvio_pixel2metric_map", "ekfvio_get_odometry", "ekfvio_get_points", "ekfvio_check_sigma", "ekfvio_set_state",
-           "ekfvio_klt_push_frame", "ekfvio_klt_track", "ekfvio_klt_track_points", "ekfvio_klt_get_level",
+           "ekfvio_remove_features", "ekfvio_klt_push_frame", "ekfvio_klt_track", "ekfvio_klt_track_points", "ekfvio_klt_get_level",
            "ekfvio_klt_uncertainty_points", "ekfvio_step_image", "ekfvio_replenish", "ekfvio_fast_detect", "ekfvio_imu", "ekfvio_imu_update",
            "ekfvio_upload_measurements", "ekfvio_run_uploaded", "ekfvio_synchronize", "ekfvio_profile_enable",
            "ekfvio_profile_reset", "ekfvio_profile_count", "ekfvio_profile_name", "ekfvio_profile_get",
@@ -79,6 +80,7 @@ def load(build_if_missing=True, hooks=False):
         "ekfvio_set_feature_cov": [vp, i32, fp], "ekfvio_metric2pixel_map": [fp, fp], "ekfvio_pixel2metric_map": [fp, fp],
         "ekfvio_get_odometry": [vp, fp, fp, fp, fp], "ekfvio_get_points": [vp, fp, fp],
         "ekfvio_check_sigma": [vp, fp, fp], "ekfvio_set_state": [vp, i32, fp, fp, fp, u8p, fp, i32],
+        "ekfvio_remove_features": [vp, u8p, i32, ip],
         "ekfvio_klt_push_frame": [vp, u8p, i32, i32, i32, fp], "ekfvio_klt_track": [vp, fp, fp, u8p],
         "ekfvio_klt_track_points": [vp, fp, fp, i32, fp, u8p],
         "ekfvio_klt_uncertainty_points": [vp, fp, fp, i32, fp],

@@ -183,6 +183,7 @@ int ekfvio_default_config(ekfvio_config* c) {
     c->gravity[0] = 0.f;
     c->gravity[1] = 9.81f;
     c->gravity[2] = 0.f;
+    c->remove_lost = 0;               // reference behaviour: a lost landmark stays in the state, flagged (TightlyCoupledEKF.cpp:528)
     return EKFVIO_OK;
 }
 
@@ -271,6 +272,7 @@ static int create_body(ekfvio_filter* f, const ekfvio_config* cfg, int device, v
     HIPC(f, dev_alloc(f->stream, &f->Wt, pm));
     HIPC(f, dev_alloc(f->stream, &f->Gm, pm));
     HIPC(f, dev_alloc(f->stream, &f->info, 4));
+    HIPC(f, dev_alloc(f->stream, &f->remove_words, 4));
     HIPC(f, hipHostMalloc((void**)&f->h_info, 16 * sizeof(int), hipHostMallocMapped | hipHostMallocCoherent));
     memset(f->h_info, 0, 16 * sizeof(int));
     HIPC(f, hipHostGetDevicePointer((void**)&f->d_hinfo, f->h_info, 0));
@@ -328,6 +330,8 @@ int ekfvio_create(const ekfvio_config* cfg, int device, void* stream, ekfvio_fil
     if (!out) return EKFVIO_EINVAL;
     *out = nullptr;
     if (!cfg || cfg->max_features < 0) return EKFVIO_EINVAL;
+    if (cfg->remove_lost != 0 && cfg->remove_lost != 1) return EKFVIO_EINVAL;
+    if (cfg->remove_lost && (size_t)cfg->max_features * 17 > 64 * 1024) return EKFVIO_ECAPACITY;  // the removal kernel's LDS (remove.hip)
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return EKFVIO_EDEVICE;
     ekfvio_filter* f = new ekfvio_filter();
@@ -351,7 +355,7 @@ int ekfvio_destroy(ekfvio_filter* f) {
     if (f->stream) (void)hipStreamSynchronize(f->stream);
     void* ptrs[] = {f->mu, f->mu_next, f->last_klt, f->del_flag, f->P,  f->P2, f->FA, f->FB, f->FD,   f->Fdense,
                     f->idx, f->inv_idx, f->zmeas,  f->Rmeas,    f->pass,     f->yres, f->Rm, f->Saug,  f->Laug,  f->Linv, f->Lsign, f->Km, f->sweep_sync, f->sweep_dbg,
-                    f->Wt,  f->Gm,     f->info,     f->seq_z,    f->seq_R, f->seq_pass};
+                    f->Wt,  f->Gm,     f->info,     f->remove_words, f->seq_z,    f->seq_R, f->seq_pass};
     for (void* p : ptrs)
         if (p) hipFree(p);
     if (f->h_info) hipHostFree(f->h_info);

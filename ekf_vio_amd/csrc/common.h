@@ -161,6 +161,7 @@ struct ekfvio_filter {
     float* Wt = nullptr;       // [ldp*m_cap]  (H Sigma)^T
     float* Gm = nullptr;       // [ldp*m_cap]  K R - T[:,idx]
     int* info = nullptr;       // [4] device words: [0] non-positive pivot seen, [1] frame counter of uploaded sequences, [2] device-side m
+    int* remove_words = nullptr;  // [4] device words of the removal kernel (remove.hip): [0] landmarks added - removed, [1] removed, [2] its ticket
     int* h_info = nullptr;     // pinned, device-mapped: [0] status word, [1] sequence number (publish_status_kernel)
     int* d_hinfo = nullptr;    // the device's address of h_info
     int status_seq = 0;
@@ -368,6 +369,12 @@ void launch_potrf_stamps(ekfvio_filter* f, const float* S, int ld, float* L, flo
 void launch_gain_from_sweep(ekfvio_filter* f, const float* Laug, int m_pad, int n_pad, int ld, int n, float* K,
                             float* scratch, int ldk, int refine, const GemmEpi* epi = nullptr);
 
+// remove.hip: Sigma, mu, last_klt, del_flag compacted in ONE launch over N + *added landmarks (added may be null); decision from
+// `remove` (device memory), null: del_flag; abort_aware: nothing removed behind an aborted persistent sweep; host_removed (may be
+// null): the count into pinned host memory too
+void launch_remove_features(ekfvio_filter* f, const uint8_t* remove, const int* added, bool abort_aware, int* host_removed);
+size_t remove_lds_bytes(const ekfvio_filter* f);
+void remove_applied(ekfvio_filter* f, int delta, int removed);  // the host side behind a launch: pointer swaps, N, n, graphs
 int klt_alloc(ekfvio_filter* f);  // klt.hip
 void klt_free(ekfvio_filter* f);
 

@@ -1424,7 +1424,8 @@ int ekfvio_step_image(ekfvio_filter* f, double stamp, const uint8_t* image, int3
         // A frame that adds no landmarks publishes its outputs and its status BETWEEN the update's two Joseph GEMMs (frame_outputs_kernel,
         // Pcol): launch_update calls back there.  (With landmarks to add the selection reads the updated mean and the outputs carry the count:
         // behind the update, as before.  EKFVIO_EARLY_OUTPUTS=0: always behind.)
-        if (f->early_outputs && f->frame_outputs && !(f->cfg.replenish && f->N < f->cfg.max_features) &&
+        // (Nor with cfg.remove_lost: the frame's final landmark count is known only behind the removal, as with a replenishing frame.)
+        if (f->early_outputs && f->frame_outputs && !(f->cfg.replenish && f->N < f->cfg.max_features) && !f->cfg.remove_lost &&
             sizeof(float) * (size_t)f->n <= 48 * 1024) {  // (the updated mean is formed in LDS)
             f->between_joseph = [](ekfvio_filter* g) {
                 const KltFrame& fr = g->frames[g->cur];
@@ -1461,11 +1462,23 @@ int ekfvio_step_image(ekfvio_filter* f, double stamp, const uint8_t* image, int3
         if (rc != EKFVIO_OK) return fail(rc);
         if (replenishing) add_features_enqueue_device_count(f, f->fast_counts + 1);
     }
+    // cfg.remove_lost: every flagged landmark leaves the state behind the replenishment (which still saw them), in front of the
+    // frame's outputs (remove.hip).  The kernel takes the landmark count from the device (N + what the replenishment added) and leaves
+    // `added - removed` in remove_words[0]: the outputs kernel counts the landmarks from it and the host reads it with the status word,
+    // so the frame keeps its single wait.  Flags only come from an update, and the flagged landmarks of earlier frames are gone: with
+    // no landmark before the frame there is nothing to remove.  Behind an aborted persistent sweep the kernel removes nothing (the
+    // update is run again below over the layout it was enqueued for); the flags stay and the next frame removes those landmarks.
+    const bool removing = f->cfg.remove_lost && f->N > 0;
+    const int* count_dev = replenishing ? f->fast_counts + 1 : nullptr;
+    if (removing) {
+        launch_remove_features(f, nullptr, count_dev, true, f->d_hinfo + 3);
+        count_dev = f->remove_words;
+    }
     // the frame's one wait: the status word, the number of new landmarks and what the node publishes after addFrame
     // (odometry, point cloud) arrive together in pinned host memory (frame_outputs_kernel)
     int bad = 0, added = 0;
     if (!f->frame_outputs) {
-        rc = wait_status(f, &bad, replenishing ? f->fast_counts + 1 : nullptr, &added);
+        rc = wait_status(f, &bad, count_dev, &added);
     } else {
         const KltFrame& fr = f->frames[f->cur];
         const int pitch = level_pitch(fr.w[0]);
@@ -1475,7 +1488,8 @@ int ekfvio_step_image(ekfvio_filter* f, double stamp, const uint8_t* image, int3
             rc = poll_status(f, early_seq, &bad, &added);
         } else {
             const int seq = next_status_seq(f);
-            hipLaunchKernelGGL(frame_outputs_kernel, dim3(1), dim3(256), 0, f->stream, f->mu, f->N, replenishing ? f->fast_counts + 1 : nullptr,
+            // (behind a removal the mean is in mu_next: the host swaps the two once it has the status word)
+            hipLaunchKernelGGL(frame_outputs_kernel, dim3(1), dim3(256), 0, f->stream, removing ? f->mu_next : f->mu, f->N, count_dev,
                                fr.img[0] + (size_t)KLT_BORDER * pitch + KLT_BORDER, pitch, fr.w[0], fr.h[0], fx, fy, cx, cy, f->d_out, f->info,
                                f->d_hinfo, seq, (const float*)nullptr);
             rc = poll_status(f, seq, &bad, &added);
@@ -1483,6 +1497,7 @@ int ekfvio_step_image(ekfvio_filter* f, double stamp, const uint8_t* image, int3
     }
     if (rc != EKFVIO_OK) return rc;
     f->out_fresh = f->frame_outputs != 0;
+    if (removing) remove_applied(f, 0, __atomic_load_n(&f->h_info[3], __ATOMIC_ACQUIRE));  // (the count of landmarks: below, with `added`)
     if (bad) HIPK(f, hipMemsetAsync(f->info, 0, sizeof(int), f->stream));
     if (bad & 2) {
         // The persistent sweep gave up (chol_persist.inc): the Joseph GEMMs wrote nothing, the state is the propagated one.
@@ -1505,7 +1520,7 @@ int ekfvio_step_image(ekfvio_filter* f, double stamp, const uint8_t* image, int3
         if (bad) HIPK(f, hipMemsetAsync(f->info, 0, sizeof(int), f->stream));
         if (bad & 2) return EKFVIO_EABORTED;
     } else if (f->N > 0) sweep_clean_update(f);
-    if (added > 0) {
+    if (added != 0) {  // (added - removed with cfg.remove_lost)
         f->N += added;
         f->n += 3 * added;
     }

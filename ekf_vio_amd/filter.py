@@ -139,6 +139,18 @@ class TightlyCoupledEKF:
         a = np.ascontiguousarray(accel, dtype=np.float32)
         self._chk(self.lib.ekfvio_imu_update(self.h, _fp(g), _fp(a)))
 
+    def removeFeatures(self, mask=None):
+        """Not in the reference, which flags a lost landmark (TightlyCoupledEKF.cpp:528) and keeps it: removes landmarks from the
+        state (mean, covariance rows and columns, last KLT results, flags), keeping the order of the rest.  mask: one entry per
+        landmark, nonzero = remove; None: the landmarks flagged for deletion.  Returns the number removed."""
+        k = C.c_int32(0)
+        if mask is None:
+            self._chk(self.lib.ekfvio_remove_features(self.h, None, 0, C.byref(k)))
+        else:
+            m = np.ascontiguousarray(np.asarray(mask).astype(bool), dtype=np.uint8).reshape(-1)
+            self._chk(self.lib.ekfvio_remove_features(self.h, _u8(m), m.shape[0], C.byref(k)))
+        return int(k.value)
+
     def checkSigma(self):
         a, b = C.c_float(0), C.c_float(0)
         self._chk(self.lib.ekfvio_check_sigma(self.h, C.byref(a), C.byref(b)))

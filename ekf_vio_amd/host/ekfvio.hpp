@@ -86,6 +86,7 @@ struct Params {
         else if (key == "default_point_depth_variance") cfg.default_point_depth_variance = (float)number(key, value);
         else if (key == "default_point_homogenous_variance") cfg.default_point_homogenous_variance = (float)number(key, value);
         else if (key == "imu_update") cfg.use_imu = (value == "true" || value == "1") ? 1 : 0;  // not a reference parameter: SURVEY 8(f) F4
+        else if (key == "remove_lost") cfg.remove_lost = (value == "true" || value == "1") ? 1 : 0;  // not a reference parameter: removes lost landmarks
         else if (key == "imu_gyro_variance") cfg.imu_gyro_variance = (float)number(key, value);
         else if (key == "imu_accel_variance") cfg.imu_accel_variance = (float)number(key, value);
         else if (key == "gravity_x") cfg.gravity[0] = (float)number(key, value);
@@ -104,7 +105,7 @@ struct Params {
                                         "min_klt_eigen_val", "min_new_feature_dist", "max_pyramids", "klt_window_size",
                                         "default_point_depth", "default_point_depth_variance",
                                         "default_point_homogenous_variance", "frame_buffer_size", "imu_update",
-                                        "imu_gyro_variance", "imu_accel_variance", "gravity_x", "gravity_y", "gravity_z"};
+                                        "imu_gyro_variance", "imu_accel_variance", "gravity_x", "gravity_y", "gravity_z", "remove_lost"};
         for (const auto& e : Params().node) out.push_back(e.first);
         for (const auto& e : ignored()) out.push_back(e.first);
         return out;
@@ -200,6 +201,13 @@ class TightlyCoupledEKF {
         if (rc == EKFVIO_ENUMERIC) return false;
         chk(rc);
         return true;
+    }
+    // Not in the reference (it flags lost landmarks, TightlyCoupledEKF.cpp:528, and keeps them): removes the landmarks whose byte
+    // of `remove` is nonzero (one per landmark), or, with no mask, those flagged for deletion.  Returns the number removed.
+    int removeFeatures(const std::vector<uint8_t>* remove = nullptr) {
+        int32_t removed = 0;
+        chk(ekfvio_remove_features(h_, remove ? remove->data() : nullptr, remove ? (int32_t)remove->size() : 0, &removed));
+        return removed;
     }
     std::vector<int> formFeatureMeasurementMap(const std::vector<uint8_t>& measured) const {
         std::vector<int> idx(2 * measured.size() + 1);

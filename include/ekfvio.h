@@ -98,6 +98,8 @@ typedef struct ekfvio_config {
     float imu_accel_variance;              /* (m/s^2)^2 per axis, default 1e-2 */
     float gravity[3];                      /* gravity in the filter's world frame (= the first camera frame), default (0, 9.81, 0):
                                               an optical frame, y down; the accelerometer model is a + b_acc - R(q)^T gravity */
+    /* landmark removal (not in the reference, which flags a lost landmark, TightlyCoupledEKF.cpp:528, and keeps it) */
+    int32_t remove_lost;                   /* 0 (reference behaviour): lost landmarks stay in the state, flagged; 1: ekfvio_step_image removes them */
 } ekfvio_config;
 
 /* Fills `cfg` with the reference defaults (Params.h D_* values). */
@@ -168,6 +170,12 @@ EKFVIO_API int ekfvio_check_sigma(ekfvio_filter* f, float* min_diag, float* max_
 EKFVIO_API int ekfvio_set_state(ekfvio_filter* f, int32_t n_features, const float* base_mu, const float* mu3N,
                      const float* last_klt2N, const uint8_t* delete_flagN, const float* sigma, int32_t ld);
 
+/* Removes landmarks from the state: mean, covariance rows/columns, last KLT results and flags, keeping the order of the rest
+ * (marginalisation of a Gaussian: exact).  remove != NULL: count must equal the landmark count, nonzero bytes are removed;
+ * remove == NULL: the landmarks flagged for deletion (the tracker lost them, TightlyCoupledEKF.cpp:528) are removed.
+ * *removed (may be NULL) receives the number removed.  Not in the reference, which flags but never removes. */
+EKFVIO_API int ekfvio_remove_features(ekfvio_filter* f, const uint8_t* remove, int32_t count, int32_t* removed);
+
 /* ---- KLT (KLTTracker::findNewFeaturePositions, KLTTracker.cpp:29-95) ----------------- */
 /* Uploads a frame (Frame.h:25-41: image + intrinsics K row-major 3x3 as in CameraInfo.K),
  * builds its pyramid and Scharr derivatives on the device and makes it the current frame;
@@ -199,7 +207,9 @@ EKFVIO_API int ekfvio_klt_get_level(ekfvio_filter* f, int32_t level, int32_t* w,
  * two replenishFeatures calls of addFrame (:154, :172) run on the device as well; with 0 the
  * caller adds landmarks (ekfvio_replenish, or its own detector + ekfvio_add_features).
  * The image is copied before the call returns; the call waits for the device once, at its end
- * (status word), the pass flags of the tracker never travel to the host.  That wait (here, in ekfvio_update and in
+ * (status word), the pass flags of the tracker never travel to the host.  With cfg.remove_lost = 1 the landmarks flagged by this
+ * frame's update (or left flagged by an earlier frame) are removed behind the replenishment, before the frame's outputs; the count
+ * of landmarks the call leaves behind arrives with the same status word.  That wait (here, in ekfvio_update and in
  * ekfvio_synchronize) polls a word the device writes into pinned host memory for up to 300 us of the calling
  * thread's time, then blocks in hipStreamSynchronize.
  * Returns EKFVIO_OK or EKFVIO_ENUMERIC. */
