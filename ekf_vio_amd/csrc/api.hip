@@ -516,16 +516,15 @@ int ekfvio_update(ekfvio_filter* f, const float* z, const float* R, const uint8_
     // launches are in the queue before this step's last kernel ends (EKFVIO_EARLY_STATUS=0: publish behind the last kernel, as rounds 1-3).
     const bool early = f->early_status != 0;  // (per handle, read at create like every other knob: ADVICE r04)
     const int seq = next_status_seq(f);
-    f->publish_after_sweep_seq = early ? seq : 0;
-    launch_update(f, m, dz, dR, dp);
-    if (f->publish_after_sweep_seq != 0 || !early) launch_publish_status(f, seq);  // (no sweep ran: nothing was published yet)
-    f->publish_after_sweep_seq = 0;
+    UpdateInputs in;
+    in.m = m, in.z = dz, in.R = dR, in.pass = dp;
+    in.publish_seq = early ? seq : 0;
+    if (!launch_update(f, in).published) launch_publish_status(f, seq);  // (not early, or no sweep ran: nothing was published yet)
     HIPC(f, hipGetLastError());
-    struct Ctx { int m; float *dz, *dR; uint8_t* dp; } ctx{m, dz, dR, dp};
+    in.publish_seq = 0;
     return finish_update_rerun(f, [](ekfvio_filter* g, void* c) {
-        const Ctx* x = static_cast<const Ctx*>(c);
-        launch_update(g, x->m, x->dz, x->dR, x->dp);  // the staged measurement is still in d_meas; the bookkeeping is idempotent
-    }, &ctx, seq);
+        launch_update(g, *static_cast<const UpdateInputs*>(c));  // the staged measurement is still in d_meas; the bookkeeping is idempotent
+    }, &in, seq);
 }
 
 int ekfvio_measurement_map(const ekfvio_filter* f, const uint8_t* measured, int32_t count, int32_t* idx, int32_t* rows) {
@@ -755,6 +754,15 @@ static void drop_graph(ekfvio_filter* f) {
     }
 }
 
+// An update of ekfvio_run_uploaded: frame i of the uploaded sequence, or the one the device-side counter names.  These launches and captures
+// carry the long wait bound (common.h, sweep_wait_ticks): nothing can run their updates again
+static UpdateInputs uploaded_update(ekfvio_filter* f, int m, int i, int* counter) {
+    UpdateInputs in;
+    in.m = m, in.z = f->seq_z + (size_t)i * 2 * f->N, in.R = f->seq_R + (size_t)i * 4 * f->N, in.pass = f->seq_pass + (size_t)i * f->N;
+    in.frame_counter = counter, in.frames = counter ? f->seq_frames : 0;
+    in.recoverable = false;
+    return in;
+}
 // Captures `steps` filter steps (process + update with m measurement rows each, bookkeeping driven by the device-side
 // frame counter) into an executable graph.  `steps` is even: the mean / covariance ping-pong nets to zero.
 static int capture_steps(ekfvio_filter* f, int steps, int m, float dt, int* counter, hipGraphExec_t* out) {
@@ -772,11 +780,12 @@ static int capture_steps(ekfvio_filter* f, int steps, int m, float dt, int* coun
         const BookArgs bk = make_book_args(f, m, f->seq_z, f->seq_R, f->seq_pass, counter);
         launch_predict(f, dt, &bk);
         // round 6: inside a graph the next step's dt is known -- every update but the graph's last lets its last GEMM linearise for the step
-        // behind it (launch_update decides whether the shape allows it; the graph's last update leaves the next replay's first step to
+        // behind it (plan_update decides whether the shape allows it; the graph's last update leaves the next replay's first step to
         // linearise for itself, so a graph needs nothing from whatever ran before it)
-        f->lin_next_dt = (k + 1 < steps) ? dt : -1.f;
-        launch_update(f, m, f->seq_z, f->seq_R, f->seq_pass, counter, f->seq_frames, true);
-        f->lin_next_dt = -1.f;
+        UpdateInputs in = uploaded_update(f, m, 0, counter);
+        in.bookkeeping_done = true;
+        in.next_dt = (k + 1 < steps) ? dt : -1.f;
+        launch_update(f, in);
     }
     f->prelinearized = false;
     hipError_t ce = hipStreamEndCapture(f->stream, &g);
@@ -799,13 +808,7 @@ int ekfvio_run_uploaded(ekfvio_filter* f, int32_t first, int32_t count, float dt
     // sweep once gave up keeps the per-step sweep for its graph replays until ekfvio_update / ekfvio_step_image, which CAN recover,
     // have tried the persistent launch again and it has come through; with a permanent obstacle (a compute-unit mask, a co-tenant
     // process) a retry from here would skip a replay's remaining updates every 2 .. 64 s for the handle's whole life)
-    const size_t N = f->N;
     int s = 0;
-    struct Unrec {  // the launches and captures of this call carry the long wait bound (common.h, sweep_wait_ticks): nothing can run their updates again
-        ekfvio_filter* f;
-        explicit Unrec(ekfvio_filter* f_) : f(f_) { f->sweep_unrecoverable = true; }
-        ~Unrec() { f->sweep_unrecoverable = false; }
-    } unrec(f);
     // hipGraph path: the same measurement-row count for every frame (one launch geometry),
     // profiling off.  The bookkeeping kernel reads the frame index from a device counter.
     // (count == 0 only prepares: the graphs are captured, nothing runs — callers that time a run call this first)
@@ -841,7 +844,7 @@ int ekfvio_run_uploaded(ekfvio_filter* f, int32_t first, int32_t count, float dt
         if (s > 0) f->sweep_flags_clean = f->graph_leaves_flags_clean;  // what the last replayed step left in device memory
         for (; s < count; s++) {  // an odd last step, eager, same counter-driven bookkeeping
             launch_predict(f, dt);
-            launch_update(f, m, f->seq_z, f->seq_R, f->seq_pass, counter, f->seq_frames);
+            launch_update(f, uploaded_update(f, m, 0, counter));
         }
         HIPC(f, hipGetLastError());
         return EKFVIO_OK;
@@ -849,7 +852,7 @@ int ekfvio_run_uploaded(ekfvio_filter* f, int32_t first, int32_t count, float dt
     for (; s < count; s++) {
         const int i = (first + s) % f->seq_frames;
         launch_predict(f, dt);
-        launch_update(f, f->seq_m[i], f->seq_z + i * 2 * N, f->seq_R + i * 4 * N, f->seq_pass + i * N);
+        launch_update(f, uploaded_update(f, f->seq_m[i], i, nullptr));
     }
     HIPC(f, hipGetLastError());
     return EKFVIO_OK;
@@ -894,7 +897,7 @@ int ekfvio_profile_update_gemms(ekfvio_filter* f, int32_t reps, double* avg_laun
     hipGraph_t g = nullptr;
     hipGraphExec_t ge = nullptr;
     HIPC(f, hipStreamBeginCapture(f->stream, hipStreamCaptureModeThreadLocal));
-    const int per_rep = launch_update_gemms_scratch(f, f->last_m, reps);
+    const int per_rep = launch_update_gemms_scratch(f, plan_update(f, f->last_m), reps);
     hipError_t ce = hipStreamEndCapture(f->stream, &g);
     if (ce != hipSuccess || !g) {
         f->last_error = std::string("graph capture: ") + hipGetErrorString(ce);
@@ -1120,14 +1123,18 @@ int ekfvio_test_cholesky_solve(ekfvio_filter* f, int32_t m, int32_t nrhs, const 
     HIPC(f, dev_alloc(f->stream, &dK, (size_t)rp * mp));
     HIPC(f, dev_alloc(f->stream, &dW, (size_t)rp * mp));
     HIPC(f, hipMemcpyAsync(dS, hs.data(), sizeof(float) * hs.size(), hipMemcpyHostToDevice, f->stream));
-    launch_chol_sweep(f, dS, dL, dLi, mp, rp, ld);
+    // the flow the handle's knobs and the process's handle count select for this shape, as for an update of the filter (plan_raw_sweep)
+    UpdatePlan plan = plan_raw_sweep(f, mp, rp);
+    launch_chol_sweep(f, plan, dS, dL, dLi, ld, plan.persistent() && !f->sweep_flags_clean);
+    if (plan.persistent()) f->sweep_flags_clean = false;  // (no GEMM of an update behind this sweep zeroes its flags)
     // one step of residual refinement against L, unless a block went through the U S U^T path (K L = Y S then, not Y)
     std::vector<unsigned long long> hsign(mp / 64);
     HIPC(f, hipMemcpyAsync(hsign.data(), f->Lsign, sizeof(unsigned long long) * hsign.size(), hipMemcpyDeviceToHost, f->stream));
     HIPC(f, hipStreamSynchronize(f->stream));
     int refine = 1;
     for (unsigned long long v : hsign) refine &= (v == 0ull);
-    launch_gain_from_sweep(f, dL, mp, rp, ld, nrhs, dK, dW, rp, refine);
+    if (refine) plan.gain = GAIN_GEMM;
+    launch_gain_from_sweep(f, plan, dL, ld, nrhs, dK, dW, rp, refine);
     std::vector<float> hl(hs.size()), hk((size_t)rp * mp);
     HIPC(f, hipMemcpyAsync(hl.data(), dL, sizeof(float) * hl.size(), hipMemcpyDeviceToHost, f->stream));
     HIPC(f, hipMemcpyAsync(hk.data(), dK, sizeof(float) * hk.size(), hipMemcpyDeviceToHost, f->stream));

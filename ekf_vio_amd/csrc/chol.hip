@@ -1109,27 +1109,19 @@ int persist_zero_words(int m_pad, int n_pad) {
     const int mb = m_pad / PB, rows = 2 * mb + n_pad / PB;
     return mb + 2 * rows * mb + 1;
 }
-static void persist_flag_pointers(ekfvio_filter* f, PersistArgs& pa, int mb, int rows) {
-    pa.ready = f->sweep_sync;
-    pa.fin = f->sweep_sync + mb;
-    pa.pan = pa.fin + rows * mb;
-    pa.abort_flag = pa.pan + rows * mb + 1;
-}
 #define EKF_GATHER_POTRF_LDS (84 * 1024)  // > half of a compute unit's 160 KB: one workgroup per compute unit
-void launch_gather_potrf(ekfvio_filter* f, int m, int m_pad, int n_pad, bool m_on_device, bool with_wt) {
+void launch_gather_potrf(ekfvio_filter* f, const UpdatePlan& p) {
     if (!f->gather_attr_set) {
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gather_potrf_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
                                   EKF_GATHER_POTRF_LDS);
         f->gather_attr_set = true;
     }
-    GatherArgs ga = make_gather_args(f, m, m_pad, n_pad);
-    if (m_on_device) ga.m_dev = f->info + 2;
-    if (sweep_is_persistent(f, m_pad, n_pad)) {
+    GatherArgs ga = make_gather_args(f, p);
+    if (p.persistent()) {  // (the persistent launch behind this one then needs no memset: launch_update)
         ga.zero_words = f->sweep_sync;
-        ga.n_zero = (int)persist_flag_words(m_pad, n_pad);
-        f->sweep_flags_clean = true;  // (launch_chol_sweep, called next, skips its memset)
+        ga.n_zero = (int)persist_flag_words(p.m_pad, p.n_pad);
     }
-    const int nb2 = with_wt ? (m_pad / 64) * (f->ldp / 64) : 0;  // 64x64 transposing tiles of Wt (only the first Joseph GEMM reads it)
+    const int nb2 = p.with_wt ? (p.m_pad / 64) * (f->ldp / 64) : 0;  // 64x64 transposing tiles of Wt (only the first Joseph GEMM reads it)
     hipLaunchKernelGGL(gather_potrf_kernel, dim3(1 + ga.nb1 + nb2), dim3(256), EKF_GATHER_POTRF_LDS, f->stream, ga, f->Laug, f->ld_aug,
                        f->Linv, f->info, f->Lsign, f->sweep_dbg);
 }
@@ -1179,10 +1171,90 @@ static int t2_skip_owners(const ekfvio_filter* f, int m_pad, int n_pad) {
     if (1 + gw + H > f->num_cus) return -1;  // the compact launch (chol_persist.inc): every workgroup has its compute unit from the start
     return (nX * (nX + 1) / 2 <= H) ? 0 : -1;
 }
-bool t2_flow_shape(const ekfvio_filter* f, int m_pad, int n_pad) { return t2_skip_owners(f, m_pad, n_pad) >= 0; }
-bool sweep_is_persistent(const ekfvio_filter* f, int m_pad, int n_pad) {
+// Which sweep runs.  filter_update: the filter's own matrices (Schur tiles and the fused front are possible); else another caller's [A; X; I].
+static SweepKind choose_sweep(const ekfvio_filter* f, int m_pad, int n_pad, bool filter_update) {
+    const int mb = m_pad / PB;
+    // (EKFVIO_SCHUR=1 takes precedence over the persistent launch, for every sweep of the handle; not in the split sweep)
+    const bool schur_shape = f->schur && mb < EKF_SWEEP_SPLIT_MB;
+    if (schur_shape && filter_update) return SWEEP_SCHUR;
     // (only for a device's sole handle: two persistent launches in flight together could starve each other of compute units)
-    return f->sweep_mode == 2 && !sweep_supports_schur(f, m_pad) && live_handles_on(f->device) <= 1 && persist_shape(f, m_pad, n_pad);
+    if (f->sweep_mode == 2 && !schur_shape && live_handles_on(f->device) <= 1 && persist_shape(f, m_pad, n_pad))
+        // round 4: where the persistent sweep applies, the gather and the first tile are part of ITS launch (launch_persist_fused)
+        return (filter_update && f->fuse_sweep && f->fuse_gather) ? SWEEP_PERSIST_FUSED : SWEEP_PERSIST;
+    // EKFVIO_SWEEP_LA=0 (diagnostic): the two-launch split sweep (panel launch + tile launch per block step)
+    static const bool la_env = getenv("EKFVIO_SWEEP_LA") ? atoi(getenv("EKFVIO_SWEEP_LA")) != 0 : true;
+    // many tiles per step: panel blocks once per step in a launch of their own instead of twice per tile
+    return mb < EKF_SWEEP_SPLIT_MB ? SWEEP_STEP : la_env ? SWEEP_SPLIT_LA : SWEEP_SPLIT;
+}
+// a shape the persistent launch forms the gain for when it runs: behind any other sweep the tile kernel whose arithmetic that launch's
+// in-sweep gain shares (chol_persist.inc, gain_tile), so that a sequence gives the same bits whichever sweep its updates take (eight
+// handles on one GPU against each one's solo run, tests/test_gpu_shapes.py)
+static bool gain_tiles_shape(const ekfvio_filter* f, int m_pad, int n_pad) { return f->persist_gain && gain_in_sweep_shape(f, m_pad, n_pad); }
+
+UpdatePlan plan_raw_sweep(const ekfvio_filter* f, int m_pad, int n_pad) {
+    UpdatePlan p;
+    p.m = p.m_pad = m_pad, p.n_pad = n_pad;
+    p.sweep = choose_sweep(f, m_pad, n_pad, false);
+    p.gain = gain_tiles_shape(f, m_pad, n_pad) ? GAIN_TILES : GAIN_GEMM;
+    return p;
+}
+
+UpdatePlan plan_update(const ekfvio_filter* f, int m, bool m_on_device, float next_dt, bool recoverable) {
+    UpdatePlan p;
+    if (m_on_device) m = 2 * f->N;  // upper bound: sizes the launches; the kernels read the true count from f->info[2]
+    const int n = f->n, ld = f->ldp, m_pad = round_up(m > 0 ? m : 1, EKF_TILE), n_pad = round_up(n, EKF_TILE);
+    p.m = m, p.m_pad = m_pad, p.n_pad = n_pad, p.m_on_device = m_on_device, p.recoverable = recoverable;
+    if (m <= 0) return p;
+    p.sweep = choose_sweep(f, m_pad, n_pad, true);
+    // T = Sigma - X A^-1 X^T and K = X A^-1 as Schur tiles of the sweep (no gain GEMM, no first Joseph GEMM, no (H Sigma)^T)
+    const bool schur = p.sweep == SWEEP_SCHUR, fused = p.sweep == SWEEP_PERSIST_FUSED;
+    p.with_wt = !schur;
+    // The gather and the first diagonal tile's factorisation share a launch while that launch is a single round of
+    // workgroups at one per compute unit (gather_potrf_kernel); beyond that (N = 1024: thousands of gather
+    // workgroups) the gather wants several workgroups per compute unit and the two stay separate.
+    if (f->fuse_gather && !fused) {
+        const int gx = (std::max(ld, m_pad) + 255) / 256;
+        p.fused_gather = 1 + gx * ((m_pad + GC * GCI - 1) / (GC * GCI)) + (schur ? 0 : (m_pad / 64) * (ld / 64)) <= f->num_cus;
+    }
+    if (schur) return p.gain = GAIN_SCHUR, p.tail = TAIL_SCHUR, p;
+    p.t2_skip = t2_skip_owners(f, m_pad, n_pad);
+    if (p.t2_skip < 0) {
+        // the transposing workgroups of the fused launch stay and form the gain while the sweep runs, as long as (nearly) every workgroup of the
+        // launch finds a compute unit at once: they hold theirs to the end
+        p.gain = !gain_tiles_shape(f, m_pad, n_pad) ? GAIN_GEMM : fused ? GAIN_SWEEP : GAIN_TILES;
+        return p.tail = TAIL_JOSEPH, p;
+    }
+    p.tail = TAIL_T2;
+    p.t2_by_sweep = p.compact = fused;
+    p.gain = fused ? GAIN_SWEEP : GAIN2_T2_TILES;
+    // a device-resident run (capture_steps): the next process(dt)'s linearisation and mean propagation ride in the one GEMM's launch, in workgroups
+    // of their own behind the tiles' (K y is final: the gain tiles' partial sums); launch_predict then only propagates Sigma
+    const int lin_blocks = (f->N + LIN_LM - 1) / LIN_LM + 1;
+    if (next_dt >= 0.f && f->lin_overlap && f->cfg.predict_mode != EKFVIO_PREDICT_DENSE && f->fuse_linearize &&
+        gemm_single_round_with(f, n, n, m_pad, 1 + lin_blocks))
+        p.lin_blocks = lin_blocks;
+    return p;
+}
+
+// What every launch that takes PersistArgs shares: the swept matrix and its block geometry, the gain's destination, the column signs, Sigma
+// and T2.  With S (chol_persist_kernel, which hands tiles over inside the launch) also the flags, the wait bounds and the fault-injection
+// hook's workgroup: the hook counts owners from workgroup 1, `lead_wgs` more workgroups come in front of them
+static PersistArgs persist_args(ekfvio_filter* f, const UpdatePlan& p, float* L, int ldl, float* K, int ldk, float* S = nullptr,
+                                float* Linv = nullptr, int lead_wgs = 0) {
+    PersistArgs pa = PersistArgs();
+    const int mb = p.m_pad / PB, nX = p.n_pad / PB, rows = 2 * mb + nX;
+    pa.L = L, pa.ldl = ldl, pa.mb = mb, pa.idb0 = mb + nX;
+    pa.K = K, pa.ldk = ldk, pa.Lsign = f->Lsign;
+    pa.Sg = f->P, pa.ldsg = f->ldp, pa.T2 = t2_buffer(f), pa.ldt = f->ldp, pa.nstate = f->n;
+    if (!S) return pa;
+    pa.S = S, pa.lds = ldl, pa.Linv = Linv, pa.nrows = rows, pa.info = f->info;
+    pa.ready = f->sweep_sync, pa.fin = pa.ready + mb, pa.pan = pa.fin + rows * mb, pa.abort_flag = pa.pan + rows * mb + 1;
+    pa.dbg = f->sweep_dbg;
+    pa.bound.spin_limit = f->sweep_spin_limit > 0 ? f->sweep_spin_limit : SWEEP_SPIN_LIMIT;
+    pa.bound.wait_ticks = p.recoverable ? f->sweep_wait_ticks : std::max(f->sweep_wait_ticks, SWEEP_WAIT_TICKS_UNRECOVERABLE);
+    pa.early_sources = f->persist_early;
+    pa.stall_wg = f->sweep_stall_wg >= 0 ? f->sweep_stall_wg + lead_wgs : -1;
+    return pa;
 }
 
 // The update's whole front in ONE launch (round 4): the measurement gather, the first diagonal tile and the sweep behind it.
@@ -1194,90 +1266,49 @@ bool sweep_is_persistent(const ekfvio_filter* f, int m_pad, int n_pad) {
 // come first and never wait, the last owners get their compute unit microseconds later and are needed last.  The launch asks for
 // > 80 KB of LDS so that every workgroup has a compute unit of its own (the pivot chain runs 2x longer on a shared one).
 #define EKF_PERSIST_FUSED_DYN_LDS (28 * 1024)
-void launch_persist_fused(ekfvio_filter* f, int m, int m_pad, int n_pad, bool m_on_device) {
+const int* launch_persist_fused(ekfvio_filter* f, const UpdatePlan& p, bool zero_flags) {
+    const int m_pad = p.m_pad, n_pad = p.n_pad, mb = m_pad / PB;
     ProfScope ps(f, PC_CHOL, (double)m_pad * m_pad * m_pad / 3.0 + (double)(n_pad + m_pad / 2) * m_pad * m_pad);
     if (!f->persist_attr_set) {
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(chol_persist_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
                                   EKF_PERSIST_FUSED_DYN_LDS);
         f->persist_attr_set = true;
     }
-    GatherArgs ga = make_gather_args(f, m, m_pad, n_pad);
-    if (m_on_device) ga.m_dev = f->info + 2;
     const int nb2 = (m_pad / 64) * (f->ldp / 64);  // 64x64 transposing tiles of Wt
-    const int mb = m_pad / PB, rb = n_pad / PB + mb, ld = f->ld_aug;
-    PersistArgs pa;
-    pa.S = f->Saug, pa.lds = ld, pa.L = f->Laug, pa.ldl = ld, pa.Linv = f->Linv;
-    pa.mb = mb, pa.idb0 = mb + n_pad / PB, pa.nrows = mb + rb;
-    pa.info = f->info, pa.Lsign = f->Lsign;
-    persist_flag_pointers(f, pa, mb, mb + rb);
+    const int lead_wgs = nb2 + (p.compact ? 0 : 2);
+    PersistArgs pa = persist_args(f, p, f->Laug, f->ld_aug, f->Km, f->ldp, f->Saug, f->Linv, lead_wgs);
     pa.fused = 1, pa.gather_wgs = nb2;
-    // the transposing workgroups stay and form the gain while the sweep runs, as long as (nearly) every workgroup of the launch finds a
-    // compute unit at once: they hold theirs to the end
-    pa.gain = (f->persist_gain && gain_in_sweep_shape(f, m_pad, n_pad)) ? 1 : 0;
-    pa.K = f->Km, pa.ldk = f->ldp;
-    f->gain_in_sweep = pa.gain != 0;
-    pa.t2_skip = t2_skip_owners(f, m_pad, n_pad);
-    pa.t2 = (pa.gain && pa.t2_skip >= 0) ? 1 : 0;
-    pa.compact = pa.t2;
-    pa.Sg = f->P, pa.ldsg = f->ldp, pa.T2 = t2_buffer(f), pa.ldt = f->ldp, pa.nstate = f->n;
-    f->t2_in_sweep = pa.t2 != 0;
-    pa.dbg = f->sweep_dbg;
-    pa.bound.spin_limit = f->sweep_spin_limit > 0 ? f->sweep_spin_limit : SWEEP_SPIN_LIMIT;
-    pa.bound.wait_ticks = f->sweep_unrecoverable ? std::max(f->sweep_wait_ticks, SWEEP_WAIT_TICKS_UNRECOVERABLE) : f->sweep_wait_ticks;
-    pa.early_sources = f->persist_early;
-    pa.stall_wg = f->sweep_stall_wg >= 0 ? f->sweep_stall_wg + pa.gather_wgs + (pa.compact ? 0 : 2) : -1;  // (the hook counts owners from workgroup 1)
-    f->sweep_abort_word = pa.abort_flag;
-    if (!f->sweep_flags_clean) (void)hipMemsetAsync(f->sweep_sync, 0, sizeof(int) * persist_flag_words(m_pad, n_pad), f->stream);
-    f->sweep_flags_clean = false;
-    hipLaunchKernelGGL(chol_persist_kernel, dim3(1 + pa.gather_wgs + (pa.compact ? 0 : 2) + persist_helpers(mb, n_pad / PB, pa.compact != 0)), dim3(256), EKF_PERSIST_FUSED_DYN_LDS,
-                       f->stream, pa, ga);
+    pa.gain = p.gain == GAIN_SWEEP, pa.t2_skip = p.t2_skip, pa.t2 = p.t2_by_sweep, pa.compact = p.compact;
+    if (zero_flags) (void)hipMemsetAsync(f->sweep_sync, 0, sizeof(int) * persist_flag_words(m_pad, n_pad), f->stream);
+    hipLaunchKernelGGL(chol_persist_kernel, dim3(1 + lead_wgs + persist_helpers(mb, n_pad / PB, p.compact)), dim3(256), EKF_PERSIST_FUSED_DYN_LDS,
+                       f->stream, pa, make_gather_args(f, p));
     f->persistent_sweeps++;
+    return pa.abort_flag;
 }
 
-void launch_chol_sweep(ekfvio_filter* f, float* Saug, float* Laug, float* Linv, int m_pad, int n_pad, int ld, bool first_tile_done,
-                       bool schur) {
+const int* launch_chol_sweep(ekfvio_filter* f, const UpdatePlan& p, float* Saug, float* Laug, float* Linv, int ld, bool zero_flags) {
+    const int m_pad = p.m_pad, n_pad = p.n_pad;
+    const bool schur = p.sweep == SWEEP_SCHUR, split = p.sweep == SWEEP_SPLIT || p.sweep == SWEEP_SPLIT_LA;
     ProfScope ps(f, PC_CHOL, (double)m_pad * m_pad * m_pad / 3.0 + (double)(n_pad + m_pad / 2) * m_pad * m_pad +
                                  (schur ? (double)n_pad * n_pad * m_pad + (double)n_pad * m_pad * m_pad : 0.0));
-    const int mb = m_pad / PB;
+    const int mb = m_pad / PB, idb0 = mb + n_pad / PB;
     const int rb = n_pad / PB + mb;        // extra row blocks: X then I
-    const int idb0 = mb + n_pad / PB;
-    f->sweep_abort_word = nullptr;
-    f->gain_in_sweep = false;
-    f->t2_in_sweep = false;
-    if (!first_tile_done)
+    if (!p.fused_gather)
         hipLaunchKernelGGL(potrf64_kernel, dim3(1), dim3(256), 0, f->stream, Saug, ld, Laug, ld, Linv, f->info, f->Lsign);
-    if (!schur && sweep_is_persistent(f, m_pad, n_pad)) {
+    if (p.sweep == SWEEP_PERSIST) {
         // ONE launch for everything behind the first diagonal tile (chol_persist.inc): flags zeroed, then the chain and its helpers
-        PersistArgs pa;
-        pa.S = Saug, pa.lds = ld, pa.L = Laug, pa.ldl = ld, pa.Linv = Linv;
-        pa.mb = mb, pa.idb0 = idb0, pa.nrows = mb + rb;
-        pa.info = f->info, pa.Lsign = f->Lsign;
-        persist_flag_pointers(f, pa, mb, mb + rb);
-        pa.fused = 0, pa.gather_wgs = 0, pa.gain = 0, pa.K = nullptr, pa.ldk = 0, pa.t2 = 0, pa.compact = 0;
-        pa.dbg = f->sweep_dbg;
-        pa.bound.spin_limit = f->sweep_spin_limit > 0 ? f->sweep_spin_limit : SWEEP_SPIN_LIMIT;
-        pa.bound.wait_ticks = f->sweep_unrecoverable ? std::max(f->sweep_wait_ticks, SWEEP_WAIT_TICKS_UNRECOVERABLE) : f->sweep_wait_ticks;
-        pa.early_sources = f->persist_early;
-        pa.stall_wg = f->sweep_stall_wg;
-        f->sweep_abort_word = pa.abort_flag;  // the kernels behind this sweep leave the state alone if it is raised (launch_update)
+        const PersistArgs pa = persist_args(f, p, Laug, ld, nullptr, 0, Saug, Linv);
         // (the flags are zero already behind an update of this handle: its last GEMM zeroes them, launch_update)
-        if (!f->sweep_flags_clean) (void)hipMemsetAsync(f->sweep_sync, 0, sizeof(int) * persist_flag_words(m_pad, n_pad), f->stream);
-        f->sweep_flags_clean = false;
+        if (zero_flags) (void)hipMemsetAsync(f->sweep_sync, 0, sizeof(int) * persist_flag_words(m_pad, n_pad), f->stream);
         hipLaunchKernelGGL(chol_persist_kernel, dim3(1 + persist_helpers(mb, n_pad / PB)), dim3(256), 0, f->stream, pa, GatherArgs());
         f->persistent_sweeps++;
-        return;
+        return pa.abort_flag;  // the kernels behind this sweep leave the state alone if it is raised (launch_update)
     }
-    // many tiles per step: panel blocks once per step in a launch of their own instead of twice per tile
-    const bool split = mb >= EKF_SWEEP_SPLIT_MB;
     SchurArgs sc;
-    if (schur && !split) {
+    if (schur) {
         f->schur_sweeps++;
         // T and K as Schur tiles of the sweep itself (chol_step_kernel): Sigma is updated in place, the gain lands in Km
-        sc.P = f->P;
-        sc.ldp = f->ldp;
-        sc.K = f->Km;
-        sc.ldk = f->ldp;
-        sc.nb = n_pad / PB;
+        sc.P = f->P, sc.ldp = f->ldp, sc.K = f->Km, sc.ldk = f->ldp, sc.nb = n_pad / PB;
         const int nT = sc.nb * (sc.nb + 1) / 2;
         for (int k = 0; k < mb; k++) {
             const int r = mb - 1 - k;
@@ -1285,11 +1316,9 @@ void launch_chol_sweep(ekfvio_filter* f, float* Saug, float* Laug, float* Linv, 
             hipLaunchKernelGGL((chol_step_kernel<true, true>), grid, dim3(256), 0, f->stream, Saug, ld, Laug, ld, Linv, k, mb, idb0,
                                f->info, f->Lsign, f->sweep_dbg, sc);
         }
-        return;
+        return nullptr;
     }
-    // EKFVIO_SWEEP_LA=0 (diagnostic): the two-launch split sweep (panel launch + tile launch per block step)
-    static const bool la_env = getenv("EKFVIO_SWEEP_LA") ? atoi(getenv("EKFVIO_SWEEP_LA")) != 0 : true;
-    if (split && la_env) {
+    if (p.sweep == SWEEP_SPLIT_LA) {
         LaArgs la;
         la.S = Saug, la.lds = ld, la.L = Laug, la.ldl = ld, la.Linv = Linv;
         la.mb = mb, la.rb = rb, la.idb0 = idb0, la.info = f->info, la.Lsign = f->Lsign;
@@ -1302,7 +1331,7 @@ void launch_chol_sweep(ekfvio_filter* f, float* Saug, float* Laug, float* Linv, 
         hipLaunchKernelGGL(chol_panel_kernel, dim3(rb), dim3(256), 0, f->stream, Saug, ld, Laug, ld, Linv, mb - 1, mb, 0, idb0, f->Lsign, 0);
         hipLaunchKernelGGL(sign_irows_kernel, dim3((m_pad + 255) / 256, mb), dim3(256), 0, f->stream, Laug, ld, idb0 * PB, m_pad,
                            f->Lsign);
-        return;
+        return nullptr;
     }
     for (int k = 0; k + 1 < mb; k++) {
         const int r = mb - 1 - k;
@@ -1322,6 +1351,7 @@ void launch_chol_sweep(ekfvio_filter* f, float* Saug, float* Laug, float* Linv, 
     if (split)  // the stored identity-row blocks were operands until now: their column signs go on last
         hipLaunchKernelGGL(sign_irows_kernel, dim3((m_pad + 255) / 256, mb), dim3(256), 0, f->stream, Laug, ld, idb0 * PB, m_pad,
                            f->Lsign);
+    return nullptr;
 }
 
 // Behind the Schur sweep: the gain gets the reference's sparseView prune (:580), G' = K R^T - (H T2)^T, i.e.
@@ -1383,17 +1413,11 @@ __global__ __launch_bounds__(256) void joseph_g_kernel(float* __restrict__ K, in
 }
 
 // The gain, G', K y's partial sums AND T2 behind a sweep that did not form them itself (gain2_t2_tiles_kernel; T2 flow)
-void launch_gain2_tiles(ekfvio_filter* f, int m, int m_pad, int n_pad, bool m_on_device) {
+void launch_gain2_tiles(ekfvio_filter* f, const UpdatePlan& p) {
     // (with T2's tile pairs in the same launch: gain2_t2_tiles_kernel)
+    const int m_pad = p.m_pad, n_pad = p.n_pad;
     ProfScope ps(f, PC_SOLVE, 2.0 * n_pad * (double)m_pad * m_pad + (double)n_pad * n_pad * m_pad);
-    PersistArgs pa = PersistArgs();
-    pa.L = f->Laug, pa.ldl = f->ld_aug;
-    pa.mb = m_pad / PB, pa.idb0 = m_pad / PB + n_pad / PB;
-    pa.K = f->Km, pa.ldk = f->ldp;
-    pa.Lsign = f->Lsign;
-    pa.Sg = f->P, pa.ldsg = f->ldp, pa.T2 = t2_buffer(f), pa.ldt = f->ldp, pa.nstate = f->n;
-    GatherArgs ga = make_gather_args(f, m, m_pad, n_pad);
-    if (m_on_device) ga.m_dev = f->info + 2;
+    const PersistArgs pa = persist_args(f, p, f->Laug, f->ld_aug, f->Km, f->ldp);
     const int nX = n_pad / PB, gain_wgs = nX * pa.mb;
     const int total = gain_wgs + nX * (nX + 1) / 2;
     // (> 80 KB of LDS with the 53 KB of tiles: one workgroup per compute unit while the launch fits the compute units)
@@ -1402,7 +1426,7 @@ void launch_gain2_tiles(ekfvio_filter* f, int m, int m_pad, int n_pad, bool m_on
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gain2_t2_tiles_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 30 * 1024);
         f->gain2_attr_set = true;
     }
-    hipLaunchKernelGGL(gain2_t2_tiles_kernel, dim3(total), dim3(256), dyn, f->stream, pa, ga, gain_wgs);
+    hipLaunchKernelGGL(gain2_t2_tiles_kernel, dim3(total), dim3(256), dyn, f->stream, pa, make_gather_args(f, p), gain_wgs);
 }
 
 void launch_joseph_g(ekfvio_filter* f, int m, int m_pad, int n_pad, bool m_on_device, const float* T) {
@@ -1416,29 +1440,18 @@ void launch_joseph_g(ekfvio_filter* f, int m, int m_pad, int n_pad, bool m_on_de
 // (:580).  refine != 0 adds one step of residual refinement against L itself,
 // K <- K + (Y - K L) L^-1 (two more GEMMs); on the filter's matrices it changes nothing
 // measurable (the error is dominated by the fp32 factor itself), so it is off by default.
-bool sweep_supports_schur(const ekfvio_filter* f, int m_pad) {
-    // (EKFVIO_SCHUR=1 takes precedence over the persistent launch: launch_chol_sweep skips that path when `schur` is set)
-    return f->schur && m_pad / PB < EKF_SWEEP_SPLIT_MB;
-}
-
-void launch_gain_from_sweep(ekfvio_filter* f, const float* Laug, int m_pad, int n_pad, int ld, int n, float* K,
-                            float* scratch, int ldk, int refine, const GemmEpi* epi) {
+void launch_gain_from_sweep(ekfvio_filter* f, const UpdatePlan& p, const float* Laug, int ld, int n, float* K, float* scratch, int ldk, int refine) {
+    const int m_pad = p.m_pad, n_pad = p.n_pad;
     ProfScope ps(f, PC_SOLVE, (refine ? 3.0 : 1.0) * n * (double)m_pad * m_pad);
-    if (!refine && !epi && f->persist_gain && gain_in_sweep_shape(f, m_pad, n_pad)) {
-        // a shape the persistent launch takes when the handle is alone on its device (this call: it is not, or EKFVIO_SWEEP=0): the
-        // tile kernel whose arithmetic that launch's in-sweep gain shares (chol_persist.inc, gain_tile), so that a sequence gives the
-        // same bits whichever sweep its updates take (eight handles on one GPU against each one's solo run, tests/test_gpu_shapes.py)
-        PersistArgs pa = PersistArgs();
-        pa.L = const_cast<float*>(Laug), pa.ldl = ld;
-        pa.mb = m_pad / PB, pa.idb0 = m_pad / PB + n_pad / PB;
-        pa.K = K, pa.ldk = ldk;
+    if (p.gain == GAIN_TILES) {
+        const PersistArgs pa = persist_args(f, p, const_cast<float*>(Laug), ld, K, ldk);
         hipLaunchKernelGGL(gain_tiles_kernel, dim3((n_pad / PB) * pa.mb), dim3(256), 0, f->stream, pa);
         return;
     }
     const float* Lf = Laug;
     const float* Y = Laug + m_pad;
     const float* LinvT = Laug + m_pad + n_pad;
-    launch_gemm(f, 1, n, m_pad, m_pad, 1.f, Y, ld, LinvT, ld, 0.f, nullptr, 0, K, ldk, refine ? 0 : 1, 1, refine ? nullptr : epi);
+    launch_gemm(f, 1, n, m_pad, m_pad, 1.f, Y, ld, LinvT, ld, 0.f, nullptr, 0, K, ldk, refine ? 0 : 1, 1);
     if (refine) {
         launch_gemm(f, 0, n, m_pad, m_pad, -1.f, K, ldk, Lf, ld, 1.f, Y, ld, scratch, ldk, 0, 1);     // Y - K L
         launch_gemm(f, 1, n, m_pad, m_pad, 1.f, scratch, ldk, LinvT, ld, 1.f, K, ldk, K, ldk, 1, 1);  // + prune

@@ -106,8 +106,8 @@ struct ekfvio_filter {
     int sweep_mode = 2;        // 2: ONE persistent launch with per-tile hand-offs behind the first diagonal tile (chol_persist.inc), where it pays and
                                // applies (3 .. 15 block columns, grid co-resident; two block columns: 43.5 against 43.0 us per step); 0 (EKFVIO_SWEEP=0): one launch per block step
     size_t sweep_sync_words = 0;
-    float lin_next_dt = -1.f;     // >= 0 (set by capture_steps around launch_update): the next process(dt)'s dt -- the update's last GEMM may linearise for it
-    bool prelinearized = false;   // ... and did: FA / FB / FD / mu_next hold the next step's Jacobian blocks and propagated mean (launch_predict then skips its own)
+    bool prelinearized = false;   // the update's last GEMM linearised for the next process(dt) (UpdateInputs::next_dt): FA / FB / FD / mu_next hold its Jacobian
+                                  // blocks and propagated mean (launch_predict then skips its own)
     int lin_overlap = 1;          // EKFVIO_LIN_OVERLAP=0 turns that off (A/B)
     int sym_joseph = 1;           // EKFVIO_SYM_JOSEPH=0: the second Joseph GEMM of the throughput regime forms both triangles (rounds 1-5)
     int gemm_order2d = 1;         // EKFVIO_GEMM_ORDER2D=0: the 64 x 64 GEMM's tiles in block-index order (rounds 1-4)
@@ -115,14 +115,9 @@ struct ekfvio_filter {
     long long schur_sweeps = 0;       // sweeps enqueued with Sigma and the gain as Schur tiles (EKFVIO_SCHUR=1): ekfvio_test_sweep_counts
     long long sweep_recoveries = 0;   // updates run again with the per-step sweep behind an aborted persistent launch
     int early_outputs = 1;            // EKFVIO_EARLY_OUTPUTS: a frame's outputs and status go out between the update's two Joseph GEMMs (klt.hip)
-    void (*between_joseph)(ekfvio_filter*) = nullptr;  // ekfvio_step_image: called by launch_update between the update's two Joseph GEMMs (the frame's outputs)
-    int hook_kyp_blocks = 0;          // > 0 while between_joseph is called from the T2 flow: K y is Wt's first rows (one per block column), not column n of P
-    int between_joseph_seq = 0;       // ... and the status sequence number its launch publishes (0: not called)
     long long early_output_frames = 0;  // frames whose outputs went out that way (test hook)
-    int publish_after_sweep_seq = 0;  // ekfvio_update: launch_update publishes the status word with this sequence number right behind the sweep (0: not asked)
     int sweep_spin_limit = 0;         // > 0: looks per wait of the persistent sweep (test hook ekfvio_test_sweep_fault); 0: SWEEP_SPIN_LIMIT
     int sweep_stall_wg = -1;          // fault injection: this workgroup of the persistent launch never raises its flag
-    const int* sweep_abort_word = nullptr;  // abort word of the persistent sweep enqueued last by launch_chol_sweep (null: another sweep)
     int early_status = 1;              // EKFVIO_EARLY_STATUS: ekfvio_update returns behind the sweep, the Joseph GEMMs still running (api.hip)
     int upload_kernel = 1;             // EKFVIO_UPLOAD_KERNEL: the frame's trip to device memory is a kernel reading mapped host memory (klt.hip)
     bool sweep_retry_armed = false;    // an aborted persistent sweep latched sweep_mode to 0: tried again at sweep_retry_at (api.hip, sweep_maybe_retry)
@@ -132,24 +127,21 @@ struct ekfvio_filter {
                                        // is run again at once (ekfvio_update, ekfvio_step_image); a device-resident run (ekfvio_run_uploaded), which
                                        // cannot, waits SWEEP_WAIT_TICKS_UNRECOVERABLE (100 ms): the counter also runs while a healthy sweep's
                                        // wavefronts are descheduled (time slicing, a profiler's serialisation), ADVICE r05
-    bool sweep_unrecoverable = false;  // set by ekfvio_run_uploaded around its launches / captures
     std::chrono::steady_clock::time_point sweep_retry_at;
     bool graph_leaves_flags_clean = false;  // sweep_flags_clean as a replay of the captured step graphs leaves it (api.hip, capture_steps)
     bool sweep_flags_clean = false;   // the persistent sweep's flags are zero for the launch enqueued next (zeroed by the last GEMM of the
-                                      // previous update, or by gather_potrf_kernel in front); otherwise the launcher enqueues a memset
+                                      // previous update); otherwise gather_potrf_kernel zeroes them in front, or launch_update has a memset enqueued
     int fuse_sweep = 1;               // 1: gather + first diagonal tile + sweep in ONE launch where the persistent sweep applies (EKFVIO_FUSE_SWEEP)
     bool persist_attr_set = false;
     bool gain2_attr_set = false;
     int persist_oversub = 0;          // > 0 (EKFVIO_PERSIST_OVERSUB): owner workgroups allowed per compute unit's worth of the persistent launch (chol.hip, persist_shape)
     int persist_gain = 1;             // 1 (EKFVIO_PERSIST_GAIN=0 turns it off): the gain's tiles are formed inside the fused persistent launch (chol_persist.inc)
-    bool gain_in_sweep = false;       // the launch enqueued last did (launch_update then skips the gain kernel)
     int persist_early = 1;            // 1 (EKFVIO_PERSIST_EARLY=0 turns it off): owners fetch their panel sources in front of the wait for ready[k] (chol_persist.inc)
     int fuse_gather = 1;       // 1: the gather and the first diagonal tile's factorisation share a launch (EKFVIO_FUSE_GATHER)
     bool gather_attr_set = false;
     int t2_flow = 1;           // 1 (EKFVIO_T2=0 turns it off): where the fused persistent launch forms the gain, freed owners also form T2 = Sigma (I - K H)^T
                                // (chol_persist.inc, t2_tile): Sigma' = T2 + K G'^T is the ONE P-update GEMM behind the launch (round 6)
     long long t2_updates = 0;  // updates enqueued (or captured) with the T2 flow: ONE P-update GEMM behind the sweep (ekfvio_get_counters [5])
-    bool t2_in_sweep = false;  // the sweep enqueued last formed T2 itself (launch_update then skips gain2_t2_tiles_kernel)
     int schur = 0;             // 1 (EKFVIO_SCHUR=1): T2 and K as Schur tiles of the sweep; 0: gain GEMM + first Joseph GEMM behind it.
                                // Measured equal in step time at N = 256, so the simpler flow is the default.
     int fuse_linearize = 1;    // 1: structured process(dt) is one launch, the Jacobian blocks are formed inside it (EKFVIO_FUSE_LINEARIZE)
@@ -283,6 +275,7 @@ void launch_gemm(ekfvio_filter* f, int transB, int M, int N, int K, float alpha,
 bool gemm_throughput_regime(const ekfvio_filter* f, int M, int N, int K);
 // would launch_gemm run A * B^T of this shape as ONE wave of gemm16_kernel workgroups with `extra` more workgroups still inside that wave?
 bool gemm_single_round_with(const ekfvio_filter* f, int M, int N, int K, int extra);
+#define LIN_LM 8  // landmarks per linearising workgroup (32 lanes each; motion_model.inc)
 
 // same, selecting a tile configuration (0 = production default chosen by shape)
 void launch_gemm_variant(ekfvio_filter* f, int variant, int transB, int M, int N, int K, float alpha, const float* A, int lda,
@@ -312,8 +305,26 @@ void launch_build_dense_F(ekfvio_filter* f, float* Fdense);
 void launch_predict(ekfvio_filter* f, float dt, const BookArgs* book = nullptr);
 // m_on_device: the host does not know how many landmarks passed (no D2H of the flags): launches are sized for m = 2N,
 // the kernels read the true row count from f->info[2] (written by the bookkeeping) and treat the rest as padding
-void launch_update(ekfvio_filter* f, int m, const float* d_z, const float* d_R, const uint8_t* d_pass,
-                   int* d_frame_counter = nullptr, int frames = 0, bool bookkeeping_done = false, bool m_on_device = false);
+struct UpdateInputs {
+    int m = 0;  // measurement rows 2 * (#passed) as the host knows them (ignored with m_on_device)
+    const float *z = nullptr, *R = nullptr;  // device-resident measurement: z, R, pass flags
+    const uint8_t* pass = nullptr;
+    int* frame_counter = nullptr;  // device-side frame index of an uploaded sequence (null: z / R / pass are one frame), of `frames` frames
+    int frames = 0;
+    bool bookkeeping_done = false;  // the measurement bookkeeping ran already (in the process(dt) launch, or in the update this one runs again)
+    bool m_on_device = false;
+    float next_dt = -1.f;  // >= 0 (capture_steps): the next process(dt)'s dt -- the update's last GEMM may linearise for it; mu is then stale until that process(dt)
+    int publish_seq = 0;       // ekfvio_update: the status word goes out with this sequence number right behind the sweep (0: not asked)
+    // ekfvio_step_image: called between the update's two Joseph GEMMs, or in front of the T2 flow's one (the frame's outputs); kyp_blocks > 0: K y is
+    // Wt's first rows (one per block column), not column n of P.  Returns the status sequence number its launch publishes
+    int (*between)(ekfvio_filter*, int kyp_blocks) = nullptr;
+    bool recoverable = true;   // false (ekfvio_run_uploaded): nothing can run an aborted update again -- the persistent sweep waits the long bound
+};
+struct UpdateResult {
+    bool published = false;  // the status went out behind the sweep (publish_seq; false: no sweep ran)
+    int between_seq = 0;     // what `between` returned (0: not reached -- no measurement, or the Schur flow)
+};
+UpdateResult launch_update(ekfvio_filter* f, const UpdateInputs& in);
 void launch_check_sigma(ekfvio_filter* f, float* d_out);
 // klt.hip helpers shared with fast.hip
 int klt_level_pitch(int w);
@@ -341,33 +352,56 @@ int poll_status(ekfvio_filter* f, int seq, int* status, int* extra_out);
 int add_features_device(ekfvio_filter* f, int k);
 void add_features_enqueue_device_count(ekfvio_filter* f, const int* count_dev);  // enqueue only; the caller updates N / n
 int replenish_enqueue(ekfvio_filter* f, int* enqueued);  // fast.hip: FAST + first-fit selection, count left in f->fast_counts[1]
-// The two P-update GEMM launches of an update with m measurement rows, `reps` times, into scratch (P2, Gm): the
+
+// The flow of ONE update, decided in one place (chol.hip, plan_update) and handed to the launchers as a value: they execute, they do not decide.
+enum SweepKind { SWEEP_NONE,           // no measurement
+                 SWEEP_SCHUR,          // one launch per block step, T2 (in place in f->P) and K (f->Km) as Schur tiles of the sweep (EKFVIO_SCHUR=1)
+                 SWEEP_PERSIST_FUSED,  // gather + first diagonal tile + persistent sweep in ONE launch (launch_persist_fused)
+                 SWEEP_PERSIST,        // the persistent launch behind a front of its own
+                 SWEEP_STEP,           // one launch per block step
+                 SWEEP_SPLIT, SWEEP_SPLIT_LA };  // m_pad >= 64 * EKF_SWEEP_SPLIT_MB: panel blocks solved once; _LA: as look-ahead tile tasks (chol_step_la.inc)
+enum GainBy { GAIN_SWEEP, GAIN_TILES, GAIN2_T2_TILES, GAIN_GEMM, GAIN_SCHUR };  // the sweep itself / gain_tiles_kernel / gain2_t2_tiles_kernel / launch_gemm / Schur tiles + joseph_g_kernel
+enum UpdateTail { TAIL_NONE, TAIL_SCHUR, TAIL_T2, TAIL_JOSEPH };  // ONE GEMM from the Schur tiles' T2 in f->P / ONE GEMM from t2_buffer / the two Joseph GEMMs
+struct UpdatePlan {
+    int m = 0, m_pad = 64, n_pad = 0;  // m: 2N with m_on_device (sizes the launches; the kernels read the true count from f->info[2])
+    bool m_on_device = false, recoverable = true;  // (UpdateInputs)
+    SweepKind sweep = SWEEP_NONE;
+    bool fused_gather = false;  // the gather and the first diagonal tile's factorisation share a launch (gather_potrf_kernel)
+    bool with_wt = false;       // the gather also transposes (H Sigma)^T into Wt (only the first Joseph GEMM reads it)
+    GainBy gain = GAIN_GEMM;
+    UpdateTail tail = TAIL_NONE;
+    int t2_skip = -1;           // PersistArgs::t2_skip (>= 0: the shape takes the T2 flow)
+    bool t2_by_sweep = false, compact = false;  // PersistArgs::t2, ::compact
+    int lin_blocks = 0;         // > 0: the last GEMM linearises for the next process(dt) in that many extra workgroups (GemmEpi::lin_blocks)
+    // chol_persist_kernel runs: its abort word goes into the GEMM epilogues, the last GEMM zeroes its flags for the next update, and in
+    // front gather_potrf_kernel zeroes them (fused_gather) or a memset does unless they are clean (ekfvio_filter::sweep_flags_clean)
+    bool persistent() const { return sweep == SWEEP_PERSIST_FUSED || sweep == SWEEP_PERSIST; }
+};
+UpdatePlan plan_update(const ekfvio_filter* f, int m, bool m_on_device = false, float next_dt = -1.f, bool recoverable = true);
+// The P-update GEMM launches of an update with plan p, `reps` times, into scratch (P2, Gm): the
 // filter state is not touched.  For timing the kernel under its production shape (ekfvio_profile_update_gemms).
-int launch_update_gemms_scratch(ekfvio_filter* f, int m, int reps);  // returns the GEMM launches per repetition (1 with the Schur sweep, else 2)
+int launch_update_gemms_scratch(ekfvio_filter* f, const UpdatePlan& p, int reps);  // returns the GEMM launches per repetition (2 with the two-GEMM tail, else 1)
+// ... and of a sweep over matrices that are not the filter's (ekfvio_test_cholesky_solve): the same choice of sweep for [A; X; I] with m_pad
+// columns and n_pad rows of X, without the update's front, Schur tiles and tail; the gain by gain_tiles_kernel or the gain GEMM
+UpdatePlan plan_raw_sweep(const ekfvio_filter* f, int m_pad, int n_pad);
 // Augmented blocked Cholesky sweep (chol.hip): Saug = [A; X; I] (row blocks of 64; A is
 // m_pad x m_pad, X has n_pad rows) -> Laug = [L; X L^-T; L^-T], both ld x m_pad column-major.
-// schur: T = Sigma - X A^-1 X^T (in place in f->P) and K = X A^-1 (f->Km) come out of the sweep itself as Schur tiles
-// (chol.hip); not in the split sweep (m_pad >= 64 * EKF_SWEEP_SPLIT_MB) nor the persistent one
-void launch_chol_sweep(ekfvio_filter* f, float* Saug, float* Laug, float* Linv, int m_pad, int n_pad, int ld,
-                       bool first_tile_done = false, bool schur = false);
-bool sweep_supports_schur(const ekfvio_filter* f, int m_pad);
-bool sweep_is_persistent(const ekfvio_filter* f, int m_pad, int n_pad);
+// zero_flags: a memset of the persistent sweep's flags goes in front.  Returns the abort word of the persistent launch (null: another sweep)
+const int* launch_chol_sweep(ekfvio_filter* f, const UpdatePlan& p, float* Saug, float* Laug, float* Linv, int ld, bool zero_flags);
+const int* launch_persist_fused(ekfvio_filter* f, const UpdatePlan& p, bool zero_flags);
 int persist_zero_words(int m_pad, int n_pad);
-void launch_persist_fused(ekfvio_filter* f, int m, int m_pad, int n_pad, bool m_on_device);
 int live_handles_on(int device);  // api.hip: handles alive on that device in this process
 // K pruned, G = K R - T[:, idx], K y partial sums (one row of f->Wt per 64 measurement columns)
 void launch_joseph_g(ekfvio_filter* f, int m, int m_pad, int n_pad, bool m_on_device, const float* T = nullptr);  // T: the covariance G' is taken from (null: f->P)
-bool t2_flow_shape(const ekfvio_filter* f, int m_pad, int n_pad);  // chol.hip: T2 = Sigma (I - K H)^T comes out of the sweep (or gain2_t2_tiles_kernel), ONE Joseph GEMM behind it
 // Where T2 lives between the sweep and the one GEMM behind it: the dense-F buffer, dead during an update in either predict mode (the dense
 // mode rebuilds F at the next process(dt)).  Not f->P2: that is process(dt)'s next output, and with T2 written there by other XCDs moments
 // earlier process(dt) measured 0.6 us longer (same-box rocprofv3: 9.51 against 8.90 us).
 inline float* t2_buffer(ekfvio_filter* f) { return f->Fdense; }
-void launch_gain2_tiles(ekfvio_filter* f, int m, int m_pad, int n_pad, bool m_on_device);
-void launch_gather_potrf(ekfvio_filter* f, int m, int m_pad, int n_pad, bool m_on_device = false, bool with_wt = true);
+void launch_gain2_tiles(ekfvio_filter* f, const UpdatePlan& p);
+void launch_gather_potrf(ekfvio_filter* f, const UpdatePlan& p);
 void launch_potrf_stamps(ekfvio_filter* f, const float* S, int ld, float* L, float* Linv, long long* d_stamps);
-// K = X A^-1 (n rows, ldk) from the sweep output: K = Y L^-1 (+ optional residual refinement).
-void launch_gain_from_sweep(ekfvio_filter* f, const float* Laug, int m_pad, int n_pad, int ld, int n, float* K,
-                            float* scratch, int ldk, int refine, const GemmEpi* epi = nullptr);
+// K = X A^-1 (n rows, ldk) from the sweep output, as the plan says: gain_tiles_kernel, or the GEMM K = Y L^-1 (+ optional residual refinement).
+void launch_gain_from_sweep(ekfvio_filter* f, const UpdatePlan& p, const float* Laug, int ld, int n, float* K, float* scratch, int ldk, int refine);
 
 // remove.hip: Sigma, mu, last_klt, del_flag compacted in ONE launch over N + *added landmarks (added may be null); decision from
 // `remove` (device memory), null: del_flag; abort_aware: nothing removed behind an aborted persistent sweep; host_removed (may be

@@ -743,153 +743,97 @@ void launch_predict(ekfvio_filter* f, float dt, const BookArgs* book) {
 }
 
 // updateWithFeaturePositions (:475-628) on device-resident z/R/pass; m = 2*(#passed) known to the host
-void launch_update(ekfvio_filter* f, int m, const float* d_z, const float* d_R, const uint8_t* d_pass, int* d_frame_counter,
-                   int frames, bool bookkeeping_done, bool m_on_device) {
-    if (m_on_device) m = 2 * f->N;  // upper bound: sizes the launches; the kernels read the true count from f->info[2]
-    const int n = f->n, ld = f->ldp;
-    const int m_pad = round_up(m > 0 ? m : 1, EKF_TILE);
-    const int n_pad = round_up(n, EKF_TILE);
-    const int lda = f->ld_aug;
+UpdateResult launch_update(ekfvio_filter* f, const UpdateInputs& in) {
+    const UpdatePlan p = plan_update(f, in.m, in.m_on_device, in.next_dt, in.recoverable);
+    const int m = p.m, m_pad = p.m_pad, n_pad = p.n_pad, n = f->n, ld = f->ldp;
+    UpdateResult out;
     f->last_m = m;
-    // The gather and the first diagonal tile's factorisation share a launch while that launch is a single round of
-    // workgroups at one per compute unit (chol.hip: gather_potrf_kernel); beyond that (N = 1024: thousands of gather
-    // workgroups) the gather wants several workgroups per compute unit and the two stay separate.
-    // T = Sigma - X A^-1 X^T and K = X A^-1 as Schur tiles of the sweep (no gain GEMM, no first Joseph GEMM, no (H Sigma)^T)
-    const bool schur = m > 0 && sweep_supports_schur(f, m_pad);
-    // round 4: where the persistent sweep applies, the gather and the first tile are part of ITS launch (chol.hip, launch_persist_fused)
-    const bool fused_front = m > 0 && !schur && f->fuse_sweep && f->fuse_gather && sweep_is_persistent(f, m_pad, n_pad);
-    bool fused_gather = false;
-    if (m > 0 && f->fuse_gather && !fused_front) {
-        const int gx = (std::max(ld, m_pad) + 255) / 256;
-        fused_gather = 1 + gx * ((m_pad + GC * GCI - 1) / (GC * GCI)) + (schur ? 0 : (m_pad / 64) * (ld / 64)) <= f->num_cus;
-    }
     {
         ProfScope ps(f, PC_GATHER);
-        if (!bookkeeping_done) {
-            BookArgs bk = make_book_args(f, m, d_z, d_R, d_pass, d_frame_counter);
-            if (m_on_device) bk.m_out = f->info + 2;
+        if (!in.bookkeeping_done) {
+            BookArgs bk = make_book_args(f, m, in.z, in.R, in.pass, in.frame_counter);
+            if (p.m_on_device) bk.m_out = f->info + 2;
             hipLaunchKernelGGL(update_bookkeeping_kernel, dim3(1), dim3(1024), 0, f->stream, bk);
         }
-        if (m > 0 && !fused_front) {
-            if (fused_gather) {
-                // the gather and the factorisation of the first diagonal tile share one launch (chol.hip)
-                launch_gather_potrf(f, m, m_pad, n_pad, m_on_device, !schur);
-            } else {
-                GatherArgs ga = make_gather_args(f, m, m_pad, n_pad);
-                if (m_on_device) ga.m_dev = f->info + 2;
-                const int nb2 = schur ? 0 : (m_pad / 64) * (ld / 64);  // 64x64 transposing tiles of Wt
-                hipLaunchKernelGGL(gather_kernel, dim3(ga.nb1 + nb2), dim3(256), 0, f->stream, ga);
-            }
+        if (p.fused_gather) {
+            // the gather and the factorisation of the first diagonal tile share one launch (chol.hip)
+            launch_gather_potrf(f, p);
+        } else if (m > 0 && p.sweep != SWEEP_PERSIST_FUSED) {
+            const GatherArgs ga = make_gather_args(f, p);
+            const int nb2 = p.with_wt ? (m_pad / 64) * (ld / 64) : 0;  // 64x64 transposing tiles of Wt
+            hipLaunchKernelGGL(gather_kernel, dim3(ga.nb1 + nb2), dim3(256), 0, f->stream, ga);
         }
     }
-    GemmEpi e2;
-    e2.mode = 2;
-    e2.mu = f->mu;
-    e2.Pcol = f->P + (size_t)n * ld;
-    e2.n = n;
-    e2.frame_counter = d_frame_counter;
-    e2.frames = frames;
-    e2.sym = f->sym_joseph;  // (heeded by the throughput-regime kernel behind the two-GEMM flow: gemm.hip)
-    if (schur) {
-        // [A; Sigma H^T; I] swept with Sigma and the gain as Schur tiles (chol.hip): K = X A^-1 (:577-580) and, in place,
-        // T2 = Sigma - X A^-1 X^T = Sigma (I - K H)^T, the RIGHT Joseph factor applied (X = Sigma H^T; Sigma is symmetric only
-        // to rounding, so this is not the transpose of the reference's (I - K H) Sigma).  Then K pruned,
-        // G' = K R^T - (H T2)^T and K y; then the left factor: Sigma' = (I - K H) T2 + K R K^T = T2 + K G'^T, which is the
-        // reference's (I - K H) Sigma (I - K H)^T + K R K^T (:594-596), pruned (:625).  Its first workgroup finishes the
-        // mean (:600-609).
-        launch_chol_sweep(f, f->Saug, f->Laug, f->Linv, m_pad, n_pad, lda, fused_gather, true);
-        if (f->publish_after_sweep_seq) launch_publish_status(f, f->publish_after_sweep_seq), f->publish_after_sweep_seq = 0;
-        launch_joseph_g(f, m, m_pad, n_pad, m_on_device);
-        ProfScope ps(f, PC_GEMM_UPDATE, 2.0 * n * (double)n * m_pad, 1);
-        e2.abort = nullptr;
-        e2.mode = 3;  // the mean takes K y from joseph_g_kernel's partial sums
-        e2.Kyp = f->Wt;
-        e2.kyp_blocks = m_pad / 64;
-        e2.kyp_ld = ld;
-        launch_gemm(f, 1, n, n, m_pad, 1.f, f->Km, ld, f->Gm, ld, 1.f, f->P, ld, f->P, ld, 1, 0, &e2);
-    } else if (m > 0) {
-        // [A; Sigma H^T; I] -> [L; Y; L^-T], then K = (Sigma H^T) A^-1  (:577-580)
-        if (fused_front) launch_persist_fused(f, m, m_pad, n_pad, m_on_device);
-        else launch_chol_sweep(f, f->Saug, f->Laug, f->Linv, m_pad, n_pad, lda, fused_gather);
-        // (ekfvio_update: the update's status is final here -- the host gets it now and returns while the GEMMs below run)
-        if (f->publish_after_sweep_seq) launch_publish_status(f, f->publish_after_sweep_seq), f->publish_after_sweep_seq = 0;
-        if (f->sweep_abort_word) {  // a persistent sweep ran: the update's last GEMM leaves its flags zero for the next one
-            e2.zero_words = f->sweep_sync;
-            e2.n_zero = persist_zero_words(m_pad, n_pad);
-            f->sweep_flags_clean = true;
-        }
-        GemmEpi e1;
-        e1.mode = 1;
-        e1.inv_idx = f->inv_idx;
-        e1.Rm = f->Rm;
-        e1.G = f->Gm;
-        e1.ldg = ld;
-        e1.abort = e2.abort = f->sweep_abort_word;  // a persistent sweep that gave up: both GEMMs write nothing
-        if (t2_flow_shape(f, m_pad, n_pad)) {
-            // Round 6: T2 = Sigma - Y S Y^T = Sigma (I - K H)^T came out of the persistent launch itself (freed owners, chol_persist.inc t2_tile; behind
-            // any other sweep of such a shape gain2_t2_tiles_kernel forms the same T2 from the stored panel blocks), in the dense-F buffer; the gain
-            // tiles of the same launch left K, G' = K R^T - (H T2)^T and the partial sums of K y.  The left Joseph factor is the ONE P-update GEMM:
-            // Sigma' = (I - K H) T2 + K R K^T = T2 + K G'^T (:594-596), pruned (:625), into f->P; its extra workgroup finishes the mean (:600-609).
-            f->t2_updates++;
-            if (!f->t2_in_sweep) launch_gain2_tiles(f, m, m_pad, n_pad, m_on_device);  // (K, G', K y and T2 in one launch behind the per-step sweep)
-            if (f->between_joseph) {  // (ekfvio_step_image: the frame's outputs, from mu and the partial sums of K y, in front of the one GEMM)
-                f->hook_kyp_blocks = m_pad / 64;
-                f->between_joseph(f);
-                f->hook_kyp_blocks = 0;
-            }
-            ProfScope ps(f, PC_GEMM_UPDATE, 2.0 * n * (double)n * m_pad, 1);
-            e2.mode = 3;  // the mean takes K y from the gain tiles' partial sums (gain_tile2: Kyp = Wt, one row of sums per block column)
-            e2.Kyp = f->Wt;
-            e2.kyp_blocks = m_pad / 64;
-            e2.kyp_ld = ld;
-            e2.abort = f->sweep_abort_word;  // a persistent sweep that gave up: the GEMM writes nothing (T2, K, G' are scratch)
-            const int lin_blocks = (f->N + LIN_LM - 1) / LIN_LM + 1;
-            if (f->lin_next_dt >= 0.f && f->lin_overlap && f->cfg.predict_mode != EKFVIO_PREDICT_DENSE && f->fuse_linearize &&
-                gemm_single_round_with(f, n, n, m_pad, 1 + lin_blocks)) {
-                // a device-resident run (capture_steps): the next process(dt)'s linearisation and mean propagation ride in this launch, in workgroups
-                // of their own behind the tiles' (K y is final: the gain tiles' partial sums); launch_predict then only propagates Sigma
-                e2.lin_blocks = lin_blocks;
-                e2.lin_N = f->N;
-                e2.lin_dt = f->lin_next_dt;
-                e2.lin_FA = f->FA, e2.lin_FB = f->FB, e2.lin_FD = f->FD;
-                e2.lin_mu_next = f->mu_next;
-                f->prelinearized = true;
-            }
-            launch_gemm(f, 1, n, n, m_pad, 1.f, f->Km, ld, f->Gm, ld, 1.f, t2_buffer(f), ld, f->P, ld, 1, 0, &e2);
-        } else {
-            if (!f->gain_in_sweep) launch_gain_from_sweep(f, f->Laug, m_pad, n_pad, lda, n, f->Km, f->Gm, ld, 0);
-            // The two P-update GEMMs, back to back (one profiler scope, two launches), both triangles:
-            //   T = Sigma - K*(H Sigma)   (I_KH * Sigma, :594) in place; also G and K*y (column n)
-            //   Sigma' = T + G*K^T, pruned (:594-596, :625); workgroup (0,0) finishes the mean
-            ProfScope ps(f, PC_GEMM_UPDATE, 2.0 * n * (double)(n + 1) * m_pad + 2.0 * n * (double)n * m_pad, 2);
-            launch_gemm(f, 1, n, n + 1, m_pad, -1.f, f->Km, ld, f->Wt, ld, 1.f, f->P, ld, f->P, ld, 0, 0, &e1);
-            if (f->between_joseph) f->between_joseph(f);  // (ekfvio_step_image: the frame's outputs, from mu and K y in column n of P)
-            launch_gemm(f, 1, n, n, m_pad, 1.f, f->Gm, ld, f->Km, ld, 1.f, f->P, ld, f->P, ld, 1, 0, &e2);
-        }
-    } else {
+    if (m <= 0) {
         // no measurement: products are empty, only the quaternion renormalisation remains (:605-609)
         ProfScope ps(f, PC_UPDATE_MISC);
         hipLaunchKernelGGL(mean_update_kernel, dim3((n + 63) / 64), dim3(256), 0, f->stream, f->Km, ld, n, 0, f->yres, f->mu,
-                           d_frame_counter, frames);
+                           in.frame_counter, in.frames);
+        return out;
     }
+    // [A; Sigma H^T; I] -> [L; Y; L^-T]; a persistent sweep finds its flags zero behind an update of this handle or behind gather_potrf_kernel
+    const bool zero_flags = p.persistent() && !p.fused_gather && !f->sweep_flags_clean;
+    const int* abort = p.sweep == SWEEP_PERSIST_FUSED ? launch_persist_fused(f, p, zero_flags)
+                                                      : launch_chol_sweep(f, p, f->Saug, f->Laug, f->Linv, f->ld_aug, zero_flags);
+    // (ekfvio_update: the update's status is final here -- the host gets it now and returns while the GEMMs below run)
+    if (in.publish_seq) launch_publish_status(f, in.publish_seq), out.published = true;
+    GemmEpi e2;  // of the update's last GEMM
+    e2.mode = 2, e2.mu = f->mu, e2.Pcol = f->P + (size_t)n * ld, e2.n = n;
+    e2.frame_counter = in.frame_counter, e2.frames = in.frames;
+    e2.sym = f->sym_joseph;  // (heeded by the throughput-regime kernel behind the two-GEMM flow: gemm.hip)
+    e2.abort = abort;        // a persistent sweep that gave up: the GEMMs write nothing (T2, K, G' are scratch)
+    if (p.persistent()) {    // ... and one that ran: the update's last GEMM leaves its flags zero for the next one
+        e2.zero_words = f->sweep_sync, e2.n_zero = persist_zero_words(m_pad, n_pad);
+        f->sweep_flags_clean = true;
+    }
+    if (p.tail == TAIL_T2) f->t2_updates++;
+    // K = (Sigma H^T) A^-1  (:577-580), unless the sweep formed it
+    if (p.gain == GAIN_SCHUR) launch_joseph_g(f, m, m_pad, n_pad, p.m_on_device);
+    else if (p.gain == GAIN2_T2_TILES) launch_gain2_tiles(f, p);  // (K, G', K y and T2 in one launch behind the per-step sweep)
+    else if (p.gain != GAIN_SWEEP) launch_gain_from_sweep(f, p, f->Laug, f->ld_aug, n, f->Km, f->Gm, ld, 0);
+    if (p.tail == TAIL_JOSEPH) {
+        GemmEpi e1;
+        e1.mode = 1, e1.inv_idx = f->inv_idx, e1.Rm = f->Rm, e1.G = f->Gm, e1.ldg = ld, e1.abort = abort;
+        // The two P-update GEMMs, back to back (one profiler scope, two launches), both triangles:
+        //   T = Sigma - K*(H Sigma)   (I_KH * Sigma, :594) in place; also G and K*y (column n)
+        //   Sigma' = T + G*K^T, pruned (:594-596, :625); workgroup (0,0) finishes the mean
+        ProfScope ps(f, PC_GEMM_UPDATE, 2.0 * n * (double)(n + 1) * m_pad + 2.0 * n * (double)n * m_pad, 2);
+        launch_gemm(f, 1, n, n + 1, m_pad, -1.f, f->Km, ld, f->Wt, ld, 1.f, f->P, ld, f->P, ld, 0, 0, &e1);
+        if (in.between) out.between_seq = in.between(f, 0);  // (ekfvio_step_image: the frame's outputs, from mu and K y in column n of P)
+        launch_gemm(f, 1, n, n, m_pad, 1.f, f->Gm, ld, f->Km, ld, 1.f, f->P, ld, f->P, ld, 1, 0, &e2);
+        return out;
+    }
+    // ONE P-update GEMM, the left Joseph factor applied to T2 = Sigma - X A^-1 X^T = Sigma (I - K H)^T, the RIGHT one (X = Sigma H^T; Sigma is symmetric
+    // only to rounding, so this is not the transpose of the reference's (I - K H) Sigma): Sigma' = (I - K H) T2 + K R K^T = T2 + K G'^T, which is the
+    // reference's (I - K H) Sigma (I - K H)^T + K R K^T (:594-596), pruned (:625), into f->P; its extra workgroup finishes the mean (:600-609).
+    // TAIL_SCHUR: [A; Sigma H^T; I] was swept with Sigma and the gain as Schur tiles (chol.hip), T2 in place in f->P; joseph_g_kernel pruned K and left
+    // G' = K R^T - (H T2)^T and K y.  TAIL_T2 (round 6): T2 came out of the persistent launch itself (freed owners, chol_persist.inc t2_tile; behind any
+    // other sweep of such a shape gain2_t2_tiles_kernel forms the same T2 from the stored panel blocks), in the dense-F buffer; the gain tiles of the
+    // same launch left K, G' and the partial sums of K y.
+    if (p.tail == TAIL_T2 && in.between) out.between_seq = in.between(f, m_pad / 64);  // (ekfvio_step_image: the frame's outputs, from mu and the partial sums of K y)
+    ProfScope ps(f, PC_GEMM_UPDATE, 2.0 * n * (double)n * m_pad, 1);
+    e2.mode = 3;  // the mean takes K y from the partial sums (joseph_g_kernel / gain_tile2: Kyp = Wt, one row of sums per block column)
+    e2.Kyp = f->Wt, e2.kyp_blocks = m_pad / 64, e2.kyp_ld = ld;
+    if (p.lin_blocks) {  // (plan_update: the next process(dt)'s linearisation rides in this launch)
+        e2.lin_blocks = p.lin_blocks, e2.lin_N = f->N, e2.lin_dt = in.next_dt;
+        e2.lin_FA = f->FA, e2.lin_FB = f->FB, e2.lin_FD = f->FD, e2.lin_mu_next = f->mu_next;
+        f->prelinearized = true;
+    }
+    launch_gemm(f, 1, n, n, m_pad, 1.f, f->Km, ld, f->Gm, ld, 1.f, p.tail == TAIL_T2 ? t2_buffer(f) : f->P, ld, f->P, ld, 1, 0, &e2);
+    return out;
 }
 
-int launch_update_gemms_scratch(ekfvio_filter* f, int m, int reps) {
-    const int n = f->n, ld = f->ldp;
-    const int m_pad = round_up(m > 0 ? m : 1, EKF_TILE);
+int launch_update_gemms_scratch(ekfvio_filter* f, const UpdatePlan& p, int reps) {
+    const int n = f->n, ld = f->ldp, m_pad = p.m_pad;
     GemmEpi e1, e2;
-    if (sweep_supports_schur(f, m_pad) || t2_flow_shape(f, m_pad, round_up(n, EKF_TILE))) {
+    if (p.tail != TAIL_JOSEPH) {
         // with the Schur sweep, and where T2 comes out of the persistent launch, the update has ONE P-update GEMM: Sigma' = T2 + K G'^T
         e2.mode = 2;
         for (int r = 0; r < reps; r++)
             launch_gemm(f, 1, n, n, m_pad, 1.f, f->Km, ld, f->Gm, ld, 1.f, f->P, ld, f->P2, ld, 1, 0, &e2);
         return 1;
     }
-    e1.mode = 1;
-    e1.inv_idx = f->inv_idx;
-    e1.Rm = f->Rm;
-    e1.G = f->Gm;
-    e1.ldg = ld;
+    e1.mode = 1, e1.inv_idx = f->inv_idx, e1.Rm = f->Rm, e1.G = f->Gm, e1.ldg = ld;
     e2.mode = 2;  // n = 0: no mean update, no frame counter
     e2.sym = f->sym_joseph;
     for (int r = 0; r < reps; r++) {

@@ -139,17 +139,18 @@ __device__ __forceinline__ void gather_body(const GatherArgs& a, int block, floa
     }
 }
 
-static GatherArgs make_gather_args(ekfvio_filter* f, int m, int m_pad, int n_pad) {
+static GatherArgs make_gather_args(ekfvio_filter* f, const UpdatePlan& p) {
+    const int m_pad = p.m_pad;
     GatherArgs a;
     a.P = f->P;
     a.ld = f->ldp;
     a.n = f->n;
     a.idx = f->idx;
     a.Rm = f->Rm;
-    a.m = m;
-    a.m_dev = nullptr;
+    a.m = p.m;
+    a.m_dev = p.m_on_device ? f->info + 2 : nullptr;
     a.m_pad = m_pad;
-    a.n_pad = n_pad;
+    a.n_pad = p.n_pad;
     a.Saug = f->Saug;
     a.lda = f->ld_aug;
     a.Wt = f->Wt;

@@ -917,7 +917,7 @@ static void launch_gemm_cfg(ekfvio_filter* f, int cfg, int transB, int M, int N,
         const int wps = cfg >= 100 ? 1 : 2;  // 132 / 148 / 164: one wavefront per SIMD (micro-benchmark only)
         const int bm = cfg % 100;
         const int tx = (M + bm - 1) / bm;
-        if (!(e.mode == 3 && e.n > 0) || tiles(bm) + 1 + e.lin_blocks > cus) e.lin_blocks = 0;  // (launch_update asked gemm_single_round_with first)
+        if (!(e.mode == 3 && e.n > 0) || tiles(bm) + 1 + e.lin_blocks > cus) e.lin_blocks = 0;  // (plan_update asked gemm_single_round_with first)
         e.mean_keep = e.lin_blocks > 0 ? 1 : 0;
         dim3 grid(tiles(bm) + ((e.mode == 2 || e.mode == 3) && e.n > 0 ? 1 : 0) + e.lin_blocks);  // (+1: gemm16_finish_mean; + the next step's linearisation)
 #define GEMM16_GO(BMv, W, EP)                                                                                           \

@@ -1416,6 +1416,8 @@ int ekfvio_step_image(ekfvio_filter* f, double stamp, const uint8_t* image, int3
     }
     int status = EKFVIO_OK;
     int early_seq = 0;
+    UpdateInputs in;  // the frame's update (and its re-run behind an aborted persistent sweep)
+    in.z = f->zmeas, in.R = f->Rmeas, in.pass = f->pass, in.m_on_device = true;
     if (f->N > 0) {  // "run update if we have enough features" (EKFVIO.cpp:166)
         rc = klt_track_device(f);
         if (rc != EKFVIO_OK) return fail(rc);
@@ -1427,27 +1429,24 @@ int ekfvio_step_image(ekfvio_filter* f, double stamp, const uint8_t* image, int3
         // (Nor with cfg.remove_lost: the frame's final landmark count is known only behind the removal, as with a replenishing frame.)
         if (f->early_outputs && f->frame_outputs && !(f->cfg.replenish && f->N < f->cfg.max_features) && !f->cfg.remove_lost &&
             sizeof(float) * (size_t)f->n <= 48 * 1024) {  // (the updated mean is formed in LDS)
-            f->between_joseph = [](ekfvio_filter* g) {
+            in.between = [](ekfvio_filter* g, int kyp_blocks) {
                 const KltFrame& fr = g->frames[g->cur];
                 const int pitch = level_pitch(fr.w[0]);
                 float fx, fy, cx, cy;
                 intrinsics(g, fr.K, &fx, &fy, &cx, &cy);
-                g->between_joseph_seq = next_status_seq(g);
+                const int seq = next_status_seq(g);
                 // (two-GEMM flow: K y is column n of P, left there by the first Joseph GEMM; T2 flow: the gain tiles' partial sums in Wt, and the
                 // outputs go out in front of the update's ONE GEMM)
-                const bool kyp = g->hook_kyp_blocks > 0;
+                const bool kyp = kyp_blocks > 0;
                 hipLaunchKernelGGL(frame_outputs_kernel, dim3(1), dim3(256), sizeof(float) * (size_t)g->n, g->stream, g->mu, g->N, (const int*)nullptr,
                                    fr.img[0] + (size_t)KLT_BORDER * pitch + KLT_BORDER, pitch, fr.w[0], fr.h[0], fx, fy, cx, cy, g->d_out, g->info,
-                                   g->d_hinfo, g->between_joseph_seq, kyp ? (const float*)nullptr : (const float*)(g->P + (size_t)g->n * g->ldp),
-                                   kyp ? (const float*)g->Wt : (const float*)nullptr, g->hook_kyp_blocks, g->ldp);
+                                   g->d_hinfo, seq, kyp ? (const float*)nullptr : (const float*)(g->P + (size_t)g->n * g->ldp),
+                                   kyp ? (const float*)g->Wt : (const float*)nullptr, kyp_blocks, g->ldp);
+                return seq;
             };
-            f->between_joseph_seq = 0;
         }
-        launch_update(f, 0, f->zmeas, f->Rmeas, f->pass, nullptr, 0, false, true);
-        f->between_joseph = nullptr;
-        early_seq = f->between_joseph_seq;  // 0: the hook was not reached (no measurement, another flow of the update)
+        early_seq = launch_update(f, in).between_seq;  // 0: the hook was not reached (no measurement, another flow of the update)
         if (early_seq) f->early_output_frames++;
-        f->between_joseph_seq = 0;
     }
     if (hipGetLastError() != hipSuccess) {
         f->last_error = "launch failed in ekfvio_step_image";
@@ -1513,7 +1512,8 @@ int ekfvio_step_image(ekfvio_filter* f, double stamp, const uint8_t* image, int3
         sweep_abort_latch(f);
         f->sweep_recoveries++;
         f->out_fresh = false;
-        launch_update(f, 0, f->zmeas, f->Rmeas, f->pass, nullptr, 0, true, true);
+        in.between = nullptr, in.bookkeeping_done = true;
+        launch_update(f, in);
         HIPK(f, hipGetLastError());
         rc = wait_status(f, &bad);
         if (rc != EKFVIO_OK) return rc;

@@ -124,7 +124,6 @@ __device__ inline float plus_delta(float x) { return (float)((double)x + 1e-3); 
 __device__ inline float minus_2delta(float x) { return (float)((double)x - 2 * 1e-3); }
 __device__ inline float two_delta() { return (float)(2 * 1e-3); }
 
-#define LIN_LM 8  // landmarks per linearising workgroup (32 lanes each)
 struct LinLds {
     float s_base[EKF_BASE];
     BaseMotion s_bm[19];        // 0: unperturbed, 1+2c: col 7+c plus, 2+2c: minus
