@@ -44,7 +44,7 @@ SYMBOLS = ["ekfvio_default_config", "ekfvio_create", "ekfvio_destroy", "ekfvio_r
            "ekfvio_klt_uncertainty_points", "ekfvio_step_image", "ekfvio_replenish", "ekfvio_fast_detect", "ekfvio_imu", "ekfvio_imu_update",
            "ekfvio_upload_measurements", "ekfvio_run_uploaded", "ekfvio_synchronize", "ekfvio_profile_enable",
            "ekfvio_profile_reset", "ekfvio_profile_count", "ekfvio_profile_name", "ekfvio_profile_get",
-           "ekfvio_profile_update_gemms", "ekfvio_get_counters"]
+           "ekfvio_profile_update_gemms", "ekfvio_get_counters", "ekfvio_set_gate", "ekfvio_get_gate"]
 # every symbol include/ekfvio_test_hooks.h declares (libekfvio_hip_hooks.so only)
 HOOK_SYMBOLS = ["ekfvio_test_klt_padded_level", "ekfvio_test_blurred_level0", "ekfvio_test_gemm", "ekfvio_test_gemm_bench", "ekfvio_test_potrf_stamps",
                 "ekfvio_test_sweep_stamps", "ekfvio_test_sweep_fault", "ekfvio_test_cholesky_solve"]
@@ -93,6 +93,7 @@ def load(build_if_missing=True, hooks=False):
         "ekfvio_profile_get": [vp, i32, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_double)],
         "ekfvio_profile_update_gemms": [vp, i32, C.POINTER(C.c_double), C.POINTER(C.c_double)],
         "ekfvio_get_counters": [vp, C.POINTER(C.c_int64)],
+        "ekfvio_set_gate": [vp, f32], "ekfvio_get_gate": [vp, fp, u8p, ip, ip, C.POINTER(C.c_int64)],
     }
     if hooks:
         sig.update({

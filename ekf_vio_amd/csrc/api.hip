@@ -355,7 +355,7 @@ int ekfvio_destroy(ekfvio_filter* f) {
     if (f->stream) (void)hipStreamSynchronize(f->stream);
     void* ptrs[] = {f->mu, f->mu_next, f->last_klt, f->del_flag, f->P,  f->P2, f->FA, f->FB, f->FD,   f->Fdense,
                     f->idx, f->inv_idx, f->zmeas,  f->Rmeas,    f->pass,     f->yres, f->Rm, f->Saug,  f->Laug,  f->Linv, f->Lsign, f->Km, f->sweep_sync, f->sweep_dbg,
-                    f->Wt,  f->Gm,     f->info,     f->remove_words, f->seq_z,    f->seq_R, f->seq_pass};
+                    f->Wt,  f->Gm,     f->info,     f->remove_words, f->seq_z,    f->seq_R, f->seq_pass, f->gate_words};
     for (void* p : ptrs)
         if (p) hipFree(p);
     if (f->h_info) hipHostFree(f->h_info);
@@ -390,6 +390,7 @@ int ekfvio_reset(ekfvio_filter* f) {
     HIPC(f, hipMemcpyAsync(f->mu + 3, &one, sizeof(float), hipMemcpyHostToDevice, f->stream));
     hipLaunchKernelGGL(init_sigma_kernel, dim3(1), dim3(32), 0, f->stream, f->P, f->ldp);
     HIPC(f, hipMemsetAsync(f->info, 0, 4 * sizeof(int), f->stream));
+    if (f->gate_words) HIPC(f, hipMemsetAsync(f->gate_words, 0, 4 * sizeof(int), f->stream));  // the gate's counts start over; its threshold stays
     HIPC(f, hipStreamSynchronize(f->stream));
     f->have_stamp = false;
     f->frames[0].valid = f->frames[1].valid = false;
@@ -522,6 +523,7 @@ int ekfvio_update(ekfvio_filter* f, const float* z, const float* R, const uint8_
     if (!launch_update(f, in).published) launch_publish_status(f, seq);  // (not early, or no sweep ran: nothing was published yet)
     HIPC(f, hipGetLastError());
     in.publish_seq = 0;
+    in.gate_counted = true;  // (a re-run gates the same propagated state again: same verdicts, counted once)
     return finish_update_rerun(f, [](ekfvio_filter* g, void* c) {
         launch_update(g, *static_cast<const UpdateInputs*>(c));  // the staged measurement is still in d_meas; the bookkeeping is idempotent
     }, &in, seq);
@@ -775,15 +777,17 @@ static int capture_steps(ekfvio_filter* f, int steps, int m, float dt, int* coun
     const bool mirror = f->sweep_flags_clean;
     f->sweep_flags_clean = false;
     HIPC(f, hipStreamBeginCapture(f->stream, hipStreamCaptureModeThreadLocal));
+    const bool gate = f->gate_chi2 > 0.f;
     for (int k = 0; k < steps; k++) {
-        // the frame's measurement bookkeeping rides in the process(dt) launch
+        // the frame's measurement bookkeeping rides in the process(dt) launch -- unless the handle gates its measurements: the gate reads the
+        // PROPAGATED state, so gate + bookkeeping are a launch of their own between process(dt) and the update (launch_update)
         const BookArgs bk = make_book_args(f, m, f->seq_z, f->seq_R, f->seq_pass, counter);
-        launch_predict(f, dt, &bk);
+        launch_predict(f, dt, gate ? nullptr : &bk);
         // round 6: inside a graph the next step's dt is known -- every update but the graph's last lets its last GEMM linearise for the step
         // behind it (plan_update decides whether the shape allows it; the graph's last update leaves the next replay's first step to
         // linearise for itself, so a graph needs nothing from whatever ran before it)
         UpdateInputs in = uploaded_update(f, m, 0, counter);
-        in.bookkeeping_done = true;
+        in.bookkeeping_done = !gate;
         in.next_dt = (k + 1 < steps) ? dt : -1.f;
         launch_update(f, in);
     }
@@ -812,10 +816,13 @@ int ekfvio_run_uploaded(ekfvio_filter* f, int32_t first, int32_t count, float dt
     // hipGraph path: the same measurement-row count for every frame (one launch geometry),
     // profiling off.  The bookkeeping kernel reads the frame index from a device counter.
     // (count == 0 only prepares: the graphs are captured, nothing runs — callers that time a run call this first)
+    // (a gated handle's geometry is m = 2N, count on the device, for every frame in which any landmark passed: launch_update)
+    const bool gate = f->gate_chi2 > 0.f;
+    auto geometry = [&](int i) { return gate && f->seq_m[i] > 0 ? 2 * f->N : f->seq_m[i]; };
     bool uniform = f->use_graph && !f->prof_on && (count >= 2 || count == 0);
-    for (int i = 0; uniform && i < f->seq_frames; i++) uniform = f->seq_m[i] == f->seq_m[0];
+    for (int i = 0; uniform && i < f->seq_frames; i++) uniform = geometry(i) == geometry(0);
     if (uniform) {
-        const int m = f->seq_m[0];
+        const int m = geometry(0);
         int* counter = f->info + 1;
         // by value (a copy from a host scalar could be overtaken by the next call's write to that scalar)
         HIPC(f, hipMemsetD32Async((hipDeviceptr_t)counter, first % f->seq_frames, 1, f->stream));
@@ -941,6 +948,46 @@ int ekfvio_profile_get(ekfvio_filter* f, int32_t cls, double* total_ms, int64_t*
     if (total_ms) *total_ms = f->prof[cls].ms;
     if (launches) *launches = f->prof[cls].launches;
     if (flops) *flops = f->prof[cls].flops;
+    return EKFVIO_OK;
+}
+
+// ---- innovation gate --------------------------------------------------------------------
+int ekfvio_set_gate(ekfvio_filter* f, float chi2) {
+    if (!f || !(chi2 >= 0.f)) return EKFVIO_EINVAL;  // (negative, NaN)
+    if (chi2 > 0.f && !f->gate_words) {
+        // the gate's device memory, ONE allocation made when a handle first asks for the gate (a handle that never does launches and
+        // allocates nothing it did not before): [4] words, then d2, verdicts and effective flags per landmark
+        HIPC(f, hipSetDevice(f->device));
+        const size_t maxf = (size_t)(f->cfg.max_features > 0 ? f->cfg.max_features : 1);
+        unsigned char* buf = nullptr;
+        HIPC(f, dev_alloc(f->stream, &buf, 4 * sizeof(int) + maxf * (sizeof(float) + 2)));
+        f->gate_words = reinterpret_cast<int*>(buf);
+        f->gate_d2 = reinterpret_cast<float*>(buf + 4 * sizeof(int));
+        f->gate_flag = buf + 4 * sizeof(int) + maxf * sizeof(float);
+        f->gate_pass = f->gate_flag + maxf;
+    }
+    f->gate_chi2 = chi2;
+    drop_graph(f);  // gated steps are another launch sequence: gate + bookkeeping behind process(dt), not inside it
+    return EKFVIO_OK;
+}
+
+int ekfvio_get_gate(ekfvio_filter* f, float* d2, uint8_t* gated, int32_t* n_landmarks, int32_t* gated_last, int64_t* gated_total) {
+    if (!f) return EKFVIO_EINVAL;
+    HIPC(f, hipSetDevice(f->device));
+    int w[4] = {0, 0, 0, 0};
+    if (f->gate_words) {  // (null: the handle never gated)
+        HIPC(f, hipMemcpyAsync(w, f->gate_words, sizeof(w), hipMemcpyDeviceToHost, f->stream));
+        HIPC(f, hipStreamSynchronize(f->stream));
+    }
+    const int seen = std::min(std::max(w[1], 0), f->cfg.max_features);
+    if (seen > 0) {
+        if (d2) HIPC(f, hipMemcpyAsync(d2, f->gate_d2, sizeof(float) * seen, hipMemcpyDeviceToHost, f->stream));
+        if (gated) HIPC(f, hipMemcpyAsync(gated, f->gate_flag, seen, hipMemcpyDeviceToHost, f->stream));
+        HIPC(f, hipStreamSynchronize(f->stream));
+    }
+    if (n_landmarks) *n_landmarks = seen;
+    if (gated_last) *gated_last = w[0];
+    if (gated_total) memcpy(gated_total, w + 2, sizeof(int64_t));
     return EKFVIO_OK;
 }
 

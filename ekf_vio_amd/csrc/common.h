@@ -153,6 +153,13 @@ struct ekfvio_filter {
     float* Wt = nullptr;       // [ldp*m_cap]  (H Sigma)^T
     float* Gm = nullptr;       // [ldp*m_cap]  K R - T[:,idx]
     int* info = nullptr;       // [4] device words: [0] non-positive pivot seen, [1] frame counter of uploaded sequences, [2] device-side m
+    // --- innovation gate (ekfvio_set_gate; gate_bookkeeping_kernel in ekf_kernels.hip) ---
+    float gate_chi2 = 0.f;        // > 0: landmarks whose squared Mahalanobis distance exceeds it are treated as failed by the tracker; 0: off
+    // (device memory: one allocation, made by the first ekfvio_set_gate with chi2 > 0; gate_words is its base)
+    float* gate_d2 = nullptr;     // [max_features] d2 of the most recent gated update (-1: not evaluated)
+    uint8_t* gate_flag = nullptr; // [max_features] 1: rejected by that update's gate
+    uint8_t* gate_pass = nullptr; // [max_features] the effective pass flags of that update (per-frame scratch: an uploaded sequence is never written)
+    int* gate_words = nullptr;    // [4] device words: [0] gated by the last update, [1] landmarks it saw, [2..3] total since create/reset (one 64-bit word)
     int* remove_words = nullptr;  // [4] device words of the removal kernel (remove.hip): [0] landmarks added - removed, [1] removed, [2] its ticket
     int* h_info = nullptr;     // pinned, device-mapped: [0] status word, [1] sequence number (publish_status_kernel)
     int* d_hinfo = nullptr;    // the device's address of h_info
@@ -298,6 +305,16 @@ struct BookArgs {
     float* Rm = nullptr;
     const int* frame_counter = nullptr;
     int* m_out = nullptr;   // receives the number of measurement rows 2 * (#passed) (device-side m, ekfvio_step_image)
+    // innovation gate (gate_bookkeeping_kernel only): the bookkeeping then runs over pass_eff, which the gate fills for this frame
+    uint8_t* pass_eff = nullptr;  // [N] effective flags = pass && accepted (never offset by the frame counter)
+    const float* mu = nullptr;    // the propagated state the update is about to read
+    const float* P = nullptr;
+    int ldp = 0;
+    float chi2 = 0.f;
+    float* d2 = nullptr;          // [N] (-1: not evaluated)
+    uint8_t* gated = nullptr;     // [N]
+    int* gate_words = nullptr;    // ekfvio_filter::gate_words
+    int count_total = 0;          // 0: a re-run of an update already counted (UpdateInputs::gate_counted)
 };
 BookArgs make_book_args(ekfvio_filter* f, int m, const float* d_z, const float* d_R, const uint8_t* d_pass, const int* d_frame_counter);
 void launch_linearize(ekfvio_filter* f, float dt, const BookArgs* book = nullptr);
@@ -313,6 +330,7 @@ struct UpdateInputs {
     int frames = 0;
     bool bookkeeping_done = false;  // the measurement bookkeeping ran already (in the process(dt) launch, or in the update this one runs again)
     bool m_on_device = false;
+    bool gate_counted = false;  // the gate of this update has been added to the running total already (the re-run behind an aborted persistent sweep)
     float next_dt = -1.f;  // >= 0 (capture_steps): the next process(dt)'s dt -- the update's last GEMM may linearise for it; mu is then stale until that process(dt)
     int publish_seq = 0;       // ekfvio_update: the status word goes out with this sequence number right behind the sweep (0: not asked)
     // ekfvio_step_image: called between the update's two Joseph GEMMs, or in front of the T2 flow's one (the frame's outputs); kyp_blocks > 0: K y is

@@ -31,7 +31,8 @@ namespace {
 // workgroup of NT threads.  zrow receives the measured coordinate of every measurement row (the residual
 // z - H mu is formed by gather_kernel, once the propagated mean exists), so this depends only on the frame's
 // measurements: it can run as an extra workgroup of the linearisation launch (BookArgs) or on its own.
-template <int NT>
+// EFF (gate_bookkeeping_kernel): the flags are the frame's effective ones, a.pass_eff, which the same thread wrote for its landmarks.
+template <int NT, bool EFF = false>
 __device__ __forceinline__ void bookkeeping_body(const BookArgs& a) {
     __shared__ int s_cnt[32];
     __shared__ int s_total;
@@ -46,6 +47,7 @@ __device__ __forceinline__ void bookkeeping_body(const BookArgs& a) {
         R += (size_t)fi * 4 * N;
         pass += (size_t)fi * N;
     }
+    if (EFF) pass = a.pass_eff;
     const int per = (N + NT - 1) / NT;
     const int lo = tid * per;
     const int hi = min(N, lo + per);
@@ -591,6 +593,63 @@ __global__ void add_noise_flush_kernel(float* P, int ld, int n, float dt) {
 // of frame *frame_counter is used and the counter advances modulo `frames`.
 __global__ __launch_bounds__(1024) void update_bookkeeping_kernel(BookArgs a) { bookkeeping_body<1024>(a); }
 
+// The innovation gate (include/ekfvio.h, ekfvio_set_gate) and the bookkeeping behind it in ONE launch of the same single workgroup: every
+// thread first evaluates the squared Mahalanobis distance of the landmarks the scan will give it -- H is a selection, so the 2 x 2 innovation
+// covariance is Sigma's (u,v) block + R: three strided loads from Sigma, two from mu, six from z / R -- and leaves the effective flag
+// pass && accepted in a.pass_eff; the bookkeeping then runs over those flags, so a rejected landmark takes the road of one the tracker failed
+// (:526-529: no rows, last_klt kept, delete flag set).  Runs behind process(dt): mu and Sigma are the propagated state.  fp32, in the order the
+// header states (this file is compiled with -ffp-contract=off), so a float32 restatement of those lines gives the same bits.
+__global__ __launch_bounds__(1024) void gate_bookkeeping_kernel(BookArgs a) {
+    __shared__ int s_gated;
+    const int tid = threadIdx.x, N = a.N;
+    const float* z = a.z;
+    const float* R = a.R;
+    const uint8_t* pass = a.pass;
+    if (a.frame_counter) {
+        const int fi = *a.frame_counter;
+        z += (size_t)fi * 2 * N;
+        R += (size_t)fi * 4 * N;
+        pass += (size_t)fi * N;
+    }
+    if (tid == 0) s_gated = 0;
+    __syncthreads();
+    const int per = (N + 1023) / 1024;  // (the partition of bookkeeping_body<1024>: a thread reads back only flags it wrote itself)
+    const int lo = tid * per, hi = min(N, lo + per);
+    int rejected = 0;
+    for (int i = lo; i < hi; i++) {
+        float d2 = -1.f;
+        uint8_t eff = 0, rej = 0;
+        if (pass[i]) {
+            const int s = EKF_BASE + 3 * i;
+            const float* Ps = a.P + (size_t)s * a.ldp + s;
+            const float y0 = z[2 * i] - a.mu[s], y1 = z[2 * i + 1] - a.mu[s + 1];
+            const float ca = Ps[0] + R[4 * i];
+            const float cb = Ps[1] + R[4 * i + 1];  // the lower triangle's element of both
+            const float cc = Ps[a.ldp + 1] + R[4 * i + 3];
+            const float det = ca * cc - cb * cb;
+            const float q = ((cc * y0) * y0 - ((2.f * cb) * y0) * y1) + (ca * y1) * y1;
+            d2 = q / det;
+            eff = (det > 0.f && d2 <= a.chi2) ? 1 : 0;  // (a NaN anywhere rejects)
+            rej = eff ^ 1;
+            rejected += rej;
+        }
+        a.d2[i] = d2;
+        a.gated[i] = rej;
+        a.pass_eff[i] = eff;
+    }
+    if (rejected) atomicAdd(&s_gated, rejected);
+    __syncthreads();
+    if (tid == 0) {
+        a.gate_words[0] = s_gated;
+        a.gate_words[1] = N;
+        if (a.count_total) {
+            long long* total = reinterpret_cast<long long*>(a.gate_words + 2);
+            *total = *total + s_gated;
+        }
+    }
+    bookkeeping_body<1024, true>(a);
+}
+
 #include "gather_body.inc"
 
 __global__ __launch_bounds__(256) void gather_kernel(GatherArgs a) {
@@ -744,7 +803,11 @@ void launch_predict(ekfvio_filter* f, float dt, const BookArgs* book) {
 
 // updateWithFeaturePositions (:475-628) on device-resident z/R/pass; m = 2*(#passed) known to the host
 UpdateResult launch_update(ekfvio_filter* f, const UpdateInputs& in) {
-    const UpdatePlan p = plan_update(f, in.m, in.m_on_device, in.next_dt, in.recoverable);
+    // The innovation gate (ekfvio_set_gate): the device decides which landmarks are measured, so the host no longer knows m -- the count is on
+    // the device for every caller.  What the host still knows is "no landmark passed": nothing to gate, m = 0 (the gate kernel still runs, so that
+    // ekfvio_get_gate reports this update).
+    const bool gate = f->gate_chi2 > 0.f && f->N > 0;
+    const UpdatePlan p = plan_update(f, in.m, in.m_on_device || (gate && in.m > 0), in.next_dt, in.recoverable);
     const int m = p.m, m_pad = p.m_pad, n_pad = p.n_pad, n = f->n, ld = f->ldp;
     UpdateResult out;
     f->last_m = m;
@@ -753,7 +816,12 @@ UpdateResult launch_update(ekfvio_filter* f, const UpdateInputs& in) {
         if (!in.bookkeeping_done) {
             BookArgs bk = make_book_args(f, m, in.z, in.R, in.pass, in.frame_counter);
             if (p.m_on_device) bk.m_out = f->info + 2;
-            hipLaunchKernelGGL(update_bookkeeping_kernel, dim3(1), dim3(1024), 0, f->stream, bk);
+            if (gate) {
+                bk.pass_eff = f->gate_pass, bk.mu = f->mu, bk.P = f->P, bk.ldp = ld, bk.chi2 = f->gate_chi2;
+                bk.d2 = f->gate_d2, bk.gated = f->gate_flag, bk.gate_words = f->gate_words, bk.count_total = in.gate_counted ? 0 : 1;
+                hipLaunchKernelGGL(gate_bookkeeping_kernel, dim3(1), dim3(1024), 0, f->stream, bk);
+            } else
+                hipLaunchKernelGGL(update_bookkeeping_kernel, dim3(1), dim3(1024), 0, f->stream, bk);
         }
         if (p.fused_gather) {
             // the gather and the factorisation of the first diagonal tile share one launch (chol.hip)

@@ -25,7 +25,7 @@ def _u8(a):
 class TightlyCoupledEKF:
     def __init__(self, max_features=100, device=0, stream=None, predict_mode=capi.PREDICT_STRUCTURED,
                  default_point_depth=0.5, default_point_depth_variance=100.0,
-                 default_point_homogenous_variance=1e-5, hooks=False, **cfg_overrides):
+                 default_point_homogenous_variance=1e-5, hooks=False, gate_chi2=0.0, **cfg_overrides):
         # hooks=True: this handle lives in libekfvio_hip_hooks.so, the build that also has include/ekfvio_test_hooks.h (tests, profiling scripts)
         self.hooks = bool(hooks)
         self.lib = capi.load(hooks=self.hooks)
@@ -48,6 +48,8 @@ class TightlyCoupledEKF:
             # a failed create releases whatever it had allocated and hands back no handle
             self.h = None
             raise capi.EkfvioError(rc, "ekfvio_create failed (device %d)" % device)
+        if gate_chi2:  # a property of the handle, not a field of the configuration (ekfvio_set_gate)
+            self.setGate(gate_chi2)
 
     def _chk(self, rc, allow=()):
         if rc != capi.OK and rc not in allow:
@@ -150,6 +152,20 @@ class TightlyCoupledEKF:
             m = np.ascontiguousarray(np.asarray(mask).astype(bool), dtype=np.uint8).reshape(-1)
             self._chk(self.lib.ekfvio_remove_features(self.h, _u8(m), m.shape[0], C.byref(k)))
         return int(k.value)
+
+    def setGate(self, chi2):
+        """Not in the reference: the innovation gate (ekfvio_set_gate).  chi2 > 0: a landmark whose squared Mahalanobis distance on
+        the propagated state exceeds it is treated as one the tracker failed; 0: off."""
+        self._chk(self.lib.ekfvio_set_gate(self.h, float(chi2)))
+
+    def gate(self):
+        """ekfvio_get_gate: dict(d2[n], gated[n], n_landmarks, gated_last, gated_total) of the most recent update."""
+        cap = max(int(self.cfg.max_features), 1)
+        d2, g = np.zeros(cap, np.float32), np.zeros(cap, np.uint8)
+        n, last, total = C.c_int32(0), C.c_int32(0), C.c_int64(0)
+        self._chk(self.lib.ekfvio_get_gate(self.h, _fp(d2), _u8(g), C.byref(n), C.byref(last), C.byref(total)))
+        return dict(d2=d2[:n.value].copy(), gated=g[:n.value].copy(), n_landmarks=int(n.value), gated_last=int(last.value),
+                    gated_total=int(total.value))
 
     def checkSigma(self):
         a, b = C.c_float(0), C.c_float(0)

@@ -45,6 +45,7 @@ struct Error : std::runtime_error {
 // file should not pass silently).  Values arrive as text, as in a launch file or a `rosparam dump`.
 struct Params {
     ekfvio_config cfg;
+    float gate_chi2 = 0.f;  // not a field of ekfvio_config: set on the handle behind ekfvio_create (ekfvio_set_gate); 0 = off
     std::map<std::string, std::string> node;  // odom_topic, camera_topic, base_frame, use_imu, publish_insight, ...
 
     Params() {
@@ -87,6 +88,10 @@ struct Params {
         else if (key == "default_point_homogenous_variance") cfg.default_point_homogenous_variance = (float)number(key, value);
         else if (key == "imu_update") cfg.use_imu = (value == "true" || value == "1") ? 1 : 0;  // not a reference parameter: SURVEY 8(f) F4
         else if (key == "remove_lost") cfg.remove_lost = (value == "true" || value == "1") ? 1 : 0;  // not a reference parameter: removes lost landmarks
+        else if (key == "gate_chi2") {  // not a reference parameter: the innovation gate's threshold on d2 (0 = off)
+            gate_chi2 = (float)number(key, value);
+            if (gate_chi2 < 0.f) throw Error(EKFVIO_EINVAL, "parameter gate_chi2: negative: " + value);
+        }
         else if (key == "imu_gyro_variance") cfg.imu_gyro_variance = (float)number(key, value);
         else if (key == "imu_accel_variance") cfg.imu_accel_variance = (float)number(key, value);
         else if (key == "gravity_x") cfg.gravity[0] = (float)number(key, value);
@@ -105,7 +110,7 @@ struct Params {
                                         "min_klt_eigen_val", "min_new_feature_dist", "max_pyramids", "klt_window_size",
                                         "default_point_depth", "default_point_depth_variance",
                                         "default_point_homogenous_variance", "frame_buffer_size", "imu_update",
-                                        "imu_gyro_variance", "imu_accel_variance", "gravity_x", "gravity_y", "gravity_z", "remove_lost"};
+                                        "imu_gyro_variance", "imu_accel_variance", "gravity_x", "gravity_y", "gravity_z", "remove_lost", "gate_chi2"};
         for (const auto& e : Params().node) out.push_back(e.first);
         for (const auto& e : ignored()) out.push_back(e.first);
         return out;
@@ -201,6 +206,24 @@ class TightlyCoupledEKF {
         if (rc == EKFVIO_ENUMERIC) return false;
         chk(rc);
         return true;
+    }
+    // Not in the reference: the innovation gate (ekfvio_set_gate).  chi2 > 0: a landmark whose squared Mahalanobis distance on the propagated
+    // state exceeds it is treated as one the tracker failed; 0: off.
+    void setGate(float chi2) { chk(ekfvio_set_gate(h_, chi2)); }
+    struct Gate {
+        std::vector<float> d2;       // per landmark of the most recent update (-1: not evaluated)
+        std::vector<uint8_t> gated;
+        int32_t gated_last = 0;
+        int64_t gated_total = 0;
+    };
+    Gate gate() {
+        Gate g;
+        g.d2.assign((size_t)(max_features_ > 0 ? max_features_ : 1), -1.f);
+        g.gated.assign(g.d2.size(), 0);
+        int32_t n = 0;
+        chk(ekfvio_get_gate(h_, g.d2.data(), g.gated.data(), &n, &g.gated_last, &g.gated_total));
+        g.d2.resize((size_t)n), g.gated.resize((size_t)n);
+        return g;
     }
     // Not in the reference (it flags lost landmarks, TightlyCoupledEKF.cpp:528, and keeps them): removes the landmarks whose byte
     // of `remove` is nonzero (one per landmark), or, with no mask, those flagged for deletion.  Returns the number removed.
@@ -348,7 +371,9 @@ class EKFVIO {
     // the node's constructor (EKFVIO.cpp:19-67): parameters by the reference's names (see Params)
     explicit EKFVIO(const Params& p, int device = 0)
         : tc_ekf(p.cfg.max_features, device, &p.cfg), tracker(tc_ekf), params(p.node), use_imu_(p.cfg.use_imu != 0),
-          scale_(p.cfg.inverse_image_scale > 1 ? p.cfg.inverse_image_scale : 1) {}
+          scale_(p.cfg.inverse_image_scale > 1 ? p.cfg.inverse_image_scale : 1) {
+        if (p.gate_chi2 > 0.f) tc_ekf.setGate(p.gate_chi2);  // (behind ekfvio_create: the gate is a property of the handle)
+    }
     TightlyCoupledEKF tc_ekf;
     KLTTracker tracker;
     std::map<std::string, std::string> params;  // node-level parameters (topics, frames, switches) for the ROS side

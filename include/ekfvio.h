@@ -111,7 +111,8 @@ EKFVIO_API int ekfvio_default_config(ekfvio_config* cfg);
  * On failure nothing is left allocated and *out is NULL. */
 EKFVIO_API int ekfvio_create(const ekfvio_config* cfg, int device, void* stream, ekfvio_filter** out);
 EKFVIO_API int ekfvio_destroy(ekfvio_filter* f);
-/* initializeBaseState(): back to mu = [0,0,0,1,0...], Sigma diag [0x7,30x9,0.5x6], no landmarks. */
+/* initializeBaseState(): back to mu = [0,0,0,1,0...], Sigma diag [0x7,30x9,0.5x6], no landmarks.  (The innovation gate's counts start
+ * over; its threshold stays.) */
 EKFVIO_API int ekfvio_reset(ekfvio_filter* f);
 EKFVIO_API const char* ekfvio_last_error(const ekfvio_filter* f);
 
@@ -175,6 +176,37 @@ EKFVIO_API int ekfvio_set_state(ekfvio_filter* f, int32_t n_features, const floa
  * remove == NULL: the landmarks flagged for deletion (the tracker lost them, TightlyCoupledEKF.cpp:528) are removed.
  * *removed (may be NULL) receives the number removed.  Not in the reference, which flags but never removes. */
 EKFVIO_API int ekfvio_remove_features(ekfvio_filter* f, const uint8_t* remove, int32_t count, int32_t* removed);
+
+/* ---- innovation gate (not in the reference: its Params.h has an "OUTLIER DETECTION" section whose thresholds nothing reads) ---------
+ * A chi-square test per landmark, evaluated on the device on the propagated state in front of the update's measurement bookkeeping
+ * (ekfvio_update, ekfvio_run_uploaded, ekfvio_step_image; the IMU update is not gated).  For every landmark i with pass[i] != 0, with
+ * s = 22 + 3 i, all in fp32, in this order, without fused multiply-add and with correctly rounded division (a NumPy float32
+ * restatement of these lines gives the same bits):
+ *
+ *     y0 = z[2i]   - mu[s]          y1 = z[2i+1] - mu[s+1]
+ *     a  = P(s,s)     + R_i(0,0)
+ *     b  = P(s+1,s)   + R_i(1,0)          (the lower triangle's element of both)
+ *     c  = P(s+1,s+1) + R_i(1,1)
+ *     det = a*c - b*b
+ *     q   = ((c*y0)*y0 - ((2*b)*y0)*y1) + (a*y1)*y1
+ *     d2  = q / det
+ *     accept  <=>  det > 0  and  d2 <= chi2        (a NaN anywhere rejects)
+ *
+ * mu, P: the state the update is about to read (behind process(dt)); R_i: the column-major 2x2 the caller or the tracker supplied.
+ * H is a selection matrix, so [[a, b], [b, c]] is the landmark's 2x2 innovation covariance.  A rejected landmark is treated in every
+ * respect as one the tracker failed (TightlyCoupledEKF.cpp:526-529): no measurement rows, last_klt kept, delete flag set -- and with
+ * cfg.remove_lost = 1 ekfvio_step_image removes it in the same frame.  Landmarks with pass[i] == 0 are not evaluated.
+ *
+ * chi2 > 0: gate on from the next update; chi2 == 0: off (default).  Negative, NaN: EKFVIO_EINVAL.
+ * Drops the handle's captured step graphs (the launch sequence differs). */
+EKFVIO_API int ekfvio_set_gate(ekfvio_filter* f, float chi2);
+/* Results of the most recent update (any pointer may be NULL): d2 per landmark as defined above
+ * (-1: not evaluated) and a gated flag per landmark, both with room for max_features entries;
+ * *n_landmarks = the landmark count that update saw (indices are its indices, before any removal or
+ * replenishment of the same frame; 0 before the first gated update); number gated by that update;
+ * total since create/reset. */
+EKFVIO_API int ekfvio_get_gate(ekfvio_filter* f, float* d2, uint8_t* gated, int32_t* n_landmarks, int32_t* gated_last,
+                               int64_t* gated_total);
 
 /* ---- KLT (KLTTracker::findNewFeaturePositions, KLTTracker.cpp:29-95) ----------------- */
 /* Uploads a frame (Frame.h:25-41: image + intrinsics K row-major 3x3 as in CameraInfo.K),
