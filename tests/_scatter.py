@@ -71,7 +71,7 @@ def backward_yardstick(st, z, R, passed, s64, c=8.0, trials=8, seed=0):
     r = 0
     for i in range(N):
         if passed[i]:
-            Rm[r:r + 2, r:r + 2] = np.asarray(R[i], np.float64).reshape(2, 2)
+            Rm[r:r + 2, r:r + 2] = np.asarray(R[i], np.float64).reshape(2, 2).T  # (R[i] is the column-major quadruple R00, R10, R01, R11)
             r += 2
     zz = np.array([z[i][a] for i in range(N) if passed[i] for a in (0, 1)], np.float64)
     y = zz - mu[idx]
