@@ -196,9 +196,9 @@ static int create_body(ekfvio_filter* f, const ekfvio_config* cfg, int device, v
         f->own_stream = true;
     }
     const int maxf = cfg->max_features;
-    f->n_cap = EKF_BASE + 3 * maxf;
-    f->ldp = round_up(f->n_cap + 1, 64);  // one spare row/column: the K*y column of the Joseph-1 GEMM
-    f->m_cap = round_up(2 * maxf > 0 ? 2 * maxf : 1, 64);
+    const FilterDims dims = filter_dims(maxf);  // (plan.h)
+    f->n_cap = dims.n_cap, f->ldp = dims.ldp, f->m_cap = dims.m_cap, f->ld_aug = dims.ld_aug, f->sweep_sync_words = dims.sweep_sync_words;
+    f->tune = tuning_from_env();  // every switch, once per handle
     const size_t pp = (size_t)f->ldp * f->ldp, pm = (size_t)f->ldp * f->m_cap;
     HIPC(f, dev_alloc(f->stream, &f->mu, f->ldp));
     HIPC(f, dev_alloc(f->stream, &f->mu_next, f->ldp));
@@ -217,56 +217,15 @@ static int create_body(ekfvio_filter* f, const ekfvio_config* cfg, int device, v
     HIPC(f, dev_alloc(f->stream, &f->pass, (size_t)maxf));
     HIPC(f, dev_alloc(f->stream, &f->yres, (size_t)f->m_cap));
     HIPC(f, dev_alloc(f->stream, &f->Rm, 2 * (size_t)f->m_cap));
-    f->ld_aug = f->m_cap + f->ldp + f->m_cap;
     HIPC(f, dev_alloc(f->stream, &f->Saug, (size_t)f->ld_aug * f->m_cap));
     HIPC(f, dev_alloc(f->stream, &f->Laug, (size_t)f->ld_aug * f->m_cap));
     HIPC(f, dev_alloc(f->stream, &f->Linv, 64 * (size_t)f->m_cap));
     HIPC(f, dev_alloc(f->stream, &f->Lsign, (size_t)(f->m_cap / 64 > 256 ? f->m_cap / 64 : 256)));  // 256: the raw-solve test hook goes up to m = 16384
-    {   // flags of the persistent sweeps (chol_persist.inc): ready[mb] + 2 x [row blocks x mb] + abort word
-        const size_t mb2 = (size_t)(f->m_cap / 64);
-        f->sweep_sync_words = std::max((size_t)1024, mb2 + 2 * (size_t)(f->ld_aug / 64 + 1) * mb2 + 8);  // (>= 1024: the test hooks sweep matrices that are not the filter's)
-        HIPC(f, dev_alloc(f->stream, &f->sweep_sync, f->sweep_sync_words));
-    }
+    HIPC(f, dev_alloc(f->stream, &f->sweep_sync, f->sweep_sync_words));  // flags of the persistent sweeps (chol_persist.inc)
     {
         hipDeviceProp_t prop;
         HIPC(f, hipGetDeviceProperties(&prop, device));
         f->num_cus = prop.multiProcessorCount;
-        const char* e = getenv("EKFVIO_EARLY_STATUS");  // 0: ekfvio_update publishes its status behind the update's last kernel (rounds 1-3)
-        if (e) f->early_status = atoi(e) ? 1 : 0;
-        e = getenv("EKFVIO_UPLOAD_KERNEL");  // 0: the frame travels by the copy engine (hipMemcpyAsync) instead of the upload kernel
-        if (e) f->upload_kernel = atoi(e) ? 1 : 0;
-        e = getenv("EKFVIO_SWEEP_WAIT_MS");  // the persistent sweep's patience per wait where the update can be run again (default 3 ms)
-        if (e && atof(e) > 0) f->sweep_wait_ticks = (int)std::min(2.0e9, 1e5 * atof(e));
-        e = getenv("EKFVIO_SWEEP_RETRY_S");  // the first pause before a handle whose persistent sweep gave up tries it again (default 2 s)
-        if (e && atof(e) > 0) f->sweep_retry_first_s = atof(e);
-        e = getenv("EKFVIO_SWEEP");  // tuning knob: 0 = one launch per block step
-        if (e) f->sweep_mode = atoi(e) ? 2 : 0;
-        e = getenv("EKFVIO_FUSE_GATHER");  // tuning knob: 0 = gather and first diagonal tile in separate launches
-        if (e) f->fuse_gather = atoi(e) ? 1 : 0;
-        e = getenv("EKFVIO_T2");  // A/B knob: 0 = gain in the sweep, two Joseph GEMMs behind it (rounds 4-5)
-        if (e) f->t2_flow = atoi(e) ? 1 : 0;
-        e = getenv("EKFVIO_SCHUR");  // tuning knob: 1 = Sigma (I - K H)^T and K as Schur tiles inside the sweep instead of two GEMMs behind it
-        if (e) f->schur = atoi(e) ? 1 : 0;
-        e = getenv("EKFVIO_FRAME_OUTPUTS");  // tuning knob: 0 = the frame's last kernel publishes the status word only
-        if (e) f->frame_outputs = atoi(e) ? 1 : 0;
-        e = getenv("EKFVIO_FUSE_SWEEP");  // tuning knob: 0 = gather + first diagonal tile and the persistent sweep as two launches (round 3)
-        if (e) f->fuse_sweep = atoi(e) ? 1 : 0;
-        e = getenv("EKFVIO_PERSIST_OVERSUB");
-        if (e) f->persist_oversub = atoi(e);
-        e = getenv("EKFVIO_EARLY_OUTPUTS");  // tuning knob: 0 = a frame's outputs behind its last kernel (rounds 1-3)
-        if (e) f->early_outputs = atoi(e) ? 1 : 0;
-        e = getenv("EKFVIO_PERSIST_GAIN");
-        if (e) f->persist_gain = atoi(e) ? 1 : 0;
-        e = getenv("EKFVIO_PERSIST_EARLY");
-        if (e) f->persist_early = atoi(e) ? 1 : 0;
-        e = getenv("EKFVIO_GEMM_ORDER2D");  // tuning knob: 0 = the throughput-regime GEMM's tiles in block-index order (rounds 1-4)
-        if (e) f->gemm_order2d = atoi(e) ? 1 : 0;
-        e = getenv("EKFVIO_LIN_OVERLAP");  // 0 = every process(dt) of a device-resident run linearises for itself (rounds 3-5)
-        if (e) f->lin_overlap = atoi(e) ? 1 : 0;
-        e = getenv("EKFVIO_SYM_JOSEPH");  // 0 = the throughput regime's second Joseph GEMM forms both triangles (rounds 1-5)
-        if (e) f->sym_joseph = atoi(e) ? 1 : 0;
-        e = getenv("EKFVIO_FUSE_LINEARIZE");  // tuning knob: 0 = linearize_kernel and the propagation as two launches
-        if (e) f->fuse_linearize = atoi(e) ? 1 : 0;
     }
     HIPC(f, dev_alloc(f->stream, &f->Km, pm));
     HIPC(f, dev_alloc(f->stream, &f->Wt, pm));
@@ -435,21 +394,21 @@ int ekfvio_linearize(ekfvio_filter* f, float dt, float* F_dense) {
 // resident: another process or stream held compute units).  Behind an aborted sweep the Joseph GEMMs write nothing, so
 // Sigma, mu and the frame counter stand where process(dt) left them, and the handle stops using the persistent launch.
 void sweep_abort_latch(ekfvio_filter* f) {
-    f->sweep_mode = 0;  // the following sweeps of this handle: one launch per block step (no co-residency needed)
+    f->sweep_latched_off = true;  // the following sweeps of this handle: one launch per block step (no co-residency needed)
     drop_graph(f);      // captured steps contain the persistent launch
     // ... and a way back: what kept the workgroups from being resident -- another process or stream on the device, a
     // compute-unit mask -- may be gone later.  The persistent launch is tried again after a pause that doubles with every abort
     // (2 s, 4 s, ... 64 s), checked at the entry points that enqueue updates (sweep_maybe_retry).
-    f->sweep_retry_pause_s = f->sweep_retry_pause_s <= 0 ? f->sweep_retry_first_s : std::min(64.0, 2.0 * f->sweep_retry_pause_s);
+    f->sweep_retry_pause_s = f->sweep_retry_pause_s <= 0 ? f->tune.sweep_retry_first_s : std::min(64.0, 2.0 * f->sweep_retry_pause_s);
     f->sweep_retry_at = std::chrono::steady_clock::now() + std::chrono::milliseconds((long long)(1e3 * f->sweep_retry_pause_s));
     f->sweep_retry_armed = true;
 }
 // Called ONLY from the entry points that can run an aborted update again (ekfvio_update, ekfvio_step_image): a retry that fails costs
 // one recovery there, nothing else.
 void sweep_maybe_retry(ekfvio_filter* f) {
-    if (!f->sweep_retry_armed || f->sweep_mode != 0 || std::chrono::steady_clock::now() < f->sweep_retry_at) return;
+    if (!f->sweep_retry_armed || !f->sweep_latched_off || std::chrono::steady_clock::now() < f->sweep_retry_at) return;
     f->sweep_retry_armed = false;
-    f->sweep_mode = 2;
+    f->sweep_latched_off = false;
     f->sweep_probation = 8;  // clean persistent sweeps until the pause starts from its first value again (sweep_clean_update)
     drop_graph(f);  // captured steps contain the per-step sweep
     // the flags AND the abort word (which no kernel ever zeroes) start from zero again
@@ -460,7 +419,7 @@ void sweep_maybe_retry(ekfvio_filter* f) {
 // its first value again (it only ever doubled, so a handle that met a few transient aborts early waited 64 s on the slow
 // sweep after any later one, even after hours of clean persistent sweeps).
 void sweep_clean_update(ekfvio_filter* f) {
-    if (f->sweep_probation > 0 && f->sweep_mode == 2 && --f->sweep_probation == 0) f->sweep_retry_pause_s = 0.0;
+    if (f->sweep_probation > 0 && f->tune.persist_sweep && !f->sweep_latched_off && --f->sweep_probation == 0) f->sweep_retry_pause_s = 0.0;
 }
 // Waits for the stream and reads the status word.  An aborted update is enqueued again by `rerun` (null: the caller cannot,
 // e.g. a graph replay of many steps: EKFVIO_EABORTED) with the per-step sweep and awaited: fresh launches, same inputs,
@@ -515,7 +474,7 @@ int ekfvio_update(ekfvio_filter* f, const float* z, const float* R, const uint8_
     // the host right behind the sweep, and the call returns while the two Joseph GEMMs are still running (everything the caller can do next
     // is ordered behind them on the handle's stream, or synchronises).  A step-by-step caller then keeps the GPU fed: the next step's
     // launches are in the queue before this step's last kernel ends (EKFVIO_EARLY_STATUS=0: publish behind the last kernel, as rounds 1-3).
-    const bool early = f->early_status != 0;  // (per handle, read at create like every other knob: ADVICE r04)
+    const bool early = f->tune.early_status != 0;  // (per handle, read at create like every other knob: ADVICE r04)
     const int seq = next_status_seq(f);
     UpdateInputs in;
     in.m = m, in.z = dz, in.R = dR, in.pass = dp;
@@ -757,7 +716,7 @@ static void drop_graph(ekfvio_filter* f) {
 }
 
 // An update of ekfvio_run_uploaded: frame i of the uploaded sequence, or the one the device-side counter names.  These launches and captures
-// carry the long wait bound (common.h, sweep_wait_ticks): nothing can run their updates again
+// carry the long wait bound (plan.h, Tuning::sweep_wait_ticks): nothing can run their updates again
 static UpdateInputs uploaded_update(ekfvio_filter* f, int m, int i, int* counter) {
     UpdateInputs in;
     in.m = m, in.z = f->seq_z + (size_t)i * 2 * f->N, in.R = f->seq_R + (size_t)i * 4 * f->N, in.pass = f->seq_pass + (size_t)i * f->N;
@@ -819,7 +778,7 @@ int ekfvio_run_uploaded(ekfvio_filter* f, int32_t first, int32_t count, float dt
     // (a gated handle's geometry is m = 2N, count on the device, for every frame in which any landmark passed: launch_update)
     const bool gate = f->gate_chi2 > 0.f;
     auto geometry = [&](int i) { return gate && f->seq_m[i] > 0 ? 2 * f->N : f->seq_m[i]; };
-    bool uniform = f->use_graph && !f->prof_on && (count >= 2 || count == 0);
+    bool uniform = !f->prof_on && (count >= 2 || count == 0);
     for (int i = 0; uniform && i < f->seq_frames; i++) uniform = geometry(i) == geometry(0);
     if (uniform) {
         const int m = geometry(0);
@@ -930,7 +889,7 @@ int ekfvio_profile_update_gemms(ekfvio_filter* f, int32_t reps, double* avg_laun
         // 64 x 64 tiles only (GemmEpi::sym)
         const double full = 2.0 * f->n * (double)f->n * m_pad;
         const int tn = (f->n + 63) / 64;
-        const bool half = per_rep == 2 && f->sym_joseph && gemm_throughput_regime(f, f->n, f->n, m_pad);
+        const bool half = per_rep == 2 && f->tune.sym_joseph && gemm_throughput_regime(f->num_cus, f->n, f->n, m_pad);
         const double second = half ? 0.5 * tn * (tn + 1) * 2.0 * 64.0 * 64.0 * m_pad : full;
         *flops_per_launch = per_rep == 2 ? 0.5 * (full + second) : full;
     }
@@ -996,7 +955,7 @@ int ekfvio_get_counters(ekfvio_filter* f, int64_t counters[8]) {
     counters[0] = f->persistent_sweeps;
     counters[1] = f->schur_sweeps;
     counters[2] = f->sweep_recoveries;
-    counters[3] = f->sweep_mode;
+    counters[3] = (f->tune.persist_sweep && !f->sweep_latched_off) ? 2 : 0;
     counters[4] = f->early_output_frames;
     counters[5] = f->t2_updates;
     counters[6] = counters[7] = 0;
@@ -1171,7 +1130,7 @@ int ekfvio_test_cholesky_solve(ekfvio_filter* f, int32_t m, int32_t nrhs, const 
     HIPC(f, dev_alloc(f->stream, &dW, (size_t)rp * mp));
     HIPC(f, hipMemcpyAsync(dS, hs.data(), sizeof(float) * hs.size(), hipMemcpyHostToDevice, f->stream));
     // the flow the handle's knobs and the process's handle count select for this shape, as for an update of the filter (plan_raw_sweep)
-    UpdatePlan plan = plan_raw_sweep(f, mp, rp);
+    UpdatePlan plan = plan_raw_sweep(f->tune, plan_shape(f), mp, rp);
     launch_chol_sweep(f, plan, dS, dL, dLi, ld, plan.persistent() && !f->sweep_flags_clean);
     if (plan.persistent()) f->sweep_flags_clean = false;  // (no GEMM of an update behind this sweep zeroes its flags)
     // one step of residual refinement against L, unless a block went through the U S U^T path (K L = Y S then, not Y)
@@ -1209,6 +1168,20 @@ int ekfvio_test_cholesky_solve(ekfvio_filter* f, int32_t m, int32_t nrhs, const 
     hipFree(dLi);
     hipFree(dK);
     hipFree(dW);
+    return EKFVIO_OK;
+}
+
+// No handle, no HIP call: plan_update (plan.h) over the environment's Tuning and the PlanShape of a capacity on a device of `num_cus` compute units
+int ekfvio_test_plan(int32_t num_cus, int32_t max_features, int32_t N, int32_t m, int32_t m_on_device, int32_t sole_handle,
+                     int32_t latched_off, int32_t dense_predict, float next_dt, int32_t plan[12]) {
+    if (!plan || max_features < 0 || N < 0 || N > max_features) return EKFVIO_EINVAL;
+    const FilterDims d = filter_dims(max_features);
+    PlanShape s;
+    s.num_cus = num_cus, s.ldp = d.ldp, s.sweep_sync_words = d.sweep_sync_words, s.N = N, s.n = EKF_BASE + 3 * N;
+    s.dense_predict = dense_predict != 0, s.sole_handle = sole_handle != 0, s.latched_off = latched_off != 0;
+    const UpdatePlan p = plan_update(tuning_from_env(), s, m, m_on_device != 0, next_dt);
+    const int32_t out[12] = {p.m, p.m_pad, p.n_pad, p.sweep, p.fused_gather, p.with_wt, p.gain, p.tail, p.t2_skip, p.t2_by_sweep, p.compact, p.lin_blocks};
+    std::copy(out, out + 12, plan);
     return EKFVIO_OK;
 }
 #endif  // EKFVIO_TEST_HOOKS

@@ -1098,17 +1098,6 @@ void launch_potrf_stamps(ekfvio_filter* f, const float* S, int ld, float* L, flo
 }
 #endif  // EKFVIO_TEST_HOOKS
 
-// layout: ready[mb], fin[rows x mb], pan[rows x mb] (panel blocks of the X / identity rows, for the gain tiles formed inside the
-// launch), one spare word, the abort word (last: whoever zeroes the flags for the next sweep leaves it alone, persist_zero_words);
-// a multiple of 16 bytes
-static size_t persist_flag_words(int m_pad, int n_pad) {
-    const int mb = m_pad / PB, rows = 2 * mb + n_pad / PB;
-    return ((size_t)(mb + 2 * rows * mb + 2) + 3) & ~(size_t)3;
-}
-int persist_zero_words(int m_pad, int n_pad) {
-    const int mb = m_pad / PB, rows = 2 * mb + n_pad / PB;
-    return mb + 2 * rows * mb + 1;
-}
 #define EKF_GATHER_POTRF_LDS (84 * 1024)  // > half of a compute unit's 160 KB: one workgroup per compute unit
 void launch_gather_potrf(ekfvio_filter* f, const UpdatePlan& p) {
     if (!f->gather_attr_set) {
@@ -1126,116 +1115,6 @@ void launch_gather_potrf(ekfvio_filter* f, const UpdatePlan& p) {
                        f->Linv, f->info, f->Lsign, f->sweep_dbg);
 }
 
-// helpers of the persistent sweep (chol_persist.inc): per block column j the rows of A from the diagonal down (without
-// (1,1)), the X row blocks and the identity row blocks 0 .. j
-static int persist_helpers(int mb, int nX, bool compact = false) {  // (compact: without the identity rows' diagonal tiles, chol_persist.inc)
-    int h = 0;
-    for (int j = 1; j < mb; j++) h += (mb - j - (j == 1 ? 1 : 0)) + nX + (j + 1 - (compact ? 1 : 0));
-    return h;
-}
-// The shapes the persistent launch takes: 3 .. EKF_SWEEP_SPLIT_MB - 1 block columns.  Up to round 3: chain + owners co-resident
-// (1 + tiles <= compute units).  Round 4: up to EKF_PERSIST_OVERSUB x that.  An owner waits only for workgroups with a LOWER block index
-// (the chain is workgroup 0, the owners are numbered block column by block column, and a tile's panel sources lie in earlier columns), so
-// with workgroups dispatched in index order -- what the hardware does, though HIP does not promise it -- the resident ones can always
-// finish, and the later columns' owners take over their compute units and catch up (their flags are all up: ~10 k cycles per step
-// against the chain's ~15.5 k).  N = 400 (params/fast_with_insight.yaml: 13 block columns, 407 owners) runs the sweep in one launch
-// this way.  Should the order ever not hold, the bounded waits end the launch and the update is run again per step (EKFVIO_EABORTED).
-// Measured (profiles/r04_oversubscribed_persistent_sweep.txt): bit-identical, the sweep itself 155.7 -> 121.2 us at N = 400, but the gain
-// kernel behind it then runs 2x longer on operands the persistent launch has left in other XCDs' L2s; +2.9 % per step in all.  Off by
-// default (1); EKFVIO_PERSIST_OVERSUB=2 turns it on, tests/test_gpu_parity.py exercises it.
-#ifndef EKF_PERSIST_OVERSUB
-#define EKF_PERSIST_OVERSUB 1
-#endif
-static bool persist_shape(const ekfvio_filter* f, int m_pad, int n_pad) {
-    const int mb = m_pad / PB;
-    const int over = f->persist_oversub > 0 ? f->persist_oversub : EKF_PERSIST_OVERSUB;
-    return mb >= 3 && mb < EKF_SWEEP_SPLIT_MB && 1 + persist_helpers(mb, n_pad / PB) <= (over > 1 ? over : 1) * f->num_cus &&
-           persist_flag_words(m_pad, n_pad) <= f->sweep_sync_words;
-}
-// ... and of those, the shapes whose gain is formed inside the fused launch: (nearly) every workgroup of that launch finds a compute unit
-// at once (the transposing / gain workgroups hold theirs to the end).  Behind every other sweep of such a shape gain_tiles_kernel runs
-// the same arithmetic; all other shapes take the gain GEMM, whichever sweep ran.
-static bool gain_in_sweep_shape(const ekfvio_filter* f, int m_pad, int n_pad) {
-    const int mb = m_pad / PB;
-    return persist_shape(f, m_pad, n_pad) && 1 + mb * (f->ldp / 64) + 2 + persist_helpers(mb, n_pad / PB) <= f->num_cus + 8;
-}
-// ... and of those, the shapes whose T2 = Sigma (I - K H)^T is formed by freed owners inside the launch (round 6, chol_persist.inc, t2_tile): there
-// must be an owner per tile pair once enough of the first owners have LEFT for every workgroup of the launch to find a compute unit (the two
-// step-0 gatherers and the gain workgroups beyond the state's row blocks leave at once).  Returns the number of owners that leave (PersistArgs::t2_skip),
-// -1 where the flow does not apply.  The flow is a property of the SHAPE, not of the sweep that runs: behind a per-step sweep of such a shape
-// gain2_t2_tiles_kernel forms the same T2, so a sequence's bits do not depend on what else the device runs.
-static int t2_skip_owners(const ekfvio_filter* f, int m_pad, int n_pad) {
-    if (!f->t2_flow || !f->persist_gain || f->schur || !gain_in_sweep_shape(f, m_pad, n_pad)) return -1;
-    const int mb = m_pad / PB, nX = n_pad / PB;
-    const int H = persist_helpers(mb, nX, true), gw = mb * (f->ldp / 64);
-    if (1 + gw + H > f->num_cus) return -1;  // the compact launch (chol_persist.inc): every workgroup has its compute unit from the start
-    return (nX * (nX + 1) / 2 <= H) ? 0 : -1;
-}
-// Which sweep runs.  filter_update: the filter's own matrices (Schur tiles and the fused front are possible); else another caller's [A; X; I].
-static SweepKind choose_sweep(const ekfvio_filter* f, int m_pad, int n_pad, bool filter_update) {
-    const int mb = m_pad / PB;
-    // (EKFVIO_SCHUR=1 takes precedence over the persistent launch, for every sweep of the handle; not in the split sweep)
-    const bool schur_shape = f->schur && mb < EKF_SWEEP_SPLIT_MB;
-    if (schur_shape && filter_update) return SWEEP_SCHUR;
-    // (only for a device's sole handle: two persistent launches in flight together could starve each other of compute units)
-    if (f->sweep_mode == 2 && !schur_shape && live_handles_on(f->device) <= 1 && persist_shape(f, m_pad, n_pad))
-        // round 4: where the persistent sweep applies, the gather and the first tile are part of ITS launch (launch_persist_fused)
-        return (filter_update && f->fuse_sweep && f->fuse_gather) ? SWEEP_PERSIST_FUSED : SWEEP_PERSIST;
-    // EKFVIO_SWEEP_LA=0 (diagnostic): the two-launch split sweep (panel launch + tile launch per block step)
-    static const bool la_env = getenv("EKFVIO_SWEEP_LA") ? atoi(getenv("EKFVIO_SWEEP_LA")) != 0 : true;
-    // many tiles per step: panel blocks once per step in a launch of their own instead of twice per tile
-    return mb < EKF_SWEEP_SPLIT_MB ? SWEEP_STEP : la_env ? SWEEP_SPLIT_LA : SWEEP_SPLIT;
-}
-// a shape the persistent launch forms the gain for when it runs: behind any other sweep the tile kernel whose arithmetic that launch's
-// in-sweep gain shares (chol_persist.inc, gain_tile), so that a sequence gives the same bits whichever sweep its updates take (eight
-// handles on one GPU against each one's solo run, tests/test_gpu_shapes.py)
-static bool gain_tiles_shape(const ekfvio_filter* f, int m_pad, int n_pad) { return f->persist_gain && gain_in_sweep_shape(f, m_pad, n_pad); }
-
-UpdatePlan plan_raw_sweep(const ekfvio_filter* f, int m_pad, int n_pad) {
-    UpdatePlan p;
-    p.m = p.m_pad = m_pad, p.n_pad = n_pad;
-    p.sweep = choose_sweep(f, m_pad, n_pad, false);
-    p.gain = gain_tiles_shape(f, m_pad, n_pad) ? GAIN_TILES : GAIN_GEMM;
-    return p;
-}
-
-UpdatePlan plan_update(const ekfvio_filter* f, int m, bool m_on_device, float next_dt, bool recoverable) {
-    UpdatePlan p;
-    if (m_on_device) m = 2 * f->N;  // upper bound: sizes the launches; the kernels read the true count from f->info[2]
-    const int n = f->n, ld = f->ldp, m_pad = round_up(m > 0 ? m : 1, EKF_TILE), n_pad = round_up(n, EKF_TILE);
-    p.m = m, p.m_pad = m_pad, p.n_pad = n_pad, p.m_on_device = m_on_device, p.recoverable = recoverable;
-    if (m <= 0) return p;
-    p.sweep = choose_sweep(f, m_pad, n_pad, true);
-    // T = Sigma - X A^-1 X^T and K = X A^-1 as Schur tiles of the sweep (no gain GEMM, no first Joseph GEMM, no (H Sigma)^T)
-    const bool schur = p.sweep == SWEEP_SCHUR, fused = p.sweep == SWEEP_PERSIST_FUSED;
-    p.with_wt = !schur;
-    // The gather and the first diagonal tile's factorisation share a launch while that launch is a single round of
-    // workgroups at one per compute unit (gather_potrf_kernel); beyond that (N = 1024: thousands of gather
-    // workgroups) the gather wants several workgroups per compute unit and the two stay separate.
-    if (f->fuse_gather && !fused) {
-        const int gx = (std::max(ld, m_pad) + 255) / 256;
-        p.fused_gather = 1 + gx * ((m_pad + GC * GCI - 1) / (GC * GCI)) + (schur ? 0 : (m_pad / 64) * (ld / 64)) <= f->num_cus;
-    }
-    if (schur) return p.gain = GAIN_SCHUR, p.tail = TAIL_SCHUR, p;
-    p.t2_skip = t2_skip_owners(f, m_pad, n_pad);
-    if (p.t2_skip < 0) {
-        // the transposing workgroups of the fused launch stay and form the gain while the sweep runs, as long as (nearly) every workgroup of the
-        // launch finds a compute unit at once: they hold theirs to the end
-        p.gain = !gain_tiles_shape(f, m_pad, n_pad) ? GAIN_GEMM : fused ? GAIN_SWEEP : GAIN_TILES;
-        return p.tail = TAIL_JOSEPH, p;
-    }
-    p.tail = TAIL_T2;
-    p.t2_by_sweep = p.compact = fused;
-    p.gain = fused ? GAIN_SWEEP : GAIN2_T2_TILES;
-    // a device-resident run (capture_steps): the next process(dt)'s linearisation and mean propagation ride in the one GEMM's launch, in workgroups
-    // of their own behind the tiles' (K y is final: the gain tiles' partial sums); launch_predict then only propagates Sigma
-    const int lin_blocks = (f->N + LIN_LM - 1) / LIN_LM + 1;
-    if (next_dt >= 0.f && f->lin_overlap && f->cfg.predict_mode != EKFVIO_PREDICT_DENSE && f->fuse_linearize &&
-        gemm_single_round_with(f, n, n, m_pad, 1 + lin_blocks))
-        p.lin_blocks = lin_blocks;
-    return p;
-}
-
 // What every launch that takes PersistArgs shares: the swept matrix and its block geometry, the gain's destination, the column signs, Sigma
 // and T2.  With S (chol_persist_kernel, which hands tiles over inside the launch) also the flags, the wait bounds and the fault-injection
 // hook's workgroup: the hook counts owners from workgroup 1, `lead_wgs` more workgroups come in front of them
@@ -1251,8 +1130,8 @@ static PersistArgs persist_args(ekfvio_filter* f, const UpdatePlan& p, float* L,
     pa.ready = f->sweep_sync, pa.fin = pa.ready + mb, pa.pan = pa.fin + rows * mb, pa.abort_flag = pa.pan + rows * mb + 1;
     pa.dbg = f->sweep_dbg;
     pa.bound.spin_limit = f->sweep_spin_limit > 0 ? f->sweep_spin_limit : SWEEP_SPIN_LIMIT;
-    pa.bound.wait_ticks = p.recoverable ? f->sweep_wait_ticks : std::max(f->sweep_wait_ticks, SWEEP_WAIT_TICKS_UNRECOVERABLE);
-    pa.early_sources = f->persist_early;
+    pa.bound.wait_ticks = p.recoverable ? f->tune.sweep_wait_ticks : std::max(f->tune.sweep_wait_ticks, SWEEP_WAIT_TICKS_UNRECOVERABLE);
+    pa.early_sources = f->tune.persist_early;
     pa.stall_wg = f->sweep_stall_wg >= 0 ? f->sweep_stall_wg + lead_wgs : -1;
     return pa;
 }

@@ -26,7 +26,7 @@
 // fault-injection hook's bound) the abort word is raised, every wait
 // falls through and info bit 1 reports it (the grid always drains); the kernels behind the sweep then leave Sigma and mu
 // untouched and the host runs the update again with one launch per block step (EKFVIO_EABORTED, api.hip finish_update).  The grid must be co-resident: the launcher admits the
-// path only when 1 + helpers <= compute units and the handle is alone on its device (chol.hip, choose_sweep); the
+// path only when 1 + helpers <= compute units and the handle is alone on its device (plan.h, choose_sweep); the
 // flags are zeroed by the launch in front (gather_potrf_kernel) or, in the test hook, by a memset.
 //
 // Bits: a tile receives its steps in ascending order, one subtraction of a k-ascending MFMA product per step, and the panel

@@ -9,23 +9,17 @@
 #include <vector>
 
 #include "../../include/ekfvio.h"
+#include "plan.h"  // HIP-free: the switches (Tuning), the sizes a capacity implies, the flow of an update (UpdatePlan, plan_update)
 #ifdef EKFVIO_TEST_HOOKS
 #include "../../include/ekfvio_test_hooks.h"
 #endif
 
-#define EKF_BASE 22
-#define EKF_TILE 64  // block size of every blocked algorithm (GEMM tile edge, Cholesky nb)
 // prune(SPARSE_THRESH, SPARSE_EPS) keeps |x| > 1e-8f*1e-5f (TightlyCoupledEKF.h:13-14, .cpp:117,580,591,625)
 #ifndef EKF_POTRF_FV
 #define EKF_POTRF_FV 12       // factor-phase variant of potrf64_lds (chol.hip): 12 = generated stream incl. its LDS traffic, LDS latency off the
                               // pivot chain (gen_ls3); 13 = the same with wider fill slots; 10 = round 1's stream; 8 = without the LDS traffic; 0 = plain
 #endif
-#ifndef EKF_SWEEP_SPLIT_MB
-#define EKF_SWEEP_SPLIT_MB 16  // from this many 64-wide block steps on, the sweep solves each panel block once (chol.hip)
-#endif
 #define EKF_FLUSH_THRESH (1e-8f * 1e-5f)
-
-static inline int round_up(int x, int m) { return (x + m - 1) / m * m; }
 
 // Kernel classes for the built-in event profiler (ekfvio_profile_*).
 enum ProfClass {
@@ -69,9 +63,8 @@ struct ekfvio_filter {
 
     int N = 0;      // landmarks
     int n = EKF_BASE;
-    int n_cap = 0;  // 22 + 3*max_features
-    int ldp = 0;    // leading dimension of every n-row matrix (multiple of 64)
-    int m_cap = 0;  // 2*max_features rounded up to 64; leading dimension of S/L
+    int n_cap = 0, ldp = 0, m_cap = 0;  // filter_dims(cfg.max_features), plan.h (as ld_aug and sweep_sync_words below)
+    Tuning tune;    // the run-time switches: written once, in ekfvio_create (plan.h, tuning_from_env)
 
     // --- state (device) ---
     float* mu = nullptr;       // [ldp]  base (22) then [u,v,1/d] per landmark
@@ -103,48 +96,27 @@ struct ekfvio_filter {
     float* Linv = nullptr;     // [64*m_cap] inverses of the 16x16 diagonal blocks of L
     unsigned long long* Lsign = nullptr;  // [>= m_cap/64] per block column: mask of negative pivots (0 = positive definite block)
     int* sweep_sync = nullptr; // flags of the persistent sweep: ready[mb], fin[row blocks x mb], abort word (sweep_sync_words ints)
-    int sweep_mode = 2;        // 2: ONE persistent launch with per-tile hand-offs behind the first diagonal tile (chol_persist.inc), where it pays and
-                               // applies (3 .. 15 block columns, grid co-resident; two block columns: 43.5 against 43.0 us per step); 0 (EKFVIO_SWEEP=0): one launch per block step
     size_t sweep_sync_words = 0;
+    bool sweep_latched_off = false;  // an aborted persistent sweep has retired the persistent launch (sweep_abort_latch sets it, sweep_maybe_retry clears it)
     bool prelinearized = false;   // the update's last GEMM linearised for the next process(dt) (UpdateInputs::next_dt): FA / FB / FD / mu_next hold its Jacobian
-                                  // blocks and propagated mean (launch_predict then skips its own)
-    int lin_overlap = 1;          // EKFVIO_LIN_OVERLAP=0 turns that off (A/B)
-    int sym_joseph = 1;           // EKFVIO_SYM_JOSEPH=0: the second Joseph GEMM of the throughput regime forms both triangles (rounds 1-5)
-    int gemm_order2d = 1;         // EKFVIO_GEMM_ORDER2D=0: the 64 x 64 GEMM's tiles in block-index order (rounds 1-4)
+                                  // blocks and propagated mean (launch_predict then skips its own); Tuning::lin_overlap
     long long persistent_sweeps = 0;  // sweeps enqueued (or captured) as chol_persist_kernel: ekfvio_test_persistent_sweeps
     long long schur_sweeps = 0;       // sweeps enqueued with Sigma and the gain as Schur tiles (EKFVIO_SCHUR=1): ekfvio_test_sweep_counts
     long long sweep_recoveries = 0;   // updates run again with the per-step sweep behind an aborted persistent launch
-    int early_outputs = 1;            // EKFVIO_EARLY_OUTPUTS: a frame's outputs and status go out between the update's two Joseph GEMMs (klt.hip)
-    long long early_output_frames = 0;  // frames whose outputs went out that way (test hook)
+    long long early_output_frames = 0;  // frames whose outputs went out between the update's two Joseph GEMMs (Tuning::early_outputs; test hook)
     int sweep_spin_limit = 0;         // > 0: looks per wait of the persistent sweep (test hook ekfvio_test_sweep_fault); 0: SWEEP_SPIN_LIMIT
     int sweep_stall_wg = -1;          // fault injection: this workgroup of the persistent launch never raises its flag
-    int early_status = 1;              // EKFVIO_EARLY_STATUS: ekfvio_update returns behind the sweep, the Joseph GEMMs still running (api.hip)
-    int upload_kernel = 1;             // EKFVIO_UPLOAD_KERNEL: the frame's trip to device memory is a kernel reading mapped host memory (klt.hip)
-    bool sweep_retry_armed = false;    // an aborted persistent sweep latched sweep_mode to 0: tried again at sweep_retry_at (api.hip, sweep_maybe_retry)
-    double sweep_retry_pause_s = 0.0, sweep_retry_first_s = 2.0;
+    bool sweep_retry_armed = false;    // sweep_latched_off is tried again at sweep_retry_at (api.hip, sweep_maybe_retry)
+    double sweep_retry_pause_s = 0.0;  // (its first value: Tuning::sweep_retry_first_s)
     int sweep_probation = 0;           // > 0: clean persistent sweeps still to come behind a retry before sweep_retry_pause_s starts over (api.hip)
-    int sweep_wait_ticks = 300000;     // the persistent sweep's patience per wait in 100 MHz ticks (3 ms; EKFVIO_SWEEP_WAIT_MS) where an aborted update
-                                       // is run again at once (ekfvio_update, ekfvio_step_image); a device-resident run (ekfvio_run_uploaded), which
-                                       // cannot, waits SWEEP_WAIT_TICKS_UNRECOVERABLE (100 ms): the counter also runs while a healthy sweep's
-                                       // wavefronts are descheduled (time slicing, a profiler's serialisation), ADVICE r05
     std::chrono::steady_clock::time_point sweep_retry_at;
     bool graph_leaves_flags_clean = false;  // sweep_flags_clean as a replay of the captured step graphs leaves it (api.hip, capture_steps)
     bool sweep_flags_clean = false;   // the persistent sweep's flags are zero for the launch enqueued next (zeroed by the last GEMM of the
                                       // previous update); otherwise gather_potrf_kernel zeroes them in front, or launch_update has a memset enqueued
-    int fuse_sweep = 1;               // 1: gather + first diagonal tile + sweep in ONE launch where the persistent sweep applies (EKFVIO_FUSE_SWEEP)
     bool persist_attr_set = false;
     bool gain2_attr_set = false;
-    int persist_oversub = 0;          // > 0 (EKFVIO_PERSIST_OVERSUB): owner workgroups allowed per compute unit's worth of the persistent launch (chol.hip, persist_shape)
-    int persist_gain = 1;             // 1 (EKFVIO_PERSIST_GAIN=0 turns it off): the gain's tiles are formed inside the fused persistent launch (chol_persist.inc)
-    int persist_early = 1;            // 1 (EKFVIO_PERSIST_EARLY=0 turns it off): owners fetch their panel sources in front of the wait for ready[k] (chol_persist.inc)
-    int fuse_gather = 1;       // 1: the gather and the first diagonal tile's factorisation share a launch (EKFVIO_FUSE_GATHER)
     bool gather_attr_set = false;
-    int t2_flow = 1;           // 1 (EKFVIO_T2=0 turns it off): where the fused persistent launch forms the gain, freed owners also form T2 = Sigma (I - K H)^T
-                               // (chol_persist.inc, t2_tile): Sigma' = T2 + K G'^T is the ONE P-update GEMM behind the launch (round 6)
     long long t2_updates = 0;  // updates enqueued (or captured) with the T2 flow: ONE P-update GEMM behind the sweep (ekfvio_get_counters [5])
-    int schur = 0;             // 1 (EKFVIO_SCHUR=1): T2 and K as Schur tiles of the sweep; 0: gain GEMM + first Joseph GEMM behind it.
-                               // Measured equal in step time at N = 256, so the simpler flow is the default.
-    int fuse_linearize = 1;    // 1: structured process(dt) is one launch, the Jacobian blocks are formed inside it (EKFVIO_FUSE_LINEARIZE)
     int num_cus = 0;
     int last_m = 0;            // measurement rows of the most recent update (shape of its GEMMs)
     long long* sweep_dbg = nullptr;  // [512] s_memtime stamps of the persistent sweep (diagnostic; null = off)
@@ -168,7 +140,6 @@ struct ekfvio_filter {
     // waits with wait_status: no device-to-host copy into pageable memory, no interrupt-driven synchronise
     float* h_out = nullptr;    // pinned, device-mapped: EKF_BASE + 4 * max_features floats
     float* d_out = nullptr;    // the device's address of h_out
-    int frame_outputs = 1;     // 1: ekfvio_step_image's last kernel also writes the node's outputs (EKFVIO_FRAME_OUTPUTS=0: status word only)
     bool out_fresh = false;    // h_out holds base_mu and the point cloud of the CURRENT state and frame: ekfvio_step_image's last
                                // kernel writes them with the status word, and every call that changes the state or the frame
                                // clears the flag; while it is set the node's getters cost a memcpy
@@ -219,7 +190,6 @@ struct ekfvio_filter {
     float* graph_mu = nullptr;      // orientation of the mean / covariance ping-pong at capture time
     float* graph_P = nullptr;
     const void* graph_seq = nullptr;
-    int use_graph = 1;
 
     // --- profiler ---
     bool prof_on = false;
@@ -278,11 +248,6 @@ struct GemmEpi {
 void launch_gemm(ekfvio_filter* f, int transB, int M, int N, int K, float alpha, const float* A, int lda, const float* B,
                  int ldb, float beta, const float* Cin, int ldcin, float* C, int ldc, int flush, int lowerB = 0,
                  const GemmEpi* epi = nullptr);
-
-bool gemm_throughput_regime(const ekfvio_filter* f, int M, int N, int K);
-// would launch_gemm run A * B^T of this shape as ONE wave of gemm16_kernel workgroups with `extra` more workgroups still inside that wave?
-bool gemm_single_round_with(const ekfvio_filter* f, int M, int N, int K, int extra);
-#define LIN_LM 8  // landmarks per linearising workgroup (32 lanes each; motion_model.inc)
 
 // same, selecting a tile configuration (0 = production default chosen by shape)
 void launch_gemm_variant(ekfvio_filter* f, int variant, int transB, int M, int N, int K, float alpha, const float* A, int lda,
@@ -371,44 +336,29 @@ int add_features_device(ekfvio_filter* f, int k);
 void add_features_enqueue_device_count(ekfvio_filter* f, const int* count_dev);  // enqueue only; the caller updates N / n
 int replenish_enqueue(ekfvio_filter* f, int* enqueued);  // fast.hip: FAST + first-fit selection, count left in f->fast_counts[1]
 
-// The flow of ONE update, decided in one place (chol.hip, plan_update) and handed to the launchers as a value: they execute, they do not decide.
-enum SweepKind { SWEEP_NONE,           // no measurement
-                 SWEEP_SCHUR,          // one launch per block step, T2 (in place in f->P) and K (f->Km) as Schur tiles of the sweep (EKFVIO_SCHUR=1)
-                 SWEEP_PERSIST_FUSED,  // gather + first diagonal tile + persistent sweep in ONE launch (launch_persist_fused)
-                 SWEEP_PERSIST,        // the persistent launch behind a front of its own
-                 SWEEP_STEP,           // one launch per block step
-                 SWEEP_SPLIT, SWEEP_SPLIT_LA };  // m_pad >= 64 * EKF_SWEEP_SPLIT_MB: panel blocks solved once; _LA: as look-ahead tile tasks (chol_step_la.inc)
-enum GainBy { GAIN_SWEEP, GAIN_TILES, GAIN2_T2_TILES, GAIN_GEMM, GAIN_SCHUR };  // the sweep itself / gain_tiles_kernel / gain2_t2_tiles_kernel / launch_gemm / Schur tiles + joseph_g_kernel
-enum UpdateTail { TAIL_NONE, TAIL_SCHUR, TAIL_T2, TAIL_JOSEPH };  // ONE GEMM from the Schur tiles' T2 in f->P / ONE GEMM from t2_buffer / the two Joseph GEMMs
-struct UpdatePlan {
-    int m = 0, m_pad = 64, n_pad = 0;  // m: 2N with m_on_device (sizes the launches; the kernels read the true count from f->info[2])
-    bool m_on_device = false, recoverable = true;  // (UpdateInputs)
-    SweepKind sweep = SWEEP_NONE;
-    bool fused_gather = false;  // the gather and the first diagonal tile's factorisation share a launch (gather_potrf_kernel)
-    bool with_wt = false;       // the gather also transposes (H Sigma)^T into Wt (only the first Joseph GEMM reads it)
-    GainBy gain = GAIN_GEMM;
-    UpdateTail tail = TAIL_NONE;
-    int t2_skip = -1;           // PersistArgs::t2_skip (>= 0: the shape takes the T2 flow)
-    bool t2_by_sweep = false, compact = false;  // PersistArgs::t2, ::compact
-    int lin_blocks = 0;         // > 0: the last GEMM linearises for the next process(dt) in that many extra workgroups (GemmEpi::lin_blocks)
-    // chol_persist_kernel runs: its abort word goes into the GEMM epilogues, the last GEMM zeroes its flags for the next update, and in
-    // front gather_potrf_kernel zeroes them (fused_gather) or a memset does unless they are clean (ekfvio_filter::sweep_flags_clean)
-    bool persistent() const { return sweep == SWEEP_PERSIST_FUSED || sweep == SWEEP_PERSIST; }
-};
-UpdatePlan plan_update(const ekfvio_filter* f, int m, bool m_on_device = false, float next_dt = -1.f, bool recoverable = true);
+int live_handles_on(int device);  // api.hip: handles alive on that device in this process
+// The flow of ONE update is decided in one place (plan.h, plan_update: a pure function of the handle's Tuning, a PlanShape and the row count) and handed
+// to the launchers as a value: they execute, they do not decide.  This is the ONE adapter from a handle to what a plan may depend on; the handle
+// count is asked per plan (capture_steps and ekfvio_run_uploaded re-capture on it: graph_sole), never cached.
+inline PlanShape plan_shape(const ekfvio_filter* f) {
+    PlanShape s;
+    s.num_cus = f->num_cus, s.ldp = f->ldp, s.sweep_sync_words = f->sweep_sync_words, s.N = f->N, s.n = f->n;
+    s.dense_predict = f->cfg.predict_mode == EKFVIO_PREDICT_DENSE;
+    s.sole_handle = live_handles_on(f->device) <= 1;
+    s.latched_off = f->sweep_latched_off;
+    return s;
+}
+inline UpdatePlan plan_update(const ekfvio_filter* f, int m, bool m_on_device = false, float next_dt = -1.f, bool recoverable = true) {
+    return plan_update(f->tune, plan_shape(f), m, m_on_device, next_dt, recoverable);
+}
 // The P-update GEMM launches of an update with plan p, `reps` times, into scratch (P2, Gm): the
 // filter state is not touched.  For timing the kernel under its production shape (ekfvio_profile_update_gemms).
 int launch_update_gemms_scratch(ekfvio_filter* f, const UpdatePlan& p, int reps);  // returns the GEMM launches per repetition (2 with the two-GEMM tail, else 1)
-// ... and of a sweep over matrices that are not the filter's (ekfvio_test_cholesky_solve): the same choice of sweep for [A; X; I] with m_pad
-// columns and n_pad rows of X, without the update's front, Schur tiles and tail; the gain by gain_tiles_kernel or the gain GEMM
-UpdatePlan plan_raw_sweep(const ekfvio_filter* f, int m_pad, int n_pad);
 // Augmented blocked Cholesky sweep (chol.hip): Saug = [A; X; I] (row blocks of 64; A is
 // m_pad x m_pad, X has n_pad rows) -> Laug = [L; X L^-T; L^-T], both ld x m_pad column-major.
 // zero_flags: a memset of the persistent sweep's flags goes in front.  Returns the abort word of the persistent launch (null: another sweep)
 const int* launch_chol_sweep(ekfvio_filter* f, const UpdatePlan& p, float* Saug, float* Laug, float* Linv, int ld, bool zero_flags);
 const int* launch_persist_fused(ekfvio_filter* f, const UpdatePlan& p, bool zero_flags);
-int persist_zero_words(int m_pad, int n_pad);
-int live_handles_on(int device);  // api.hip: handles alive on that device in this process
 // K pruned, G = K R - T[:, idx], K y partial sums (one row of f->Wt per 64 measurement columns)
 void launch_joseph_g(ekfvio_filter* f, int m, int m_pad, int n_pad, bool m_on_device, const float* T = nullptr);  // T: the covariance G' is taken from (null: f->P)
 // Where T2 lives between the sweep and the one GEMM behind it: the dense-F buffer, dead during an update in either predict mode (the dense

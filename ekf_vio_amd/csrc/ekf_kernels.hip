@@ -768,7 +768,7 @@ void launch_predict(ekfvio_filter* f, float dt, const BookArgs* book) {
     // propagated mean are in place, the propagation kernel only carries the bookkeeping along
     const bool pre = f->prelinearized && f->cfg.predict_mode != EKFVIO_PREDICT_DENSE;
     f->prelinearized = false;
-    const bool lin_in_predict = !pre && f->cfg.predict_mode != EKFVIO_PREDICT_DENSE && f->fuse_linearize && tiles_side * tiles_side <= 4 * f->num_cus;
+    const bool lin_in_predict = !pre && f->cfg.predict_mode != EKFVIO_PREDICT_DENSE && f->tune.fuse_linearize && tiles_side * tiles_side <= 4 * f->num_cus;
     if (!lin_in_predict && !pre) launch_linearize(f, dt, book);
     const int n = f->n, ld = f->ldp;
     dim3 grid((n + 255) / 256, n);
@@ -848,7 +848,7 @@ UpdateResult launch_update(ekfvio_filter* f, const UpdateInputs& in) {
     GemmEpi e2;  // of the update's last GEMM
     e2.mode = 2, e2.mu = f->mu, e2.Pcol = f->P + (size_t)n * ld, e2.n = n;
     e2.frame_counter = in.frame_counter, e2.frames = in.frames;
-    e2.sym = f->sym_joseph;  // (heeded by the throughput-regime kernel behind the two-GEMM flow: gemm.hip)
+    e2.sym = f->tune.sym_joseph;  // (heeded by the throughput-regime kernel behind the two-GEMM flow: gemm.hip)
     e2.abort = abort;        // a persistent sweep that gave up: the GEMMs write nothing (T2, K, G' are scratch)
     if (p.persistent()) {    // ... and one that ran: the update's last GEMM leaves its flags zero for the next one
         e2.zero_words = f->sweep_sync, e2.n_zero = persist_zero_words(m_pad, n_pad);
@@ -903,7 +903,7 @@ int launch_update_gemms_scratch(ekfvio_filter* f, const UpdatePlan& p, int reps)
     }
     e1.mode = 1, e1.inv_idx = f->inv_idx, e1.Rm = f->Rm, e1.G = f->Gm, e1.ldg = ld;
     e2.mode = 2;  // n = 0: no mean update, no frame counter
-    e2.sym = f->sym_joseph;
+    e2.sym = f->tune.sym_joseph;
     for (int r = 0; r < reps; r++) {
         launch_gemm(f, 1, n, n + 1, m_pad, -1.f, f->Km, ld, f->Wt, ld, 1.f, f->P, ld, f->P2, ld, 0, 0, &e1);
         launch_gemm(f, 1, n, n, m_pad, 1.f, f->Gm, ld, f->Km, ld, 1.f, f->P2, ld, f->P2, ld, 1, 0, &e2);

@@ -29,9 +29,7 @@ struct GatherArgs {
     int n_zero;
 };
 
-#define GC 4   // measurement columns whose loads one element workgroup keeps in flight together
-#define GCI 4  // ... and how many such groups it walks through (GC*GCI columns per workgroup)
-
+// (GC, GCI: plan.h -- the plan counts these workgroups too)
 // S(c,r) = Sigma(idx[c], idx[r]) + R(c,r), identity outside the measured block: element (r,c) of A = S^T
 __device__ __forceinline__ float gather_a_elem(float sigma_cr, int r, int c, int m, float rd, float ro) {
     if (r < m && c < m) {
@@ -157,8 +155,8 @@ static GatherArgs make_gather_args(ekfvio_filter* f, const UpdatePlan& p) {
     a.zrow = f->yres;
     a.mu = f->mu;
     a.G = f->Gm;
-    a.gx = ((f->ldp > m_pad ? f->ldp : m_pad) + 255) / 256;
-    a.nb1 = a.gx * ((m_pad + GC * GCI - 1) / (GC * GCI));
+    a.gx = gather_gx(f->ldp, m_pad);
+    a.nb1 = gather_element_wgs(f->ldp, m_pad);
     a.zero_words = nullptr;
     a.n_zero = 0;
     return a;

@@ -873,21 +873,6 @@ __global__ __launch_bounds__(256 * WPS) void gemm16_kernel(int M, int N, int K, 
     GSTAMP(38);
 }
 
-// true where launch_gemm forms A * B^T with the 64 x 64 kernel (more 64-row tiles than compute units): the regime in which GemmEpi::sym is heeded
-bool gemm_throughput_regime(const ekfvio_filter* f, int M, int N, int K) {
-    const int cus = f->num_cus > 0 ? f->num_cus : 256;
-    return !(K % 64 == 0 && ((M + 63) / 64) * ((N + 63) / 64) <= cus);
-}
-
-bool gemm_single_round_with(const ekfvio_filter* f, int M, int N, int K, int extra) {
-    if (K % 64 != 0) return false;
-    const int cus = f->num_cus > 0 ? f->num_cus : 256;
-    const int ty = (N + 63) / 64;
-    for (int bm : {32, 48, 64})
-        if (((M + bm - 1) / bm) * ty <= cus) return ((M + bm - 1) / bm) * ty + extra <= cus;
-    return false;
-}
-
 // cfg: 0 = choose by shape; 1 / 2 = the 64x64 kernel with 256 / 512 threads; 32, 48, 64 = gemm16_kernel with that BM
 // (512 threads); +100 = the same with 256 threads
 static void launch_gemm_cfg(ekfvio_filter* f, int cfg, int transB, int M, int N, int K, float alpha, const float* A, int lda,
@@ -900,26 +885,17 @@ static void launch_gemm_cfg(ekfvio_filter* f, int cfg, int transB, int M, int N,
     e.stamps = f->gemm_stamps;
     const int cus = f->num_cus > 0 ? f->num_cus : 256;  // per handle: handles on different devices may differ
     const int ty = (N + 63) / 64;
-    auto tiles = [&](int bm) { return ((M + bm - 1) / bm) * ty; };
-    if (cfg == 0) {
-        cfg = 1;
-        if (transB && K % 64 == 0) {
-            // latency regime: the smallest tile height whose grid is still a single wave of workgroups
-            for (int bm : {32, 48, 64}) {
-                if (tiles(bm) <= cus) {
-                    cfg = bm;
-                    break;
-                }
-            }
-        }
+    if (cfg == 0) {  // latency regime: the smallest tile height whose grid is still a single wave of workgroups; else the 64 x 64 kernel (plan.h)
+        const int bm = gemm_tile_height(cus, M, N, K, transB != 0);
+        cfg = bm ? bm : 1;
     }
     if (cfg >= 32) {
         const int wps = cfg >= 100 ? 1 : 2;  // 132 / 148 / 164: one wavefront per SIMD (micro-benchmark only)
         const int bm = cfg % 100;
         const int tx = (M + bm - 1) / bm;
-        if (!(e.mode == 3 && e.n > 0) || tiles(bm) + 1 + e.lin_blocks > cus) e.lin_blocks = 0;  // (plan_update asked gemm_single_round_with first)
+        if (!(e.mode == 3 && e.n > 0) || gemm_tiles(bm, M, N) + 1 + e.lin_blocks > cus) e.lin_blocks = 0;  // (a plan's lin_blocks fit: gemm_single_round_with, plan.h)
         e.mean_keep = e.lin_blocks > 0 ? 1 : 0;
-        dim3 grid(tiles(bm) + ((e.mode == 2 || e.mode == 3) && e.n > 0 ? 1 : 0) + e.lin_blocks);  // (+1: gemm16_finish_mean; + the next step's linearisation)
+        dim3 grid(gemm_tiles(bm, M, N) + ((e.mode == 2 || e.mode == 3) && e.n > 0 ? 1 : 0) + e.lin_blocks);  // (+1: gemm16_finish_mean; + the next step's linearisation)
 #define GEMM16_GO(BMv, W, EP)                                                                                           \
     hipLaunchKernelGGL((gemm16_kernel<BMv, W, EP>), grid, dim3(256 * W), 0, s, M, N, K, alpha, A, lda, B, ldb, beta, Cin, ldcin, C, \
                        ldc, flush, lowerB, e, tx, ty)
@@ -950,7 +926,7 @@ static void launch_gemm_cfg(ekfvio_filter* f, int cfg, int transB, int M, int N,
     }
     // throughput regime (several tiles per compute unit and a full contraction per tile): compact 2-D patches per XCD.  Not for the
     // triangular-aware gain GEMM: its tiles' work falls with the tile column, and strips of columns would load the XCDs unevenly.
-    e.order2d = (!e.sym && f->gemm_order2d && !lowerB && (int)(grid.x * grid.y) >= 2 * cus) ? 1 : 0;
+    e.order2d = (!e.sym && f->tune.gemm_order2d && !lowerB && (int)(grid.x * grid.y) >= 2 * cus) ? 1 : 0;
 #define GEMM_GO(TB, G, EP)                                                                                             \
     hipLaunchKernelGGL((gemm_f32_mfma_kernel<TB, G, EP>), grid, dim3(256 * G), 0, s, M, N, K, alpha, A, lda, B, ldb, beta, \
                        Cin, ldcin, C, ldc, flush, lowerB, e)

@@ -1203,7 +1203,7 @@ static int push_frame_enqueue(ekfvio_filter* f, const uint8_t* image, int32_t wi
         for (int y = 0; y < height; y++) memcpy(f->h_image + (size_t)y * width, image + (size_t)y * stride, width);
     }
     hipStream_t st = f->stream;
-    const int upload_kernel = f->upload_kernel;  // (per handle, read at create)
+    const int upload_kernel = f->tune.upload_kernel;  // (per handle, read at create)
     if (upload_kernel) {
         const int n16 = (int)(((size_t)width * height + 15) / 16);
         void* dsrc = nullptr;  // the device's address of the mapped buffer (the same pointer under unified addressing; asked for, not assumed)
@@ -1427,7 +1427,7 @@ int ekfvio_step_image(ekfvio_filter* f, double stamp, const uint8_t* image, int3
         // Pcol): launch_update calls back there.  (With landmarks to add the selection reads the updated mean and the outputs carry the count:
         // behind the update, as before.  EKFVIO_EARLY_OUTPUTS=0: always behind.)
         // (Nor with cfg.remove_lost: the frame's final landmark count is known only behind the removal, as with a replenishing frame.)
-        if (f->early_outputs && f->frame_outputs && !(f->cfg.replenish && f->N < f->cfg.max_features) && !f->cfg.remove_lost &&
+        if (f->tune.early_outputs && f->tune.frame_outputs && !(f->cfg.replenish && f->N < f->cfg.max_features) && !f->cfg.remove_lost &&
             sizeof(float) * (size_t)f->n <= 48 * 1024) {  // (the updated mean is formed in LDS)
             in.between = [](ekfvio_filter* g, int kyp_blocks) {
                 const KltFrame& fr = g->frames[g->cur];
@@ -1476,7 +1476,7 @@ int ekfvio_step_image(ekfvio_filter* f, double stamp, const uint8_t* image, int3
     // the frame's one wait: the status word, the number of new landmarks and what the node publishes after addFrame
     // (odometry, point cloud) arrive together in pinned host memory (frame_outputs_kernel)
     int bad = 0, added = 0;
-    if (!f->frame_outputs) {
+    if (!f->tune.frame_outputs) {
         rc = wait_status(f, &bad, count_dev, &added);
     } else {
         const KltFrame& fr = f->frames[f->cur];
@@ -1495,7 +1495,7 @@ int ekfvio_step_image(ekfvio_filter* f, double stamp, const uint8_t* image, int3
         }
     }
     if (rc != EKFVIO_OK) return rc;
-    f->out_fresh = f->frame_outputs != 0;
+    f->out_fresh = f->tune.frame_outputs != 0;
     if (removing) remove_applied(f, 0, __atomic_load_n(&f->h_info[3], __ATOMIC_ACQUIRE));  // (the count of landmarks: below, with `added`)
     if (bad) HIPK(f, hipMemsetAsync(f->info, 0, sizeof(int), f->stream));
     if (bad & 2) {

@@ -1,0 +1,294 @@
+// ekf_vio_amd/csrc/plan.h — everything that DECIDES: the run-time switches, the sizes a capacity implies, and the flow of one update.
+// Standard headers only (no HIP, no project header): integer arithmetic over a Tuning, a PlanShape and a row count, so the decision
+// table of the product is checked on a machine without a GPU (include/ekfvio_test_hooks.h, ekfvio_test_plan; tests/test_plan_cpu.py).
+// The launchers (chol.hip, ekf_kernels.hip, gemm.hip) execute an UpdatePlan; they do not decide.
+#ifndef EKFVIO_PLAN_H_
+#define EKFVIO_PLAN_H_
+#include <stddef.h>
+#include <stdlib.h>
+
+#include <algorithm>
+
+#define EKF_BASE 22
+#define EKF_TILE 64  // block size of every blocked algorithm (GEMM tile edge, Cholesky nb; chol.hip's PB)
+#ifndef EKF_SWEEP_SPLIT_MB
+#define EKF_SWEEP_SPLIT_MB 16  // from this many 64-wide block steps on, the sweep solves each panel block once (chol.hip)
+#endif
+#define LIN_LM 8  // landmarks per linearising workgroup (32 lanes each; motion_model.inc)
+#define GC 4      // measurement columns whose loads one element workgroup of the gather keeps in flight together (gather_body.inc)
+#define GCI 4     // ... and how many such groups it walks through (GC*GCI columns per workgroup)
+
+static inline int round_up(int x, int m) { return (x + m - 1) / m * m; }
+
+// ---- the switches --------------------------------------------------------------------------------------------------------------
+// Read ONCE per handle, in ekfvio_create; every member's default is the production flow.
+struct Tuning {
+    int early_status = 1;    // EKFVIO_EARLY_STATUS: ekfvio_update returns behind the sweep, the Joseph GEMMs still running (api.hip); 0: behind the update's last kernel (rounds 1-3)
+    int upload_kernel = 1;   // EKFVIO_UPLOAD_KERNEL: the frame's trip to device memory is a kernel reading mapped host memory (klt.hip); 0: the copy engine
+    int sweep_wait_ticks = 300000;  // the persistent sweep's patience per wait in 100 MHz ticks (3 ms; EKFVIO_SWEEP_WAIT_MS) where an aborted update
+                                    // is run again at once (ekfvio_update, ekfvio_step_image); a device-resident run (ekfvio_run_uploaded), which
+                                    // cannot, waits SWEEP_WAIT_TICKS_UNRECOVERABLE (100 ms): the counter also runs while a healthy sweep's
+                                    // wavefronts are descheduled (time slicing, a profiler's serialisation), ADVICE r05
+    double sweep_retry_first_s = 2.0;  // EKFVIO_SWEEP_RETRY_S: the first pause before a handle whose persistent sweep gave up tries it again
+    int persist_sweep = 1;   // 1: ONE persistent launch with per-tile hand-offs behind the first diagonal tile (chol_persist.inc), where it pays and applies
+                             // (3 .. 15 block columns, grid co-resident; two block columns: 43.5 against 43.0 us per step); EKFVIO_SWEEP=0: one launch per block step
+    int sweep_la = 1;        // EKFVIO_SWEEP_LA=0 (diagnostic): the two-launch split sweep (panel launch + tile launch per block step)
+    int fuse_gather = 1;     // 1: the gather and the first diagonal tile's factorisation share a launch (EKFVIO_FUSE_GATHER)
+    int fuse_sweep = 1;      // 1: gather + first diagonal tile + sweep in ONE launch where the persistent sweep applies (EKFVIO_FUSE_SWEEP; 0: two launches, round 3)
+    int t2_flow = 1;         // 1 (EKFVIO_T2=0 turns it off: rounds 4-5): where the fused persistent launch forms the gain, freed owners also form T2 = Sigma (I - K H)^T
+                             // (chol_persist.inc, t2_tile): Sigma' = T2 + K G'^T is the ONE P-update GEMM behind the launch (round 6)
+    int schur = 0;           // 1 (EKFVIO_SCHUR=1): T2 and K as Schur tiles of the sweep; 0: gain GEMM + first Joseph GEMM behind it.
+                             // Measured equal in step time at N = 256, so the simpler flow is the default.
+    int persist_oversub = 0; // > 0 (EKFVIO_PERSIST_OVERSUB): owner workgroups allowed per compute unit's worth of the persistent launch (persist_shape)
+    int persist_gain = 1;    // 1 (EKFVIO_PERSIST_GAIN=0 turns it off): the gain's tiles are formed inside the fused persistent launch (chol_persist.inc)
+    int persist_early = 1;   // 1 (EKFVIO_PERSIST_EARLY=0 turns it off): owners fetch their panel sources in front of the wait for ready[k] (chol_persist.inc)
+    int frame_outputs = 1;   // 1: ekfvio_step_image's last kernel also writes the node's outputs (EKFVIO_FRAME_OUTPUTS=0: status word only)
+    int early_outputs = 1;   // EKFVIO_EARLY_OUTPUTS: a frame's outputs and status go out between the update's two Joseph GEMMs (klt.hip); 0: behind its last kernel
+    int gemm_order2d = 1;    // EKFVIO_GEMM_ORDER2D=0: the 64 x 64 GEMM's tiles in block-index order (rounds 1-4)
+    int lin_overlap = 1;     // EKFVIO_LIN_OVERLAP=0: every process(dt) of a device-resident run linearises for itself (rounds 3-5)
+    int sym_joseph = 1;      // EKFVIO_SYM_JOSEPH=0: the second Joseph GEMM of the throughput regime forms both triangles (rounds 1-5)
+    int fuse_linearize = 1;  // 1: structured process(dt) is one launch, the Jacobian blocks are formed inside it (EKFVIO_FUSE_LINEARIZE; 0: two launches)
+};
+
+// The ONE place the environment is read for a switch.  FLAG: atoi(e) ? 1 : 0; RAW: atoi(e); WAIT_MS: only if atof(e) > 0, in 100 MHz
+// ticks; POSITIVE: only if atof(e) > 0.
+inline Tuning tuning_from_env() {
+    enum Kind { FLAG, RAW, WAIT_MS, POSITIVE };
+    struct Entry {
+        const char* name;
+        Kind kind;
+        int Tuning::*i;
+        double Tuning::*d;
+    };
+    static const Entry table[] = {
+        {"EKFVIO_EARLY_STATUS", FLAG, &Tuning::early_status, nullptr},
+        {"EKFVIO_UPLOAD_KERNEL", FLAG, &Tuning::upload_kernel, nullptr},
+        {"EKFVIO_SWEEP_WAIT_MS", WAIT_MS, &Tuning::sweep_wait_ticks, nullptr},
+        {"EKFVIO_SWEEP_RETRY_S", POSITIVE, nullptr, &Tuning::sweep_retry_first_s},
+        {"EKFVIO_SWEEP", FLAG, &Tuning::persist_sweep, nullptr},
+        {"EKFVIO_SWEEP_LA", FLAG, &Tuning::sweep_la, nullptr},
+        {"EKFVIO_FUSE_GATHER", FLAG, &Tuning::fuse_gather, nullptr},
+        {"EKFVIO_FUSE_SWEEP", FLAG, &Tuning::fuse_sweep, nullptr},
+        {"EKFVIO_T2", FLAG, &Tuning::t2_flow, nullptr},
+        {"EKFVIO_SCHUR", FLAG, &Tuning::schur, nullptr},
+        {"EKFVIO_PERSIST_OVERSUB", RAW, &Tuning::persist_oversub, nullptr},
+        {"EKFVIO_PERSIST_GAIN", FLAG, &Tuning::persist_gain, nullptr},
+        {"EKFVIO_PERSIST_EARLY", FLAG, &Tuning::persist_early, nullptr},
+        {"EKFVIO_FRAME_OUTPUTS", FLAG, &Tuning::frame_outputs, nullptr},
+        {"EKFVIO_EARLY_OUTPUTS", FLAG, &Tuning::early_outputs, nullptr},
+        {"EKFVIO_GEMM_ORDER2D", FLAG, &Tuning::gemm_order2d, nullptr},
+        {"EKFVIO_LIN_OVERLAP", FLAG, &Tuning::lin_overlap, nullptr},
+        {"EKFVIO_SYM_JOSEPH", FLAG, &Tuning::sym_joseph, nullptr},
+        {"EKFVIO_FUSE_LINEARIZE", FLAG, &Tuning::fuse_linearize, nullptr},
+    };
+    Tuning t;
+    for (const Entry& k : table) {
+        const char* e = getenv(k.name);
+        if (!e) continue;
+        if (k.kind == FLAG) t.*k.i = atoi(e) ? 1 : 0;
+        else if (k.kind == RAW) t.*k.i = atoi(e);
+        else if (atof(e) > 0) {
+            if (k.kind == WAIT_MS) t.*k.i = (int)std::min(2.0e9, 1e5 * atof(e));
+            else t.*k.d = atof(e);
+        }
+    }
+    return t;
+}
+
+// ---- the sizes a capacity implies ----------------------------------------------------------------------------------------------
+struct FilterDims {
+    int n_cap;   // 22 + 3*max_features
+    int ldp;     // leading dimension of every n-row matrix (multiple of 64); one spare row/column: the K*y column of the Joseph-1 GEMM
+    int m_cap;   // 2*max_features rounded up to 64; leading dimension of S/L
+    int ld_aug;  // m_cap + ldp + m_cap
+    size_t sweep_sync_words;  // flags of the persistent sweeps (chol_persist.inc): ready[mb] + 2 x [row blocks x mb] + abort word
+                              // (>= 1024: the test hooks sweep matrices that are not the filter's)
+};
+inline FilterDims filter_dims(int max_features) {
+    FilterDims d;
+    d.n_cap = EKF_BASE + 3 * max_features;
+    d.ldp = round_up(d.n_cap + 1, 64);
+    d.m_cap = round_up(2 * max_features > 0 ? 2 * max_features : 1, 64);
+    d.ld_aug = d.m_cap + d.ldp + d.m_cap;
+    const size_t mb2 = (size_t)(d.m_cap / 64);
+    d.sweep_sync_words = std::max((size_t)1024, mb2 + 2 * (size_t)(d.ld_aug / 64 + 1) * mb2 + 8);
+    return d;
+}
+
+// What a plan may depend on besides the Tuning and the row count -- and nothing else (common.h, plan_shape fills it from a handle).
+struct PlanShape {
+    int num_cus = 0;              // compute units of the handle's device
+    int ldp = 0;                  // FilterDims::ldp
+    size_t sweep_sync_words = 0;  // FilterDims::sweep_sync_words
+    int N = 0, n = EKF_BASE;      // landmarks in the state, and its dimension 22 + 3 N
+    bool dense_predict = false;   // cfg.predict_mode == EKFVIO_PREDICT_DENSE
+    bool sole_handle = true;      // the only live handle on its device in this process (api.hip, live_handles_on: evaluated per plan)
+    bool latched_off = false;     // an aborted persistent sweep has retired the persistent launch for now (api.hip, sweep_abort_latch)
+};
+
+// ---- shared small decisions of the launchers -----------------------------------------------------------------------------------
+// The tile height launch_gemm forms C[MxN] = A * op(B) with: 32 / 48 / 64 = gemm16_kernel at the smallest height whose grid is still a
+// single wave of workgroups (latency regime; only A * B^T with K a multiple of 64), 0 = the 64 x 64 kernel (throughput regime).
+inline int gemm_tiles(int bm, int M, int N) { return ((M + bm - 1) / bm) * ((N + 63) / 64); }
+inline int gemm_tile_height(int cus, int M, int N, int K, bool transB) {
+    if (cus <= 0) cus = 256;
+    if (!transB || K % 64 != 0) return 0;
+    for (int bm : {32, 48, 64})
+        if (gemm_tiles(bm, M, N) <= cus) return bm;
+    return 0;
+}
+// true where launch_gemm forms A * B^T with the 64 x 64 kernel (more 64-row tiles than compute units): the regime in which GemmEpi::sym is heeded
+inline bool gemm_throughput_regime(int cus, int M, int N, int K) { return gemm_tile_height(cus, M, N, K, true) == 0; }
+// would launch_gemm run A * B^T of this shape as ONE wave of gemm16_kernel workgroups with `extra` more workgroups still inside that wave?
+inline bool gemm_single_round_with(int cus, int M, int N, int K, int extra) {
+    const int bm = gemm_tile_height(cus, M, N, K, true);
+    return bm && gemm_tiles(bm, M, N) + extra <= (cus > 0 ? cus : 256);
+}
+// The gather's element workgroups (gather_body.inc): gx per GC*GCI measurement columns; the Wt tiles come behind them
+inline int gather_gx(int ldp, int m_pad) { return (std::max(ldp, m_pad) + 255) / 256; }
+inline int gather_element_wgs(int ldp, int m_pad) { return gather_gx(ldp, m_pad) * ((m_pad + GC * GCI - 1) / (GC * GCI)); }
+
+// ---- the flow of ONE update ----------------------------------------------------------------------------------------------------
+enum SweepKind { SWEEP_NONE,           // no measurement
+                 SWEEP_SCHUR,          // one launch per block step, T2 (in place in f->P) and K (f->Km) as Schur tiles of the sweep (EKFVIO_SCHUR=1)
+                 SWEEP_PERSIST_FUSED,  // gather + first diagonal tile + persistent sweep in ONE launch (launch_persist_fused)
+                 SWEEP_PERSIST,        // the persistent launch behind a front of its own
+                 SWEEP_STEP,           // one launch per block step
+                 SWEEP_SPLIT, SWEEP_SPLIT_LA };  // m_pad >= 64 * EKF_SWEEP_SPLIT_MB: panel blocks solved once; _LA: as look-ahead tile tasks (chol_step_la.inc)
+enum GainBy { GAIN_SWEEP, GAIN_TILES, GAIN2_T2_TILES, GAIN_GEMM, GAIN_SCHUR };  // the sweep itself / gain_tiles_kernel / gain2_t2_tiles_kernel / launch_gemm / Schur tiles + joseph_g_kernel
+enum UpdateTail { TAIL_NONE, TAIL_SCHUR, TAIL_T2, TAIL_JOSEPH };  // ONE GEMM from the Schur tiles' T2 in f->P / ONE GEMM from t2_buffer / the two Joseph GEMMs
+struct UpdatePlan {
+    int m = 0, m_pad = 64, n_pad = 0;  // m: 2N with m_on_device (sizes the launches; the kernels read the true count from f->info[2])
+    bool m_on_device = false, recoverable = true;  // (UpdateInputs)
+    SweepKind sweep = SWEEP_NONE;
+    bool fused_gather = false;  // the gather and the first diagonal tile's factorisation share a launch (gather_potrf_kernel)
+    bool with_wt = false;       // the gather also transposes (H Sigma)^T into Wt (only the first Joseph GEMM reads it)
+    GainBy gain = GAIN_GEMM;
+    UpdateTail tail = TAIL_NONE;
+    int t2_skip = -1;           // PersistArgs::t2_skip (>= 0: the shape takes the T2 flow)
+    bool t2_by_sweep = false, compact = false;  // PersistArgs::t2, ::compact
+    int lin_blocks = 0;         // > 0: the last GEMM linearises for the next process(dt) in that many extra workgroups (GemmEpi::lin_blocks)
+    // chol_persist_kernel runs: its abort word goes into the GEMM epilogues, the last GEMM zeroes its flags for the next update, and in
+    // front gather_potrf_kernel zeroes them (fused_gather) or a memset does unless they are clean (ekfvio_filter::sweep_flags_clean)
+    bool persistent() const { return sweep == SWEEP_PERSIST_FUSED || sweep == SWEEP_PERSIST; }
+};
+
+// layout: ready[mb], fin[rows x mb], pan[rows x mb] (panel blocks of the X / identity rows, for the gain tiles formed inside the
+// launch), one spare word, the abort word (last: whoever zeroes the flags for the next sweep leaves it alone, persist_zero_words);
+// a multiple of 16 bytes
+inline size_t persist_flag_words(int m_pad, int n_pad) {
+    const int mb = m_pad / EKF_TILE, rows = 2 * mb + n_pad / EKF_TILE;
+    return ((size_t)(mb + 2 * rows * mb + 2) + 3) & ~(size_t)3;
+}
+inline int persist_zero_words(int m_pad, int n_pad) {
+    const int mb = m_pad / EKF_TILE, rows = 2 * mb + n_pad / EKF_TILE;
+    return mb + 2 * rows * mb + 1;
+}
+// helpers of the persistent sweep (chol_persist.inc): per block column j the rows of A from the diagonal down (without
+// (1,1)), the X row blocks and the identity row blocks 0 .. j
+inline int persist_helpers(int mb, int nX, bool compact = false) {  // (compact: without the identity rows' diagonal tiles, chol_persist.inc)
+    int h = 0;
+    for (int j = 1; j < mb; j++) h += (mb - j - (j == 1 ? 1 : 0)) + nX + (j + 1 - (compact ? 1 : 0));
+    return h;
+}
+// The shapes the persistent launch takes: 3 .. EKF_SWEEP_SPLIT_MB - 1 block columns.  Up to round 3: chain + owners co-resident
+// (1 + tiles <= compute units).  Round 4: up to EKF_PERSIST_OVERSUB x that.  An owner waits only for workgroups with a LOWER block index
+// (the chain is workgroup 0, the owners are numbered block column by block column, and a tile's panel sources lie in earlier columns), so
+// with workgroups dispatched in index order -- what the hardware does, though HIP does not promise it -- the resident ones can always
+// finish, and the later columns' owners take over their compute units and catch up (their flags are all up: ~10 k cycles per step
+// against the chain's ~15.5 k).  N = 400 (params/fast_with_insight.yaml: 13 block columns, 407 owners) runs the sweep in one launch
+// this way.  Should the order ever not hold, the bounded waits end the launch and the update is run again per step (EKFVIO_EABORTED).
+// Measured (profiles/r04_oversubscribed_persistent_sweep.txt): bit-identical, the sweep itself 155.7 -> 121.2 us at N = 400, but the gain
+// kernel behind it then runs 2x longer on operands the persistent launch has left in other XCDs' L2s; +2.9 % per step in all.  Off by
+// default (1); EKFVIO_PERSIST_OVERSUB=2 turns it on, tests/test_gpu_parity.py exercises it.
+#ifndef EKF_PERSIST_OVERSUB
+#define EKF_PERSIST_OVERSUB 1
+#endif
+inline bool persist_shape(const Tuning& t, const PlanShape& s, int m_pad, int n_pad) {
+    const int mb = m_pad / EKF_TILE;
+    const int over = t.persist_oversub > 0 ? t.persist_oversub : EKF_PERSIST_OVERSUB;
+    return mb >= 3 && mb < EKF_SWEEP_SPLIT_MB && 1 + persist_helpers(mb, n_pad / EKF_TILE) <= (over > 1 ? over : 1) * s.num_cus &&
+           persist_flag_words(m_pad, n_pad) <= s.sweep_sync_words;
+}
+// ... and of those, the shapes whose gain is formed inside the fused launch: (nearly) every workgroup of that launch finds a compute unit
+// at once (the transposing / gain workgroups hold theirs to the end).  Behind every other sweep of such a shape gain_tiles_kernel runs
+// the same arithmetic; all other shapes take the gain GEMM, whichever sweep ran.
+inline bool gain_in_sweep_shape(const Tuning& t, const PlanShape& s, int m_pad, int n_pad) {
+    const int mb = m_pad / EKF_TILE;
+    return persist_shape(t, s, m_pad, n_pad) && 1 + mb * (s.ldp / 64) + 2 + persist_helpers(mb, n_pad / EKF_TILE) <= s.num_cus + 8;
+}
+// ... and of those, the shapes whose T2 = Sigma (I - K H)^T is formed by freed owners inside the launch (round 6, chol_persist.inc, t2_tile): there
+// must be an owner per tile pair once enough of the first owners have LEFT for every workgroup of the launch to find a compute unit (the two
+// step-0 gatherers and the gain workgroups beyond the state's row blocks leave at once).  Returns the number of owners that leave (PersistArgs::t2_skip),
+// -1 where the flow does not apply.  The flow is a property of the SHAPE, not of the sweep that runs: behind a per-step sweep of such a shape
+// gain2_t2_tiles_kernel forms the same T2, so a sequence's bits do not depend on what else the device runs.
+inline int t2_skip_owners(const Tuning& t, const PlanShape& s, int m_pad, int n_pad) {
+    if (!t.t2_flow || !t.persist_gain || t.schur || !gain_in_sweep_shape(t, s, m_pad, n_pad)) return -1;
+    const int mb = m_pad / EKF_TILE, nX = n_pad / EKF_TILE;
+    const int H = persist_helpers(mb, nX, true), gw = mb * (s.ldp / 64);
+    if (1 + gw + H > s.num_cus) return -1;  // the compact launch (chol_persist.inc): every workgroup has its compute unit from the start
+    return (nX * (nX + 1) / 2 <= H) ? 0 : -1;
+}
+// Which sweep runs.  filter_update: the filter's own matrices (Schur tiles and the fused front are possible); else another caller's [A; X; I].
+inline SweepKind choose_sweep(const Tuning& t, const PlanShape& s, int m_pad, int n_pad, bool filter_update) {
+    const int mb = m_pad / EKF_TILE;
+    // (EKFVIO_SCHUR=1 takes precedence over the persistent launch, for every sweep of the handle; not in the split sweep)
+    const bool schur_shape = t.schur && mb < EKF_SWEEP_SPLIT_MB;
+    if (schur_shape && filter_update) return SWEEP_SCHUR;
+    // (only for a device's sole handle: two persistent launches in flight together could starve each other of compute units)
+    if (t.persist_sweep && !s.latched_off && !schur_shape && s.sole_handle && persist_shape(t, s, m_pad, n_pad))
+        // round 4: where the persistent sweep applies, the gather and the first tile are part of ITS launch (launch_persist_fused)
+        return (filter_update && t.fuse_sweep && t.fuse_gather) ? SWEEP_PERSIST_FUSED : SWEEP_PERSIST;
+    // many tiles per step: panel blocks once per step in a launch of their own instead of twice per tile
+    return mb < EKF_SWEEP_SPLIT_MB ? SWEEP_STEP : t.sweep_la ? SWEEP_SPLIT_LA : SWEEP_SPLIT;
+}
+// a shape the persistent launch forms the gain for when it runs: behind any other sweep the tile kernel whose arithmetic that launch's
+// in-sweep gain shares (chol_persist.inc, gain_tile), so that a sequence gives the same bits whichever sweep its updates take (eight
+// handles on one GPU against each one's solo run, tests/test_gpu_shapes.py)
+inline bool gain_tiles_shape(const Tuning& t, const PlanShape& s, int m_pad, int n_pad) { return t.persist_gain && gain_in_sweep_shape(t, s, m_pad, n_pad); }
+
+// A sweep over matrices that are not the filter's (ekfvio_test_cholesky_solve): the same choice of sweep for [A; X; I] with m_pad
+// columns and n_pad rows of X, without the update's front, Schur tiles and tail; the gain by gain_tiles_kernel or the gain GEMM
+inline UpdatePlan plan_raw_sweep(const Tuning& t, const PlanShape& s, int m_pad, int n_pad) {
+    UpdatePlan p;
+    p.m = p.m_pad = m_pad, p.n_pad = n_pad;
+    p.sweep = choose_sweep(t, s, m_pad, n_pad, false);
+    p.gain = gain_tiles_shape(t, s, m_pad, n_pad) ? GAIN_TILES : GAIN_GEMM;
+    return p;
+}
+
+// m_on_device: the host does not know the row count; next_dt >= 0: the next process(dt)'s dt of a device-resident run (UpdateInputs)
+inline UpdatePlan plan_update(const Tuning& t, const PlanShape& s, int m, bool m_on_device = false, float next_dt = -1.f, bool recoverable = true) {
+    UpdatePlan p;
+    if (m_on_device) m = 2 * s.N;  // upper bound: sizes the launches; the kernels read the true count from f->info[2]
+    const int n = s.n, ld = s.ldp, m_pad = round_up(m > 0 ? m : 1, EKF_TILE), n_pad = round_up(n, EKF_TILE);
+    p.m = m, p.m_pad = m_pad, p.n_pad = n_pad, p.m_on_device = m_on_device, p.recoverable = recoverable;
+    if (m <= 0) return p;
+    p.sweep = choose_sweep(t, s, m_pad, n_pad, true);
+    // T = Sigma - X A^-1 X^T and K = X A^-1 as Schur tiles of the sweep (no gain GEMM, no first Joseph GEMM, no (H Sigma)^T)
+    const bool schur = p.sweep == SWEEP_SCHUR, fused = p.sweep == SWEEP_PERSIST_FUSED;
+    p.with_wt = !schur;
+    // The gather and the first diagonal tile's factorisation share a launch while that launch is a single round of
+    // workgroups at one per compute unit (gather_potrf_kernel); beyond that (N = 1024: thousands of gather
+    // workgroups) the gather wants several workgroups per compute unit and the two stay separate.
+    if (t.fuse_gather && !fused)
+        p.fused_gather = 1 + gather_element_wgs(ld, m_pad) + (schur ? 0 : (m_pad / 64) * (ld / 64)) <= s.num_cus;
+    if (schur) return p.gain = GAIN_SCHUR, p.tail = TAIL_SCHUR, p;
+    p.t2_skip = t2_skip_owners(t, s, m_pad, n_pad);
+    if (p.t2_skip < 0) {
+        // the transposing workgroups of the fused launch stay and form the gain while the sweep runs, as long as (nearly) every workgroup of the
+        // launch finds a compute unit at once: they hold theirs to the end
+        p.gain = !gain_tiles_shape(t, s, m_pad, n_pad) ? GAIN_GEMM : fused ? GAIN_SWEEP : GAIN_TILES;
+        return p.tail = TAIL_JOSEPH, p;
+    }
+    p.tail = TAIL_T2;
+    p.t2_by_sweep = p.compact = fused;
+    p.gain = fused ? GAIN_SWEEP : GAIN2_T2_TILES;
+    // a device-resident run (capture_steps): the next process(dt)'s linearisation and mean propagation ride in the one GEMM's launch, in workgroups
+    // of their own behind the tiles' (K y is final: the gain tiles' partial sums); launch_predict then only propagates Sigma
+    const int lin_blocks = (s.N + LIN_LM - 1) / LIN_LM + 1;
+    if (next_dt >= 0.f && t.lin_overlap && !s.dense_predict && t.fuse_linearize && gemm_single_round_with(s.num_cus, n, n, m_pad, 1 + lin_blocks))
+        p.lin_blocks = lin_blocks;
+    return p;
+}
+#endif  // EKFVIO_PLAN_H_

@@ -32,7 +32,11 @@ EKFVIO_API int ekfvio_test_sweep_stamps(ekfvio_filter* f, int enable, int64_t st
 EKFVIO_API int ekfvio_test_sweep_fault(ekfvio_filter* f, int32_t spin_limit, int32_t stall_workgroup);
 EKFVIO_API int ekfvio_test_cholesky_solve(ekfvio_filter* f, int32_t m, int32_t nrhs, const float* S, const float* Crhs,
                                float* L_out, float* X_out, int32_t* info);
-
+/* The flow an update would take (csrc/plan.h, plan_update), without a handle or a device: the switches from the environment, the sizes of a
+ * handle of `max_features` on a device of `num_cus` compute units holding N landmarks.  plan[12] = m, m_pad, n_pad, sweep (SweepKind),
+ * fused_gather, with_wt, gain (GainBy), tail (UpdateTail), t2_skip, t2_by_sweep, compact, lin_blocks. */
+EKFVIO_API int ekfvio_test_plan(int32_t num_cus, int32_t max_features, int32_t N, int32_t m, int32_t m_on_device, int32_t sole_handle,
+                                int32_t latched_off, int32_t dense_predict, float next_dt, int32_t plan[12]);
 
 #ifdef __cplusplus
 }

@@ -659,7 +659,7 @@ def test_persistent_per_tile_sweep_is_bit_identical_to_the_per_step_sweep(monkey
             p[(7 * q + 3 * s + 1) % N] = 0
     out = {}
     if N > 300:
-        monkeypatch.setenv("EKFVIO_PERSIST_OVERSUB", "2")  # (off by default: measured, +2.9 % only -- chol.hip, persist_shape)
+        monkeypatch.setenv("EKFVIO_PERSIST_OVERSUB", "2")  # (off by default: measured, +2.9 % only -- plan.h, persist_shape)
     for mode in ("0", "2"):
         monkeypatch.setenv("EKFVIO_SWEEP", mode)
         for replay in (False, True):
@@ -694,46 +694,26 @@ def test_split_sweep_forms_agree_bit_for_bit(monkeypatch, N, fails):
     solve, far columns every second launch) against the plain two-launch form (panel launch + tile launch per block step,
     EKFVIO_SWEEP_LA=0): every tile receives the same steps in the same order, so every bit of the state must agree.  (Round 4's third
     driver, one persistent launch for the same tasks, was measured slower and left the product in round 5.)  EKFVIO_SWEEP_LA is read once
-    per process: the second form runs in a child process."""
-    import json, subprocess, sys, os
+    per handle, in ekfvio_create, like every switch: both forms run here, one handle each."""
     sc = Scenario(N, seed=13)
     fr = list(sc.frames(3))
     for s, (z, R, p) in enumerate(fr):
         for q in range(fails):
             p[(7 * q + 3 * s + 1) % N] = 0
-    g = TightlyCoupledEKF(max_features=N)
-    g.addNewFeatures(sc.initial_features())
-    for z, R, p in fr:
-        g.process(sc.dt)
-        assert g.updateWithFeaturePositions(z, R, p) in (capi.OK, capi.ENUMERIC)
-    st = g.get_state()
-    assert g.persistent_sweeps() == 0
-    g.close()
-    assert np.isfinite(st["Sigma"]).all()
-    code = (
-        "import sys, numpy as np, hashlib\n"
-        "sys.path.insert(0, %r)\n"
-        "from ekf_vio_amd import TightlyCoupledEKF\n"
-        "from ekf_vio_amd.sim import Scenario\n"
-        "N, fails = %d, %d\n"
-        "sc = Scenario(N, seed=13)\n"
-        "fr = list(sc.frames(3))\n"
-        "for s, (z, R, p) in enumerate(fr):\n"
-        "    for q in range(fails):\n"
-        "        p[(7 * q + 3 * s + 1) %% N] = 0\n"
-        "g = TightlyCoupledEKF(max_features=N)\n"
-        "g.addNewFeatures(sc.initial_features())\n"
-        "for z, R, p in fr:\n"
-        "    g.process(sc.dt); g.updateWithFeaturePositions(z, R, p)\n"
-        "st = g.get_state()\n"
-        "print(' '.join(hashlib.sha256(np.ascontiguousarray(st[k]).tobytes()).hexdigest() for k in ('base_mu', 'feat_mu', 'Sigma', 'last_klt', 'del_flag')))\n"
-    ) % (os.path.dirname(os.path.dirname(os.path.abspath(__file__))), N, fails)
-    env = dict(os.environ, EKFVIO_SWEEP_LA="0")
-    out = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=600)
-    assert out.returncode == 0, out.stderr[-2000:]
-    import hashlib
-    mine = " ".join(hashlib.sha256(np.ascontiguousarray(st[k]).tobytes()).hexdigest() for k in ("base_mu", "feat_mu", "Sigma", "last_klt", "del_flag"))
-    assert out.stdout.strip().splitlines()[-1] == mine
+    out = {}
+    for la in ("1", "0"):
+        monkeypatch.setenv("EKFVIO_SWEEP_LA", la)
+        g = TightlyCoupledEKF(max_features=N)
+        g.addNewFeatures(sc.initial_features())
+        for z, R, p in fr:
+            g.process(sc.dt)
+            assert g.updateWithFeaturePositions(z, R, p) in (capi.OK, capi.ENUMERIC)
+        out[la] = g.get_state()
+        assert g.persistent_sweeps() == 0
+        g.close()
+        assert np.isfinite(out[la]["Sigma"]).all()
+    for k in ("base_mu", "feat_mu", "Sigma", "last_klt", "del_flag"):
+        assert np.array_equal(out["1"][k], out["0"][k]), k
 
 
 @pytest.mark.parametrize("where", [(3,), (40,), (3, 40, 70, 120)])

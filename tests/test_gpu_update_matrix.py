@@ -1,6 +1,6 @@
 """The measurement update against the fp64 oracle in every flow, row count and R shape (cases: tests/_update_cases.py).
 
-The update is the one part of the product that is not bit-exact by construction, and since plan_update (chol.hip) it takes one of several
+The update is the one part of the product that is not bit-exact by construction, and since plan_update (plan.h) it takes one of several
 kernel flows chosen from the number of rows measured IN THAT FRAME.  The rest of the suite compares it with an independent reference almost
 only at "everything measured", with a constant diagonal R, and otherwise HIP against HIP.  Here: one teacher-forced update per case from a
 dense warmed state, evaluated by the HIP kernels, the fp32 oracle and the fp64 oracle from identical fp32 inputs,
