@@ -726,7 +726,8 @@ static UpdateInputs uploaded_update(ekfvio_filter* f, int m, int i, int* counter
 }
 // Captures `steps` filter steps (process + update with m measurement rows each, bookkeeping driven by the device-side
 // frame counter) into an executable graph.  `steps` is even: the mean / covariance ping-pong nets to zero.
-static int capture_steps(ekfvio_filter* f, int steps, int m, float dt, int* counter, hipGraphExec_t* out) {
+// *pre_out: how many of its process(dt) launches were captured pre-linearised (counted per replay by ekfvio_run_uploaded).
+static int capture_steps(ekfvio_filter* f, int steps, int m, float dt, int* counter, hipGraphExec_t* out, int* pre_out) {
     hipGraph_t g = nullptr;
     HIPC(f, hipStreamSynchronize(f->stream));
     // sweep_flags_clean mirrors DEVICE state on the host, and a capture records launches without running them: the
@@ -735,6 +736,7 @@ static int capture_steps(ekfvio_filter* f, int steps, int m, float dt, int* coun
     // separately (graph_leaves_flags_clean) and applied after every hipGraphLaunch.
     const bool mirror = f->sweep_flags_clean;
     f->sweep_flags_clean = false;
+    const long long pre0 = f->prelinearized_steps;  // (nothing runs here either: launch_predict's counts of the capture go to *pre_out)
     HIPC(f, hipStreamBeginCapture(f->stream, hipStreamCaptureModeThreadLocal));
     const bool gate = f->gate_chi2 > 0.f;
     for (int k = 0; k < steps; k++) {
@@ -751,6 +753,8 @@ static int capture_steps(ekfvio_filter* f, int steps, int m, float dt, int* coun
         launch_update(f, in);
     }
     f->prelinearized = false;
+    *pre_out = (int)(f->prelinearized_steps - pre0);
+    f->prelinearized_steps = pre0;
     hipError_t ce = hipStreamEndCapture(f->stream, &g);
     f->graph_leaves_flags_clean = f->sweep_flags_clean;  // (the same for every step count: the last update's last GEMM decides)
     f->sweep_flags_clean = mirror;
@@ -788,9 +792,9 @@ int ekfvio_run_uploaded(ekfvio_filter* f, int32_t first, int32_t count, float dt
         if (!f->step_graph || f->graph_N != f->N || f->graph_m != m || f->graph_dt != dt || f->graph_mu != f->mu || f->graph_P != f->P ||
             f->graph_seq != f->seq_z || f->graph_frames != f->seq_frames || f->graph_sole != (live_handles_on(f->device) <= 1)) {
             drop_graph(f);
-            int rc = capture_steps(f, EKF_GRAPH_STEPS, m, dt, counter, &f->step_graph);
+            int rc = capture_steps(f, EKF_GRAPH_STEPS, m, dt, counter, &f->step_graph, &f->graph_pre);
             if (rc != EKFVIO_OK) return rc;
-            rc = capture_steps(f, 2, m, dt, counter, &f->step_graph_pair);
+            rc = capture_steps(f, 2, m, dt, counter, &f->step_graph_pair, &f->graph_pre_pair);
             if (rc != EKFVIO_OK) return rc;
             f->graph_N = f->N; f->graph_m = m; f->graph_dt = dt; f->graph_mu = f->mu; f->graph_P = f->P; f->graph_seq = f->seq_z;
             f->graph_frames = f->seq_frames;
@@ -800,13 +804,19 @@ int ekfvio_run_uploaded(ekfvio_filter* f, int32_t first, int32_t count, float dt
         // captured together with the short graph (i.e. in a caller's warm-up call) whenever the uploaded sequence is
         // long enough to make runs of that length plausible, never lazily inside a long run
         if (f->seq_frames >= 2 * EKF_GRAPH_STEPS_BIG && !f->step_graph_big) {
-            int rc = capture_steps(f, EKF_GRAPH_STEPS_BIG, m, dt, counter, &f->step_graph_big);
+            int rc = capture_steps(f, EKF_GRAPH_STEPS_BIG, m, dt, counter, &f->step_graph_big, &f->graph_pre_big);
             if (rc != EKFVIO_OK) return rc;
         }
+        // (a replay runs no host code: its steps and its pre-linearised ones are counted here, ekfvio_get_counters [6] and [7])
+        auto replay = [&](hipGraphExec_t g, int steps, int pre) {
+            const hipError_t e = hipGraphLaunch(g, f->stream);
+            if (e == hipSuccess) s += steps, f->graph_steps += steps, f->prelinearized_steps += pre;
+            return e;
+        };
         if (f->step_graph_big)
-            for (; s + EKF_GRAPH_STEPS_BIG <= count; s += EKF_GRAPH_STEPS_BIG) HIPC(f, hipGraphLaunch(f->step_graph_big, f->stream));
-        for (; s + EKF_GRAPH_STEPS <= count; s += EKF_GRAPH_STEPS) HIPC(f, hipGraphLaunch(f->step_graph, f->stream));
-        for (; s + 2 <= count; s += 2) HIPC(f, hipGraphLaunch(f->step_graph_pair, f->stream));
+            while (s + EKF_GRAPH_STEPS_BIG <= count) HIPC(f, replay(f->step_graph_big, EKF_GRAPH_STEPS_BIG, f->graph_pre_big));
+        while (s + EKF_GRAPH_STEPS <= count) HIPC(f, replay(f->step_graph, EKF_GRAPH_STEPS, f->graph_pre));
+        while (s + 2 <= count) HIPC(f, replay(f->step_graph_pair, 2, f->graph_pre_pair));
         if (s > 0) f->sweep_flags_clean = f->graph_leaves_flags_clean;  // what the last replayed step left in device memory
         for (; s < count; s++) {  // an odd last step, eager, same counter-driven bookkeeping
             launch_predict(f, dt);
@@ -958,7 +968,8 @@ int ekfvio_get_counters(ekfvio_filter* f, int64_t counters[8]) {
     counters[3] = (f->tune.persist_sweep && !f->sweep_latched_off) ? 2 : 0;
     counters[4] = f->early_output_frames;
     counters[5] = f->t2_updates;
-    counters[6] = counters[7] = 0;
+    counters[6] = f->graph_steps;
+    counters[7] = f->prelinearized_steps;
     return EKFVIO_OK;
 }
 

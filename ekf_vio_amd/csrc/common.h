@@ -117,6 +117,8 @@ struct ekfvio_filter {
     bool gain2_attr_set = false;
     bool gather_attr_set = false;
     long long t2_updates = 0;  // updates enqueued (or captured) with the T2 flow: ONE P-update GEMM behind the sweep (ekfvio_get_counters [5])
+    long long graph_steps = 0;          // filter steps enqueued as graph replays (ekfvio_run_uploaded; ekfvio_get_counters [6])
+    long long prelinearized_steps = 0;  // process(dt) launches, replayed or eager, that found their linearisation done by the previous update's GEMM ([7])
     int num_cus = 0;
     int last_m = 0;            // measurement rows of the most recent update (shape of its GEMMs)
     long long* sweep_dbg = nullptr;  // [512] s_memtime stamps of the persistent sweep (diagnostic; null = off)
@@ -184,6 +186,7 @@ struct ekfvio_filter {
     hipGraphExec_t step_graph = nullptr;      // EKF_GRAPH_STEPS filter steps
     hipGraphExec_t step_graph_big = nullptr;  // EKF_GRAPH_STEPS_BIG filter steps (long runs: fewer graph launches)
     hipGraphExec_t step_graph_pair = nullptr; // 2 filter steps (tails and short runs)
+    int graph_pre = 0, graph_pre_big = 0, graph_pre_pair = 0;  // steps of each graph captured pre-linearised: a replay runs no host code (prelinearized_steps)
     int graph_N = -1, graph_m = -1, graph_frames = -1;
     bool graph_sole = true;   // the graphs were captured while this was the device's only handle (persistent sweep inside)
     float graph_dt = -1.f;

@@ -768,6 +768,7 @@ void launch_predict(ekfvio_filter* f, float dt, const BookArgs* book) {
     // propagated mean are in place, the propagation kernel only carries the bookkeeping along
     const bool pre = f->prelinearized && f->cfg.predict_mode != EKFVIO_PREDICT_DENSE;
     f->prelinearized = false;
+    if (pre) f->prelinearized_steps++;  // (a capture takes its count back and adds it per replay: capture_steps)
     const bool lin_in_predict = !pre && f->cfg.predict_mode != EKFVIO_PREDICT_DENSE && f->tune.fuse_linearize && tiles_side * tiles_side <= 4 * f->num_cus;
     if (!lin_in_predict && !pre) launch_linearize(f, dt, book);
     const int n = f->n, ld = f->ldp;

@@ -301,7 +301,9 @@ EKFVIO_API int ekfvio_profile_update_gemms(ekfvio_filter* f, int32_t reps, doubl
  * per block step), [4] frames of ekfvio_step_image whose outputs and status were published in front of the update's last GEMM,
  * [5] updates whose right Joseph factor T2 = Sigma (I - K H)^T came out of the Cholesky sweep's launch (or the tile kernel that stands in for
  * it behind a per-step sweep), leaving ONE P-update GEMM behind it (where the fused persistent launch forms the gain: about 65 .. 265
- * landmarks, all measured), [6..7] reserved (0). */
+ * landmarks, all measured), [6] filter steps of ekfvio_run_uploaded enqueued as replays of its captured graphs (the others ran as eager launches),
+ * [7] process(dt) launches, replayed or eager, that found their linearisation and mean propagation already done by the previous update's
+ * one P-update GEMM (inside a replayed graph of S steps in the T2 flow: S - 1 of them; EKFVIO_LIN_OVERLAP=0: none). */
 EKFVIO_API int ekfvio_get_counters(ekfvio_filter* f, int64_t counters[8]);
 
 #ifdef __cplusplus

@@ -846,14 +846,17 @@ def test_linearisation_inside_the_update_gemm_gives_the_per_call_bits(monkeypatc
     known, and in the T2 flow K y is final before the update's one GEMM: that launch carries the NEXT process(dt)'s numericallyLinearizeProcess
     and mean propagation in workgroups of its own behind the tiles' (motion_model.inc: the same device functions, at mu + K y formed by the
     same sums), and the covariance propagation behind it has only the strips left.  Same bits as one ekfvio_process + ekfvio_update per frame
-    (which linearises inside process(dt)), with and without it (EKFVIO_LIN_OVERLAP=0), including a frame with failed landmarks and across the
-    boundary between two captured graphs (40 frames = 32 + 8)."""
-    frames = 40
+    (which linearises inside process(dt)), with and without it (EKFVIO_LIN_OVERLAP=0), across the boundaries between captured graphs: 72 uniform
+    frames uploaded and run = two replays of the 32-step graph (captured for sequences of 64 frames or more) and one of the 8-step graph.  The
+    handle's counters say that the graphs were replayed and how many process(dt) launches found their linearisation done: 31 + 31 + 7 (a
+    graph's first step linearises for itself).  Every frame measures every landmark: the row count of each uploaded frame is counted on the
+    HOST, so a single frame with a failed landmark would send the whole run through the eager loop (no graph, no overlap) -- that sequence,
+    with the gate off (the eager fallback) and on (graphs), is a case of tests/test_gpu_resident_run.py."""
+    frames = 72
     sc = Scenario(N, seed=6)
     fr = list(sc.frames(frames))
     z, R, p = (np.stack([f[i] for f in fr]) for i in range(3))
-    p = p.copy()
-    p[7, [1, N // 2]] = 0  # a ragged frame (the measured set is device data: the graph is the same)
+    assert p.all()
     states = {}
     for mode in ("percall", "0", "1"):
         if mode != "percall":
@@ -868,6 +871,9 @@ def test_linearisation_inside_the_update_gemm_gives_the_per_call_bits(monkeypatc
             g.upload_measurements(z, R, p)
             g.run_uploaded(0, frames, sc.dt)
             g.synchronize()
+        c = g.counters()
+        assert c["graph_steps"] == (0 if mode == "percall" else 72), (mode, c)
+        assert c["prelinearized_steps"] == (69 if mode == "1" else 0), (mode, c)
         states[mode] = g.get_state()
         g.close()
     for key in ("base_mu", "feat_mu", "last_klt", "del_flag", "Sigma"):
