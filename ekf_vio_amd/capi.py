@@ -47,7 +47,7 @@ SYMBOLS = ["ekfvio_default_config", "ekfvio_create", "ekfvio_destroy", "ekfvio_r
            "ekfvio_profile_update_gemms", "ekfvio_get_counters", "ekfvio_set_gate", "ekfvio_get_gate"]
 # every symbol include/ekfvio_test_hooks.h declares (libekfvio_hip_hooks.so only)
 HOOK_SYMBOLS = ["ekfvio_test_klt_padded_level", "ekfvio_test_blurred_level0", "ekfvio_test_gemm", "ekfvio_test_gemm_bench", "ekfvio_test_potrf_stamps",
-                "ekfvio_test_sweep_stamps", "ekfvio_test_sweep_fault", "ekfvio_test_cholesky_solve", "ekfvio_test_plan"]
+                "ekfvio_test_sweep_stamps", "ekfvio_test_sweep_fault", "ekfvio_test_cholesky_solve", "ekfvio_test_plan", "ekfvio_test_persist_grid", "ekfvio_test_t2_pair"]
 
 _libs = {}
 
@@ -106,6 +106,8 @@ def load(build_if_missing=True, hooks=False):
             "ekfvio_test_sweep_fault": [vp, i32, i32],
             "ekfvio_test_gemm_bench": [vp, i32, i32, i32, i32, i32, i32, i32, C.POINTER(C.c_double)],
             "ekfvio_test_plan": [i32] * 8 + [f32, ip],  # no handle: csrc/plan.h's plan_update, on any machine
+            "ekfvio_test_persist_grid": [i32] * 8 + [f32, ip, i32, ip],  # ... and the PersistGrid / PersistFlags of that plan
+            "ekfvio_test_t2_pair": [i32, ip],
         })
     for name, args in sig.items():
         fn = getattr(lib, name)

@@ -1195,6 +1195,40 @@ int ekfvio_test_plan(int32_t num_cus, int32_t max_features, int32_t N, int32_t m
     std::copy(out, out + 12, plan);
     return EKFVIO_OK;
 }
+
+// No handle, no HIP call: the grid and the flag layout (plan.h, PersistGrid / PersistFlags) of the persistent launch that plan selects
+int ekfvio_test_persist_grid(int32_t num_cus, int32_t max_features, int32_t N, int32_t m, int32_t m_on_device, int32_t sole_handle,
+                             int32_t latched_off, int32_t dense_predict, float next_dt, int32_t* roles, int32_t max_blocks, int32_t out[10]) {
+    if (!out || max_features < 0 || N < 0 || N > max_features) return EKFVIO_EINVAL;
+    const FilterDims d = filter_dims(max_features);
+    PlanShape s;
+    s.num_cus = num_cus, s.ldp = d.ldp, s.sweep_sync_words = d.sweep_sync_words, s.N = N, s.n = EKF_BASE + 3 * N;
+    s.dense_predict = dense_predict != 0, s.sole_handle = sole_handle != 0, s.latched_off = latched_off != 0;
+    const UpdatePlan p = plan_update(tuning_from_env(), s, m, m_on_device != 0, next_dt);
+    std::fill(out, out + 10, 0);
+    if (!p.persistent()) return EKFVIO_OK;
+    const PersistGrid g = persist_grid(p, d.ldp);
+    const PersistFlags fl(p.m_pad, p.n_pad);
+    const int32_t res[10] = {g.total(), g.kind, g.owners(), fl.ready(), fl.fin(), fl.pan(), fl.abort_word(), (int32_t)fl.words(), fl.zero_words(),
+                             (int32_t)d.sweep_sync_words};
+    std::copy(res, res + 10, out);
+    if (!roles) return EKFVIO_OK;
+    if (max_blocks < g.total()) return EKFVIO_ECAPACITY;
+    for (int b = 0; b < g.total(); b++) {
+        const PersistRole r = g.role(b);
+        roles[4 * b] = r.kind, roles[4 * b + 1] = r.a, roles[4 * b + 2] = r.b;
+        roles[4 * b + 3] = r.kind == ROLE_OWNER ? g.owner_block(r.n) : -1;
+    }
+    return EKFVIO_OK;
+}
+// ... and tile pair p of T2 (plan.h, t2_pair)
+int ekfvio_test_t2_pair(int32_t p, int32_t pair[2]) {
+    if (p < 0 || !pair) return EKFVIO_EINVAL;
+    int ta, tb;
+    t2_pair(p, ta, tb);
+    pair[0] = ta, pair[1] = tb;
+    return EKFVIO_OK;
+}
 #endif  // EKFVIO_TEST_HOOKS
 
 }  // extern "C"

@@ -1116,50 +1116,48 @@ void launch_gather_potrf(ekfvio_filter* f, const UpdatePlan& p) {
 }
 
 // What every launch that takes PersistArgs shares: the swept matrix and its block geometry, the gain's destination, the column signs, Sigma
-// and T2.  With S (chol_persist_kernel, which hands tiles over inside the launch) also the flags, the wait bounds and the fault-injection
-// hook's workgroup: the hook counts owners from workgroup 1, `lead_wgs` more workgroups come in front of them
+// and T2.  With S (chol_persist_kernel, which hands tiles over inside the launch) also its grid (plan.h, PersistGrid), the flags (PersistFlags),
+// the wait bounds and the fault-injection hook's workgroup: the hook counts owners from 1
 static PersistArgs persist_args(ekfvio_filter* f, const UpdatePlan& p, float* L, int ldl, float* K, int ldk, float* S = nullptr,
-                                float* Linv = nullptr, int lead_wgs = 0) {
+                                float* Linv = nullptr) {
     PersistArgs pa = PersistArgs();
-    const int mb = p.m_pad / PB, nX = p.n_pad / PB, rows = 2 * mb + nX;
-    pa.L = L, pa.ldl = ldl, pa.mb = mb, pa.idb0 = mb + nX;
+    const PersistGrid g = persist_grid(p, f->ldp);
+    const PersistFlags fl(p.m_pad, p.n_pad);
+    const int mb = g.mb, nX = g.nX;
+    pa.L = L, pa.ldl = ldl, pa.mb = mb, pa.idb0 = mb + nX, pa.grid = g;
     pa.K = K, pa.ldk = ldk, pa.Lsign = f->Lsign;
     pa.Sg = f->P, pa.ldsg = f->ldp, pa.T2 = t2_buffer(f), pa.ldt = f->ldp, pa.nstate = f->n;
     if (!S) return pa;
-    pa.S = S, pa.lds = ldl, pa.Linv = Linv, pa.nrows = rows, pa.info = f->info;
-    pa.ready = f->sweep_sync, pa.fin = pa.ready + mb, pa.pan = pa.fin + rows * mb, pa.abort_flag = pa.pan + rows * mb + 1;
+    pa.S = S, pa.lds = ldl, pa.Linv = Linv, pa.info = f->info;
+    pa.ready = f->sweep_sync + fl.ready(), pa.fin = f->sweep_sync + fl.fin(), pa.pan = f->sweep_sync + fl.pan(), pa.abort_flag = f->sweep_sync + fl.abort_word();
     pa.dbg = f->sweep_dbg;
     pa.bound.spin_limit = f->sweep_spin_limit > 0 ? f->sweep_spin_limit : SWEEP_SPIN_LIMIT;
     pa.bound.wait_ticks = p.recoverable ? f->tune.sweep_wait_ticks : std::max(f->tune.sweep_wait_ticks, SWEEP_WAIT_TICKS_UNRECOVERABLE);
     pa.early_sources = f->tune.persist_early;
-    pa.stall_wg = f->sweep_stall_wg >= 0 ? f->sweep_stall_wg + lead_wgs : -1;
+    pa.stall_wg = f->sweep_stall_wg >= 0 ? g.owner_block(f->sweep_stall_wg - 1) : -1;
     return pa;
 }
 
 // The update's whole front in ONE launch (round 4): the measurement gather, the first diagonal tile and the sweep behind it.
-// Nobody writes the whole augmented matrix [A; X; I] any more: workgroup 0 gathers tile (0,0) straight from Sigma, factors it, keeps
-// it in LDS and goes on as the chain; every owner gathers ITS tile and the two block-column-0 panel sources of its first step itself
-// (chol_persist.inc, GTile); two workgroups gather the chain's first two tiles, (1,0) and (1,1), and hand them over like finished
-// tiles; workgroups 1 .. G transpose (H Sigma)^T into Wt for the first Joseph GEMM and wait for nothing.  Against gather_potrf_kernel + chol_persist_kernel: no kernel boundary on the chain, no store and cold reload of
-// L_00, no 5.5 MB of Saug written and read back.  A few more workgroups than compute units at N = 256 (260): the transposing ones
-// come first and never wait, the last owners get their compute unit microseconds later and are needed last.  The launch asks for
-// > 80 KB of LDS so that every workgroup has a compute unit of its own (the pivot chain runs 2x longer on a shared one).
+// Nobody writes the whole augmented matrix [A; X; I] any more: the chain gathers tile (0,0) straight from Sigma, factors it and keeps it in LDS;
+// every owner gathers ITS tile and the two block-column-0 panel sources of its first step itself (chol_persist.inc, GTile); the grid: plan.h,
+// PersistGrid.  Against gather_potrf_kernel + chol_persist_kernel: no kernel boundary on the chain, no store and cold reload of L_00, no 5.5 MB
+// of Saug written and read back.  GRID_FUSED has a few more workgroups than compute units at N = 256 (260): the transposing ones come first
+// and never wait, the last owners get their compute unit microseconds later and are needed last.  The launch asks for > 80 KB of LDS so that
+// every workgroup has a compute unit of its own (the pivot chain runs 2x longer on a shared one).
 #define EKF_PERSIST_FUSED_DYN_LDS (28 * 1024)
 const int* launch_persist_fused(ekfvio_filter* f, const UpdatePlan& p, bool zero_flags) {
-    const int m_pad = p.m_pad, n_pad = p.n_pad, mb = m_pad / PB;
+    const int m_pad = p.m_pad, n_pad = p.n_pad;
     ProfScope ps(f, PC_CHOL, (double)m_pad * m_pad * m_pad / 3.0 + (double)(n_pad + m_pad / 2) * m_pad * m_pad);
     if (!f->persist_attr_set) {
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(chol_persist_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
                                   EKF_PERSIST_FUSED_DYN_LDS);
         f->persist_attr_set = true;
     }
-    const int nb2 = (m_pad / 64) * (f->ldp / 64);  // 64x64 transposing tiles of Wt
-    const int lead_wgs = nb2 + (p.compact ? 0 : 2);
-    PersistArgs pa = persist_args(f, p, f->Laug, f->ld_aug, f->Km, f->ldp, f->Saug, f->Linv, lead_wgs);
-    pa.fused = 1, pa.gather_wgs = nb2;
-    pa.gain = p.gain == GAIN_SWEEP, pa.t2_skip = p.t2_skip, pa.t2 = p.t2_by_sweep, pa.compact = p.compact;
+    PersistArgs pa = persist_args(f, p, f->Laug, f->ld_aug, f->Km, f->ldp, f->Saug, f->Linv);
+    pa.gain = p.gain == GAIN_SWEEP, pa.t2 = p.t2_by_sweep;
     if (zero_flags) (void)hipMemsetAsync(f->sweep_sync, 0, sizeof(int) * persist_flag_words(m_pad, n_pad), f->stream);
-    hipLaunchKernelGGL(chol_persist_kernel, dim3(1 + lead_wgs + persist_helpers(mb, n_pad / PB, p.compact)), dim3(256), EKF_PERSIST_FUSED_DYN_LDS,
+    hipLaunchKernelGGL(chol_persist_kernel, dim3(pa.grid.total()), dim3(256), EKF_PERSIST_FUSED_DYN_LDS,
                        f->stream, pa, make_gather_args(f, p));
     f->persistent_sweeps++;
     return pa.abort_flag;
@@ -1179,7 +1177,7 @@ const int* launch_chol_sweep(ekfvio_filter* f, const UpdatePlan& p, float* Saug,
         const PersistArgs pa = persist_args(f, p, Laug, ld, nullptr, 0, Saug, Linv);
         // (the flags are zero already behind an update of this handle: its last GEMM zeroes them, launch_update)
         if (zero_flags) (void)hipMemsetAsync(f->sweep_sync, 0, sizeof(int) * persist_flag_words(m_pad, n_pad), f->stream);
-        hipLaunchKernelGGL(chol_persist_kernel, dim3(1 + persist_helpers(mb, n_pad / PB)), dim3(256), 0, f->stream, pa, GatherArgs());
+        hipLaunchKernelGGL(chol_persist_kernel, dim3(pa.grid.total()), dim3(256), 0, f->stream, pa, GatherArgs());
         f->persistent_sweeps++;
         return pa.abort_flag;  // the kernels behind this sweep leave the state alone if it is raised (launch_update)
     }
@@ -1297,8 +1295,8 @@ void launch_gain2_tiles(ekfvio_filter* f, const UpdatePlan& p) {
     const int m_pad = p.m_pad, n_pad = p.n_pad;
     ProfScope ps(f, PC_SOLVE, 2.0 * n_pad * (double)m_pad * m_pad + (double)n_pad * n_pad * m_pad);
     const PersistArgs pa = persist_args(f, p, f->Laug, f->ld_aug, f->Km, f->ldp);
-    const int nX = n_pad / PB, gain_wgs = nX * pa.mb;
-    const int total = gain_wgs + nX * (nX + 1) / 2;
+    const int gain_wgs = pa.grid.nX * pa.mb;
+    const int total = gain_wgs + t2_pairs(pa.grid.nX);
     // (> 80 KB of LDS with the 53 KB of tiles: one workgroup per compute unit while the launch fits the compute units)
     const int dyn = total <= f->num_cus ? 30 * 1024 : 0;
     if (dyn && !f->gain2_attr_set) {

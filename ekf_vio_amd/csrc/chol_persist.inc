@@ -25,9 +25,8 @@
 // itself, behind its own match.  Every wait is bounded: after PersistArgs::bound.wait_ticks of wall clock (3 ms; or bound.spin_limit looks, the
 // fault-injection hook's bound) the abort word is raised, every wait
 // falls through and info bit 1 reports it (the grid always drains); the kernels behind the sweep then leave Sigma and mu
-// untouched and the host runs the update again with one launch per block step (EKFVIO_EABORTED, api.hip finish_update).  The grid must be co-resident: the launcher admits the
-// path only when 1 + helpers <= compute units and the handle is alone on its device (plan.h, choose_sweep); the
-// flags are zeroed by the launch in front (gather_potrf_kernel) or, in the test hook, by a memset.
+// untouched and the host runs the update again with one launch per block step (EKFVIO_EABORTED, api.hip finish_update).  Which workgroup does what,
+// the shapes whose grid is admitted and the flags' layout and zeroing: plan.h (PersistGrid, persist_shape / choose_sweep, PersistFlags).
 //
 // Bits: a tile receives its steps in ascending order, one subtraction of a k-ascending MFMA product per step, and the panel
 // blocks are the same substitutions on the same final tiles as in chol_step_kernel: identical to the per-step sweep.
@@ -42,21 +41,18 @@ struct PersistArgs {
     int ldl;
     float* Linv;        // 16x16 inverse blocks per block column
     int mb, idb0;       // block columns; first identity row block
-    int nrows;          // row blocks of the augmented matrix
     int* info;
     unsigned long long* Lsign;
     int* ready;         // [mb]   4 (one per wavefront of the chain): L_kk, its inverses and Lsign[k] are in memory
-    int* fin;           // [nrows * mb] tile (i,j) is final in S
+    int* fin;           // [row blocks * mb] tile (i,j) is final in S
     int* abort_flag;
     long long* dbg;
-    int fused;          // 1: the measurement gather and the first diagonal tile are part of this launch (round 4): workgroup 0 gathers and
-                        // factors tile (0,0) before its chain, workgroups 1 .. gather_wgs are the gather's, the tile owners follow
-    int gather_wgs;
+    PersistGrid grid;   // which workgroup does what (plan.h); fused(): the measurement gather and the first diagonal tile are part of this launch (round 4)
     int gain;           // 1 (fused launch only): the transposing workgroups stay and form the Kalman gain K = Y L^-1 tile by tile as the panel blocks
                         // of the X rows (Y) and of the identity rows (L^-T) come out of the sweep (round 4): no gain GEMM behind the launch
     float* K;           // gain out, column-major, ld ldk
     int ldk;
-    int* pan;           // [nrows * mb] panel block (i,k), i >= mb, is in L (write-through) -- raised by whoever stores it
+    int* pan;           // [row blocks * mb] panel block (i,k), i >= mb, is in L (write-through) -- raised by whoever stores it
     int early_sources;  // 1: an owner fetches its two panel sources as soon as THEY are final, in front of its wait for ready[k] (EKFVIO_PERSIST_EARLY)
     PollBound bound;    // spin_limit: looks per wait before the sweep is given up (the fault-injection hook's bound; production: SWEEP_SPIN_LIMIT, never
                         // reached); wait_ticks: the production bound, wall-clock time in 100 MHz s_memrealtime ticks per wait, checked every 32 looks
@@ -64,14 +60,11 @@ struct PersistArgs {
     int stall_wg;       // fault injection (ekfvio_test_sweep_fault): this workgroup never raises its tile's flag; -1 = none
     int t2;             // 1 (fused launch with the gain inside, round 6): owners whose tile is finished adopt a tile pair (a,b) / (b,a) of
                         // T2 = Sigma - Y S Y^T = Sigma (I - K H)^T and subtract Y_ak S_k Y_bk^T block column by block column as the X rows' panel
-                        // blocks come out of the sweep (t2_tile): no first Joseph GEMM behind the launch
-    int t2_skip;        // the first t2_skip owners leave instead of adopting a pair (0 with the compact launch)
-    int compact;        // 1 (with t2): the launch fits the compute units with nobody waiting for one -- no (H Sigma)^T to transpose (nothing reads it
-                        // without the first Joseph GEMM), step 0's two tiles are gathered by two of the gain workgroups that have least to do, and the
-                        // identity row blocks' diagonal tiles (idb0 + c, c), which are the identity and have no step to receive, have no owner: whoever
-                        // needs one as a panel source writes it into LDS itself.  (Measured, profiles/r06_persistent_t2.txt: a workgroup past the 256th
-                        // of a launch does not get the first compute unit that falls free on its XCC but waits for particular ones; with the owners
-                        // staying for T2 that was 35 us later than before, and the gain tiles that need its tile ended the launch 12 us late.)
+                        // blocks come out of the sweep (t2_tile, grid.t2_pair_of): no first Joseph GEMM behind the launch.  With it the grid is compact
+                        // (plan.h, GRID_COMPACT): whoever needs an identity row block's diagonal tile (idb0 + c, c) as a panel source writes it into LDS
+                        // itself.  (Measured, profiles/r06_persistent_t2.txt: a workgroup past the 256th of a launch does not get the first compute unit
+                        // that falls free on its XCC but waits for particular ones; with the owners staying for T2 that was 35 us later than before, and
+                        // the gain tiles that need its tile ended the launch 12 us late.)
     const float* Sg;    // Sigma (n_pad x n_pad readable, zero padding), ld ldsg
     int ldsg;
     float* T2;          // T2 out (another buffer than Sigma: late owners may still be gathering from Sigma), ld ldt
@@ -252,7 +245,7 @@ __device__ __forceinline__ void gain_tile(const PersistArgs& a, float* Ti, float
             // final tiles as the owners' (chol_panel_kernel's in the per-step sweep): the same bits.
             const __amdgpu_buffer_rsrc_t bS = persist_rsrc(a.S, (unsigned)a.lds * (unsigned)(mb * PB));
             const __amdgpu_buffer_rsrc_t bI = persist_rsrc(a.Linv, (unsigned)(mb * PB * PB));
-            const bool zi = a.compact && cb == kb;  // (compact launch: tile (idb0 + mb-1, mb-1) is the identity and nobody's)
+            const bool zi = a.grid.compact() && cb == kb;  // (compact launch: tile (idb0 + mb-1, mb-1) is the identity and nobody's)
             persist_wait(nullptr, a.fin + iy * mb + kb, zi ? nullptr : a.fin + iz * mb + kb, a.abort_flag, a.info, tid, a.bound, 1, true);
             load_tile_sc1(Ti, bS, (unsigned)(kb * PB) * (unsigned)a.lds + (unsigned)(iy * PB), a.lds, tid);
             if (zi) identity_tile(Tj, tid);
@@ -490,7 +483,7 @@ __device__ __forceinline__ void gain_tile2(const PersistArgs& a, const GatherArg
         const int kl = mb - 1, k6 = mb - 2;
         const bool gk6 = k6 >= cb;
         const __amdgpu_buffer_rsrc_t bI = persist_rsrc(a.Linv, (unsigned)(mb * PB * PB));
-        const bool zi = a.compact && cb == kl;  // (compact launch: tile (idb0 + mb-1, mb-1) is the identity and nobody's)
+        const bool zi = a.grid.compact() && cb == kl;  // (compact launch: tile (idb0 + mb-1, mb-1) is the identity and nobody's)
         __syncthreads();
         // column mb-2's panel blocks as soon as THEY are out (their flags also cover column mb-1's finished tiles, see above): its operands travel
         // while ready[mb-1] is still on its way
@@ -728,12 +721,6 @@ __device__ __forceinline__ void t2_tile(const PersistArgs& a, float* Ti, float* 
     if (!diag) store_tile(Tj, a.T2 + (size_t)ta * PB * a.ldt + (size_t)tb * PB, a.ldt, tid);
     if (dbg && tid == 0) dbg[15] = (long long)__builtin_amdgcn_s_memrealtime();
 }
-// tile pair p of T2's nX (nX + 1) / 2: (ta, tb), ta >= tb
-__device__ __forceinline__ void t2_pair(int p, int& ta, int& tb) {
-    ta = 0;
-    while ((ta + 1) * (ta + 2) / 2 <= p) ta++;
-    tb = p - ta * (ta + 1) / 2;
-}
 
 template <bool SC1>
 __device__ __forceinline__ float persist_ldf(const float* p) {
@@ -875,6 +862,8 @@ __global__ __launch_bounds__(256) void chol_persist_kernel(PersistArgs a, Gather
     const int wr = wave & 1, wc = wave >> 1;
     const int r = wr * 32 + (lane & 31);
     const int mb = a.mb, lds = a.lds, ldl = a.ldl;
+    const bool fused = a.grid.fused(), compact = a.grid.compact();
+    const PersistRole role = a.grid.role((int)blockIdx.x);  // (plan.h, PersistGrid: the grid is described there)
     float* S = a.S;
     float* L = a.L;
     const __amdgpu_buffer_rsrc_t bS = persist_rsrc(S, (unsigned)lds * (unsigned)(mb * PB));
@@ -900,7 +889,7 @@ __global__ __launch_bounds__(256) void chol_persist_kernel(PersistArgs a, Gather
         asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
         a.dbg[176 + blockIdx.x - 252] = (long long)(xcc & 15);
     }
-    if (blockIdx.x == 0) {
+    if (role.kind == ROLE_CHAIN) {
         // ---------------- the chain ----------------
         // Per step k: L_ik = A_ik L_kk^-T (i = k+1), A_ii -= L_ik S L_ik^T, A_ii = L_ii L_ii^T.  What is on the path between two
         // pivot chains is kept short:
@@ -929,7 +918,7 @@ __global__ __launch_bounds__(256) void chol_persist_kernel(PersistArgs a, Gather
         float* Lk = Tl;   // L_kk
         float* Dn = Tj;   // the next diagonal tile
         unsigned long long neg;
-        if (a.fused) {
+        if (fused) {
             // ---- tile (0,0): gathered straight from Sigma (the elements the two-launch form's gather writes to Saug, through the same
             // gather_a_elem), factored here and kept in LDS for step 0; it leaves write-through for the owners.  (Step 0's two tiles,
             // (1,0) and (1,1), are gathered by two workgroups of their own meanwhile and arrive like every later step's: a 64x64
@@ -1006,8 +995,8 @@ __global__ __launch_bounds__(256) void chol_persist_kernel(PersistArgs a, Gather
         }
         const int li = lane & 15, g = lane >> 4;
         int seen = 1;  // lanes 0 / 1 of every wavefront: the early look at the next step's two flags
-        const int kf = a.fused ? 0 : 1;  // the first step whose tiles (and whose ready[k]) are handed over inside this launch
-        if (a.fused && lane < 2) seen = __hip_atomic_load(lane == 0 ? a.fin + 1 * mb + 0 : a.fin + 1 * mb + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        const int kf = fused ? 0 : 1;  // the first step whose tiles (and whose ready[k]) are handed over inside this launch
+        if (fused && lane < 2) seen = __hip_atomic_load(lane == 0 ? a.fin + 1 * mb + 0 : a.fin + 1 * mb + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         for (int k = 0; k + 1 < mb; k++) {
             const int i = k + 1;
             PSTAMP(32 + 8 * k + 0);
@@ -1136,18 +1125,14 @@ __global__ __launch_bounds__(256) void chol_persist_kernel(PersistArgs a, Gather
         PEXIT();
     }
 
-    // ---------------- a helper: tile (i,j) for the whole sweep ----------------
-    // helper h -> tile (i,j), block column by block column (the tiles the chain asks for first are dispatched first): in
-    // column j the rows j .. mb-1 of A (without (1,1): the chain's from the start), the X row blocks, and the identity
-    // row blocks c = 0 .. j (block (I_c, j) is zero, and stays unused, for j < c)
-    if (a.fused && (int)blockIdx.x <= a.gather_wgs) {
+    // ---------------- a helper: tile (i,j) for the whole sweep (block (I_c, j) of an identity row block c is zero, and stays unused, for j < c) ----
+    if (role.kind == ROLE_LEAD || role.kind == ROLE_LEAD_GATHER0) {
         // ---- a transposing workgroup of the fused launch: its 64x64 tile of Wt = (H Sigma)^T (read by the first Joseph GEMM, a
         // later launch: plain stores) and the zero padding columns of G.  It waits for nothing. ----
-        if (!a.compact) gather_body<false>(ga, ga.nb1 + (int)blockIdx.x - 1, persist_dyn_lds);
-        else if (((int)blockIdx.x - 1) % mb == mb - 1 && ((int)blockIdx.x - 1) / mb < 2) {
-            // compact launch: the gain tiles of the last block column have one product to form, at the very end -- two of them first gather the
-            // chain's step-0 tiles, (1,0) and (1,1), store them write-through and announce them like an owner's finished tile
-            const int cb = ((int)blockIdx.x - 1) / mb;
+        if (!compact) gather_body<false>(ga, ga.nb1 + role.n, persist_dyn_lds);
+        else if (role.kind == ROLE_LEAD_GATHER0) {
+            // compact launch: first the chain's step-0 tile (1, cb), stored write-through and announced like an owner's finished tile
+            const int cb = role.a;
             const int m = ga.m_dev ? *ga.m_dev : ga.m;
             GTile t;
             gtile_idx(t, ga, m, 1, cb, mb, a.idb0, tid);
@@ -1160,21 +1145,21 @@ __global__ __launch_bounds__(256) void chol_persist_kernel(PersistArgs a, Gather
             persist_publish(a.fin + 1 * mb + cb, tid);
         }
         if (a.gain) {  // ... and stays: tile (ib, cb) of the gain, formed as its operands come out of the sweep
-            const int tb = (int)blockIdx.x - 1, tiles_c = mb;
+            const int tb = role.n;
             __syncthreads();
-            if (tb / tiles_c < a.idb0 - mb) {  // (Wt has tiles up to the handle's capacity; the gain only X's row blocks)
-                if (a.t2) gain_tile2<true>(a, ga, Ti, Tj, Tl, Tinv, persist_dyn_lds, persist_dyn_lds + PB * PLD, tb / tiles_c, tb % tiles_c, tid);
-                else gain_tile<true>(a, Ti, Tj, Tl, Tinv, tb / tiles_c, tb % tiles_c, tid);
+            if (role.a < a.idb0 - mb) {  // (Wt has tiles up to the handle's capacity; the gain only X's row blocks)
+                if (a.t2) gain_tile2<true>(a, ga, Ti, Tj, Tl, Tinv, persist_dyn_lds, persist_dyn_lds + PB * PLD, role.a, role.b, tid);
+                else gain_tile<true>(a, Ti, Tj, Tl, Tinv, role.a, role.b, tid);
                 if (a.dbg && tid == 0 && tb < 104) a.dbg[200 + tb] = (long long)__builtin_amdgcn_s_memrealtime();
             }
         }
         PEXIT();
     }
     const int idb0 = a.idb0;
-    if (a.fused && !a.compact && (int)blockIdx.x <= a.gather_wgs + 2) {
+    if (role.kind == ROLE_GATHER0) {
         // ---- fused launch: the two tiles of the chain's step 0, (1,0) and (1,1), gathered from Sigma by a workgroup each, stored
         // write-through and announced like an owner's finished tile ----
-        const int cb = (int)blockIdx.x - a.gather_wgs - 1;  // 0: tile (1,0), 1: tile (1,1)
+        const int cb = role.a;  // 0: tile (1,0), 1: tile (1,1)
         const int m = ga.m_dev ? *ga.m_dev : ga.m;
         GTile t;
         gtile_idx(t, ga, m, 1, cb, mb, idb0, tid);
@@ -1187,30 +1172,12 @@ __global__ __launch_bounds__(256) void chol_persist_kernel(PersistArgs a, Gather
         persist_publish(a.fin + 1 * mb + cb, tid);
         PEXIT();
     }
-    int i, j;
-    const int hidx = (int)blockIdx.x - 1 - (a.fused ? a.gather_wgs + (a.compact ? 0 : 2) : 0);
-    {
-        int h = hidx;
-        const int nX = idb0 - mb;
-        j = 1;
-        for (;;) {
-            const int nA = mb - j - (j == 1 ? 1 : 0);
-            const int cnt = nA + nX + (j + 1 - (a.compact ? 1 : 0));  // (compact: the identity rows' diagonal tile (idb0 + j, j) has no owner)
-            if (h < cnt || j == mb - 1) {
-                if (h < nA) i = j + h + (j == 1 ? 1 : 0);
-                else if (h < nA + nX) i = mb + (h - nA);
-                else i = idb0 + (h - nA - nX);
-                break;
-            }
-            h -= cnt;
-            j++;
-        }
-    }
+    const int i = role.a, j = role.b, hidx = role.n;
     const int k0 = (i >= idb0) ? (i - idb0) : 0;     // identity block row c: block (i,k) is zero for k < c
     const int klast = (i == j) ? j - 2 : j - 1;       // a diagonal tile is handed to the chain one step early
     const unsigned oij = (unsigned)(j * PB) * (unsigned)lds + (unsigned)(i * PB);
     float tv[16];                                     // the tile, in the product's accumulator layout, for the whole sweep
-    if (a.fused) {
+    if (fused) {
         // the owner gathers ITS tile of [A; X; I] straight from Sigma (through L_kk's LDS tile into the accumulator layout), and with it
         // the two panel sources of step 0, (i,0) and (j,0): block column 0 exists nowhere but in Sigma
         const int m = ga.m_dev ? *ga.m_dev : ga.m;
@@ -1256,7 +1223,7 @@ __global__ __launch_bounds__(256) void chol_persist_kernel(PersistArgs a, Gather
         const bool lazy = !(k == klast && i <= j + 1);
         const bool early = a.early_sources && k >= 1;
         // compact launch: an identity row block's first step takes its own diagonal tile (idb0 + c, c) as panel source: the identity, nobody's
-        const bool src_ident = a.compact && k >= 1 && i >= idb0 && i - idb0 == k;
+        const bool src_ident = compact && k >= 1 && i >= idb0 && i - idb0 == k;
         const int* fin_ik = src_ident ? nullptr : a.fin + i * mb + k;
         if (early) {
             // the panel sources (i,k), (j,k) are final about a third of a chain step before L_kk is: they are in LDS when ready[k] comes
@@ -1267,10 +1234,10 @@ __global__ __launch_bounds__(256) void chol_persist_kernel(PersistArgs a, Gather
             if (i != j) load_tile_sc1(Tj, bS, (unsigned)(k * PB) * (unsigned)lds + (unsigned)(j * PB), lds, tid);
             persist_wait(a.ready + k, nullptr, nullptr, a.abort_flag, a.info, tid, a.bound, 4, lazy);
         } else if (k >= 1) persist_wait(a.ready + k, fin_ik, (i != j) ? a.fin + j * mb + k : nullptr, a.abort_flag, a.info, tid, a.bound, 4, lazy);
-        else if (a.fused) persist_wait(a.ready, nullptr, nullptr, a.abort_flag, a.info, tid, a.bound, 4, lazy);  // L_00 of this launch
+        else if (fused) persist_wait(a.ready, nullptr, nullptr, a.abort_flag, a.info, tid, a.bound, 4, lazy);  // L_00 of this launch
         else __syncthreads();  // (the barrier: the previous step's readers of Ti / Tj / Tl are done)
         HSTAMP(1);
-        if (k >= 1 || a.fused) {  // four requests in flight together: one round trip
+        if (k >= 1 || fused) {  // four requests in flight together: one round trip
             load_tile_sc1(Tl, bL, (unsigned)(k * PB) * (unsigned)ldl + (unsigned)(k * PB), ldl, tid);
             load_inv_sc1(Tinv, bI, (unsigned)(k * PB * PB), tid);
             if (k >= 1 && !early) {  // (fused launch, step 0: the two panel sources were gathered from Sigma at the start)
@@ -1303,7 +1270,7 @@ __global__ __launch_bounds__(256) void chol_persist_kernel(PersistArgs a, Gather
     k = klast;
     // the finished tile goes out once (write-through, whole 128-byte lines through L_kk's LDS tile, free since the
     // substitutions) and is announced
-    if (klast >= k0 || a.fused) {  // (fused launch: a tile without steps -- an identity block -- exists nowhere yet either)
+    if (klast >= k0 || fused) {  // (fused launch: a tile without steps -- an identity block -- exists nowhere yet either)
         if (klast < k0) __syncthreads();
 #pragma unroll
         for (int q = 0; q < 16; q++) Tl[(wc * 32 + (q & 3) + 8 * (q >> 2) + 4 * (lane >> 5)) * PLD + r] = tv[q];
@@ -1330,15 +1297,15 @@ __global__ __launch_bounds__(256) void chol_persist_kernel(PersistArgs a, Gather
         // round 6: this workgroup's tile is done and nothing else is left for an owner of a launch that forms the gain itself -- it adopts
         // a tile pair of T2 (the first t2_skip owners leave: the launch has a few more workgroups than compute units).  It starts with
         // the block columns that are out already (their `pan` flags are up) and then keeps step with the sweep.
-        const int p = hidx - a.t2_skip, nXb = idb0 - mb;
+        const int p = a.grid.t2_pair_of(hidx);
         if (a.dbg && tid == 0 && hidx < 8) {
             a.dbg[192 + hidx] = (long long)__builtin_amdgcn_s_memrealtime();
         }
-        if (p >= 0 && p < nXb * (nXb + 1) / 2) {
+        if (p >= 0) {
             int ta, tb;
             t2_pair(p, ta, tb);
             long long* td = nullptr;  // diagnostic (scripts/t2_stamps.py): the first, a middle and the last pair's block-column times on the 100 MHz clock
-            const int np_ = nXb * (nXb + 1) / 2;
+            const int np_ = t2_pairs(a.grid.nX);
             if (a.dbg && (p == 0 || p == np_ / 2 || p == np_ - 1)) {
                 td = a.dbg + 840 + 16 * (p == 0 ? 0 : p == np_ - 1 ? 2 : 1);
                 if (tid == 0) td[14] = (long long)__builtin_amdgcn_s_memrealtime();  // adopted

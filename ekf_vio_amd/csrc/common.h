@@ -95,7 +95,7 @@ struct ekfvio_filter {
     int ld_aug = 0;            // m_cap + ldp + m_cap
     float* Linv = nullptr;     // [64*m_cap] inverses of the 16x16 diagonal blocks of L
     unsigned long long* Lsign = nullptr;  // [>= m_cap/64] per block column: mask of negative pivots (0 = positive definite block)
-    int* sweep_sync = nullptr; // flags of the persistent sweep: ready[mb], fin[row blocks x mb], abort word (sweep_sync_words ints)
+    int* sweep_sync = nullptr; // flags of the persistent sweep, laid out by plan.h's PersistFlags (sweep_sync_words ints)
     size_t sweep_sync_words = 0;
     bool sweep_latched_off = false;  // an aborted persistent sweep has retired the persistent launch (sweep_abort_latch sets it, sweep_maybe_retry clears it)
     bool prelinearized = false;   // the update's last GEMM linearised for the next process(dt) (UpdateInputs::next_dt): FA / FB / FD / mu_next hold its Jacobian

@@ -95,14 +95,35 @@ inline Tuning tuning_from_env() {
     return t;
 }
 
+// ---- the persistent sweep's flags (chol_persist.inc): laid out HERE, once, for the allocation, the planner, the launchers and the GEMM epilogue ----
+#ifdef __HIPCC__
+#define PLAN_HD __host__ __device__ __forceinline__  // (inlined: a call would take the address of the kernel's by-value arguments and send them to scratch)
+#else
+#define PLAN_HD inline
+#endif
+// The flags in ekfvio_filter::sweep_sync, in words: ready[mb], fin[rows x mb], pan[rows x mb] (panel blocks of the X / identity rows, for the
+// gain tiles formed inside the launch), one spare word, the abort word.  Two extents are zeroed, as found: the update's last GEMM zeroes
+// zero_words(), which stops short of the abort word; gather_potrf_kernel and the launchers' memsets zero words(), which includes it.
+struct PersistFlags {
+    int mb, rows;  // block columns, row blocks of [A; X; I]
+    PersistFlags(int m_pad, int n_pad) : mb(m_pad / EKF_TILE), rows(2 * (m_pad / EKF_TILE) + n_pad / EKF_TILE) {}
+    int ready() const { return 0; }
+    int fin() const { return mb; }
+    int pan() const { return fin() + rows * mb; }
+    int abort_word() const { return pan() + rows * mb + 1; }
+    int zero_words() const { return abort_word(); }
+    size_t words() const { return ((size_t)abort_word() + 1 + 3) & ~(size_t)3; }  // a multiple of 16 bytes
+};
+inline size_t persist_flag_words(int m_pad, int n_pad) { return PersistFlags(m_pad, n_pad).words(); }
+inline int persist_zero_words(int m_pad, int n_pad) { return PersistFlags(m_pad, n_pad).zero_words(); }
+
 // ---- the sizes a capacity implies ----------------------------------------------------------------------------------------------
 struct FilterDims {
     int n_cap;   // 22 + 3*max_features
     int ldp;     // leading dimension of every n-row matrix (multiple of 64); one spare row/column: the K*y column of the Joseph-1 GEMM
     int m_cap;   // 2*max_features rounded up to 64; leading dimension of S/L
     int ld_aug;  // m_cap + ldp + m_cap
-    size_t sweep_sync_words;  // flags of the persistent sweeps (chol_persist.inc): ready[mb] + 2 x [row blocks x mb] + abort word
-                              // (>= 1024: the test hooks sweep matrices that are not the filter's)
+    size_t sweep_sync_words;  // flags of the persistent sweeps (PersistFlags; >= 1024: the test hooks sweep matrices that are not the filter's)
 };
 inline FilterDims filter_dims(int max_features) {
     FilterDims d;
@@ -110,8 +131,8 @@ inline FilterDims filter_dims(int max_features) {
     d.ldp = round_up(d.n_cap + 1, 64);
     d.m_cap = round_up(2 * max_features > 0 ? 2 * max_features : 1, 64);
     d.ld_aug = d.m_cap + d.ldp + d.m_cap;
-    const size_t mb2 = (size_t)(d.m_cap / 64);
-    d.sweep_sync_words = std::max((size_t)1024, mb2 + 2 * (size_t)(d.ld_aug / 64 + 1) * mb2 + 8);
+    // (as allocated so far: the layout of the largest sweep with one row block more, and seven words)
+    d.sweep_sync_words = std::max((size_t)1024, (size_t)PersistFlags(d.m_cap, d.ldp + EKF_TILE).abort_word() + 7);
     return d;
 }
 
@@ -165,36 +186,85 @@ struct UpdatePlan {
     bool with_wt = false;       // the gather also transposes (H Sigma)^T into Wt (only the first Joseph GEMM reads it)
     GainBy gain = GAIN_GEMM;
     UpdateTail tail = TAIL_NONE;
-    int t2_skip = -1;           // PersistArgs::t2_skip (>= 0: the shape takes the T2 flow)
-    bool t2_by_sweep = false, compact = false;  // PersistArgs::t2, ::compact
+    int t2_skip = -1;           // PersistGrid::t2_skip (>= 0: the shape takes the T2 flow)
+    bool t2_by_sweep = false, compact = false;  // PersistArgs::t2, GRID_COMPACT
     int lin_blocks = 0;         // > 0: the last GEMM linearises for the next process(dt) in that many extra workgroups (GemmEpi::lin_blocks)
     // chol_persist_kernel runs: its abort word goes into the GEMM epilogues, the last GEMM zeroes its flags for the next update, and in
     // front gather_potrf_kernel zeroes them (fused_gather) or a memset does unless they are clean (ekfvio_filter::sweep_flags_clean)
     bool persistent() const { return sweep == SWEEP_PERSIST_FUSED || sweep == SWEEP_PERSIST; }
 };
 
-// layout: ready[mb], fin[rows x mb], pan[rows x mb] (panel blocks of the X / identity rows, for the gain tiles formed inside the
-// launch), one spare word, the abort word (last: whoever zeroes the flags for the next sweep leaves it alone, persist_zero_words);
-// a multiple of 16 bytes
-inline size_t persist_flag_words(int m_pad, int n_pad) {
-    const int mb = m_pad / EKF_TILE, rows = 2 * mb + n_pad / EKF_TILE;
-    return ((size_t)(mb + 2 * rows * mb + 2) + 3) & ~(size_t)3;
+// ---- the persistent sweep's grid: chol_persist_kernel's workgroups by block index, described HERE for the planner, the launchers and the kernel ----
+//   block 0              the chain
+//   lead workgroups tb   (fused kinds) mb * lead_rows, (ib, cb) = (tb / mb, tb % mb).  GRID_FUSED: transposes tile tb of (H Sigma)^T.  Where the launch forms
+//                        the gain (PersistArgs::gain) and ib < nX: tile (ib, cb) of the gain; otherwise it leaves.  GRID_COMPACT: (0, mb-1) and (1, mb-1) --
+//                        gain tiles with one product to form, at the very end -- first gather the chain's step-0 tiles (1,0), (1,1): ROLE_LEAD_GATHER0
+//   step-0 gatherers cb  (GRID_FUSED only) two: tile (1, cb)
+//   owners h             of tile (i, j), block column by block column (the tiles the chain asks for first are dispatched first): in column j = 1 .. mb-1
+//                        the rows j .. mb-1 of A (without (1,1): the chain's from the start), the nX row blocks of X, and the identity row blocks 0 .. j
+//                        (GRID_COMPACT: 0 .. j-1; tile (idb0 + j, j) is the identity and nobody's)
+// An owner's panel sources (i,k), (j,k), k < j, lie in earlier block columns: their owners have LOWER block indices (persist_shape's dispatch-order
+// argument).  tests/test_persist_grid_cpu.py holds role() to this description for every block of every planned shape.
+enum PersistGridKind { GRID_PLAIN,      // the sweep behind a front of its own (launch_chol_sweep)
+                       GRID_FUSED,      // gather + first diagonal tile + sweep in one launch (launch_persist_fused)
+                       GRID_COMPACT };  // ... that fits the compute units with nobody waiting for one (the T2 flow)
+enum PersistRoleKind { ROLE_CHAIN, ROLE_LEAD, ROLE_LEAD_GATHER0, ROLE_GATHER0, ROLE_OWNER, ROLE_NONE };
+struct PersistRole {
+    int kind, a, b, n;  // lead: (a, b) = (ib, cb); a step-0 gatherer of either kind: tile (1, a); owner: tile (a, b).  n: its number among its role's (tb, cb, h)
+};
+// tile pairs (ta, tb), ta >= tb, of the nX x nX tiles of T2 (chol_persist.inc, t2_tile), and pair p of them
+PLAN_HD constexpr int t2_pairs(int nX) { return nX * (nX + 1) / 2; }
+PLAN_HD void t2_pair(int p, int& ta, int& tb) {
+    ta = 0;
+    while ((ta + 1) * (ta + 2) / 2 <= p) ta++;
+    tb = p - ta * (ta + 1) / 2;
 }
-inline int persist_zero_words(int m_pad, int n_pad) {
-    const int mb = m_pad / EKF_TILE, rows = 2 * mb + n_pad / EKF_TILE;
-    return mb + 2 * rows * mb + 1;
-}
-// helpers of the persistent sweep (chol_persist.inc): per block column j the rows of A from the diagonal down (without
-// (1,1)), the X row blocks and the identity row blocks 0 .. j
-inline int persist_helpers(int mb, int nX, bool compact = false) {  // (compact: without the identity rows' diagonal tiles, chol_persist.inc)
-    int h = 0;
-    for (int j = 1; j < mb; j++) h += (mb - j - (j == 1 ? 1 : 0)) + nX + (j + 1 - (compact ? 1 : 0));
-    return h;
-}
+struct PersistGrid {
+    int kind = GRID_PLAIN;
+    int mb = 0, nX = 0;  // block columns, row blocks of X
+    int lead_rows = 0;   // ldp / 64: tile rows of the lead workgroups (fused kinds)
+    int t2_skip = 0;     // the first t2_skip owners leave instead of adopting a tile pair of T2 (UpdatePlan::t2_skip)
+    PLAN_HD bool fused() const { return kind != GRID_PLAIN; }
+    PLAN_HD bool compact() const { return kind == GRID_COMPACT; }
+    PLAN_HD int lead() const { return fused() ? mb * lead_rows : 0; }
+    PLAN_HD int gatherers() const { return kind == GRID_FUSED ? 2 : 0; }
+    PLAN_HD int a_rows(int j) const { return mb - j - (j == 1 ? 1 : 0); }
+    PLAN_HD int column_owners(int j) const { return a_rows(j) + nX + (j + 1 - (compact() ? 1 : 0)); }
+    PLAN_HD int owners() const {
+        int h = 0;
+        for (int j = 1; j < mb; j++) h += column_owners(j);
+        return h;
+    }
+    PLAN_HD int owner_block(int h) const { return 1 + lead() + gatherers() + h; }
+    PLAN_HD int total() const { return owner_block(owners()); }
+    // the tile pair of T2 owner h adopts once its tile is finished, -1: none
+    PLAN_HD int t2_pair_of(int h) const { return (h >= t2_skip && h - t2_skip < t2_pairs(nX)) ? h - t2_skip : -1; }
+    PLAN_HD PersistRole role(int block) const {  // (chol_persist_kernel sits at its register limit: compare its resource usage after touching this)
+        if (block == 0) return {ROLE_CHAIN, 0, 0, 0};
+        int h = block - 1;
+        if (h < lead()) {
+            const int ib = h / mb, cb = h % mb;
+            if (compact() && cb == mb - 1 && ib < 2) return {ROLE_LEAD_GATHER0, ib, cb, h};
+            return {ROLE_LEAD, ib, cb, h};
+        }
+        h -= lead();
+        if (h < gatherers()) return {ROLE_GATHER0, h, 0, h};
+        h -= gatherers();
+        const int n = h;
+        for (int j = 1; j < mb; j++) {
+            const int nA = a_rows(j);
+            if (h < column_owners(j)) {
+                const int i = h < nA ? j + h + (j == 1 ? 1 : 0) : h < nA + nX ? mb + (h - nA) : mb + nX + (h - nA - nX);
+                return {ROLE_OWNER, i, j, n};
+            }
+            h -= column_owners(j);
+        }
+        return {ROLE_NONE, 0, 0, n};  // (past total(): never launched)
+    }
+};
 // The shapes the persistent launch takes: 3 .. EKF_SWEEP_SPLIT_MB - 1 block columns.  Up to round 3: chain + owners co-resident
-// (1 + tiles <= compute units).  Round 4: up to EKF_PERSIST_OVERSUB x that.  An owner waits only for workgroups with a LOWER block index
-// (the chain is workgroup 0, the owners are numbered block column by block column, and a tile's panel sources lie in earlier columns), so
-// with workgroups dispatched in index order -- what the hardware does, though HIP does not promise it -- the resident ones can always
+// (PersistGrid::total() <= compute units).  Round 4: up to EKF_PERSIST_OVERSUB x that.  An owner waits only for workgroups with a LOWER block
+// index (PersistGrid), so with workgroups dispatched in index order -- what the hardware does, though HIP does not promise it -- the resident ones can always
 // finish, and the later columns' owners take over their compute units and catch up (their flags are all up: ~10 k cycles per step
 // against the chain's ~15.5 k).  N = 400 (params/fast_with_insight.yaml: 13 block columns, 407 owners) runs the sweep in one launch
 // this way.  Should the order ever not hold, the bounded waits end the launch and the update is run again per step (EKFVIO_EABORTED).
@@ -207,7 +277,7 @@ inline int persist_helpers(int mb, int nX, bool compact = false) {  // (compact:
 inline bool persist_shape(const Tuning& t, const PlanShape& s, int m_pad, int n_pad) {
     const int mb = m_pad / EKF_TILE;
     const int over = t.persist_oversub > 0 ? t.persist_oversub : EKF_PERSIST_OVERSUB;
-    return mb >= 3 && mb < EKF_SWEEP_SPLIT_MB && 1 + persist_helpers(mb, n_pad / EKF_TILE) <= (over > 1 ? over : 1) * s.num_cus &&
+    return mb >= 3 && mb < EKF_SWEEP_SPLIT_MB && PersistGrid{GRID_PLAIN, mb, n_pad / EKF_TILE}.total() <= (over > 1 ? over : 1) * s.num_cus &&
            persist_flag_words(m_pad, n_pad) <= s.sweep_sync_words;
 }
 // ... and of those, the shapes whose gain is formed inside the fused launch: (nearly) every workgroup of that launch finds a compute unit
@@ -215,19 +285,22 @@ inline bool persist_shape(const Tuning& t, const PlanShape& s, int m_pad, int n_
 // the same arithmetic; all other shapes take the gain GEMM, whichever sweep ran.
 inline bool gain_in_sweep_shape(const Tuning& t, const PlanShape& s, int m_pad, int n_pad) {
     const int mb = m_pad / EKF_TILE;
-    return persist_shape(t, s, m_pad, n_pad) && 1 + mb * (s.ldp / 64) + 2 + persist_helpers(mb, n_pad / EKF_TILE) <= s.num_cus + 8;
+    return persist_shape(t, s, m_pad, n_pad) && PersistGrid{GRID_FUSED, mb, n_pad / EKF_TILE, s.ldp / 64}.total() <= s.num_cus + 8;
 }
 // ... and of those, the shapes whose T2 = Sigma (I - K H)^T is formed by freed owners inside the launch (round 6, chol_persist.inc, t2_tile): there
 // must be an owner per tile pair once enough of the first owners have LEFT for every workgroup of the launch to find a compute unit (the two
-// step-0 gatherers and the gain workgroups beyond the state's row blocks leave at once).  Returns the number of owners that leave (PersistArgs::t2_skip),
+// step-0 gatherers and the gain workgroups beyond the state's row blocks leave at once).  Returns the number of owners that leave (PersistGrid::t2_skip),
 // -1 where the flow does not apply.  The flow is a property of the SHAPE, not of the sweep that runs: behind a per-step sweep of such a shape
 // gain2_t2_tiles_kernel forms the same T2, so a sequence's bits do not depend on what else the device runs.
 inline int t2_skip_owners(const Tuning& t, const PlanShape& s, int m_pad, int n_pad) {
     if (!t.t2_flow || !t.persist_gain || t.schur || !gain_in_sweep_shape(t, s, m_pad, n_pad)) return -1;
-    const int mb = m_pad / EKF_TILE, nX = n_pad / EKF_TILE;
-    const int H = persist_helpers(mb, nX, true), gw = mb * (s.ldp / 64);
-    if (1 + gw + H > s.num_cus) return -1;  // the compact launch (chol_persist.inc): every workgroup has its compute unit from the start
-    return (nX * (nX + 1) / 2 <= H) ? 0 : -1;
+    const PersistGrid g{GRID_COMPACT, m_pad / EKF_TILE, n_pad / EKF_TILE, s.ldp / 64};
+    if (g.total() > s.num_cus) return -1;  // the compact launch: every workgroup has its compute unit from the start
+    return (t2_pairs(g.nX) <= g.owners()) ? 0 : -1;
+}
+// The grid of the persistent launch a plan selects (launch_persist_fused / launch_chol_sweep); ldp: FilterDims::ldp
+inline PersistGrid persist_grid(const UpdatePlan& p, int ldp) {
+    return {p.sweep != SWEEP_PERSIST_FUSED ? GRID_PLAIN : p.compact ? GRID_COMPACT : GRID_FUSED, p.m_pad / EKF_TILE, p.n_pad / EKF_TILE, ldp / 64, p.t2_skip};
 }
 // Which sweep runs.  filter_update: the filter's own matrices (Schur tiles and the fused front are possible); else another caller's [A; X; I].
 inline SweepKind choose_sweep(const Tuning& t, const PlanShape& s, int m_pad, int n_pad, bool filter_update) {

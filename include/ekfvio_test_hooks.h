@@ -37,6 +37,16 @@ EKFVIO_API int ekfvio_test_cholesky_solve(ekfvio_filter* f, int32_t m, int32_t n
  * fused_gather, with_wt, gain (GainBy), tail (UpdateTail), t2_skip, t2_by_sweep, compact, lin_blocks. */
 EKFVIO_API int ekfvio_test_plan(int32_t num_cus, int32_t max_features, int32_t N, int32_t m, int32_t m_on_device, int32_t sole_handle,
                                 int32_t latched_off, int32_t dense_predict, float next_dt, int32_t plan[12]);
+/* The grid and the flag layout of the persistent sweep launch that plan selects (csrc/plan.h, PersistGrid / PersistFlags), likewise without a
+ * handle or a device.  out[10] = total() (0: the planned sweep is not persistent, nothing else is filled), kind (PersistGridKind), owners,
+ * the offsets of ready, fin, pan and the abort word, words(), zero_words(), FilterDims::sweep_sync_words.  roles (may be NULL; room for
+ * max_blocks blocks of four words, EKFVIO_ECAPACITY if that is fewer than total()) receives per block: role (PersistRoleKind), a, b, and
+ * for an owner the block owner_block() gives for its owner number (-1 for every other role). */
+EKFVIO_API int ekfvio_test_persist_grid(int32_t num_cus, int32_t max_features, int32_t N, int32_t m, int32_t m_on_device, int32_t sole_handle,
+                                        int32_t latched_off, int32_t dense_predict, float next_dt, int32_t* roles, int32_t max_blocks,
+                                        int32_t out[10]);
+/* Tile pair p of T2's (csrc/plan.h, t2_pair): pair[2] = ta, tb. */
+EKFVIO_API int ekfvio_test_t2_pair(int32_t p, int32_t pair[2]);
 
 #ifdef __cplusplus
 }
