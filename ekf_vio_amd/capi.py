@@ -25,7 +25,7 @@ class Config(C.Structure):
                 ("min_new_feature_dist", C.c_int32), ("fast_blur_sigma", C.c_float), ("replenish", C.c_int32),
                 ("sample_based_uncertainty", C.c_int32), ("use_imu", C.c_int32), ("imu_gyro_variance", C.c_float),
                 ("imu_accel_variance", C.c_float), ("gravity", C.c_float * 3),
-                ("remove_lost", C.c_int32)]
+                ("klt_fb_max_px", C.c_float), ("remove_lost", C.c_int32)]
 
 
 class EkfvioError(RuntimeError):
@@ -44,7 +44,8 @@ SYMBOLS = ["ekfvio_default_config", "ekfvio_create", "ekfvio_destroy", "ekfvio_r
            "ekfvio_klt_uncertainty_points", "ekfvio_step_image", "ekfvio_replenish", "ekfvio_fast_detect", "ekfvio_imu", "ekfvio_imu_update",
            "ekfvio_upload_measurements", "ekfvio_run_uploaded", "ekfvio_synchronize", "ekfvio_profile_enable",
            "ekfvio_profile_reset", "ekfvio_profile_count", "ekfvio_profile_name", "ekfvio_profile_get",
-           "ekfvio_profile_update_gemms", "ekfvio_get_counters", "ekfvio_set_gate", "ekfvio_get_gate"]
+           "ekfvio_profile_update_gemms", "ekfvio_get_counters", "ekfvio_set_gate", "ekfvio_get_gate",
+           "ekfvio_set_klt_fb", "ekfvio_get_klt_fb", "ekfvio_klt_track_points_fb"]
 # every symbol include/ekfvio_test_hooks.h declares (libekfvio_hip_hooks.so only)
 HOOK_SYMBOLS = ["ekfvio_test_klt_padded_level", "ekfvio_test_blurred_level0", "ekfvio_test_gemm", "ekfvio_test_gemm_bench", "ekfvio_test_potrf_stamps",
                 "ekfvio_test_sweep_stamps", "ekfvio_test_sweep_fault", "ekfvio_test_cholesky_solve", "ekfvio_test_plan", "ekfvio_test_persist_grid", "ekfvio_test_t2_pair"]
@@ -94,6 +95,8 @@ def load(build_if_missing=True, hooks=False):
         "ekfvio_profile_update_gemms": [vp, i32, C.POINTER(C.c_double), C.POINTER(C.c_double)],
         "ekfvio_get_counters": [vp, C.POINTER(C.c_int64)],
         "ekfvio_set_gate": [vp, f32], "ekfvio_get_gate": [vp, fp, u8p, ip, ip, C.POINTER(C.c_int64)],
+        "ekfvio_set_klt_fb": [vp, f32], "ekfvio_get_klt_fb": [vp, fp, u8p, ip, ip, C.POINTER(C.c_int64)],
+        "ekfvio_klt_track_points_fb": [vp, fp, fp, i32, fp, u8p, fp, fp, u8p],
     }
     if hooks:
         sig.update({

@@ -183,6 +183,7 @@ int ekfvio_default_config(ekfvio_config* c) {
     c->gravity[0] = 0.f;
     c->gravity[1] = 9.81f;
     c->gravity[2] = 0.f;
+    c->klt_fb_max_px = 0.f;           // reference behaviour: no forward-backward check of the tracker's results
     c->remove_lost = 0;               // reference behaviour: a lost landmark stays in the state, flagged (TightlyCoupledEKF.cpp:528)
     return EKFVIO_OK;
 }
@@ -291,6 +292,7 @@ int ekfvio_create(const ekfvio_config* cfg, int device, void* stream, ekfvio_fil
     if (!cfg || cfg->max_features < 0) return EKFVIO_EINVAL;
     if (cfg->remove_lost != 0 && cfg->remove_lost != 1) return EKFVIO_EINVAL;
     if (cfg->remove_lost && (size_t)cfg->max_features * 17 > 64 * 1024) return EKFVIO_ECAPACITY;  // the removal kernel's LDS (remove.hip)
+    if (!(cfg->klt_fb_max_px >= 0.f)) return EKFVIO_EINVAL;  // (negative, NaN)
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return EKFVIO_EDEVICE;
     ekfvio_filter* f = new ekfvio_filter();
@@ -314,7 +316,7 @@ int ekfvio_destroy(ekfvio_filter* f) {
     if (f->stream) (void)hipStreamSynchronize(f->stream);
     void* ptrs[] = {f->mu, f->mu_next, f->last_klt, f->del_flag, f->P,  f->P2, f->FA, f->FB, f->FD,   f->Fdense,
                     f->idx, f->inv_idx, f->zmeas,  f->Rmeas,    f->pass,     f->yres, f->Rm, f->Saug,  f->Laug,  f->Linv, f->Lsign, f->Km, f->sweep_sync, f->sweep_dbg,
-                    f->Wt,  f->Gm,     f->info,     f->remove_words, f->seq_z,    f->seq_R, f->seq_pass, f->gate_words};
+                    f->Wt,  f->Gm,     f->info,     f->remove_words, f->seq_z,    f->seq_R, f->seq_pass, f->gate_words, f->fb_words};
     for (void* p : ptrs)
         if (p) hipFree(p);
     if (f->h_info) hipHostFree(f->h_info);
@@ -350,6 +352,7 @@ int ekfvio_reset(ekfvio_filter* f) {
     hipLaunchKernelGGL(init_sigma_kernel, dim3(1), dim3(32), 0, f->stream, f->P, f->ldp);
     HIPC(f, hipMemsetAsync(f->info, 0, 4 * sizeof(int), f->stream));
     if (f->gate_words) HIPC(f, hipMemsetAsync(f->gate_words, 0, 4 * sizeof(int), f->stream));  // the gate's counts start over; its threshold stays
+    if (f->fb_words) HIPC(f, hipMemsetAsync(f->fb_words, 0, 8 * sizeof(int), f->stream));  // ... and the forward-backward check's, likewise
     HIPC(f, hipStreamSynchronize(f->stream));
     f->have_stamp = false;
     f->frames[0].valid = f->frames[1].valid = false;
@@ -957,6 +960,33 @@ int ekfvio_get_gate(ekfvio_filter* f, float* d2, uint8_t* gated, int32_t* n_land
     if (n_landmarks) *n_landmarks = seen;
     if (gated_last) *gated_last = w[0];
     if (gated_total) memcpy(gated_total, w + 2, sizeof(int64_t));
+    return EKFVIO_OK;
+}
+
+// ---- forward-backward check of the tracker (the kernel side: klt.hip) ----------------------
+int ekfvio_set_klt_fb(ekfvio_filter* f, float max_px) {
+    if (!f || !(max_px >= 0.f)) return EKFVIO_EINVAL;  // (negative, NaN)
+    f->cfg.klt_fb_max_px = max_px;  // (read by the next track; the tracker is in no captured graph)
+    return EKFVIO_OK;
+}
+
+int ekfvio_get_klt_fb(ekfvio_filter* f, float* err2, uint8_t* rejected, int32_t* n_landmarks, int32_t* rejected_last, int64_t* rejected_total) {
+    if (!f) return EKFVIO_EINVAL;
+    HIPC(f, hipSetDevice(f->device));
+    int w[4] = {0, 0, 0, 0};
+    if (f->fb_words) {  // (null: no track of this handle ran the check)
+        HIPC(f, hipMemcpyAsync(w, f->fb_words, sizeof(w), hipMemcpyDeviceToHost, f->stream));
+        HIPC(f, hipStreamSynchronize(f->stream));
+    }
+    const int seen = std::min(std::max(w[1], 0), f->cfg.max_features);
+    if (seen > 0) {
+        if (err2) HIPC(f, hipMemcpyAsync(err2, f->fb_err2, sizeof(float) * seen, hipMemcpyDeviceToHost, f->stream));
+        if (rejected) HIPC(f, hipMemcpyAsync(rejected, f->fb_flag, seen, hipMemcpyDeviceToHost, f->stream));
+        HIPC(f, hipStreamSynchronize(f->stream));
+    }
+    if (n_landmarks) *n_landmarks = seen;
+    if (rejected_last) *rejected_last = w[0];
+    if (rejected_total) memcpy(rejected_total, w + 2, sizeof(int64_t));
     return EKFVIO_OK;
 }
 

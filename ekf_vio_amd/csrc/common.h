@@ -134,6 +134,15 @@ struct ekfvio_filter {
     uint8_t* gate_flag = nullptr; // [max_features] 1: rejected by that update's gate
     uint8_t* gate_pass = nullptr; // [max_features] the effective pass flags of that update (per-frame scratch: an uploaded sequence is never written)
     int* gate_words = nullptr;    // [4] device words: [0] gated by the last update, [1] landmarks it saw, [2..3] total since create/reset (one 64-bit word)
+    // --- forward-backward check of the tracker (ekfvio_set_klt_fb; threshold: cfg.klt_fb_max_px, 0 = off; klt_track_kernel in klt.hip) ---
+    // (device memory: one allocation, made by the first track that needs it; fb_words is its base)
+    int* fb_words = nullptr;      // [8] device words: [0] landmarks rejected by the last track, [1] landmarks it saw, [2..3] total since create/reset (one 64-bit
+                                  // word), [4] the running count and [5] the ticket of a launch (zero between launches)
+    float* fb_err2 = nullptr;     // [max_features] squared round-trip error of the last track (-1: forward track failed, -2: backward track failed)
+    uint8_t* fb_flag = nullptr;   // [max_features] 1: tracked forward and rejected by the check
+    float* fb_pt_err2 = nullptr;  // [max_features], fb_pt_back [2*max_features], fb_pt_flag [max_features]: the same and the backward result for the
+    float* fb_pt_back = nullptr;  // points of ekfvio_klt_track_points_fb
+    uint8_t* fb_pt_flag = nullptr;
     int* remove_words = nullptr;  // [4] device words of the removal kernel (remove.hip): [0] landmarks added - removed, [1] removed, [2] its ticket
     int* h_info = nullptr;     // pinned, device-mapped: [0] status word, [1] sequence number (publish_status_kernel)
     int* d_hinfo = nullptr;    // the device's address of h_info

@@ -476,25 +476,35 @@ struct TrackFuse {
     float* z = nullptr;
     float* R = nullptr;
     uint8_t* pass = nullptr;
+    // forward-backward check (include/ekfvio.h, ekfvio_set_klt_fb): the point's wavefront tracks its forward result back into the
+    // previous frame, in this launch, for the reason given above -- a helper launch costs more than the pass
+    int fb = 0;                 // 0: off (no instruction of the launch differs); 1: landmarks (verdict into the finish, counts);
+                                // 2: ekfvio_klt_track_points_fb (fb_flag receives fb_ok, fb_back the backward result)
+    float fb_t2 = 0.f;          // max_px^2, formed on the host; 0 (mode 2 only): fb_ok = the backward status alone
+    float* fb_err2 = nullptr;   // [n] e2; -1: forward track failed, not evaluated; -2: backward track failed
+    uint8_t* fb_flag = nullptr; // [n] mode 1: rejected = s_f == 1 and not fb_ok; mode 2: fb_ok
+    float* fb_back = nullptr;   // [2 n] mode 2: r where s_f == 1, else p
+    int* fb_words = nullptr;    // mode 1: ekfvio_filter::fb_words
 };
 
-// One wavefront per point, three lanes per window row.  Mirrors LKTrackerInvoker; every scalar expression is evaluated
-// redundantly (and identically) by all 64 lanes.  Per level everything the wavefront reads from memory
-// (template image, its derivatives, the search region) is fetched with aligned 4-byte loads into LDS first;
-// the per-pixel work then runs out of LDS.
-__global__ __launch_bounds__(64) void klt_track_kernel(PyrView P, PyrView Q, float* prev_px, float* next_px, uint8_t* status, int n,
-                                                       int win, int max_iter, float eps2, float min_eig, long long* dbg, TrackFuse tf) {
 #define KSTAMP(slot)                                                                                   \
     do {                                                                                               \
         if (dbg && blockIdx.x == 0 && threadIdx.x == 0) dbg[900 + (slot)] = (long long)__builtin_amdgcn_s_memtime(); \
     } while (0)
-    KSTAMP(0);
+
+// One Lucas-Kanade pass of a point's wavefront, all pyramid levels: template = frame P at (ppx0, ppy0), search in frame Q from the
+// guess (ox, oy), which the result replaces; returns the status (the backward pass calls it with the two frames swapped).  Three lanes per window row.  Mirrors LKTrackerInvoker; every
+// scalar expression is evaluated redundantly (and identically) by all 64 lanes.  Per level everything the wavefront reads from
+// memory (template image, its derivatives, the search region) is fetched with aligned 4-byte loads into LDS first; the per-pixel
+// work then runs out of LDS.  The staging buffers belong to the pass that is running: every level opens with a barrier behind the
+// LDS readers before it, which is also what separates the backward pass from the forward one.  Inlined at both call sites, with
+// the views as the kernel's own arguments: nothing of a pass lives in scratch.  dbg: the forward pass's diagnostic stamps.
+__device__ __forceinline__ bool klt_lk_pass(const PyrView& P, const PyrView& Q, const float ppx0, const float ppy0, float& ox, float& oy,
+                                            const int win, const int max_iter, const float eps2, const float min_eig, const int lane,
+                                            long long* dbg, unsigned& itpack) {
     __shared__ unsigned regJ[KLT_RS * KLT_JP];         // search region of J, rows of aligned dwords
     __shared__ unsigned regI[KLT_TW * KLT_TIP];        // template image rows
     __shared__ unsigned regD[KLT_TW * KLT_TW];         // template derivatives, one (dx,dy) short pair per pixel
-    const int pt = blockIdx.x;
-    const int lane = threadIdx.x;
-    if (pt >= n) return;
     const int levels = min(P.levels, Q.levels);
     const int W_BITS = 14;
     const float FLT_SCALE = 1.f / (1 << 20);
@@ -514,24 +524,7 @@ __global__ __launch_bounds__(64) void klt_track_kernel(PyrView P, PyrView Q, flo
         w1 = __builtin_amdgcn_alignbyte(d2, d1, o & 3);
     };
     auto byte_of = [](unsigned w0, unsigned w1, int k) -> int { return (int)(((k < 4 ? w0 : w1) >> (8 * (k & 3))) & 0xffu); };
-    float ppx0, ppy0, ox, oy;
-    if (tf.from_state) {
-        ppx0 = tf.last_klt[2 * pt] * tf.fxp + tf.cxp;
-        ppy0 = tf.last_klt[2 * pt + 1] * tf.fyp + tf.cyp;
-        ox = tf.fxc * tf.mu[EKF_BASE + 3 * pt] + tf.cxc;
-        oy = tf.fyc * tf.mu[EKF_BASE + 3 * pt + 1] + tf.cyc;
-        if (lane == 0) {  // the sample-based covariance reads them
-            prev_px[2 * pt] = ppx0;
-            prev_px[2 * pt + 1] = ppy0;
-        }
-    } else {
-        ppx0 = prev_px[2 * pt];
-        ppy0 = prev_px[2 * pt + 1];
-        ox = next_px[2 * pt];
-        oy = next_px[2 * pt + 1];
-    }
     bool ok = true;
-    unsigned itpack = 0u;
     for (int level = levels - 1; level >= 0; level--) {
         const LevelView I = P.lv[level];
         const LevelView J = Q.lv[level];
@@ -694,13 +687,83 @@ __global__ __launch_bounds__(64) void klt_track_kernel(PyrView P, PyrView Q, flo
             if (fx < -win || fx >= J.w || fy < -win || fy >= J.h) ok = false;
         }
     }
+    return ok;
+}
+
+// One wavefront per point: the forward pass from the previous frame (P) into the current one (Q) and, with the forward-backward
+// check on, the pass back from its result.
+__global__ __launch_bounds__(64) void klt_track_kernel(PyrView P, PyrView Q, float* prev_px, float* next_px, uint8_t* status, int n,
+                                                       int win, int max_iter, float eps2, float min_eig, long long* dbg, TrackFuse tf) {
+    KSTAMP(0);
+    const int pt = blockIdx.x;
+    const int lane = threadIdx.x;
+    if (pt >= n) return;
+    float ppx0, ppy0, ox, oy;
+    if (tf.from_state) {
+        ppx0 = tf.last_klt[2 * pt] * tf.fxp + tf.cxp;
+        ppy0 = tf.last_klt[2 * pt + 1] * tf.fyp + tf.cyp;
+        ox = tf.fxc * tf.mu[EKF_BASE + 3 * pt] + tf.cxc;
+        oy = tf.fyc * tf.mu[EKF_BASE + 3 * pt + 1] + tf.cyc;
+        if (lane == 0) {  // the sample-based covariance reads them
+            prev_px[2 * pt] = ppx0;
+            prev_px[2 * pt + 1] = ppy0;
+        }
+    } else {
+        ppx0 = prev_px[2 * pt];
+        ppy0 = prev_px[2 * pt + 1];
+        ox = next_px[2 * pt];
+        oy = next_px[2 * pt + 1];
+    }
+    const float gx0 = ox, gy0 = oy;  // the guess: the check applies the predicted flow backwards
+    unsigned itpack = 0u;
+    const bool ok = klt_lk_pass(P, Q, ppx0, ppy0, ox, oy, win, max_iter, eps2, min_eig, lane, dbg, itpack);
     if (dbg && lane == 0 && pt < 896) dbg[pt] = (long long)itpack;  // (scripts/klt_iterations.py)
+    bool fb_ok = true;
+    if (tf.fb) {  // (kernel argument: uniform over the launch)
+        // include/ekfvio.h, forward-backward check: fp32, line by line
+        float rx = ppx0, ry = ppy0, e2 = -1.f;
+        fb_ok = false;
+        if (__builtin_amdgcn_readfirstlane((int)ok)) {  // every lane holds the same status: a scalar branch around the second pass
+            const float bx = ox - (gx0 - ppx0), by = oy - (gy0 - ppy0);
+            rx = bx, ry = by;
+            unsigned itback = 0u;
+            const bool sb = klt_lk_pass(Q, P, ox, oy, rx, ry, win, max_iter, eps2, min_eig, lane, nullptr, itback);
+            const float dx = rx - ppx0, dy = ry - ppy0;
+            e2 = dx * dx + dy * dy;
+            fb_ok = sb && (tf.fb_t2 > 0.f ? e2 <= tf.fb_t2 : true);  // (a NaN rejects)
+            if (!sb) e2 = -2.f;
+        }
+        if (lane == 0) {
+            const bool rej = ok && !fb_ok;
+            tf.fb_err2[pt] = e2;
+            if (tf.fb == 2) {
+                tf.fb_flag[pt] = fb_ok ? 1 : 0;
+                tf.fb_back[2 * pt] = rx;
+                tf.fb_back[2 * pt + 1] = ry;
+            } else {
+                tf.fb_flag[pt] = rej ? 1 : 0;
+                // The frame's count without a launch to zero it: rejections add to words[4], every wavefront takes a ticket behind its add,
+                // and the one that takes the last ticket moves the sum into the published words and leaves [4], [5] zero for the next
+                // launch.  Atomics of one lane throughout (agent scope: the wavefronts of a launch run on every XCD).
+                int* w = tf.fb_words;
+                if (rej) (void)__hip_atomic_fetch_add(w + 4, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                const int t = __hip_atomic_fetch_add(w + 5, 1, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
+                if (t == n - 1) {
+                    const int c = __hip_atomic_exchange(w + 4, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    __hip_atomic_store(w + 5, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    __hip_atomic_store(w, c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    __hip_atomic_store(w + 1, n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    (void)__hip_atomic_fetch_add(reinterpret_cast<long long*>(w + 2), (long long)c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                }
+            }
+        }
+    }
     if (lane == 0) {
         next_px[2 * pt] = ox;
         next_px[2 * pt + 1] = oy;
         status[pt] = ok ? 1 : 0;
         if (tf.finish) {
-            const bool p = ok && !(ox < tf.kill_pad || oy < tf.kill_pad || tf.w - ox < tf.kill_pad || tf.h - oy < tf.kill_pad);
+            const bool p = ok && fb_ok && !(ox < tf.kill_pad || oy < tf.kill_pad || tf.w - ox < tf.kill_pad || tf.h - oy < tf.kill_pad);
             tf.pass[pt] = p ? 1 : 0;
             tf.z[2 * pt] = p ? (ox - tf.cxc) / tf.fxc : 0.f;
             tf.z[2 * pt + 1] = p ? (oy - tf.cyc) / tf.fyc : 0.f;
@@ -711,6 +774,7 @@ __global__ __launch_bounds__(64) void klt_track_kernel(PyrView P, PyrView Q, flo
         }
     }
 }
+#undef KSTAMP
 
 
 // EKFVIO::publishPoints (EKFVIO.cpp:479-518): camera-frame point (u/rho, v/rho, 1/rho) per landmark -- p(2) = 1.0/p(2)
@@ -922,11 +986,13 @@ __global__ __launch_bounds__(64) void klt_uncertainty_kernel(const uint8_t* __re
 // scaled by (1/fx)^2 on row 0 and (1/fy)^2 on row 1.
 __global__ void klt_finish_kernel(const float* __restrict__ next_px, const uint8_t* __restrict__ status, int N, int w,
                                   int h, int kill_pad, float fx, float fy, float cx, float cy, float r0, float r1,
-                                  const float* __restrict__ cov_px, float s0, float s1, float* z, float* R, uint8_t* pass) {
+                                  const float* __restrict__ cov_px, float s0, float s1, float* z, float* R, uint8_t* pass,
+                                  const uint8_t* __restrict__ fb_rejected) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= N) return;
     const float x = next_px[2 * i], y = next_px[2 * i + 1];
-    const bool p = status[i] == 1 && !(x < kill_pad || y < kill_pad || w - x < kill_pad || h - y < kill_pad);
+    // fb_rejected (null: the forward-backward check is off): the tracker's verdict, a rejected point goes the road of a lost one
+    const bool p = status[i] == 1 && !(fb_rejected && fb_rejected[i]) && !(x < kill_pad || y < kill_pad || w - x < kill_pad || h - y < kill_pad);
     pass[i] = p ? 1 : 0;
     if (p) {
         z[2 * i] = (x - cx) / fx;
@@ -1108,6 +1174,26 @@ static void intrinsics(const ekfvio_filter* f, const float* K, float* fx, float*
     *cy = f->cfg.use_principal_point ? K[5] : 0.f;
 }
 
+// The forward-backward check's device memory, ONE allocation made when a handle first needs it (a handle that never does allocates
+// nothing it did not before): [8] words; e2 per landmark; e2 and the backward result per point of ekfvio_klt_track_points_fb (which
+// leaves the landmarks' results of the last frame alone); then the verdict bytes of both.
+static int klt_fb_ensure(ekfvio_filter* f) {
+    if (f->fb_words) return EKFVIO_OK;
+    HIPK(f, hipSetDevice(f->device));
+    const size_t maxf = (size_t)(f->cfg.max_features > 0 ? f->cfg.max_features : 1);
+    const size_t bytes = 8 * sizeof(int) + maxf * (4 * sizeof(float) + 2);
+    unsigned char* buf = nullptr;
+    HIPK(f, hipMalloc((void**)&buf, bytes));
+    f->fb_words = reinterpret_cast<int*>(buf);  // (from here on ekfvio_destroy releases it)
+    HIPK(f, hipMemsetAsync(buf, 0, bytes, f->stream));
+    f->fb_err2 = reinterpret_cast<float*>(buf + 8 * sizeof(int));
+    f->fb_pt_err2 = f->fb_err2 + maxf;
+    f->fb_pt_back = f->fb_err2 + 2 * maxf;
+    f->fb_flag = buf + 8 * sizeof(int) + maxf * 4 * sizeof(float);
+    f->fb_pt_flag = f->fb_flag + maxf;
+    return EKFVIO_OK;
+}
+
 static int track_points_device(ekfvio_filter* f, int n, const TrackFuse& tf = TrackFuse()) {
     const KltFrame& prev = f->frames[f->cur ^ 1];
     const KltFrame& cur = f->frames[f->cur];
@@ -1156,12 +1242,20 @@ int klt_track_device(ekfvio_filter* f) {
     tf.w = cur.w[0], tf.h = cur.h[0], tf.kill_pad = f->cfg.kill_pad;
     tf.r0 = r0, tf.r1 = r1;
     tf.z = f->zmeas, tf.R = f->Rmeas, tf.pass = f->pass;
+    const bool fb = f->cfg.klt_fb_max_px > 0.f;  // forward-backward check (ekfvio_set_klt_fb); off: the launches are what they were
+    if (fb) {
+        const int rc = klt_fb_ensure(f);
+        if (rc != EKFVIO_OK) return rc;
+        tf.fb = 1;
+        tf.fb_t2 = f->cfg.klt_fb_max_px * f->cfg.klt_fb_max_px;
+        tf.fb_err2 = f->fb_err2, tf.fb_flag = f->fb_flag, tf.fb_words = f->fb_words;
+    }
     track_points_device(f, N, tf);
     if (f->cfg.sample_based_uncertainty) {  // estimateUncertaintySampleBased(lf, prev_fts[i], cf, new_fts[i])
         uncertainty_device(f, N);
         hipLaunchKernelGGL(klt_finish_kernel, dim3((N + 255) / 256), dim3(256), 0, f->stream, f->klt_next_px, f->klt_status, N,
                            cur.w[0], cur.h[0], f->cfg.kill_pad, fxc, fyc, cxc, cyc, r0, r1, f->klt_cov_px, s0, s1, f->zmeas,
-                           f->Rmeas, f->pass);
+                           f->Rmeas, f->pass, fb ? (const uint8_t*)f->fb_flag : (const uint8_t*)nullptr);
     }
     return EKFVIO_OK;
 }
@@ -1314,6 +1408,38 @@ int ekfvio_klt_track_points(ekfvio_filter* f, const float* prev_px, const float*
     track_points_device(f, count);
     if (out_px) HIPK(f, hipMemcpyAsync(out_px, f->klt_next_px, sizeof(float) * 2 * count, hipMemcpyDeviceToHost, f->stream));
     if (status) HIPK(f, hipMemcpyAsync(status, f->klt_status, count, hipMemcpyDeviceToHost, f->stream));
+    HIPK(f, hipGetLastError());
+    HIPK(f, hipStreamSynchronize(f->stream));
+    return EKFVIO_OK;
+}
+
+int ekfvio_klt_track_points_fb(ekfvio_filter* f, const float* prev_px, const float* init_px, int32_t count, float* out_px,
+                               uint8_t* status, float* back_px, float* err2, uint8_t* fb_ok) {
+    if (!f || !prev_px || !init_px || count < 0) return EKFVIO_EINVAL;
+    if (count > f->cfg.max_features) return EKFVIO_ECAPACITY;
+    if (!f->frames[0].valid || !f->frames[1].valid) {
+        f->last_error = "KLT needs two frames";
+        return EKFVIO_ESTATE;
+    }
+    if (count == 0) return EKFVIO_OK;
+    HIPK(f, hipSetDevice(f->device));
+    const int rc = klt_fb_ensure(f);
+    if (rc != EKFVIO_OK) return rc;
+    HIPK(f, hipMemcpyAsync(f->klt_prev_px, prev_px, sizeof(float) * 2 * count, hipMemcpyHostToDevice, f->stream));
+    HIPK(f, hipMemcpyAsync(f->klt_next_px, init_px, sizeof(float) * 2 * count, hipMemcpyHostToDevice, f->stream));
+    TrackFuse tf;
+    tf.fb = 2;  // the backward pass runs whatever the threshold; the landmarks' per-frame results (ekfvio_get_klt_fb) are not touched
+    tf.fb_t2 = f->cfg.klt_fb_max_px * f->cfg.klt_fb_max_px;
+    float* d_err2 = f->fb_pt_err2;
+    float* d_back = f->fb_pt_back;
+    uint8_t* d_ok = f->fb_pt_flag;
+    tf.fb_err2 = d_err2, tf.fb_back = d_back, tf.fb_flag = d_ok;
+    track_points_device(f, count, tf);
+    if (out_px) HIPK(f, hipMemcpyAsync(out_px, f->klt_next_px, sizeof(float) * 2 * count, hipMemcpyDeviceToHost, f->stream));
+    if (status) HIPK(f, hipMemcpyAsync(status, f->klt_status, count, hipMemcpyDeviceToHost, f->stream));
+    if (back_px) HIPK(f, hipMemcpyAsync(back_px, d_back, sizeof(float) * 2 * count, hipMemcpyDeviceToHost, f->stream));
+    if (err2) HIPK(f, hipMemcpyAsync(err2, d_err2, sizeof(float) * count, hipMemcpyDeviceToHost, f->stream));
+    if (fb_ok) HIPK(f, hipMemcpyAsync(fb_ok, d_ok, count, hipMemcpyDeviceToHost, f->stream));
     HIPK(f, hipGetLastError());
     HIPK(f, hipStreamSynchronize(f->stream));
     return EKFVIO_OK;

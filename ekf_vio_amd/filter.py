@@ -25,7 +25,7 @@ def _u8(a):
 class TightlyCoupledEKF:
     def __init__(self, max_features=100, device=0, stream=None, predict_mode=capi.PREDICT_STRUCTURED,
                  default_point_depth=0.5, default_point_depth_variance=100.0,
-                 default_point_homogenous_variance=1e-5, hooks=False, gate_chi2=0.0, **cfg_overrides):
+                 default_point_homogenous_variance=1e-5, hooks=False, gate_chi2=0.0, klt_fb_max_px=0.0, **cfg_overrides):
         # hooks=True: this handle lives in libekfvio_hip_hooks.so, the build that also has include/ekfvio_test_hooks.h (tests, profiling scripts)
         self.hooks = bool(hooks)
         self.lib = capi.load(hooks=self.hooks)
@@ -36,6 +36,7 @@ class TightlyCoupledEKF:
         cfg.default_point_depth = default_point_depth
         cfg.default_point_depth_variance = default_point_depth_variance
         cfg.default_point_homogenous_variance = default_point_homogenous_variance
+        cfg.klt_fb_max_px = klt_fb_max_px  # the tracker's forward-backward check, in pixels of the resized frame (0: off)
         for k, v in cfg_overrides.items():
             if k == "gravity":
                 cfg.gravity[0], cfg.gravity[1], cfg.gravity[2] = (float(x) for x in v)
@@ -166,6 +167,21 @@ class TightlyCoupledEKF:
         self._chk(self.lib.ekfvio_get_gate(self.h, _fp(d2), _u8(g), C.byref(n), C.byref(last), C.byref(total)))
         return dict(d2=d2[:n.value].copy(), gated=g[:n.value].copy(), n_landmarks=int(n.value), gated_last=int(last.value),
                     gated_total=int(total.value))
+
+    def setKltFb(self, max_px):
+        """Not in the reference: the tracker's forward-backward check (ekfvio_set_klt_fb).  max_px > 0: a landmark whose forward
+        track, tracked back into the previous frame, ends more than max_px pixels from where it started is treated as one the
+        tracker lost; 0: off."""
+        self._chk(self.lib.ekfvio_set_klt_fb(self.h, float(max_px)))
+
+    def klt_fb(self):
+        """ekfvio_get_klt_fb: dict(err2[n], rejected[n], n_landmarks, rejected_last, rejected_total) of the most recent checked track."""
+        cap = max(int(self.cfg.max_features), 1)
+        e2, r = np.zeros(cap, np.float32), np.zeros(cap, np.uint8)
+        n, last, total = C.c_int32(0), C.c_int32(0), C.c_int64(0)
+        self._chk(self.lib.ekfvio_get_klt_fb(self.h, _fp(e2), _u8(r), C.byref(n), C.byref(last), C.byref(total)))
+        return dict(err2=e2[:n.value].copy(), rejected=r[:n.value].copy(), n_landmarks=int(n.value), rejected_last=int(last.value),
+                    rejected_total=int(total.value))
 
     def checkSigma(self):
         a, b = C.c_float(0), C.c_float(0)
@@ -335,6 +351,18 @@ class KLTTracker:
         st = np.zeros(pp.shape[0], np.uint8)
         self.ekf._chk(self.lib.ekfvio_klt_track_points(self.ekf.h, _fp(pp), _fp(ii), pp.shape[0], _fp(out), _u8(st)))
         return out, st
+
+    def track_points_fb(self, prev_px, init_px):
+        """track_points with the forward-backward check (ekfvio_klt_track_points_fb): (out_px, status, back_px, err2, fb_ok).  The
+        backward pass runs whatever the handle's threshold; with a threshold of 0, fb_ok is the backward status alone."""
+        pp = np.ascontiguousarray(prev_px, dtype=np.float32).reshape(-1, 2)
+        ii = np.ascontiguousarray(init_px, dtype=np.float32).reshape(-1, 2)
+        out, back = np.zeros_like(pp), np.zeros_like(pp)
+        st, ok = np.zeros(pp.shape[0], np.uint8), np.zeros(pp.shape[0], np.uint8)
+        e2 = np.zeros(pp.shape[0], np.float32)
+        self.ekf._chk(self.lib.ekfvio_klt_track_points_fb(self.ekf.h, _fp(pp), _fp(ii), pp.shape[0], _fp(out), _u8(st), _fp(back), _fp(e2),
+                                                          _u8(ok)))
+        return out, st, back, e2, ok
 
     def uncertainty_points(self, ref_px, cur_px):
         """KLTTracker::estimateUncertaintySampleBased (KLTTracker.cpp:111-175) for arbitrary points between the two

@@ -92,6 +92,10 @@ struct Params {
             gate_chi2 = (float)number(key, value);
             if (gate_chi2 < 0.f) throw Error(EKFVIO_EINVAL, "parameter gate_chi2: negative: " + value);
         }
+        else if (key == "klt_fb_max_px") {  // not a reference parameter: the tracker's forward-backward check, in pixels of the RESIZED frame (0 = off)
+            cfg.klt_fb_max_px = (float)number(key, value);
+            if (cfg.klt_fb_max_px < 0.f) throw Error(EKFVIO_EINVAL, "parameter klt_fb_max_px: negative: " + value);
+        }
         else if (key == "imu_gyro_variance") cfg.imu_gyro_variance = (float)number(key, value);
         else if (key == "imu_accel_variance") cfg.imu_accel_variance = (float)number(key, value);
         else if (key == "gravity_x") cfg.gravity[0] = (float)number(key, value);
@@ -110,7 +114,8 @@ struct Params {
                                         "min_klt_eigen_val", "min_new_feature_dist", "max_pyramids", "klt_window_size",
                                         "default_point_depth", "default_point_depth_variance",
                                         "default_point_homogenous_variance", "frame_buffer_size", "imu_update",
-                                        "imu_gyro_variance", "imu_accel_variance", "gravity_x", "gravity_y", "gravity_z", "remove_lost", "gate_chi2"};
+                                        "imu_gyro_variance", "imu_accel_variance", "gravity_x", "gravity_y", "gravity_z", "remove_lost", "gate_chi2",
+                                        "klt_fb_max_px"};
         for (const auto& e : Params().node) out.push_back(e.first);
         for (const auto& e : ignored()) out.push_back(e.first);
         return out;
@@ -224,6 +229,24 @@ class TightlyCoupledEKF {
         chk(ekfvio_get_gate(h_, g.d2.data(), g.gated.data(), &n, &g.gated_last, &g.gated_total));
         g.d2.resize((size_t)n), g.gated.resize((size_t)n);
         return g;
+    }
+    // Not in the reference: the tracker's forward-backward check (ekfvio_set_klt_fb).  max_px > 0: a landmark whose forward track, tracked back
+    // into the previous frame, ends more than max_px pixels from where it started is treated as one the tracker lost; 0: off.
+    void setKltFb(float max_px) { chk(ekfvio_set_klt_fb(h_, max_px)); }
+    struct KltFb {
+        std::vector<float> err2;     // per landmark of the most recent checked track (-1: forward track failed, -2: backward track failed)
+        std::vector<uint8_t> rejected;
+        int32_t rejected_last = 0;
+        int64_t rejected_total = 0;
+    };
+    KltFb kltFb() {
+        KltFb r;
+        r.err2.assign((size_t)(max_features_ > 0 ? max_features_ : 1), -1.f);
+        r.rejected.assign(r.err2.size(), 0);
+        int32_t n = 0;
+        chk(ekfvio_get_klt_fb(h_, r.err2.data(), r.rejected.data(), &n, &r.rejected_last, &r.rejected_total));
+        r.err2.resize((size_t)n), r.rejected.resize((size_t)n);
+        return r;
     }
     // Not in the reference (it flags lost landmarks, TightlyCoupledEKF.cpp:528, and keeps them): removes the landmarks whose byte
     // of `remove` is nonzero (one per landmark), or, with no mask, those flagged for deletion.  Returns the number removed.

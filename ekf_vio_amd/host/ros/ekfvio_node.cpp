@@ -75,6 +75,8 @@ class EkfvioNode {
    public:
     EkfvioNode() : it_(nh_) {
         // the ~48 private parameters of EKFVIO::EKFVIO (EKFVIO.cpp:20-67) by the reference's names
+        // (and this backend's own: imu_update, remove_lost, gate_chi2, klt_fb_max_px -- the tracker's forward-backward threshold in pixels of
+        // the resized frame, which reaches the handle inside ekfvio_config)
         for (const std::string& name : ekfvio::Params::names()) {
             XmlRpc::XmlRpcValue v;
             if (ros::param::get("~" + name, v)) params_.set(name, to_text(v));

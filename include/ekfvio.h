@@ -98,6 +98,10 @@ typedef struct ekfvio_config {
     float imu_accel_variance;              /* (m/s^2)^2 per axis, default 1e-2 */
     float gravity[3];                      /* gravity in the filter's world frame (= the first camera frame), default (0, 9.81, 0):
                                               an optical frame, y down; the accelerometer model is a + b_acc - R(q)^T gravity */
+    /* forward-backward check of the tracker (not in the reference; see ekfvio_set_klt_fb).  The struct carries no size, so every caller is
+       compiled against the header it runs with, wherever a new field goes: this one stands in front of remove_lost, which
+       tests/test_remove_cpu.py pins as the last field */
+    float klt_fb_max_px;                   /* 0 (reference behaviour): off; > 0: a track that does not come back to within this many pixels is treated as lost */
     /* landmark removal (not in the reference, which flags a lost landmark, TightlyCoupledEKF.cpp:528, and keeps it) */
     int32_t remove_lost;                   /* 0 (reference behaviour): lost landmarks stay in the state, flagged; 1: ekfvio_step_image removes them */
 } ekfvio_config;
@@ -112,7 +116,7 @@ EKFVIO_API int ekfvio_default_config(ekfvio_config* cfg);
 EKFVIO_API int ekfvio_create(const ekfvio_config* cfg, int device, void* stream, ekfvio_filter** out);
 EKFVIO_API int ekfvio_destroy(ekfvio_filter* f);
 /* initializeBaseState(): back to mu = [0,0,0,1,0...], Sigma diag [0x7,30x9,0.5x6], no landmarks.  (The innovation gate's counts start
- * over; its threshold stays.) */
+ * over; its threshold stays.  The same holds for the tracker's forward-backward check.) */
 EKFVIO_API int ekfvio_reset(ekfvio_filter* f);
 EKFVIO_API const char* ekfvio_last_error(const ekfvio_filter* f);
 
@@ -222,6 +226,43 @@ EKFVIO_API int ekfvio_klt_track(ekfvio_filter* f, float* z2N, float* R4N, uint8_
  * OPTFLOW_USE_INITIAL_FLOW) between the two resident frames; for tests. */
 EKFVIO_API int ekfvio_klt_track_points(ekfvio_filter* f, const float* prev_px, const float* init_px, int32_t count,
                             float* out_px, uint8_t* status);
+
+/* ---- forward-backward check (not in the reference, whose tracker trusts every converged track) --------------------------------------
+ * A Lucas-Kanade track can converge, with status 1, on the wrong piece of image: a neighbouring corner, or whatever now covers the
+ * landmark.  The check tracks the forward result back into the previous frame and rejects the track if it does not come home.  It runs
+ * on the device, in the tracker's own launch, in ekfvio_klt_track and ekfvio_step_image.  LK(template; search) is the tracker as it is
+ * (calcOpticalFlowPyrLK with OPTFLOW_USE_INITIAL_FLOW: template window around a point of one frame, searched in the other frame from a
+ * guess; result and status).  For a point with p: reference pixel in the previous frame, g: initial guess in the current frame (for a
+ * landmark: its last KLT result and its predicted position, both in pixels), all in fp32, in this order, without fused multiply-add
+ * (a NumPy float32 restatement of these lines around two calls of the oracle's tracker gives the same bits):
+ *
+ *     forward (unchanged):   (q, s_f) = LK(template: previous frame at p; search: current frame from g)
+ *     if s_f == 1:
+ *         bx = qx - (gx - px)          by = qy - (gy - py)        (the predicted flow, applied backwards)
+ *         (r, s_b) = LK(template: current frame at q; search: previous frame from b)   same window, levels, iterations, epsilon, min_eigen
+ *         dx = rx - px   dy = ry - py   e2 = dx*dx + dy*dy
+ *         fb_ok  <=>  s_b == 1  and  e2 <= t2        t2 = max_px*max_px, formed once on the host in fp32; a NaN rejects
+ *     pass = s_f == 1 and fb_ok and inside the kill pad (as today, on q)
+ *
+ * A point that fails the check takes in every respect the road of a point the tracker lost: pass = 0, z and R zero, no measurement
+ * rows, last_klt kept, delete flag set by the update (TightlyCoupledEKF.cpp:526-529) -- and with cfg.remove_lost = 1 ekfvio_step_image
+ * removes it in the same frame.  The innovation gate never sees it (its d2 is -1).  q is never changed by the backward pass.
+ *
+ * max_px > 0: on from the next track; max_px == 0: off (default; then no launch differs and every output keeps its bits).  Negative,
+ * NaN: EKFVIO_EINVAL.  The value is cfg.klt_fb_max_px of ekfvio_create until this call replaces it. */
+EKFVIO_API int ekfvio_set_klt_fb(ekfvio_filter* f, float max_px);
+/* Results of the most recent checked track of the landmarks (any pointer may be NULL): err2 = e2 per landmark as defined above
+ * (-1: the forward track failed, so the point was not evaluated; -2: the backward track failed) and a rejected flag per landmark
+ * (s_f == 1 and not fb_ok), both with room for max_features entries; *n_landmarks = the landmark count that track saw (0 before the
+ * first checked track); number rejected by that track; total since create/reset. */
+EKFVIO_API int ekfvio_get_klt_fb(ekfvio_filter* f, float* err2, uint8_t* rejected, int32_t* n_landmarks, int32_t* rejected_last,
+                                 int64_t* rejected_total);
+/* The check in pixel space, for arbitrary points between the two resident frames (tests, callers with their own points): out_px and
+ * status as ekfvio_klt_track_points gives them (status keeps its forward meaning).  The backward pass runs whatever the handle's
+ * threshold is; with a threshold of 0, fb_ok means s_b == 1 alone.  back_px = r where s_f == 1 (whatever s_b is), else p; err2 as
+ * above; fb_ok = 0 where s_f == 0.  Output pointers may be NULL.  Leaves the results ekfvio_get_klt_fb reports untouched. */
+EKFVIO_API int ekfvio_klt_track_points_fb(ekfvio_filter* f, const float* prev_px, const float* init_px, int32_t count, float* out_px,
+                                          uint8_t* status, float* back_px, float* err2, uint8_t* fb_ok);
 
 /* KLTTracker::estimateUncertaintySampleBased (KLTTracker.cpp:111-175) between the two resident frames: for every
  * point a pixel-space 2x2 covariance (row-major, px^2) from 25 samples (offsets -10..10 step 5 around cur_px) of 5x5
