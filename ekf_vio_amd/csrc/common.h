@@ -54,6 +54,13 @@ struct KltFrame {
     int cap_w = 0, cap_h = 0;  // level-0 size the planes were allocated for (they grow with the first larger frame)
 };
 
+// What the rectification map of a handle was formed for (rectify.hip): compared as bits
+struct RectifyKey {
+    float K[4];   // fx, cx, fy, cy of the K passed with the frame
+    double D[5];
+    int w, h;
+};
+
 struct ekfvio_filter {
     ekfvio_config cfg;
     int device = 0;
@@ -176,6 +183,16 @@ struct ekfvio_filter {
     uint8_t* staging = nullptr;    // device staging for the uploaded image
     uint8_t* h_image = nullptr;    // pinned host staging: the caller's frame is copied here, so its buffer is free on return without a stream sync
     size_t src_cap = 0;            // bytes of staging / h_image (the uploaded, un-resized frame)
+    // --- rectification of distorted frames (ekfvio_set_distortion; rectify.hip) ---
+    double dist[5] = {0, 0, 0, 0, 0};  // k1, k2, p1, p2, k3
+    bool rect_on = false;          // some coefficient is nonzero: frames pass rectify_kernel between the upload and the pyramid
+    // (device memory: allocated with the first frame pushed while rect_on, ensure_frame_capacity in klt.hip)
+    int* rect_sx = nullptr;        // [rect_cap + 16] the map, fixed point with 5 fractional bits; INT32_MIN: no source pixel
+    int* rect_sy = nullptr;
+    uint8_t* rect_img = nullptr;   // [rect_cap + 16] the rectified full-size frame: a second staging plane, what the pyramid kernel then reads
+    size_t rect_cap = 0;           // pixels the three were allocated for
+    RectifyKey rect_key;           // what the map in rect_sx / rect_sy was formed for
+    bool rect_key_valid = false;
     // --- frame ingest + replenishment (fast.hip) ---
     uint8_t* blurred = nullptr;    // replenishFeatures' cv::GaussianBlur output (only with cfg.fast_blur_sigma != 0)
     unsigned* fast_row_kp = nullptr;  // [w*h] per image row its keypoints in x order, (score << 16) | x
@@ -389,6 +406,10 @@ void launch_gain_from_sweep(ekfvio_filter* f, const UpdatePlan& p, const float* 
 void launch_remove_features(ekfvio_filter* f, const uint8_t* remove, const int* added, bool abort_aware, int* host_removed);
 size_t remove_lds_bytes(const ekfvio_filter* f);
 void remove_applied(ekfvio_filter* f, int delta, int removed);  // the host side behind a launch: pointer swaps, N, n, graphs
+// rectify.hip
+int rectify_ensure(ekfvio_filter* f, size_t src);  // the map planes and the second staging buffer for a frame of src pixels (the caller has waited for the stream)
+void rectify_free(ekfvio_filter* f);
+const uint8_t* rectify_enqueue(ekfvio_filter* f, const uint8_t* src, int w, int h, const float K[9], hipStream_t st);  // returns the rectified frame
 int klt_alloc(ekfvio_filter* f);  // klt.hip
 void klt_free(ekfvio_filter* f);
 

@@ -1070,7 +1070,8 @@ static int frame_planes_alloc(ekfvio_filter* f, KltFrame& fr, int w, int h) {
 static int ensure_frame_capacity(ekfvio_filter* f, int sw, int sh, int w, int h) {
     const size_t src = (size_t)sw * sh;
     KltFrame& fr = f->frames[f->cur ^ 1];
-    if (src <= f->src_cap && w <= fr.cap_w && h <= fr.cap_h && w <= f->fast_cap_w && h <= f->fast_cap_h) return EKFVIO_OK;
+    const bool rect = f->rect_on && src > f->rect_cap;  // rectification on (ekfvio_set_distortion) and its buffers not there yet, or too small
+    if (src <= f->src_cap && w <= fr.cap_w && h <= fr.cap_h && w <= f->fast_cap_w && h <= f->fast_cap_h && !rect) return EKFVIO_OK;
     HIPK(f, hipSetDevice(f->device));
     HIPK(f, hipStreamSynchronize(f->stream));
     if (src > f->src_cap) {
@@ -1083,6 +1084,10 @@ static int ensure_frame_capacity(ekfvio_filter* f, int sw, int sh, int w, int h)
     }
     if (w > fr.cap_w || h > fr.cap_h) {
         const int rc = frame_planes_alloc(f, fr, std::max(w, fr.cap_w), std::max(h, fr.cap_h));
+        if (rc != EKFVIO_OK) return rc;
+    }
+    if (rect) {
+        const int rc = rectify_ensure(f, src);
         if (rc != EKFVIO_OK) return rc;
     }
     return fast_ensure(f, w, h);
@@ -1122,6 +1127,7 @@ void klt_free(ekfvio_filter* f) {
     if (f->klt_cov_px) (void)hipFree(f->klt_cov_px);
     if (f->staging) (void)hipFree(f->staging);
     if (f->h_image) (void)hipHostFree(f->h_image);
+    rectify_free(f);
 }
 
 // Device-side part of klt_push_frame: staging -> pyramid + derivatives of frames[cur]
@@ -1316,7 +1322,9 @@ static int push_frame_enqueue(ekfvio_filter* f, const uint8_t* image, int32_t wi
         fr.K[4] = (float)((double)K[4] / s);
         fr.K[5] = (float)((double)K[5] / s);
     }
-    build_pyramid(f, fr, f->staging, width, height, w, h, st);
+    // ekfvio_set_distortion: the full-size frame is rectified first (with the K as passed), and the pyramid reads that plane instead
+    const uint8_t* full = f->rect_on ? rectify_enqueue(f, f->staging, width, height, K, st) : f->staging;
+    build_pyramid(f, fr, full, width, height, w, h, st);
     fr.valid = true;
     HIPK(f, hipGetLastError());
     return EKFVIO_OK;

@@ -1,0 +1,180 @@
+// ekf_vio_amd/csrc/rectify.hip — rectification of distorted frames on the device, between a frame's upload and its pyramid.
+//
+// What a deployment of the reference runs in front of the node (image_proc/rectify: cv::initUndistortRectifyMap with R = I and the new
+// camera matrix = K, then cv::remap(INTER_LINEAR, BORDER_CONSTANT 0)); the reference itself assumes a pinhole image (Frame.h:31, its D at
+// :32 is never read; EKFVIO.cpp:429 "TODO add distortion coeffs").  The arithmetic is specified line by line in include/ekfvio.h
+// (ekfvio_set_distortion): rectify_map_entry below is that block, compiled for the host (ekfvio_rectify_map) and for the device
+// (rectify_map_kernel) out of the same lines, in fp64 without contraction, so that both give the bits of a NumPy restatement.
+//
+// Kernels: rectify_map_kernel writes the two fixed-point planes (once per camera: the host keeps the key it was formed for);
+// rectify_kernel reads the uploaded frame through them and writes a second staging plane, which the pyramid kernel is then given in
+// place of the first.  With distortion off neither is launched and nothing is allocated.
+#include <math.h>
+#include <string.h>
+
+#include "common.h"
+
+#define HIPR(f, expr)                                                              \
+    do {                                                                           \
+        hipError_t e__ = (expr);                                                   \
+        if (e__ != hipSuccess) {                                                   \
+            (f)->last_error = std::string(#expr) + ": " + hipGetErrorString(e__);  \
+            return EKFVIO_EDEVICE;                                                 \
+        }                                                                          \
+    } while (0)
+
+namespace {
+
+struct RectifyCam {
+    double fx, cx, fy, cy;
+    double k1, k2, p1, p2, k3;
+};
+
+// include/ekfvio.h, rectification: the fp64 block, line by line
+__host__ __device__ inline void rectify_map_entry(const RectifyCam& c, int x, int y, int* sx, int* sy) {
+    const double xn = ((double)x - c.cx) / c.fx, yn = ((double)y - c.cy) / c.fy;
+    const double xx = xn * xn, yy = yn * yn, xy = xn * yn, r2 = xx + yy;
+    const double rad = 1.0 + ((c.k3 * r2 + c.k2) * r2 + c.k1) * r2;
+    const double xd = (xn * rad + (2.0 * c.p1) * xy) + c.p2 * (r2 + 2.0 * xx);
+    const double yd = (yn * rad + c.p1 * (r2 + 2.0 * yy)) + (2.0 * c.p2) * xy;
+    const double u = c.fx * xd + c.cx, v = c.fy * yd + c.cy;
+    const bool valid = fabs(u) <= 1048576.0 && fabs(v) <= 1048576.0;  // (a NaN compares false)
+    *sx = valid ? (int)rint(u * 32.0) : INT32_MIN;  // |u * 32| <= 2^25: the conversion is exact
+    *sy = valid ? (int)rint(v * 32.0) : INT32_MIN;
+}
+
+RectifyCam rectify_cam(const float K[9], const double D[5]) {
+    RectifyCam c;
+    c.fx = (double)K[0], c.cx = (double)K[2], c.fy = (double)K[4], c.cy = (double)K[5];
+    c.k1 = D[0], c.k2 = D[1], c.p1 = D[2], c.p2 = D[3], c.k3 = D[4];
+    return c;
+}
+
+// D, count of the two entry points -> five coefficients; false: EKFVIO_EINVAL
+bool rectify_coefficients(const double* D, int32_t count, double out[5]) {
+    if (!(count == 0 || count == 4 || count == 5) || (count > 0 && !D)) return false;
+    for (int i = 0; i < 5; i++) out[i] = i < count ? D[i] : 0.0;
+    for (int i = 0; i < 5; i++)
+        if (!__builtin_isfinite(out[i])) return false;
+    return true;
+}
+
+// The frame as ONE run of w * h pixels, the planes likewise (no pitch: every row of four entries is 16-byte aligned whatever the
+// width).  n4 = ceil(w h / 4) lanes' worth of entries are written; those behind the frame's last pixel hold the sentinel.
+__global__ __launch_bounds__(256) void rectify_map_kernel(RectifyCam c, int w, int npix, int n4, int* __restrict__ sx, int* __restrict__ sy) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= 4 * n4) return;
+    int vx = INT32_MIN, vy = INT32_MIN;
+    if (i < npix) rectify_map_entry(c, i % w, i / w, &vx, &vy);
+    sx[i] = vx;
+    sy[i] = vy;
+}
+
+// Four consecutive destination pixels per lane: the map arrives as two 16-byte loads per lane (a wavefront reads 2 x 1 KiB in a row),
+// the result leaves as one dword.  The taps are single bytes of the uploaded frame, which neighbouring lanes share and L2 holds (a
+// 640 x 480 frame is 300 KB): all sixteen of a lane are requested from clamped addresses before the first is used, and a tap outside
+// the frame is multiplied by zero instead of branched around.
+__global__ __launch_bounds__(256) void rectify_kernel(const uint8_t* __restrict__ src, int w, int h, int n4, const int4* __restrict__ sx4,
+                                                      const int4* __restrict__ sy4, unsigned* __restrict__ dst) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n4) return;
+    const int4 mx = sx4[i], my = sy4[i];
+    const int sxs[4] = {mx.x, mx.y, mx.z, mx.w}, sys[4] = {my.x, my.y, my.z, my.w};
+    int t[4][4], wt[4][4];
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        const int ix = sxs[k] >> 5, ax = sxs[k] & 31, iy = sys[k] >> 5, ay = sys[k] & 31;
+        const bool x0 = ix >= 0 && ix < w, x1 = ix + 1 >= 0 && ix + 1 < w, y0 = iy >= 0 && iy < h, y1 = iy + 1 >= 0 && iy + 1 < h;
+        const int cx0 = min(max(ix, 0), w - 1), cx1 = min(max(ix + 1, 0), w - 1);
+        const size_t r0 = (size_t)min(max(iy, 0), h - 1) * w, r1 = (size_t)min(max(iy + 1, 0), h - 1) * w;
+        t[k][0] = src[r0 + cx0], t[k][1] = src[r0 + cx1], t[k][2] = src[r1 + cx0], t[k][3] = src[r1 + cx1];
+        wt[k][0] = (x0 && y0) ? (32 - ax) * (32 - ay) : 0;
+        wt[k][1] = (x1 && y0) ? ax * (32 - ay) : 0;
+        wt[k][2] = (x0 && y1) ? (32 - ax) * ay : 0;
+        wt[k][3] = (x1 && y1) ? ax * ay : 0;
+    }
+    unsigned out = 0u;
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        const int sum = t[k][0] * wt[k][0] + t[k][1] * wt[k][1] + t[k][2] * wt[k][2] + t[k][3] * wt[k][3];
+        out |= (unsigned)((sum + 512) >> 10) << (8 * k);  // at most 255 * 1024 + 512: a byte
+    }
+    dst[i] = out;
+}
+
+}  // namespace
+
+// The planes and the second staging buffer for an uploaded frame of `src` bytes (ensure_frame_capacity, klt.hip, which has waited
+// for the stream): allocated when the first frame arrives with distortion on, regrown with a larger frame.
+int rectify_ensure(ekfvio_filter* f, size_t src) {
+    if (!f->rect_on || src <= f->rect_cap) return EKFVIO_OK;
+    rectify_free(f);
+    // (+16: the kernels move whole groups of four entries, and the pyramid's source has the slack of the upload staging)
+    HIPR(f, hipMalloc((void**)&f->rect_sx, sizeof(int) * (src + 16)));
+    HIPR(f, hipMalloc((void**)&f->rect_sy, sizeof(int) * (src + 16)));
+    HIPR(f, hipMalloc((void**)&f->rect_img, src + 16));
+    f->rect_cap = src;
+    return EKFVIO_OK;
+}
+
+void rectify_free(ekfvio_filter* f) {
+    if (f->rect_sx) (void)hipFree(f->rect_sx);
+    if (f->rect_sy) (void)hipFree(f->rect_sy);
+    if (f->rect_img) (void)hipFree(f->rect_img);
+    f->rect_sx = f->rect_sy = nullptr;
+    f->rect_img = nullptr;
+    f->rect_cap = 0;
+    f->rect_key_valid = false;
+}
+
+// staging (w x h, tightly packed) -> the rectified frame, which is returned: what build_pyramid reads in its place.  The map is
+// formed first if the camera, the coefficients or the size are not the ones it was formed for (compared as bits).
+const uint8_t* rectify_enqueue(ekfvio_filter* f, const uint8_t* src, int w, int h, const float K[9], hipStream_t st) {
+    RectifyKey key;
+    memset(&key, 0, sizeof(key));
+    key.K[0] = K[0], key.K[1] = K[2], key.K[2] = K[4], key.K[3] = K[5];
+    for (int i = 0; i < 5; i++) key.D[i] = f->dist[i];
+    key.w = w, key.h = h;
+    const int npix = w * h, n4 = (npix + 3) / 4;
+    ProfScope ps(f, PC_KLT_PYRAMID);
+    if (!f->rect_key_valid || memcmp(&key, &f->rect_key, sizeof(key)) != 0) {
+        hipLaunchKernelGGL(rectify_map_kernel, dim3((4 * n4 + 255) / 256), dim3(256), 0, st, rectify_cam(K, f->dist), w, npix, n4, f->rect_sx,
+                           f->rect_sy);
+        f->rect_key = key;
+        f->rect_key_valid = true;
+        ps.launches = 2;
+    }
+    hipLaunchKernelGGL(rectify_kernel, dim3((n4 + 255) / 256), dim3(256), 0, st, src, w, h, n4, reinterpret_cast<const int4*>(f->rect_sx),
+                       reinterpret_cast<const int4*>(f->rect_sy), reinterpret_cast<unsigned*>(f->rect_img));
+    return f->rect_img;
+}
+
+extern "C" {
+
+int ekfvio_set_distortion(ekfvio_filter* f, const double* D, int32_t count) {
+    double d[5];
+    if (!f || !rectify_coefficients(D, count, d)) return EKFVIO_EINVAL;
+    bool on = false;
+    for (int i = 0; i < 5; i++) {
+        f->dist[i] = d[i];
+        on = on || d[i] != 0.0;
+    }
+    f->rect_on = on;  // (read by the next pushed frame; frame ingest is in no captured graph)
+    return EKFVIO_OK;
+}
+
+int ekfvio_rectify_map(const float K[9], const double* D, int32_t count, int32_t width, int32_t height, int32_t* sx, int32_t* sy) {
+    double d[5];
+    if (!K || !sx || !sy || width < 1 || height < 1 || width > 16384 || height > 16384 || !rectify_coefficients(D, count, d)) return EKFVIO_EINVAL;
+    const RectifyCam c = rectify_cam(K, d);
+    for (int y = 0; y < height; y++)
+        for (int x = 0; x < width; x++) {
+            int vx, vy;
+            rectify_map_entry(c, x, y, &vx, &vy);
+            sx[(size_t)y * width + x] = vx;
+            sy[(size_t)y * width + x] = vy;
+        }
+    return EKFVIO_OK;
+}
+
+}  // extern "C"

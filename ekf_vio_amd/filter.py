@@ -25,7 +25,7 @@ def _u8(a):
 class TightlyCoupledEKF:
     def __init__(self, max_features=100, device=0, stream=None, predict_mode=capi.PREDICT_STRUCTURED,
                  default_point_depth=0.5, default_point_depth_variance=100.0,
-                 default_point_homogenous_variance=1e-5, hooks=False, gate_chi2=0.0, klt_fb_max_px=0.0, **cfg_overrides):
+                 default_point_homogenous_variance=1e-5, hooks=False, gate_chi2=0.0, klt_fb_max_px=0.0, distortion=None, **cfg_overrides):
         # hooks=True: this handle lives in libekfvio_hip_hooks.so, the build that also has include/ekfvio_test_hooks.h (tests, profiling scripts)
         self.hooks = bool(hooks)
         self.lib = capi.load(hooks=self.hooks)
@@ -51,6 +51,8 @@ class TightlyCoupledEKF:
             raise capi.EkfvioError(rc, "ekfvio_create failed (device %d)" % device)
         if gate_chi2:  # a property of the handle, not a field of the configuration (ekfvio_set_gate)
             self.setGate(gate_chi2)
+        if distortion is not None:  # likewise a property of the handle (ekfvio_set_distortion)
+            self.setDistortion(distortion)
 
     def _chk(self, rc, allow=()):
         if rc != capi.OK and rc not in allow:
@@ -182,6 +184,13 @@ class TightlyCoupledEKF:
         self._chk(self.lib.ekfvio_get_klt_fb(self.h, _fp(e2), _u8(r), C.byref(n), C.byref(last), C.byref(total)))
         return dict(err2=e2[:n.value].copy(), rejected=r[:n.value].copy(), n_landmarks=int(n.value), rejected_last=int(last.value),
                     rejected_total=int(total.value))
+
+    def setDistortion(self, D):
+        """Not in the reference, which assumes a pinhole image (Frame.h:31): plumb_bob coefficients (k1, k2, p1, p2[, k3]) of the camera
+        (ekfvio_set_distortion).  From the next pushed frame on, frames are rectified on the device between the upload and the pyramid;
+        None, () or all zeros: off."""
+        d = np.ascontiguousarray([] if D is None else D, dtype=np.float64).reshape(-1)
+        self._chk(self.lib.ekfvio_set_distortion(self.h, d.ctypes.data_as(C.POINTER(C.c_double)) if d.size else None, int(d.size)))
 
     def checkSigma(self):
         a, b = C.c_float(0), C.c_float(0)
@@ -397,6 +406,19 @@ def _ip(a):
     return a.ctypes.data_as(C.POINTER(C.c_int32))
 
 
+def rectify_map(K, D, width, height):
+    """ekfvio_rectify_map: the fixed-point map (sx, sy), int32 [height, width] each, that a handle with the coefficients D (k1, k2, p1, p2[, k3])
+    rectifies a width x height frame with intrinsics K through; INT32_MIN where no source pixel exists.  A host function: no GPU involved."""
+    lib = capi.load()
+    K = np.ascontiguousarray(K, dtype=np.float32).reshape(9)
+    d = np.ascontiguousarray([] if D is None else D, dtype=np.float64).reshape(-1)
+    sx, sy = np.zeros((int(height), int(width)), np.int32), np.zeros((int(height), int(width)), np.int32)
+    rc = lib.ekfvio_rectify_map(_fp(K), d.ctypes.data_as(C.POINTER(C.c_double)) if d.size else None, int(d.size), int(width), int(height), _ip(sx), _ip(sy))
+    if rc != capi.OK:
+        raise capi.EkfvioError(rc, "ekfvio_rectify_map")
+    return sx, sy
+
+
 class EKFVIO:
     """Host mirror of the step sequence of EKFVIO::addFrame / updateStateWithNewImage
     (include/ekf_vio/EKFVIO.cpp:139-219) without ROS: frames in, odometry + landmark cloud out.
@@ -404,7 +426,7 @@ class EKFVIO:
     on the device; otherwise call replenishFeatures() (or addNewFeatures) yourself."""
 
     def __init__(self, **kw):
-        self.tc_ekf = TightlyCoupledEKF(**kw)
+        self.tc_ekf = TightlyCoupledEKF(**kw)  # (distortion=(k1, k2, p1, p2[, k3]): raw frames are rectified on the device, setDistortion below)
         self.tracker = KLTTracker(self.tc_ekf)
         self._imu_queue = []      # (stamp, gyro, accel), kept in stamp order; only used with use_imu = 1
         self._t_filter = None     # the stamp the device state stands at
@@ -424,6 +446,10 @@ class EKFVIO:
             self._t_filter = float(stamp) if self._t_filter is None else max(self._t_filter, float(stamp))
             self._last_K = K.copy()
         return self.tc_ekf._chk(rc, allow=(capi.ENUMERIC,))
+
+    def setDistortion(self, D):
+        """The camera's plumb_bob coefficients (TightlyCoupledEKF.setDistortion): from the next frame on addFrame takes raw frames."""
+        self.tc_ekf.setDistortion(D)
 
     def replenishFeatures(self):
         """EKFVIO::replenishFeatures (EKFVIO.cpp:224-311) on the current frame, on the device: FAST-9/16 with

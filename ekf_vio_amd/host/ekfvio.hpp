@@ -46,6 +46,11 @@ struct Error : std::runtime_error {
 struct Params {
     ekfvio_config cfg;
     float gate_chi2 = 0.f;  // not a field of ekfvio_config: set on the handle behind ekfvio_create (ekfvio_set_gate); 0 = off
+    // Not in the reference, whose deployment rectifies in front of the node (image_proc/rectify): with rectify = 1 the camera topic carries RAW
+    // frames and the handle rectifies them on the device (ekfvio_set_distortion).  The plumb_bob coefficients k1 k2 p1 p2 k3 come from
+    // CameraInfo.D (the ROS node) or from the distortion_* parameters (a caller without CameraInfo, the replay driver); all zero = off.
+    int rectify = 0;
+    std::array<double, 5> distortion{};
     std::map<std::string, std::string> node;  // odom_topic, camera_topic, base_frame, use_imu, publish_insight, ...
 
     Params() {
@@ -96,6 +101,12 @@ struct Params {
             cfg.klt_fb_max_px = (float)number(key, value);
             if (cfg.klt_fb_max_px < 0.f) throw Error(EKFVIO_EINVAL, "parameter klt_fb_max_px: negative: " + value);
         }
+        else if (key == "rectify") rectify = (value == "true" || value == "1") ? 1 : 0;
+        else if (key == "distortion_k1") distortion[0] = number(key, value);
+        else if (key == "distortion_k2") distortion[1] = number(key, value);
+        else if (key == "distortion_p1") distortion[2] = number(key, value);
+        else if (key == "distortion_p2") distortion[3] = number(key, value);
+        else if (key == "distortion_k3") distortion[4] = number(key, value);
         else if (key == "imu_gyro_variance") cfg.imu_gyro_variance = (float)number(key, value);
         else if (key == "imu_accel_variance") cfg.imu_accel_variance = (float)number(key, value);
         else if (key == "gravity_x") cfg.gravity[0] = (float)number(key, value);
@@ -115,7 +126,7 @@ struct Params {
                                         "default_point_depth", "default_point_depth_variance",
                                         "default_point_homogenous_variance", "frame_buffer_size", "imu_update",
                                         "imu_gyro_variance", "imu_accel_variance", "gravity_x", "gravity_y", "gravity_z", "remove_lost", "gate_chi2",
-                                        "klt_fb_max_px"};
+                                        "klt_fb_max_px", "rectify", "distortion_k1", "distortion_k2", "distortion_p1", "distortion_p2", "distortion_k3"};
         for (const auto& e : Params().node) out.push_back(e.first);
         for (const auto& e : ignored()) out.push_back(e.first);
         return out;
@@ -248,6 +259,9 @@ class TightlyCoupledEKF {
         r.err2.resize((size_t)n), r.rejected.resize((size_t)n);
         return r;
     }
+    // Not in the reference, which assumes a pinhole image (Frame.h:31): the camera's plumb_bob coefficients k1 k2 p1 p2 [k3] (ekfvio_set_distortion).
+    // From the next frame on, frames are rectified on the device between the upload and the pyramid; empty or all zero: off.
+    void setDistortion(const std::vector<double>& D) { chk(ekfvio_set_distortion(h_, D.empty() ? nullptr : D.data(), (int32_t)D.size())); }
     // Not in the reference (it flags lost landmarks, TightlyCoupledEKF.cpp:528, and keeps them): removes the landmarks whose byte
     // of `remove` is nonzero (one per landmark), or, with no mask, those flagged for deletion.  Returns the number removed.
     int removeFeatures(const std::vector<uint8_t>* remove = nullptr) {
@@ -396,6 +410,7 @@ class EKFVIO {
         : tc_ekf(p.cfg.max_features, device, &p.cfg), tracker(tc_ekf), params(p.node), use_imu_(p.cfg.use_imu != 0),
           scale_(p.cfg.inverse_image_scale > 1 ? p.cfg.inverse_image_scale : 1) {
         if (p.gate_chi2 > 0.f) tc_ekf.setGate(p.gate_chi2);  // (behind ekfvio_create: the gate is a property of the handle)
+        if (p.rectify) tc_ekf.setDistortion(std::vector<double>(p.distortion.begin(), p.distortion.end()));  // (likewise; a node replaces them with CameraInfo.D)
     }
     TightlyCoupledEKF tc_ekf;
     KLTTracker tracker;

@@ -71,6 +71,17 @@ bool to_grey(const sensor_msgs::Image& img, std::vector<uint8_t>& grey, const ui
     return true;
 }
 
+// CameraInfo.distortion_model where the message type carries it (sensor_msgs of every ROS release does; a declaration-only stand-in
+// for the header may carry D alone, and is then taken at its word)
+template <class Info>
+auto distortion_model_of(const Info& c, int) -> decltype(std::string(c.distortion_model)) {
+    return c.distortion_model;
+}
+template <class Info>
+std::string distortion_model_of(const Info&, long) {
+    return "plumb_bob";
+}
+
 class EkfvioNode {
    public:
     EkfvioNode() : it_(nh_) {
@@ -117,6 +128,18 @@ class EkfvioNode {
     }
 
    private:
+    // The coefficients travel with every CameraInfo (plumb_bob: k1 k2 p1 p2 k3); the handle is told when they change.  Another model is
+    // refused loudly and the frames go through as they are: the equidistant and rational models are not implemented on the device.
+    void setDistortionFrom(const sensor_msgs::CameraInfo& cam) {
+        const bool plumb_bob = distortion_model_of(cam, 0) == "plumb_bob" && (cam.D.empty() || cam.D.size() == 4 || cam.D.size() == 5);
+        if (!plumb_bob) ROS_ERROR_THROTTLE(5.0, "rectify: only the plumb_bob model with 4 or 5 coefficients is supported; frames are not rectified");
+        const std::vector<double> D = plumb_bob ? cam.D : std::vector<double>();
+        if (have_D_ && D == last_D_) return;
+        vio_->tc_ekf.setDistortion(D);
+        last_D_ = D;
+        have_D_ = true;
+    }
+
     void imuCallback(const sensor_msgs::ImuConstPtr& msg) {
         const ekfvio::Vector3f gyro{(float)msg->angular_velocity.x, (float)msg->angular_velocity.y, (float)msg->angular_velocity.z};
         const ekfvio::Vector3f acc{(float)msg->linear_acceleration.x, (float)msg->linear_acceleration.y,
@@ -144,6 +167,7 @@ class EkfvioNode {
         for (int i = 0; i < 9; i++) f.K[i] = (float)cam->K[i];
         f.t = img->header.stamp.toSec();
         try {
+            if (params_.rectify) setDistortionFrom(*cam);  // rectify = 1: the topic carries raw frames, the device rectifies them
             if (!vio_->addFrame(f)) ROS_ERROR_THROTTLE(1.0, "innovation covariance not positive definite (NumericalIssue)");
         } catch (const ekfvio::Error& e) {
             ROS_ERROR_STREAM("ekfvio: " << e.what());
@@ -238,6 +262,8 @@ class EkfvioNode {
     std::unique_ptr<ekfvio::EKFVIO> vio_;
     std::vector<uint8_t> grey_;
     bool publish_insight_ = false;
+    std::vector<double> last_D_;  // the coefficients the handle was told last (rectify = 1)
+    bool have_D_ = false;
     double dt_sum_ = 0;
     int dt_count_ = 0;
 };

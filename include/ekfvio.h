@@ -116,7 +116,8 @@ EKFVIO_API int ekfvio_default_config(ekfvio_config* cfg);
 EKFVIO_API int ekfvio_create(const ekfvio_config* cfg, int device, void* stream, ekfvio_filter** out);
 EKFVIO_API int ekfvio_destroy(ekfvio_filter* f);
 /* initializeBaseState(): back to mu = [0,0,0,1,0...], Sigma diag [0x7,30x9,0.5x6], no landmarks.  (The innovation gate's counts start
- * over; its threshold stays.  The same holds for the tracker's forward-backward check.) */
+ * over; its threshold stays.  The same holds for the tracker's forward-backward check.  The distortion coefficients of
+ * ekfvio_set_distortion stay too.) */
 EKFVIO_API int ekfvio_reset(ekfvio_filter* f);
 EKFVIO_API const char* ekfvio_last_error(const ekfvio_filter* f);
 
@@ -211,6 +212,43 @@ EKFVIO_API int ekfvio_set_gate(ekfvio_filter* f, float chi2);
  * total since create/reset. */
 EKFVIO_API int ekfvio_get_gate(ekfvio_filter* f, float* d2, uint8_t* gated, int32_t* n_landmarks, int32_t* gated_last,
                                int64_t* gated_total);
+
+/* ---- rectification of distorted frames (not in the reference: Frame.h:31 "for now the image must be undistorted for simplicity", its D
+ * at :32 is never read, and its deployment runs image_proc/rectify in front of the node) ------------------------------------------------
+ * With distortion coefficients set, every pushed frame (ekfvio_klt_push_frame, ekfvio_step_image) is rectified on the device between
+ * its upload and the pyramid: cv::initUndistortRectifyMap(K, D, R = I, new camera matrix = K, CV_16SC2) + cv::remap(INTER_LINEAR,
+ * BORDER_CONSTANT 0) of the full-size frame, plumb_bob model D = (k1, k2, p1, p2, k3).  The lines below are the specification; they
+ * restate OpenCV's fixed-point remap (INTER_BITS = 5) from memory, not from its source, and a NumPy restatement of them
+ * (tests/_rectify.py) is what the device is held to, bit for bit.  For destination pixel (x, y) of the full-size w x h frame, with
+ * fx, cx, fy, cy = K[0], K[2], K[4], K[5] of the K passed with the frame (before the division by inverse_image_scale; cx, cy are the true
+ * ones whatever use_principal_point says), everything in fp64, in this order, without fused multiply-add:
+ *
+ *     xn = (x - cx) / fx        yn = (y - cy) / fy
+ *     xx = xn*xn   yy = yn*yn   xy = xn*yn   r2 = xx + yy
+ *     rad = 1 + ((k3*r2 + k2)*r2 + k1)*r2
+ *     xd = (xn*rad + (2*p1)*xy) + p2*(r2 + 2*xx)
+ *     yd = (yn*rad + p1*(r2 + 2*yy)) + (2*p2)*xy
+ *     u = fx*xd + cx            v = fy*yd + cy
+ *     valid  <=>  |u| <= 2^20  and  |v| <= 2^20          (a NaN is invalid)
+ *     sx = rint(u*32), sy = rint(v*32) as int32 (round half to even);  invalid: sx = sy = INT32_MIN
+ *
+ * then in integers: ix = sx >> 5, ax = sx & 31 (arithmetic shift), the same for y; the four taps (ix,iy), (ix+1,iy), (ix,iy+1),
+ * (ix+1,iy+1) of the uploaded frame with the weights (32-ax)(32-ay), ax(32-ay), (32-ax)ay, ax*ay; a tap outside [0,w) x [0,h)
+ * contributes 0 (so the sentinel gives 0 by itself); out = (sum + 512) >> 10.  With D = 0 the map is exactly (32x, 32y) and the frame
+ * keeps every byte.  The rectified full-size frame then takes the road of an uploaded one: the resize and the pyramid read it, K is
+ * unchanged, and the intensity channel of ekfvio_get_points reads it.  The map is formed on the device once per (fx, cx, fy, cy, D, w, h)
+ * and kept.  Out of scope: the equidistant and rational models, a new camera matrix or alpha crop, and a mask that keeps the detector
+ * away from the black border (image_proc/rectify leaves the same border).
+ *
+ * count = 5: D as above; count = 4: k3 = 0; count = 0 (D may be NULL) or all coefficients zero: off (default; then no launch differs and
+ * every output keeps its bits).  A non-finite coefficient, any other count, NULL with count > 0: EKFVIO_EINVAL, and the setting stays
+ * what it was.  A property of the handle: it holds from the next pushed frame and survives ekfvio_reset. */
+EKFVIO_API int ekfvio_set_distortion(ekfvio_filter* f, const double* D, int32_t count);
+/* The map itself, sx and sy as defined above, row-major width x height int32 each: a pure host function (no handle, no device) that
+ * compiles the very inline function the device's map kernel compiles.  Callers take the valid region of the rectified frame from it
+ * (a tap outside the frame means no data there).  D, count as above (count = 0: the identity map). */
+EKFVIO_API int ekfvio_rectify_map(const float K[9], const double* D, int32_t count, int32_t width, int32_t height, int32_t* sx,
+                                  int32_t* sy);
 
 /* ---- KLT (KLTTracker::findNewFeaturePositions, KLTTracker.cpp:29-95) ----------------- */
 /* Uploads a frame (Frame.h:25-41: image + intrinsics K row-major 3x3 as in CameraInfo.K),
