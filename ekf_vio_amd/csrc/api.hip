@@ -1148,6 +1148,17 @@ int ekfvio_test_sweep_fault(ekfvio_filter* f, int32_t spin_limit, int32_t stall_
     return EKFVIO_OK;
 }
 
+int ekfvio_test_sweep_delay(ekfvio_filter* f, int32_t workgroup, int32_t point, int32_t ticks) {
+    // at most 1 ms, a third of the DEFAULT wait bound (Tuning::sweep_wait_ticks, 3 ms): under that bound a delay cannot turn into an abort.  A handle
+    // created with EKFVIO_SWEEP_WAIT_MS below 1 has a shorter bound and can abort on a long delay: the tests clear that variable
+    if (!f || (point != 0 && point != 1) || ticks < 0 || ticks > EKFVIO_TEST_SWEEP_DELAY_MAX_TICKS) return EKFVIO_EINVAL;
+    f->sweep_delay_wg = workgroup >= 0 ? workgroup : -1;
+    f->sweep_delay_point = point;
+    f->sweep_delay_ticks = ticks;
+    drop_graph(f);  // captured launches carry the old arguments
+    return EKFVIO_OK;
+}
+
 int ekfvio_test_cholesky_solve(ekfvio_filter* f, int32_t m, int32_t nrhs, const float* S, const float* Crhs,
                                float* L_out, float* X_out, int32_t* info) {
     // S: m x m (ld m) SPD; Crhs: nrhs x m (ld nrhs); L_out m x m; X_out = Crhs * S^-1 (nrhs x m).

@@ -1135,6 +1135,10 @@ static PersistArgs persist_args(ekfvio_filter* f, const UpdatePlan& p, float* L,
     pa.bound.wait_ticks = p.recoverable ? f->tune.sweep_wait_ticks : std::max(f->tune.sweep_wait_ticks, SWEEP_WAIT_TICKS_UNRECOVERABLE);
     pa.early_sources = f->tune.persist_early;
     pa.stall_wg = f->sweep_stall_wg >= 0 ? g.owner_block(f->sweep_stall_wg - 1) : -1;
+#ifdef EKFVIO_TEST_HOOKS
+    pa.delay_wg = f->sweep_delay_wg >= 0 ? g.owner_block(f->sweep_delay_wg - 1) : -1;  // (numbered like stall_wg)
+    pa.delay_point = f->sweep_delay_point, pa.delay_ticks = f->sweep_delay_ticks;
+#endif
     return pa;
 }
 

@@ -70,6 +70,11 @@ struct PersistArgs {
     float* T2;          // T2 out (another buffer than Sigma: late owners may still be gathering from Sigma), ld ldt
     int ldt;
     int nstate;         // n: T2 is written as zero outside n x n
+#ifdef EKFVIO_TEST_HOOKS
+    int delay_wg;       // hooks build only (ekfvio_test_sweep_delay): this owner workgroup arrives late -- it waits delay_ticks of the 100 MHz clock in FRONT
+    int delay_point;    // of the store of its finished tile (point 0) or of its panel block (point 1), so that a consumer that did not wait for the flag
+    int delay_ticks;    // finds the previous update's contents there; -1 = none.  Nothing is withheld: the store and the flag follow as always
+#endif
 };
 
 // 16-byte agent-scope (sc1, write-through) accesses for the data handed over inside the launch: buffer loads / stores
@@ -205,6 +210,19 @@ __device__ __forceinline__ void persist_publish_wave(int* flag, int lane) {
     wait_vm0();
     if (lane == 0) __hip_atomic_fetch_add(flag, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
+#ifdef EKFVIO_TEST_HOOKS
+// ekfvio_test_sweep_delay: the chosen workgroup idles `delay_ticks` of the 100 MHz clock here (every wavefront for itself, on scalar registers only;
+// at most 1 ms, a third of the shortest wait bound: api.hip refuses more), then goes on as it would have
+#define PERSIST_TEST_DELAY(a, point)                                                                                        \
+    do {                                                                                                                    \
+        if ((int)blockIdx.x == (a).delay_wg && (a).delay_point == (point)) {                                                \
+            const unsigned long long t0_ = __builtin_amdgcn_s_memrealtime();                                                \
+            while (__builtin_amdgcn_s_memrealtime() - t0_ < (unsigned long long)(unsigned)(a).delay_ticks) __builtin_amdgcn_s_sleep(8); \
+        }                                                                                                                   \
+    } while (0)
+#else
+#define PERSIST_TEST_DELAY(a, point) do { } while (0)
+#endif
 __device__ __forceinline__ unsigned long long ld_sign_sc1(const unsigned long long* p) {
     return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
@@ -303,8 +321,8 @@ __device__ __forceinline__ void sign_cols(float* dst, const float* src, unsigned
 }
 
 // Up to six flags and the abort word in one look (lanes 0-5 a flag each, lane 6 the abort word), then the workgroup's barrier: the waits of
-// gain_tile2, which needs two panel blocks of its own and up to three of the row blocks its measurement rows lie in -- and, for the last
-// block column, ready[mb-1] with them (flag 0 is a count: need0).
+// gain_tile2, which needs two panel blocks of its own and those of the row blocks its measurement rows lie in (the first three in the same look,
+// any further ones in looks of their own: gather_rows_wait) -- and, for the last block column, ready[mb-1] with them (flag 0 is a count: need0).
 __device__ __forceinline__ void persist_wait6(const int* f0, const int* f1, const int* f2, const int* f3, const int* f4, const int* f5, int need0,
                                               int* abort_flag, int* info, int tid, PollBound pb, bool lazy, int need5 = 1) {
     if (tid < 64) {
@@ -339,11 +357,25 @@ __device__ __forceinline__ void persist_wait6(const int* f0, const int* f1, cons
     __syncthreads();
 }
 
+// The panel blocks (mb + a0 .. mb + a1, kb) of further X row blocks, six flags a look: gain_tile2's row gather reads EVERY row block its block
+// column's measurement rows lie in, and with failed landmarks in between (idx skips them) those are more than the three its first look has room
+// for -- pass_mask(256, 161, "run"): block column 1 holds landmarks 32..39 and 135..158, row blocks 1 .. 7.  Workgroup-uniform; never entered
+// while every landmark is measured (64 rows are 96 state rows: at most three row blocks).  tests/test_gpu_handoff_delay.py.
+__device__ __forceinline__ void gather_rows_wait(const PersistArgs& a, int a0, int a1, int kb, int tid, bool lazy) {
+    for (; a0 <= a1; a0 += 6) {
+        const int* f = a.pan + (a.mb + a0) * a.mb + kb;
+        const int st = a.mb;
+        persist_wait6(f, a0 + 1 <= a1 ? f + st : nullptr, a0 + 2 <= a1 ? f + 2 * st : nullptr, a0 + 3 <= a1 ? f + 3 * st : nullptr,
+                      a0 + 4 <= a1 ? f + 4 * st : nullptr, a0 + 5 <= a1 ? f + 5 * st : nullptr, 1, a.abort_flag, a.info, tid, a.bound, lazy);
+    }
+}
+
 // Round 6: one 64x64 tile of the gain AND everything of the update's second Joseph term that belongs to it, so that ONE GEMM is left behind the
 // launch: Sigma' = T2 + K G'^T with T2 = Sigma (I - K H)^T from t2_tile and G' = K R^T - (H T2)^T (chol.hip, SchurArgs; TightlyCoupledEKF.cpp:586-600).
 //   K(ib,cb)  = sum_{kb >= cb} Y(ib,kb) Z(cb,kb)^T                                  as gain_tile: the same products, the same order, the same prune;
 //   W2(ib,cb) = (H T2)^T's tile = (H Sigma)^T(ib,cb) - sum_kb Y(ib,kb) S_kb HY(cb,kb)^T, HY(cb,kb) = the rows idx[64 cb ..] of block column kb of Y
-//               (a row gather out of the one to three X row blocks the tile's measurement rows lie in; X L^-T acts on rows one by one, so the
+//               (a row gather out of the X row blocks alo .. ahi the tile's measurement rows lie in -- one to three while every landmark is measured, more
+//               with failed landmarks in between, and each one's flag is awaited: gather_rows_wait; X L^-T acts on rows one by one, so the
 //               gathered rows of Y are the rows of Y whoever solves them) -- the tile's own copy of the rows idx[.] of T2, summed like t2_tile's;
 //   G'(ib,cb) = K R^T - W2 (the pruned K, ascending measurement index, as joseph_g_kernel), K y's partial sums over the tile's columns -> Kyp[cb].
 // WAIT: inside the persistent launch (operands awaited per block column; the LAST block column's three panel blocks are solved here from the
@@ -406,6 +438,7 @@ __device__ __forceinline__ void gain_tile2(const PersistArgs& a, const GatherArg
             persist_wait6(a.pan + iy * mb + kb, gk ? a.pan + iz * mb + kb : nullptr, alo <= ahi ? a.pan + (mb + alo) * mb + kb : nullptr,
                           alo + 1 <= ahi ? a.pan + (mb + alo + 1) * mb + kb : nullptr, alo + 2 <= ahi ? a.pan + (mb + alo + 2) * mb + kb : nullptr, nullptr, 1,
                           a.abort_flag, a.info, tid, a.bound, kb < mb - 2);
+            if (ahi - alo > 2) gather_rows_wait(a, alo + 3, ahi, kb, tid, kb < mb - 2);
             load_tile_sc1(Ti, bL, (unsigned)(kb * PB) * (unsigned)ldl + (unsigned)(iy * PB), ldl, tid);
             if (gk) load_tile_sc1(Tj, bL, (unsigned)(kb * PB) * (unsigned)ldl + (unsigned)(iz * PB), ldl, tid);
 #pragma unroll
@@ -490,6 +523,7 @@ __device__ __forceinline__ void gain_tile2(const PersistArgs& a, const GatherArg
         persist_wait6(a.pan + iy * mb + k6, gk6 ? a.pan + iz * mb + k6 : (zi ? nullptr : a.fin + iz * mb + kl), alo <= ahi ? a.pan + (mb + alo) * mb + k6 : nullptr,
                       alo + 1 <= ahi ? a.pan + (mb + alo + 1) * mb + k6 : nullptr, alo + 2 <= ahi ? a.pan + (mb + alo + 2) * mb + k6 : nullptr, nullptr, 1,
                       a.abort_flag, a.info, tid, a.bound, false);
+        if (ahi - alo > 2) gather_rows_wait(a, alo + 3, ahi, k6, tid, false);  // (their flags also cover the rows gathered from column mb-1's finished tiles)
         float4 ql[4], qi[4], qj[4];
         float hq[16];
         unsigned long long neg6;
@@ -1275,6 +1309,7 @@ __global__ __launch_bounds__(256) void chol_persist_kernel(PersistArgs a, Gather
 #pragma unroll
         for (int q = 0; q < 16; q++) Tl[(wc * 32 + (q & 3) + 8 * (q >> 2) + 4 * (lane >> 5)) * PLD + r] = tv[q];
         __syncthreads();
+        PERSIST_TEST_DELAY(a, 0);
         store_tile_sc1<false>(Tl, bS, oij, lds, tid);
     }
     if ((int)blockIdx.x != a.stall_wg) persist_publish(a.fin + i * mb + j, tid);
@@ -1284,6 +1319,7 @@ __global__ __launch_bounds__(256) void chol_persist_kernel(PersistArgs a, Gather
     if (klast >= k0 && i != j) {  // the panel block of row block i in block column j-1
         if (a.gain && i >= mb) {  // an X or identity row block: an operand of the gain tiles formed inside this launch
             const unsigned od = (unsigned)(klast * PB) * (unsigned)ldl + (unsigned)(i * PB);
+            PERSIST_TEST_DELAY(a, 1);
             if (neg != 0ull && i >= idb0) store_tile_signed_sc1(Ti, bL, od, ldl, tid, neg);
             else store_tile_sc1<false>(Ti, bL, od, ldl, tid);
             persist_publish(a.pan + i * mb + klast, tid);

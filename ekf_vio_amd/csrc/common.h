@@ -113,6 +113,9 @@ struct ekfvio_filter {
     long long early_output_frames = 0;  // frames whose outputs went out between the update's two Joseph GEMMs (Tuning::early_outputs; test hook)
     int sweep_spin_limit = 0;         // > 0: looks per wait of the persistent sweep (test hook ekfvio_test_sweep_fault); 0: SWEEP_SPIN_LIMIT
     int sweep_stall_wg = -1;          // fault injection: this workgroup of the persistent launch never raises its flag
+#ifdef EKFVIO_TEST_HOOKS
+    int sweep_delay_wg = -1, sweep_delay_point = 0, sweep_delay_ticks = 0;  // ekfvio_test_sweep_delay: this owner of the persistent launch stores late (PersistArgs::delay_wg)
+#endif
     bool sweep_retry_armed = false;    // sweep_latched_off is tried again at sweep_retry_at (api.hip, sweep_maybe_retry)
     double sweep_retry_pause_s = 0.0;  // (its first value: Tuning::sweep_retry_first_s)
     int sweep_probation = 0;           // > 0: clean persistent sweeps still to come behind a retry before sweep_retry_pause_s starts over (api.hip)

@@ -312,6 +312,12 @@ class TightlyCoupledEKF:
         self._need_hooks()
         self._chk(self.lib.ekfvio_test_sweep_fault(self.h, int(spin_limit), int(stall_workgroup)))
 
+    def sweep_delay(self, workgroup=-1, point=0, ticks=0):
+        """Owner `workgroup` of the persistent sweep (numbered like sweep_fault's stall_workgroup; -1: none) stores its finished tile (point 0)
+        or its panel block (point 1) `ticks` of the 100 MHz clock late (ekfvio_test_sweep_delay; hooks build)."""
+        self._need_hooks()
+        self._chk(self.lib.ekfvio_test_sweep_delay(self.h, int(workgroup), int(point), int(ticks)))
+
     def test_cholesky_solve(self, S, Crhs):
         """Returns (L, X = Crhs @ inv(S), info).  (hooks build)"""
         self._need_hooks()

@@ -30,6 +30,17 @@ EKFVIO_API int ekfvio_test_sweep_stamps(ekfvio_filter* f, int enable, int64_t st
 /* Fault injection for the persistent sweep: at most `spin_limit` looks per wait (0: the production limit), and workgroup
    `stall_workgroup` of the launch never raises its tile's flag (-1: none), so every wait behind it runs out. */
 EKFVIO_API int ekfvio_test_sweep_fault(ekfvio_filter* f, int32_t spin_limit, int32_t stall_workgroup);
+/* Arrival order of the persistent sweep's hand-offs (NOT fault injection: nothing is withheld and no wait runs out).  Owner workgroup `workgroup`
+   of the launch -- numbered like stall_workgroup, mapped through PersistGrid::owner_block; -1: none -- idles `ticks` of the 100 MHz clock and then
+   goes on as always.  point 0: in front of the store of its finished tile (the store behind which fin[i][j] goes up); point 1: in front of the
+   store of its panel block (the store behind which pan[i][j-1] goes up).  The idling comes BEFORE the data, not between data and flag: a consumer
+   that reads without waiting for the flag finds what the previous update left there.  EKFVIO_EINVAL for another point or more than
+   EKFVIO_TEST_SWEEP_DELAY_MAX_TICKS (1 ms, a third of the default 3 ms wait bound; EKFVIO_SWEEP_WAIT_MS can set a shorter one).  An owner
+   has a panel block to store only where it is an operand of the gain formed inside the launch (an X or identity row block off the diagonal);
+   for every other owner point 1 does nothing.  A launch that forms no gain inside solves the last block column's panel blocks in a branch
+   the hook does not reach. */
+#define EKFVIO_TEST_SWEEP_DELAY_MAX_TICKS 100000
+EKFVIO_API int ekfvio_test_sweep_delay(ekfvio_filter* f, int32_t workgroup, int32_t point, int32_t ticks);
 EKFVIO_API int ekfvio_test_cholesky_solve(ekfvio_filter* f, int32_t m, int32_t nrhs, const float* S, const float* Crhs,
                                float* L_out, float* X_out, int32_t* info);
 /* The flow an update would take (csrc/plan.h, plan_update), without a handle or a device: the switches from the environment, the sizes of a

@@ -332,8 +332,10 @@ def test_uploaded_runs_gate_on_the_device_and_leave_the_sequence_alone():
 # ------------------------------------------------------------------ 7. clustered rejections across sweeps
 def test_clustered_rejections_give_the_same_bits_under_both_sweeps(monkeypatch):
     """A contiguous run of rejected landmarks plus scattered tracker failures: whole 64-row blocks of the measurement map shift, the shape
-    ADVICE.md's open finding on gain_tile2<true>'s waits describes.  The persistent sweep must give the per-step sweep's bits.  (It does on
-    the MI355X: this shape does not confirm the finding, and chol_persist.inc is as it was.)"""
+    ADVICE.md's finding on gain_tile2<true>'s waits describes.  The persistent sweep must give the per-step sweep's bits.  (It did on an
+    idle MI355X before the finding was dealt with, too: a missing wait shows only when the producer is late.  tests/test_gpu_handoff_delay.py
+    makes each owner late in turn, with this mask as its case C; that confirmed the finding, and gain_tile2<true> now looks at the flag of
+    every row block it gathers from: profiles/handoff_delay.txt.)"""
     N = 256
     dt, st, (fr,) = warmed(N)
     z, R, _ = fr
