@@ -219,6 +219,8 @@ __device__ __forceinline__ f32x16 mma64(const float* As, int a_si, int a_sq, con
     }
     return acc;
 }
+// the column j of a wavefront's acc[reg] (the layout above)
+__device__ __forceinline__ int mma64_col(int wc, int lane, int reg) { return wc * 32 + (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5); }
 // The same product with the column signs of an indefinite block applied to A's k index (bit q of `neg` set: column q
 // of the panel belongs to a negative pivot): sum_q s_q A(i,q) B(j,q).  Rare path (see the header).
 // Not inlined: the rare path must not shape the register allocation and scheduling of the kernels' hot loops.
@@ -937,7 +939,7 @@ __global__ __launch_bounds__(256) void chol_step_kernel(float* __restrict__ S, i
         // next diagonal tile: update into LDS and factor it now (look-ahead)
 #pragma unroll
         for (int q = 0; q < 16; q++) {
-            const int c = wc * 32 + (q & 3) + 8 * (q >> 2) + 4 * (lane >> 5);
+            const int c = mma64_col(wc, lane, q);
             Tl[c * PLD + r] = tgt[q] - up[q];
         }
         __syncthreads();
@@ -967,7 +969,7 @@ __global__ __launch_bounds__(256) void chol_step_kernel(float* __restrict__ S, i
             __syncthreads();
 #pragma unroll
             for (int q = 0; q < 16; q++) {
-                const int c = wc * 32 + (q & 3) + 8 * (q >> 2) + 4 * (lane >> 5);
+                const int c = mma64_col(wc, lane, q);
                 Tl[c * PLD + r] = Sij[(size_t)c * lds + r] - up[q];
             }
             neg1 = potrf64_signed(Tl, Tinv, tid);
@@ -990,12 +992,12 @@ __global__ __launch_bounds__(256) void chol_step_kernel(float* __restrict__ S, i
         float tv[16];
 #pragma unroll
         for (int q = 0; q < 16; q++) {
-            const int c = wc * 32 + (q & 3) + 8 * (q >> 2) + 4 * (lane >> 5);
+            const int c = mma64_col(wc, lane, q);
             tv[q] = first ? 0.f : Sij[(size_t)c * ldt + r];
         }
 #pragma unroll
         for (int q = 0; q < 16; q++) {
-            const int c = wc * 32 + (q & 3) + 8 * (q >> 2) + 4 * (lane >> 5);
+            const int c = mma64_col(wc, lane, q);
             Sij[(size_t)c * ldt + r] = tv[q] + up[q];
         }
     } else {
@@ -1004,7 +1006,7 @@ __global__ __launch_bounds__(256) void chol_step_kernel(float* __restrict__ S, i
         float tv[16];
 #pragma unroll
         for (int q = 0; q < 16; q++) {
-            const int c = wc * 32 + (q & 3) + 8 * (q >> 2) + 4 * (lane >> 5);
+            const int c = mma64_col(wc, lane, q);
             tv[q] = Sij[(size_t)c * ldt + r];
         }
         float tm[16];
@@ -1014,20 +1016,20 @@ __global__ __launch_bounds__(256) void chol_step_kernel(float* __restrict__ S, i
             float* Mji = sc.P + (size_t)(i - mb) * PB * sc.ldp + (size_t)(j - mb) * PB;
 #pragma unroll
             for (int q = 0; q < 16; q++) {
-                const int c = wc * 32 + (q & 3) + 8 * (q >> 2) + 4 * (lane >> 5);
+                const int c = mma64_col(wc, lane, q);
                 tm[q] = Mji[(size_t)c * ldt + r];
                 Tl[r * PLD + c] = up[q];
             }
             __syncthreads();
 #pragma unroll
             for (int q = 0; q < 16; q++) {
-                const int c = wc * 32 + (q & 3) + 8 * (q >> 2) + 4 * (lane >> 5);
+                const int c = mma64_col(wc, lane, q);
                 Mji[(size_t)c * ldt + r] = tm[q] - Tl[c * PLD + r];
             }
         }
 #pragma unroll
         for (int q = 0; q < 16; q++) {
-            const int c = wc * 32 + (q & 3) + 8 * (q >> 2) + 4 * (lane >> 5);
+            const int c = mma64_col(wc, lane, q);
             Sij[(size_t)c * ldt + r] = tv[q] - up[q];
         }
     }

@@ -20,8 +20,8 @@
 // Visibility (MI355X_MICROARCH.md, inter-workgroup visibility): everything handed over inside the launch is stored with
 // agent-scope (sc1, write-through) 16-byte buffer stores; every storing wavefront waits for its stores (vmcnt) and the flag
 // goes up behind that -- a helper's by one lane behind the workgroup's barrier, ready[k] by each of the chain's four
-// wavefronts adding 1 for itself.  A consumer looks at its flags with ONE load instruction (lanes 0-2 a flag each, lane 3
-// the abort word; relaxed agent-scope loads) and reads the data with sc1 loads only, behind a barrier or, a wavefront for
+// wavefronts adding 1 for itself.  A consumer looks at its flags with ONE load instruction (a lane per flag, lane 63
+// the abort word; relaxed agent-scope loads: persist_poll) and reads the data with sc1 loads only, behind a barrier or, a wavefront for
 // itself, behind its own match.  Every wait is bounded: after PersistArgs::bound.wait_ticks of wall clock (3 ms; or bound.spin_limit looks, the
 // fault-injection hook's bound) the abort word is raised, every wait
 // falls through and info bit 1 reports it (the grid always drains); the kernels behind the sweep then leave Sigma and mu
@@ -30,6 +30,15 @@
 //
 // Bits: a tile receives its steps in ascending order, one subtraction of a k-ascending MFMA product per step, and the panel
 // blocks are the same substitutions on the same final tiles as in chol_step_kernel: identical to the per-step sweep.
+
+#ifndef PERSIST_POLL_SLEEP_LAZY
+#define PERSIST_POLL_SLEEP_LAZY 12
+#endif
+#ifndef PERSIST_POLL_SLEEP
+#define PERSIST_POLL_SLEEP 2  // 64-cycle units between two looks of a wavefront the chain waits for; the others: _LAZY (same-box A/B at N=256:
+                               // every waiting wavefront looking back to back, the first version, costs 1.5 % of the step -- the looks load the
+                               // fabric the chain reads through; 12 .. 24 units for the others and 2 .. 4 for the critical ones measure the same)
+#endif
 
 struct PollBound {
     int spin_limit, wait_ticks;
@@ -94,25 +103,39 @@ __device__ __forceinline__ void st_sc1(__amdgpu_buffer_rsrc_t b, unsigned off, f
 }
 __device__ __forceinline__ void wait_vm0() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
 
-// 64x64 tile at float offset `base` (leading dimension ld) <-> LDS tile
-__device__ __forceinline__ void load_tile_sc1(float* T, __amdgpu_buffer_rsrc_t b, unsigned base, int ld, int tid) {
+// A 64x64 tile on its way from memory to an LDS tile, in registers (four 16-byte pieces per thread): requested with sc1 loads at float offset
+// `base` (leading dimension ld), put once it is wanted -- the loads stay in flight across whatever lies between the two
+struct RegTile {
     float4 v[4];
+    __device__ __forceinline__ void request(__amdgpu_buffer_rsrc_t b, unsigned base, int ld, int tid) {
 #pragma unroll
-    for (int it = 0; it < 4; it++) {
-        const int e = tid + it * 256;
-        v[it] = ld_sc1(b, base + (unsigned)(e >> 4) * (unsigned)ld + (unsigned)(e & 15) * 4u);
+        for (int it = 0; it < 4; it++) {
+            const int e = tid + it * 256;
+            v[it] = ld_sc1(b, base + (unsigned)(e >> 4) * (unsigned)ld + (unsigned)(e & 15) * 4u);
+        }
     }
+    __device__ __forceinline__ void put(float* T, int tid) const {
 #pragma unroll
-    for (int it = 0; it < 4; it++) {
-        const int e = tid + it * 256;
-        *reinterpret_cast<float4*>(T + (e >> 4) * PLD + (e & 15) * 4) = v[it];
+        for (int it = 0; it < 4; it++) {
+            const int e = tid + it * 256;
+            *reinterpret_cast<float4*>(T + (e >> 4) * PLD + (e & 15) * 4) = v[it];
+        }
     }
-}
-__device__ __forceinline__ void load_inv_sc1(float* Tinv, __amdgpu_buffer_rsrc_t b, unsigned base, int tid) {
-    const float4 v = ld_sc1(b, base + tid * 4);
+};
+// a thread's 16 bytes of a block column's 16x16 inverses (requested at float offset base + 4 tid) into their LDS layout
+__device__ __forceinline__ void inv_put(float4 v, float* Tinv, int tid) {
     const int p = tid >> 6, c = (tid >> 2) & 15, r4 = (tid & 3) * 4;
     float* t = Tinv + p * 16 * ILD + c * ILD + r4;
     t[0] = v.x; t[1] = v.y; t[2] = v.z; t[3] = v.w;
+}
+// 64x64 tile at float offset `base` (leading dimension ld) <-> LDS tile
+__device__ __forceinline__ void load_tile_sc1(float* T, __amdgpu_buffer_rsrc_t b, unsigned base, int ld, int tid) {
+    RegTile t;
+    t.request(b, base, ld, tid);
+    t.put(T, tid);
+}
+__device__ __forceinline__ void load_inv_sc1(float* Tinv, __amdgpu_buffer_rsrc_t b, unsigned base, int tid) {
+    inv_put(ld_sc1(b, base + tid * 4), Tinv, tid);
 }
 template <bool LOWER>
 __device__ __forceinline__ void store_tile_sc1(const float* T, __amdgpu_buffer_rsrc_t b, unsigned base, int ld, int tid) {
@@ -152,28 +175,26 @@ __device__ __forceinline__ void store_tile_signed_sc1(const float* T, __amdgpu_b
     }
 }
 
-// Lanes 0-2 of the polling wavefront look at one flag each and lane 3 at the abort word: ONE load instruction, one memory
-// round trip per look (three flags and the abort word looked at one after the other by one lane cost four round trips per
-// look: that was most of a helper's reaction time).  need_a: the first flag is a count (ready: 4), the others are 0 / 1.
-__device__ __forceinline__ void persist_poll(const int* a, const int* b, const int* c, int* abort_flag, int* info, int lane, int need_a, PollBound pb, bool lazy = false) {
-    const int* p = lane == 0 ? a : lane == 1 ? b : lane == 2 ? c : lane == 3 ? abort_flag : nullptr;
-    const int need = lane == 0 ? need_a : 1;
+// What ONE lane of the polling wavefront looks at: a flag and the value it waits for (a count for ready[]: 4; 0 / 1 for the others).
+// flag == nullptr: nothing.  Lanes 0 .. PERSIST_POLL_FLAGS - 1 (plan.h) have a flag each, lane 63 always looks at the abort word.
+struct PollLane {
+    const int* flag;
+    int need;
+};
+// Every flag a consumer needs and the abort word in ONE load instruction, one memory round trip per look (three flags and the abort word
+// looked at one after the other by one lane cost four round trips per look: that was most of a helper's reaction time).  A look is one
+// instruction however many lanes take part, so a wait names ALL its flags here, lane by lane, from the same range its loads are addressed by.
+__device__ __forceinline__ void persist_poll(const PersistArgs& a, PollLane pl, int lane, bool lazy) {
+    const int* p = lane == 63 ? a.abort_flag : pl.flag;
+    const int need = pl.need;
     int spins = 0;
     unsigned long long t0 = 0ull;  // (read at the first re-look only: a wait that is satisfied at once costs nothing)
     for (;;) {
         int v = need;
         if (p) v = __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        const bool more = lane < 3 && v < need;
-        const bool aborted = lane == 3 && v != 0;
+        const bool more = lane < 63 && v < need;
+        const bool aborted = lane == 63 && v != 0;
         if (__ballot(more) == 0ull || __ballot(aborted) != 0ull) break;
-#ifndef PERSIST_POLL_SLEEP_LAZY
-#define PERSIST_POLL_SLEEP_LAZY 12
-#endif
-#ifndef PERSIST_POLL_SLEEP
-#define PERSIST_POLL_SLEEP 2  // 64-cycle units between two looks of a wavefront the chain waits for; the others: _LAZY (same-box A/B at N=256:
-                               // every waiting wavefront looking back to back, the first version, costs 1.5 % of the step -- the looks load the
-                               // fabric the chain reads through; 12 .. 24 units for the others and 2 .. 4 for the critical ones measure the same)
-#endif
         if (lazy) __builtin_amdgcn_s_sleep(PERSIST_POLL_SLEEP_LAZY);  // (whose result the chain does not wait for: fewer looks on the fabric)
         else if (PERSIST_POLL_SLEEP) __builtin_amdgcn_s_sleep(PERSIST_POLL_SLEEP);
         // Bounded by wall-clock time (ADVICE r04): a workgroup that is not resident -- compute units masked, or held by another
@@ -183,21 +204,31 @@ __device__ __forceinline__ void persist_poll(const int* a, const int* b, const i
         if ((spins & 31) == 0) {
             const unsigned long long now = __builtin_amdgcn_s_memrealtime();
             if (spins == 0) t0 = now;
-            else timed_out = now - t0 > (unsigned long long)(unsigned)pb.wait_ticks;
+            else timed_out = now - t0 > (unsigned long long)(unsigned)a.bound.wait_ticks;
         }
-        if (++spins > pb.spin_limit || timed_out) {
+        if (++spins > a.bound.spin_limit || timed_out) {
             if (lane == 0) {
-                __hip_atomic_store(abort_flag, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                atomicOr(info, 2);
+                __hip_atomic_store(a.abort_flag, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                atomicOr(a.info, 2);
             }
             break;
         }
     }
 }
-// The first wavefront polls up to three flags (null = nothing to wait for), then the workgroup meets at a barrier.
-__device__ __forceinline__ void persist_wait(const int* a, const int* b, const int* c, int* abort_flag, int* info, int tid, PollBound pb, int need_a = 1, bool lazy = false) {
-    if (tid < 64) persist_poll(a, b, c, abort_flag, info, tid, need_a, pb, lazy);
+// up to three flags, lanes 0-2 (null = nothing to wait for).  need0: the first flag is a count (ready: 4), the others are 0 / 1
+__device__ __forceinline__ PollLane poll_lane3(const int* f0, const int* f1, const int* f2, int need0, int lane) {
+    return {lane == 0 ? f0 : lane == 1 ? f1 : lane == 2 ? f2 : nullptr, lane == 0 ? need0 : 1};
+}
+__device__ __forceinline__ void persist_poll(const PersistArgs& a, const int* f0, const int* f1, const int* f2, int lane, int need0 = 1, bool lazy = false) {
+    persist_poll(a, poll_lane3(f0, f1, f2, need0, lane), lane, lazy);
+}
+// The first wavefront polls (pl: what thread tid < 64 looks at), then the workgroup meets at a barrier.
+__device__ __forceinline__ void persist_wait(const PersistArgs& a, PollLane pl, int tid, bool lazy) {
+    if (tid < 64) persist_poll(a, pl, tid, lazy);
     __syncthreads();
+}
+__device__ __forceinline__ void persist_wait(const PersistArgs& a, const int* f0, const int* f1, const int* f2, int tid, int need0 = 1, bool lazy = false) {
+    persist_wait(a, poll_lane3(f0, f1, f2, need0, tid), tid, lazy);
 }
 // every wavefront's write-through stores have completed, then one lane raises the flag
 __device__ __forceinline__ void persist_publish(int* flag, int tid) {
@@ -230,9 +261,8 @@ __device__ __forceinline__ unsigned long long ld_sign_sc1(const unsigned long lo
 // One 64x64 tile of the Kalman gain, K(ib, cb) = sum_{kb >= cb} Y(ib,kb) Z(cb,kb)^T with Y(ib,kb) the panel block of X row block ib and
 // Z(cb,kb) that of identity row block cb (= block (cb,kb) of L^-T, signs applied) in block column kb: K = Y L^-1 with the structurally
 // zero blocks skipped (TightlyCoupledEKF.cpp:577-580).  Per kb one k-ascending MFMA product from zero, added in ascending kb; then the
-// reference's sparseView prune (:580).  The SAME function forms the gain inside the persistent launch (WAIT: the operands arrive while the
-// sweep runs) and in gain_tiles_kernel behind every other sweep of fewer than EKF_SWEEP_SPLIT_MB block columns: identical bits.
-template <bool WAIT>
+// reference's sparseView prune (:580).  Inside the persistent launch: the operands arrive while the sweep runs.  The stand-alone form of
+// the same arithmetic, behind every other sweep of fewer than EKF_SWEEP_SPLIT_MB block columns, is gain_tiles_kernel: identical bits.
 __device__ __forceinline__ void gain_tile(const PersistArgs& a, float* Ti, float* Tj, float* Tl, float* Tinv, int ib, int cb, int tid) {
     const int lane = tid & 63, wave = tid >> 6, wr = wave & 1, wc = wave >> 1;
     const int r = wr * 32 + (lane & 31);
@@ -242,33 +272,21 @@ __device__ __forceinline__ void gain_tile(const PersistArgs& a, float* Ti, float
 #pragma unroll
     for (int q = 0; q < 16; q++) kv[q] = 0.f;
     const int iy = mb + ib, iz = a.idb0 + cb;
-    float4 va[4], vb[4];  // (stand-alone form) the next block column's two operands, requested a product ahead
-    auto request = [&](int kb) {
-        const float* ya = a.L + (size_t)kb * PB * ldl + (size_t)iy * PB;
-        const float* za = a.L + (size_t)kb * PB * ldl + (size_t)iz * PB;
-#pragma unroll
-        for (int it = 0; it < 4; it++) {
-            const int e = tid + it * 256;
-            va[it] = *reinterpret_cast<const float4*>(ya + (size_t)(e >> 4) * ldl + (e & 15) * 4);
-            vb[it] = *reinterpret_cast<const float4*>(za + (size_t)(e >> 4) * ldl + (e & 15) * 4);
-        }
-    };
-    if constexpr (!WAIT) request(cb);
     for (int kb = cb; kb < mb; kb++) {
         bool signed_last = false;
         unsigned long long negl = 0ull;
-        if (WAIT && kb == mb - 1) {
+        if (kb == mb - 1) {
             // The LAST block column's two panel blocks are solved here, not by their tiles' owners (who would store them, flag them, and
             // be noticed): the launch ends with this product, and the detour is ~3 k cycles of it.  Same substitution on the same
             // final tiles as the owners' (chol_panel_kernel's in the per-step sweep): the same bits.
             const __amdgpu_buffer_rsrc_t bS = persist_rsrc(a.S, (unsigned)a.lds * (unsigned)(mb * PB));
             const __amdgpu_buffer_rsrc_t bI = persist_rsrc(a.Linv, (unsigned)(mb * PB * PB));
             const bool zi = a.grid.compact() && cb == kb;  // (compact launch: tile (idb0 + mb-1, mb-1) is the identity and nobody's)
-            persist_wait(nullptr, a.fin + iy * mb + kb, zi ? nullptr : a.fin + iz * mb + kb, a.abort_flag, a.info, tid, a.bound, 1, true);
+            persist_wait(a, nullptr, a.fin + iy * mb + kb, zi ? nullptr : a.fin + iz * mb + kb, tid, 1, true);
             load_tile_sc1(Ti, bS, (unsigned)(kb * PB) * (unsigned)a.lds + (unsigned)(iy * PB), a.lds, tid);
             if (zi) identity_tile(Tj, tid);
             else load_tile_sc1(Tj, bS, (unsigned)(kb * PB) * (unsigned)a.lds + (unsigned)(iz * PB), a.lds, tid);
-            persist_wait(a.ready + kb, nullptr, nullptr, a.abort_flag, a.info, tid, a.bound, 4, false);
+            persist_wait(a, a.ready + kb, nullptr, nullptr, tid, 4, false);
             load_tile_sc1(Tl, bL, (unsigned)(kb * PB) * (unsigned)ldl + (unsigned)(kb * PB), ldl, tid);
             load_inv_sc1(Tinv, bI, (unsigned)(kb * PB * PB), tid);
             negl = ld_sign_sc1(a.Lsign + kb);
@@ -276,23 +294,12 @@ __device__ __forceinline__ void gain_tile(const PersistArgs& a, float* Ti, float
             tri_solve_fwd2(Ti, Tj, Tl, Tinv, wave, lane);
             if (a.dbg && tid == 0 && ib * mb + cb < 104) a.dbg[400 + ib * mb + cb] = (long long)__builtin_amdgcn_s_memrealtime();
             signed_last = negl != 0ull;  // (the identity rows' block carries the column signs into the gain: applied inside the product)
-        } else if constexpr (WAIT) {
-            persist_wait(nullptr, a.pan + iy * mb + kb, a.pan + iz * mb + kb, a.abort_flag, a.info, tid, a.bound, 1, true);
+        } else {
+            persist_wait(a, nullptr, a.pan + iy * mb + kb, a.pan + iz * mb + kb, tid, 1, true);
             load_tile_sc1(Ti, bL, (unsigned)(kb * PB) * (unsigned)ldl + (unsigned)(iy * PB), ldl, tid);
             load_tile_sc1(Tj, bL, (unsigned)(kb * PB) * (unsigned)ldl + (unsigned)(iz * PB), ldl, tid);
-        } else {
-            __syncthreads();
-#pragma unroll
-            for (int it = 0; it < 4; it++) {
-                const int e = tid + it * 256;
-                *reinterpret_cast<float4*>(Ti + (e >> 4) * PLD + (e & 15) * 4) = va[it];
-                *reinterpret_cast<float4*>(Tj + (e >> 4) * PLD + (e & 15) * 4) = vb[it];
-            }
         }
         __syncthreads();
-        if constexpr (!WAIT) {
-            if (kb + 1 < mb) request(kb + 1);
-        }
         const f32x16 up = signed_last ? mma64_signed(Ti, 1, PLD, Tj, 1, PLD, wr, wc, lane, negl) : mma64(Ti, 1, PLD, Tj, 1, PLD, wr, wc, lane);
 #pragma unroll
         for (int q = 0; q < 16; q++) kv[q] = kv[q] + up[q];
@@ -300,7 +307,7 @@ __device__ __forceinline__ void gain_tile(const PersistArgs& a, float* Ti, float
     float* Kt = a.K + (size_t)(cb * PB) * a.ldk + (size_t)ib * PB;
 #pragma unroll
     for (int q = 0; q < 16; q++) {
-        const int c = wc * 32 + (q & 3) + 8 * (q >> 2) + 4 * (lane >> 5);
+        const int c = mma64_col(wc, lane, q);
         Kt[(size_t)c * a.ldk + r] = (fabsf(kv[q]) > EKF_FLUSH_THRESH) ? kv[q] : 0.f;  // .sparseView(SPARSE_THRESH, SPARSE_EPS)
     }
 }
@@ -320,62 +327,12 @@ __device__ __forceinline__ void sign_cols(float* dst, const float* src, unsigned
     }
 }
 
-// Up to six flags and the abort word in one look (lanes 0-5 a flag each, lane 6 the abort word), then the workgroup's barrier: the waits of
-// gain_tile2, which needs two panel blocks of its own and those of the row blocks its measurement rows lie in (the first three in the same look,
-// any further ones in looks of their own: gather_rows_wait) -- and, for the last block column, ready[mb-1] with them (flag 0 is a count: need0).
-__device__ __forceinline__ void persist_wait6(const int* f0, const int* f1, const int* f2, const int* f3, const int* f4, const int* f5, int need0,
-                                              int* abort_flag, int* info, int tid, PollBound pb, bool lazy, int need5 = 1) {
-    if (tid < 64) {
-        const int lane = tid;
-        const int* p = lane == 0 ? f0 : lane == 1 ? f1 : lane == 2 ? f2 : lane == 3 ? f3 : lane == 4 ? f4 : lane == 5 ? f5 : lane == 6 ? abort_flag : nullptr;
-        const int need = lane == 0 ? need0 : lane == 5 ? need5 : 1;
-        int spins = 0;
-        unsigned long long t0 = 0ull;
-        for (;;) {
-            int v = need;
-            if (p) v = __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            const bool more = lane < 6 && v < need;
-            const bool aborted = lane == 6 && v != 0;
-            if (__ballot(more) == 0ull || __ballot(aborted) != 0ull) break;
-            if (lazy) __builtin_amdgcn_s_sleep(PERSIST_POLL_SLEEP_LAZY);
-            else if (PERSIST_POLL_SLEEP) __builtin_amdgcn_s_sleep(PERSIST_POLL_SLEEP);
-            bool timed_out = false;
-            if ((spins & 31) == 0) {
-                const unsigned long long now = __builtin_amdgcn_s_memrealtime();
-                if (spins == 0) t0 = now;
-                else timed_out = now - t0 > (unsigned long long)(unsigned)pb.wait_ticks;
-            }
-            if (++spins > pb.spin_limit || timed_out) {
-                if (lane == 0) {
-                    __hip_atomic_store(abort_flag, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    atomicOr(info, 2);
-                }
-                break;
-            }
-        }
-    }
-    __syncthreads();
-}
-
-// The panel blocks (mb + a0 .. mb + a1, kb) of further X row blocks, six flags a look: gain_tile2's row gather reads EVERY row block its block
-// column's measurement rows lie in, and with failed landmarks in between (idx skips them) those are more than the three its first look has room
-// for -- pass_mask(256, 161, "run"): block column 1 holds landmarks 32..39 and 135..158, row blocks 1 .. 7.  Workgroup-uniform; never entered
-// while every landmark is measured (64 rows are 96 state rows: at most three row blocks).  tests/test_gpu_handoff_delay.py.
-__device__ __forceinline__ void gather_rows_wait(const PersistArgs& a, int a0, int a1, int kb, int tid, bool lazy) {
-    for (; a0 <= a1; a0 += 6) {
-        const int* f = a.pan + (a.mb + a0) * a.mb + kb;
-        const int st = a.mb;
-        persist_wait6(f, a0 + 1 <= a1 ? f + st : nullptr, a0 + 2 <= a1 ? f + 2 * st : nullptr, a0 + 3 <= a1 ? f + 3 * st : nullptr,
-                      a0 + 4 <= a1 ? f + 4 * st : nullptr, a0 + 5 <= a1 ? f + 5 * st : nullptr, 1, a.abort_flag, a.info, tid, a.bound, lazy);
-    }
-}
-
 // Round 6: one 64x64 tile of the gain AND everything of the update's second Joseph term that belongs to it, so that ONE GEMM is left behind the
 // launch: Sigma' = T2 + K G'^T with T2 = Sigma (I - K H)^T from t2_tile and G' = K R^T - (H T2)^T (chol.hip, SchurArgs; TightlyCoupledEKF.cpp:586-600).
 //   K(ib,cb)  = sum_{kb >= cb} Y(ib,kb) Z(cb,kb)^T                                  as gain_tile: the same products, the same order, the same prune;
 //   W2(ib,cb) = (H T2)^T's tile = (H Sigma)^T(ib,cb) - sum_kb Y(ib,kb) S_kb HY(cb,kb)^T, HY(cb,kb) = the rows idx[64 cb ..] of block column kb of Y
 //               (a row gather out of the X row blocks alo .. ahi the tile's measurement rows lie in -- one to three while every landmark is measured, more
-//               with failed landmarks in between, and each one's flag is awaited: gather_rows_wait; X L^-T acts on rows one by one, so the
+//               with failed landmarks in between, and each one's flag is awaited: column_flags; X L^-T acts on rows one by one, so the
 //               gathered rows of Y are the rows of Y whoever solves them) -- the tile's own copy of the rows idx[.] of T2, summed like t2_tile's;
 //   G'(ib,cb) = K R^T - W2 (the pruned K, ascending measurement index, as joseph_g_kernel), K y's partial sums over the tile's columns -> Kyp[cb].
 // WAIT: inside the persistent launch (operands awaited per block column; the LAST block column's three panel blocks are solved here from the
@@ -412,6 +369,15 @@ __device__ __forceinline__ void gain_tile2(const PersistArgs& a, const GatherArg
         }
         tab[tid] = yq, tab[64 + tid] = rd, tab[128 + tid] = ro;
     }
+    // What a wait for block column kb's operands looks at, lane by lane: lane 0 the tile's own Y panel block, lane 1 its Z panel block (zflag; null:
+    // none), lanes 2 .. the panel block of EVERY X row block alo .. ahi -- the range the row gather's addresses (sqc) come from.  One to three row
+    // blocks while every landmark is measured (64 rows are 96 state rows); with failed landmarks in between more -- pass_mask(256, 161, "run"): block
+    // column 1 holds landmarks 32..39 and 135..158, row blocks 1 .. 7 (tests/test_gpu_handoff_delay.py); never more than the nX <=
+    // PERSIST_POLL_FLAGS - 2 of a shape that takes this flow (plan.h, t2_skip_owners).
+    auto column_flags = [&](int kb, const int* zflag) -> PollLane {
+        const int ax = alo + tid - 2;
+        return {tid == 0 ? a.pan + iy * mb + kb : tid == 1 ? zflag : (tid >= 2 && ax <= ahi) ? a.pan + (mb + ax) * mb + kb : nullptr, 1};
+    };
     float kv[16], w2[16];
     {   // (H Sigma)^T(ib, cb): Sigma(idx[c], i) with the lanes along c, turned through LDS (gather_body's Wt tile, without the residual row)
         float wv[16];
@@ -426,7 +392,7 @@ __device__ __forceinline__ void gain_tile2(const PersistArgs& a, const GatherArg
 #pragma unroll
         for (int q = 0; q < 16; q++) {
             kv[q] = 0.f;
-            w2[q] = Th[r * 65 + wc * 32 + (q & 3) + 8 * (q >> 2) + 4 * (lane >> 5)];
+            w2[q] = Th[r * 65 + mma64_col(wc, lane, q)];
         }
     }
     // one block column's operands into LDS (inside the launch: every block column but the last; behind a sweep: all of them)
@@ -435,10 +401,7 @@ __device__ __forceinline__ void gain_tile2(const PersistArgs& a, const GatherArg
         float hv[16];
         unsigned long long neg;
         if constexpr (WAIT) {
-            persist_wait6(a.pan + iy * mb + kb, gk ? a.pan + iz * mb + kb : nullptr, alo <= ahi ? a.pan + (mb + alo) * mb + kb : nullptr,
-                          alo + 1 <= ahi ? a.pan + (mb + alo + 1) * mb + kb : nullptr, alo + 2 <= ahi ? a.pan + (mb + alo + 2) * mb + kb : nullptr, nullptr, 1,
-                          a.abort_flag, a.info, tid, a.bound, kb < mb - 2);
-            if (ahi - alo > 2) gather_rows_wait(a, alo + 3, ahi, kb, tid, kb < mb - 2);
+            persist_wait(a, column_flags(kb, gk ? a.pan + iz * mb + kb : nullptr), tid, kb < mb - 2);
             load_tile_sc1(Ti, bL, (unsigned)(kb * PB) * (unsigned)ldl + (unsigned)(iy * PB), ldl, tid);
             if (gk) load_tile_sc1(Tj, bL, (unsigned)(kb * PB) * (unsigned)ldl + (unsigned)(iz * PB), ldl, tid);
 #pragma unroll
@@ -519,47 +482,31 @@ __device__ __forceinline__ void gain_tile2(const PersistArgs& a, const GatherArg
         const bool zi = a.grid.compact() && cb == kl;  // (compact launch: tile (idb0 + mb-1, mb-1) is the identity and nobody's)
         __syncthreads();
         // column mb-2's panel blocks as soon as THEY are out (their flags also cover column mb-1's finished tiles, see above): its operands travel
-        // while ready[mb-1] is still on its way
-        persist_wait6(a.pan + iy * mb + k6, gk6 ? a.pan + iz * mb + k6 : (zi ? nullptr : a.fin + iz * mb + kl), alo <= ahi ? a.pan + (mb + alo) * mb + k6 : nullptr,
-                      alo + 1 <= ahi ? a.pan + (mb + alo + 1) * mb + k6 : nullptr, alo + 2 <= ahi ? a.pan + (mb + alo + 2) * mb + k6 : nullptr, nullptr, 1,
-                      a.abort_flag, a.info, tid, a.bound, false);
-        if (ahi - alo > 2) gather_rows_wait(a, alo + 3, ahi, k6, tid, false);  // (their flags also cover the rows gathered from column mb-1's finished tiles)
-        float4 ql[4], qi[4], qj[4];
+        // while ready[mb-1] is still on its way.  (A tile with no Z panel block in column mb-2 looks at the finished tile (iz, mb-1) instead, which it
+        // reads behind ready[mb-1]; the row blocks' flags also cover the rows gathered from column mb-1's finished tiles.)
+        persist_wait(a, column_flags(k6, gk6 ? a.pan + iz * mb + k6 : (zi ? nullptr : a.fin + iz * mb + kl)), tid, false);
+        RegTile ql, qi, qj;
         float hq[16];
         unsigned long long neg6;
         {
-            float4 pi6[4], pj6[4];
+            RegTile pi6, pj6;
             float h6[16];
-#pragma unroll
-            for (int it = 0; it < 4; it++) {
-                const int e = tid + it * 256;
-                const unsigned o = (unsigned)(e >> 4), c4 = (unsigned)(e & 15) * 4u;
-                pi6[it] = ld_sc1(bL, (unsigned)(k6 * PB) * (unsigned)ldl + (unsigned)(iy * PB) + o * (unsigned)ldl + c4);
-                pj6[it] = gk6 ? ld_sc1(bL, (unsigned)(k6 * PB) * (unsigned)ldl + (unsigned)(iz * PB) + o * (unsigned)ldl + c4) : make_float4(0.f, 0.f, 0.f, 0.f);
-            }
+            pi6.request(bL, (unsigned)(k6 * PB) * (unsigned)ldl + (unsigned)(iy * PB), ldl, tid);
+            if (gk6) pj6.request(bL, (unsigned)(k6 * PB) * (unsigned)ldl + (unsigned)(iz * PB), ldl, tid);
 #pragma unroll
             for (int ps = 0; ps < 16; ps++)
                 h6[ps] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(bL, ((unsigned)(k6 * PB + wave + 4 * ps) * (unsigned)ldl + (unsigned)(mb * PB) + sqc) * 4u, 0, 16));
             neg6 = ld_sign_sc1(a.Lsign + k6);
-#pragma unroll
-            for (int it = 0; it < 4; it++) {
-                const int e = tid + it * 256;
-                *reinterpret_cast<float4*>(Ti + (e >> 4) * PLD + (e & 15) * 4) = pi6[it];
-                if (gk6) *reinterpret_cast<float4*>(Tj + (e >> 4) * PLD + (e & 15) * 4) = pj6[it];
-            }
+            pi6.put(Ti, tid);
+            if (gk6) pj6.put(Tj, tid);
 #pragma unroll
             for (int ps = 0; ps < 16; ps++) Th[(wave + 4 * ps) * PLD + lane] = (sq >= 0) ? h6[ps] : 0.f;
         }
         // ... then the last column's (its look also is the barrier behind column mb-2's LDS writes): requested into registers, under column mb-2's products
-        persist_wait(a.ready + kl, nullptr, nullptr, a.abort_flag, a.info, tid, a.bound, 4, false);
-#pragma unroll
-        for (int it = 0; it < 4; it++) {
-            const int e = tid + it * 256;
-            const unsigned o = (unsigned)(e >> 4), c4 = (unsigned)(e & 15) * 4u;
-            ql[it] = ld_sc1(bL, (unsigned)(kl * PB) * (unsigned)ldl + (unsigned)(kl * PB) + o * (unsigned)ldl + c4);
-            qi[it] = ld_sc1(bS, (unsigned)(kl * PB) * (unsigned)a.lds + (unsigned)(iy * PB) + o * (unsigned)a.lds + c4);
-            qj[it] = zi ? make_float4(0.f, 0.f, 0.f, 0.f) : ld_sc1(bS, (unsigned)(kl * PB) * (unsigned)a.lds + (unsigned)(iz * PB) + o * (unsigned)a.lds + c4);
-        }
+        persist_wait(a, a.ready + kl, nullptr, nullptr, tid, 4, false);
+        ql.request(bL, (unsigned)(kl * PB) * (unsigned)ldl + (unsigned)(kl * PB), ldl, tid);
+        qi.request(bS, (unsigned)(kl * PB) * (unsigned)a.lds + (unsigned)(iy * PB), a.lds, tid);
+        if (!zi) qj.request(bS, (unsigned)(kl * PB) * (unsigned)a.lds + (unsigned)(iz * PB), a.lds, tid);
         const float4 qv = ld_sc1(bI, (unsigned)(kl * PB * PB) + tid * 4);
         const unsigned long long neg7 = ld_sign_sc1(a.Lsign + kl);
 #pragma unroll
@@ -567,19 +514,11 @@ __device__ __forceinline__ void gain_tile2(const PersistArgs& a, const GatherArg
             hq[ps] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(bS, ((unsigned)(kl * PB + wave + 4 * ps) * (unsigned)a.lds + (unsigned)(mb * PB) + sqc) * 4u, 0, 16));
         products(mb - 2, neg6, false);
         __syncthreads();
-#pragma unroll
-        for (int it = 0; it < 4; it++) {
-            const int e = tid + it * 256;
-            *reinterpret_cast<float4*>(Tl + (e >> 4) * PLD + (e & 15) * 4) = ql[it];
-            *reinterpret_cast<float4*>(Ti + (e >> 4) * PLD + (e & 15) * 4) = qi[it];
-            if (!zi) *reinterpret_cast<float4*>(Tj + (e >> 4) * PLD + (e & 15) * 4) = qj[it];
-        }
+        ql.put(Tl, tid);
+        qi.put(Ti, tid);
         if (zi) identity_tile(Tj, tid);
-        {
-            const int pq = tid >> 6, c = (tid >> 2) & 15, r4 = (tid & 3) * 4;
-            float* t = Tinv + pq * 16 * ILD + c * ILD + r4;
-            t[0] = qv.x; t[1] = qv.y; t[2] = qv.z; t[3] = qv.w;
-        }
+        else qj.put(Tj, tid);
+        inv_put(qv, Tinv, tid);
 #pragma unroll
         for (int ps = 0; ps < 16; ps++) Th[(wave + 4 * ps) * PLD + lane] = (sq >= 0) ? hq[ps] : 0.f;
         __syncthreads();
@@ -596,7 +535,7 @@ __device__ __forceinline__ void gain_tile2(const PersistArgs& a, const GatherArg
     float acc = 0.f;
 #pragma unroll
     for (int q = 0; q < 16; q++) {
-        const int c = wc * 32 + (q & 3) + 8 * (q >> 2) + 4 * (lane >> 5), cg = cb * PB + c;
+        const int c = mma64_col(wc, lane, q), cg = cb * PB + c;
         Kt[(size_t)c * a.ldk + r] = kv[q];
         float g = 0.f;
         if (cg < m) {
@@ -635,7 +574,7 @@ __device__ __forceinline__ void t2_tile(const PersistArgs& a, float* Ti, float* 
         const float* sba = a.Sg + (size_t)ta * PB * a.ldsg + (size_t)tb * PB;
 #pragma unroll
         for (int q = 0; q < 16; q++) {
-            const int c = wc * 32 + (q & 3) + 8 * (q >> 2) + 4 * (lane >> 5);
+            const int c = mma64_col(wc, lane, q);
             tab[q] = sab[(size_t)c * a.ldsg + r];
             tba[q] = diag ? 0.f : sba[(size_t)c * a.ldsg + r];
         }
@@ -661,17 +600,17 @@ __device__ __forceinline__ void t2_tile(const PersistArgs& a, float* Ti, float* 
         for (int q = 0; q < 16; q++) tab[q] = tab[q] - up[q];
         if (!diag) {
 #pragma unroll
-            for (int q = 0; q < 16; q++) Tl[r * PLD + wc * 32 + (q & 3) + 8 * (q >> 2) + 4 * (lane >> 5)] = up[q];
+            for (int q = 0; q < 16; q++) Tl[r * PLD + mma64_col(wc, lane, q)] = up[q];
             __syncthreads();
 #pragma unroll
-            for (int q = 0; q < 16; q++) tba[q] = tba[q] - Tl[(wc * 32 + (q & 3) + 8 * (q >> 2) + 4 * (lane >> 5)) * PLD + r];
+            for (int q = 0; q < 16; q++) tba[q] = tba[q] - Tl[mma64_col(wc, lane, q) * PLD + r];
         }
         if (dbg && tid == 0) dbg[kb] = (long long)__builtin_amdgcn_s_memrealtime();
     };
     if constexpr (WAIT) {
         for (int kb = 0; kb < mb - 2; kb++) {
             __syncthreads();  // (the previous product's readers of Ti / Tj, the previous turn's of Tl)
-            persist_wait(nullptr, a.pan + ia * mb + kb, diag ? nullptr : a.pan + ib * mb + kb, a.abort_flag, a.info, tid, a.bound, 1, true);
+            persist_wait(a, nullptr, a.pan + ia * mb + kb, diag ? nullptr : a.pan + ib * mb + kb, tid, 1, true);
             load_tile_sc1(Ti, bL, (unsigned)(kb * PB) * (unsigned)ldl + (unsigned)(ia * PB), ldl, tid);
             if (!diag) load_tile_sc1(Tj, bL, (unsigned)(kb * PB) * (unsigned)ldl + (unsigned)(ib * PB), ldl, tid);
             const unsigned long long neg = ld_sign_sc1(a.Lsign + kb);
@@ -695,47 +634,25 @@ __device__ __forceinline__ void t2_tile(const PersistArgs& a, float* Ti, float* 
         const __amdgpu_buffer_rsrc_t bS = persist_rsrc(a.S, (unsigned)a.lds * (unsigned)(mb * PB));
         const __amdgpu_buffer_rsrc_t bI = persist_rsrc(a.Linv, (unsigned)(mb * PB * PB));
         __syncthreads();
-        persist_wait(a.ready + kl, a.pan + ia * mb + k6, diag ? nullptr : a.pan + ib * mb + k6, a.abort_flag, a.info, tid, a.bound, 4, false);
-        float4 pi6[4], pj6[4], ql[4], qi[4], qj[4];
-#pragma unroll
-        for (int it = 0; it < 4; it++) {
-            const int e = tid + it * 256;
-            const unsigned o = (unsigned)(e >> 4), c4 = (unsigned)(e & 15) * 4u;
-            pi6[it] = ld_sc1(bL, (unsigned)(k6 * PB) * (unsigned)ldl + (unsigned)(ia * PB) + o * (unsigned)ldl + c4);
-            pj6[it] = diag ? make_float4(0.f, 0.f, 0.f, 0.f) : ld_sc1(bL, (unsigned)(k6 * PB) * (unsigned)ldl + (unsigned)(ib * PB) + o * (unsigned)ldl + c4);
-        }
+        persist_wait(a, a.ready + kl, a.pan + ia * mb + k6, diag ? nullptr : a.pan + ib * mb + k6, tid, 4, false);
+        RegTile pi6, pj6, ql, qi, qj;
+        pi6.request(bL, (unsigned)(k6 * PB) * (unsigned)ldl + (unsigned)(ia * PB), ldl, tid);
+        if (!diag) pj6.request(bL, (unsigned)(k6 * PB) * (unsigned)ldl + (unsigned)(ib * PB), ldl, tid);
         const unsigned long long neg6 = ld_sign_sc1(a.Lsign + k6);
-#pragma unroll
-        for (int it = 0; it < 4; it++) {
-            const int e = tid + it * 256;
-            const unsigned o = (unsigned)(e >> 4), c4 = (unsigned)(e & 15) * 4u;
-            ql[it] = ld_sc1(bL, (unsigned)(kl * PB) * (unsigned)ldl + (unsigned)(kl * PB) + o * (unsigned)ldl + c4);
-            qi[it] = ld_sc1(bS, (unsigned)(kl * PB) * (unsigned)a.lds + (unsigned)(ia * PB) + o * (unsigned)a.lds + c4);
-            qj[it] = diag ? make_float4(0.f, 0.f, 0.f, 0.f) : ld_sc1(bS, (unsigned)(kl * PB) * (unsigned)a.lds + (unsigned)(ib * PB) + o * (unsigned)a.lds + c4);
-        }
+        ql.request(bL, (unsigned)(kl * PB) * (unsigned)ldl + (unsigned)(kl * PB), ldl, tid);
+        qi.request(bS, (unsigned)(kl * PB) * (unsigned)a.lds + (unsigned)(ia * PB), a.lds, tid);
+        if (!diag) qj.request(bS, (unsigned)(kl * PB) * (unsigned)a.lds + (unsigned)(ib * PB), a.lds, tid);
         const float4 qv = ld_sc1(bI, (unsigned)(kl * PB * PB) + tid * 4);
         const unsigned long long neg7 = ld_sign_sc1(a.Lsign + kl);
-#pragma unroll
-        for (int it = 0; it < 4; it++) {
-            const int e = tid + it * 256;
-            *reinterpret_cast<float4*>(Ti + (e >> 4) * PLD + (e & 15) * 4) = pi6[it];
-            if (!diag) *reinterpret_cast<float4*>(Tj + (e >> 4) * PLD + (e & 15) * 4) = pj6[it];
-        }
+        pi6.put(Ti, tid);
+        if (!diag) pj6.put(Tj, tid);
         __syncthreads();
         apply(k6, neg6);
         __syncthreads();
-#pragma unroll
-        for (int it = 0; it < 4; it++) {
-            const int e = tid + it * 256;
-            *reinterpret_cast<float4*>(Tl + (e >> 4) * PLD + (e & 15) * 4) = ql[it];
-            *reinterpret_cast<float4*>(Ti + (e >> 4) * PLD + (e & 15) * 4) = qi[it];
-            if (!diag) *reinterpret_cast<float4*>(Tj + (e >> 4) * PLD + (e & 15) * 4) = qj[it];
-        }
-        {
-            const int pq = tid >> 6, c = (tid >> 2) & 15, r4 = (tid & 3) * 4;
-            float* t = Tinv + pq * 16 * ILD + c * ILD + r4;
-            t[0] = qv.x; t[1] = qv.y; t[2] = qv.z; t[3] = qv.w;
-        }
+        ql.put(Tl, tid);
+        qi.put(Ti, tid);
+        if (!diag) qj.put(Tj, tid);
+        inv_put(qv, Tinv, tid);
         __syncthreads();
         if (diag) tri_solve_fwd(Ti, Tl, Tinv, wave, lane);
         else tri_solve_fwd2(Ti, Tj, Tl, Tinv, wave, lane);
@@ -746,7 +663,7 @@ __device__ __forceinline__ void t2_tile(const PersistArgs& a, float* Ti, float* 
     __syncthreads();
 #pragma unroll
     for (int q = 0; q < 16; q++) {
-        const int c = wc * 32 + (q & 3) + 8 * (q >> 2) + 4 * (lane >> 5);
+        const int c = mma64_col(wc, lane, q);
         Ti[c * PLD + r] = (ta * PB + r < a.nstate && tb * PB + c < a.nstate) ? tab[q] : 0.f;
         if (!diag) Tj[c * PLD + r] = (tb * PB + r < a.nstate && ta * PB + c < a.nstate) ? tba[q] : 0.f;
     }
@@ -1039,7 +956,7 @@ __global__ __launch_bounds__(256) void chol_persist_kernel(PersistArgs a, Gather
             const unsigned oik = (unsigned)(k * PB) * (unsigned)lds + (unsigned)(i * PB);  // tile (i,k)
             const unsigned oii = (unsigned)(i * PB) * (unsigned)lds + (unsigned)(i * PB);  // tile (i,i)
             f32x4 x[1][4];
-            float4 dt[4];
+            RegTile dt;
             // final column tile (i,k), and the diagonal tile with steps 0 .. k-1 applied.  Every wavefront has looked at the
             // two flags for itself right behind the previous factorisation; if both were up (they are, unless the helpers
             // are late) it requests its rows of tile (i,k) and its share of the diagonal tile now, behind its own match.
@@ -1058,26 +975,21 @@ __global__ __launch_bounds__(256) void chol_persist_kernel(PersistArgs a, Gather
                 }
                 persist_tile_x_buf(x[0], bS, oik, lds, wave, lane);
 #pragma unroll
-                for (int it = 0; it < 4; it++) dt[it] = ld_sc1(bS, od[it]);
+                for (int it = 0; it < 4; it++) dt.v[it] = ld_sc1(bS, od[it]);
                 // the previous step's factor is out: this wavefront's stores were issued in front of these 20 loads
                 asm volatile("s_waitcnt vmcnt(20)" ::: "memory");
                 if (lane == 0) __hip_atomic_fetch_add(a.ready + k, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             } else if (k >= kf) {
                 persist_publish_wave(a.ready + k, lane);  // the previous step's factor is out
-                persist_poll(a.fin + i * mb + k, a.fin + i * mb + i, nullptr, a.abort_flag, a.info, lane, 1, a.bound);  // (per wavefront: no barrier here, the
-                                                                                                               // wavefronts need not agree on `hit`)
+                persist_poll(a, a.fin + i * mb + k, a.fin + i * mb + i, nullptr, lane);  // (per wavefront: no barrier here, the wavefronts need not agree on `hit`)
                 persist_tile_x<true>(x[0], S + oik, lds, wave, lane);
-#pragma unroll
-                for (int it = 0; it < 4; it++) {
-                    const int e = tid + it * 256;
-                    dt[it] = ld_sc1(bS, oii + (unsigned)(e >> 4) * (unsigned)lds + (unsigned)(e & 15) * 4u);
-                }
+                dt.request(bS, oii, lds, tid);
             } else {
                 persist_tile_x<false>(x[0], S + oik, lds, wave, lane);
 #pragma unroll
                 for (int it = 0; it < 4; it++) {
                     const int e = tid + it * 256;
-                    dt[it] = *reinterpret_cast<const float4*>(S + oii + (size_t)(e >> 4) * lds + (e & 15) * 4);
+                    dt.v[it] = *reinterpret_cast<const float4*>(S + oii + (size_t)(e >> 4) * lds + (e & 15) * 4);
                 }
             }
             PSTAMP(32 + 8 * k + 1);
@@ -1085,11 +997,7 @@ __global__ __launch_bounds__(256) void chol_persist_kernel(PersistArgs a, Gather
             PSTAMP(32 + 8 * k + 2);
             float* const txs[1] = {Ti};
             tri_solve_run<1>(x, txs, ops, wave, lane);  // L_ik into Ti
-#pragma unroll
-            for (int it = 0; it < 4; it++) {  // the diagonal tile has had the substitution's time to arrive
-                const int e = tid + it * 256;
-                *reinterpret_cast<float4*>(Dn + (e >> 4) * PLD + (e & 15) * 4) = dt[it];
-            }
+            dt.put(Dn, tid);  // the diagonal tile has had the substitution's time to arrive
             {   // the panel block (read by later launches only) leaves from the registers
                 float* Pdst = L + (size_t)k * PB * ldl + (size_t)i * PB + 16 * wave + li;
 #pragma unroll
@@ -1136,7 +1044,7 @@ __global__ __launch_bounds__(256) void chol_persist_kernel(PersistArgs a, Gather
                 const f32x16 up = (neg == 0ull) ? mma64(Ti, 1, PLD, Ti, 1, PLD, wr, wc, lane) : mma64_signed(Ti, 1, PLD, Ti, 1, PLD, wr, wc, lane, neg);
 #pragma unroll
                 for (int q = 0; q < 16; q++) {
-                    const int c = wc * 32 + (q & 3) + 8 * (q >> 2) + 4 * (lane >> 5);
+                    const int c = mma64_col(wc, lane, q);
                     Dn[c * PLD + r] = Dn[c * PLD + r] - up[q];
                 }
                 neg1 = potrf64_signed(Dn, Tinv, tid);
@@ -1183,7 +1091,7 @@ __global__ __launch_bounds__(256) void chol_persist_kernel(PersistArgs a, Gather
             __syncthreads();
             if (role.a < a.idb0 - mb) {  // (Wt has tiles up to the handle's capacity; the gain only X's row blocks)
                 if (a.t2) gain_tile2<true>(a, ga, Ti, Tj, Tl, Tinv, persist_dyn_lds, persist_dyn_lds + PB * PLD, role.a, role.b, tid);
-                else gain_tile<true>(a, Ti, Tj, Tl, Tinv, role.a, role.b, tid);
+                else gain_tile(a, Ti, Tj, Tl, Tinv, role.a, role.b, tid);
                 if (a.dbg && tid == 0 && tb < 104) a.dbg[200 + tb] = (long long)__builtin_amdgcn_s_memrealtime();
             }
         }
@@ -1237,11 +1145,11 @@ __global__ __launch_bounds__(256) void chol_persist_kernel(PersistArgs a, Gather
         }
         __syncthreads();
 #pragma unroll
-        for (int q = 0; q < 16; q++) tv[q] = Tl[(wc * 32 + (q & 3) + 8 * (q >> 2) + 4 * (lane >> 5)) * PLD + r];
+        for (int q = 0; q < 16; q++) tv[q] = Tl[mma64_col(wc, lane, q) * PLD + r];
         __syncthreads();  // (Tl is loaded with L_00 below)
     } else {
 #pragma unroll
-        for (int q = 0; q < 16; q++) tv[q] = S[oij + (size_t)(wc * 32 + (q & 3) + 8 * (q >> 2) + 4 * (lane >> 5)) * lds + r];
+        for (int q = 0; q < 16; q++) tv[q] = S[oij + (size_t)mma64_col(wc, lane, q) * lds + r];
     }
     // diagnostic stamps of the sub-diagonal tiles' last steps (the tiles the chain waits for)
 #define HSTAMP(n)                                                                                                       \
@@ -1262,13 +1170,13 @@ __global__ __launch_bounds__(256) void chol_persist_kernel(PersistArgs a, Gather
         if (early) {
             // the panel sources (i,k), (j,k) are final about a third of a chain step before L_kk is: they are in LDS when ready[k] comes
             // up, and only L_kk, its inverses and the sign mask are left for the round trip behind it
-            persist_wait(nullptr, fin_ik, (i != j) ? a.fin + j * mb + k : nullptr, a.abort_flag, a.info, tid, a.bound, 1, lazy);
+            persist_wait(a, nullptr, fin_ik, (i != j) ? a.fin + j * mb + k : nullptr, tid, 1, lazy);
             if (src_ident) identity_tile(Ti, tid);
             else load_tile_sc1(Ti, bS, (unsigned)(k * PB) * (unsigned)lds + (unsigned)(i * PB), lds, tid);
             if (i != j) load_tile_sc1(Tj, bS, (unsigned)(k * PB) * (unsigned)lds + (unsigned)(j * PB), lds, tid);
-            persist_wait(a.ready + k, nullptr, nullptr, a.abort_flag, a.info, tid, a.bound, 4, lazy);
-        } else if (k >= 1) persist_wait(a.ready + k, fin_ik, (i != j) ? a.fin + j * mb + k : nullptr, a.abort_flag, a.info, tid, a.bound, 4, lazy);
-        else if (fused) persist_wait(a.ready, nullptr, nullptr, a.abort_flag, a.info, tid, a.bound, 4, lazy);  // L_00 of this launch
+            persist_wait(a, a.ready + k, nullptr, nullptr, tid, 4, lazy);
+        } else if (k >= 1) persist_wait(a, a.ready + k, fin_ik, (i != j) ? a.fin + j * mb + k : nullptr, tid, 4, lazy);
+        else if (fused) persist_wait(a, a.ready, nullptr, nullptr, tid, 4, lazy);  // L_00 of this launch
         else __syncthreads();  // (the barrier: the previous step's readers of Ti / Tj / Tl are done)
         HSTAMP(1);
         if (k >= 1 || fused) {  // four requests in flight together: one round trip
@@ -1307,7 +1215,7 @@ __global__ __launch_bounds__(256) void chol_persist_kernel(PersistArgs a, Gather
     if (klast >= k0 || fused) {  // (fused launch: a tile without steps -- an identity block -- exists nowhere yet either)
         if (klast < k0) __syncthreads();
 #pragma unroll
-        for (int q = 0; q < 16; q++) Tl[(wc * 32 + (q & 3) + 8 * (q >> 2) + 4 * (lane >> 5)) * PLD + r] = tv[q];
+        for (int q = 0; q < 16; q++) Tl[mma64_col(wc, lane, q) * PLD + r] = tv[q];
         __syncthreads();
         PERSIST_TEST_DELAY(a, 0);
         store_tile_sc1<false>(Tl, bS, oij, lds, tid);
@@ -1355,13 +1263,13 @@ __global__ __launch_bounds__(256) void chol_persist_kernel(PersistArgs a, Gather
         // last block column: this row block's panel solve against L_last (was chol_panel_kernel's launch)
         if (i >= idb0 && i - idb0 > j) PEXIT();  // identity block row beyond the last column: block stays zero, unused
         if (a.gain) PEXIT();  // (the gain workgroups solve the last block column's panel blocks themselves: gain_tile)
-        persist_wait(a.ready + j, nullptr, nullptr, a.abort_flag, a.info, tid, a.bound, 4, false);  // (its barrier: the tile's store has left Tl)
+        persist_wait(a, a.ready + j, nullptr, nullptr, tid, 4, false);  // (its barrier: the tile's store has left Tl)
         load_tile_sc1(Tj, bL, (unsigned)(j * PB) * (unsigned)ldl + (unsigned)(j * PB), ldl, tid);
         load_inv_sc1(Tinv, bI, (unsigned)(j * PB * PB), tid);
         const unsigned long long negl = ld_sign_sc1(a.Lsign + j);
         if (klast < k0) {  // (otherwise the finished tile is in Tl already)
 #pragma unroll
-            for (int q = 0; q < 16; q++) Tl[(wc * 32 + (q & 3) + 8 * (q >> 2) + 4 * (lane >> 5)) * PLD + r] = tv[q];
+            for (int q = 0; q < 16; q++) Tl[mma64_col(wc, lane, q) * PLD + r] = tv[q];
         }
         __syncthreads();
         tri_solve_fwd(Tl, Tj, Tinv, wave, lane);
@@ -1385,9 +1293,9 @@ __global__ __launch_bounds__(256) void chol_persist_kernel(PersistArgs a, Gather
 
 // The gain behind every other sweep of fewer than EKF_SWEEP_SPLIT_MB block columns (per-step sweep, Schur-free): one workgroup per
 // 64x64 tile of K, the arithmetic of gain_tile -- the persistent launch and the per-step sweep stay bit-identical end to end.
-// (round 5: gain_tile<false>'s arithmetic with a block column's two operands requested TWO products ahead, into one of two register sets, the loop
+// (round 5: gain_tile's arithmetic with a block column's two operands requested TWO products ahead, into one of two register sets, the loop
 // unrolled by two so that the sets are compile-time: one ahead left 1-2 k cycles of their latency in front of every product.  The same products from
-// zero, added in the same ascending order, the same prune: the same bits as gain_tile<true> inside the persistent launch.)
+// zero, added in the same ascending order, the same prune: the same bits as gain_tile inside the persistent launch.)
 __global__ __launch_bounds__(256) void gain_tiles_kernel(PersistArgs a) {
     __shared__ __attribute__((aligned(16))) float Ti[PB * PLD];
     __shared__ __attribute__((aligned(16))) float Tj[PB * PLD];
@@ -1434,7 +1342,7 @@ __global__ __launch_bounds__(256) void gain_tiles_kernel(PersistArgs a) {
     float* Kt = a.K + (size_t)(cb * PB) * a.ldk + (size_t)ib * PB;
 #pragma unroll
     for (int q = 0; q < 16; q++) {
-        const int c = wc * 32 + (q & 3) + 8 * (q >> 2) + 4 * (lane >> 5);
+        const int c = mma64_col(wc, lane, q);
         Kt[(size_t)c * a.ldk + r] = (fabsf(kv[q]) > EKF_FLUSH_THRESH) ? kv[q] : 0.f;  // .sparseView(SPARSE_THRESH, SPARSE_EPS)
     }
 }

@@ -96,13 +96,13 @@ __device__ __forceinline__ void la_tile(const LaArgs& a, int l, bool near, int i
         float tv[16];  // the target tile's round trip runs under the product
 #pragma unroll
         for (int q = 0; q < 16; q++) {
-            const int c = wc * 32 + (q & 3) + 8 * (q >> 2) + 4 * (lane >> 5);
+            const int c = mma64_col(wc, lane, q);
             tv[q] = Sij[(size_t)c * lds + rw];
         }
         const f32x16 up = (neg0 == 0ull) ? mma64(Ti, 1, PLD, Bj, 1, PLD, wr, wc, lane) : mma64_signed(Ti, 1, PLD, Bj, 1, PLD, wr, wc, lane, neg0);
 #pragma unroll
         for (int q = 0; q < 16; q++) {
-            const int c = wc * 32 + (q & 3) + 8 * (q >> 2) + 4 * (lane >> 5);
+            const int c = mma64_col(wc, lane, q);
             const float v0 = hasa ? tv[q] - upa[q] : tv[q];
             Sij[(size_t)c * lds + rw] = v0 - up[q];
         }
@@ -145,13 +145,13 @@ __device__ __forceinline__ void la_tile(const LaArgs& a, int l, bool near, int i
         float tv[16];
 #pragma unroll
         for (int q = 0; q < 16; q++) {
-            const int c = wc * 32 + (q & 3) + 8 * (q >> 2) + 4 * (lane >> 5);
+            const int c = mma64_col(wc, lane, q);
             tv[q] = Sij[(size_t)c * lds + rw];
         }
         const f32x16 up1 = (neg1 == 0ull) ? mma64(Ti, 1, PLD, Tj, 1, PLD, wr, wc, lane) : mma64_signed(Ti, 1, PLD, Tj, 1, PLD, wr, wc, lane, neg1);
 #pragma unroll
         for (int q = 0; q < 16; q++) {
-            const int c = wc * 32 + (q & 3) + 8 * (q >> 2) + 4 * (lane >> 5);
+            const int c = mma64_col(wc, lane, q);
             const float v0 = has0 ? tv[q] - up0[q] : tv[q];
             Sij[(size_t)c * lds + rw] = v0 - up1[q];
         }
@@ -193,7 +193,7 @@ __device__ __forceinline__ void la_tile(const LaArgs& a, int l, bool near, int i
     float* Tl = Tj;  // every wavefront is past its substitution (barrier above): L_ll's tile takes the updated diagonal tile
 #pragma unroll
     for (int q = 0; q < 16; q++) {
-        const int c = wc * 32 + (q & 3) + 8 * (q >> 2) + 4 * (lane >> 5);
+        const int c = mma64_col(wc, lane, q);
         const float v0 = has0 ? tgt[q] - up0[q] : tgt[q];
         Tl[c * PLD + rw] = v0 - up1[q];
     }
@@ -220,7 +220,7 @@ __device__ __forceinline__ void la_tile(const LaArgs& a, int l, bool near, int i
         __syncthreads();
 #pragma unroll
         for (int q = 0; q < 16; q++) {
-            const int c = wc * 32 + (q & 3) + 8 * (q >> 2) + 4 * (lane >> 5);
+            const int c = mma64_col(wc, lane, q);
             const float v0 = has0 ? Sij[(size_t)c * lds + rw] - up0[q] : Sij[(size_t)c * lds + rw];
             Tl[c * PLD + rw] = v0 - up1[q];
         }

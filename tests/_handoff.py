@@ -15,7 +15,7 @@ A case is one update at N = 256 on a handle of capacity 256 from _update_cases.w
   B  pass_mask(256, 161, "run"), host      the T2 flow, 6 block columns; block column 1 holds landmarks 32..39 and 135..158: X row blocks 1..7
   C  outliers on landmarks 100..149 (rejected by the gate at CHI2) and default_rng(11).choice(256, 51) failed, device-sized: planned for
      m = 2N, 8 block columns (tests/test_gpu_gate.py::test_clustered_rejections_give_the_same_bits_under_both_sweeps' mask)
-  D  pass_mask(256, 128, "every"), host    ("persist", "sweep", "joseph"): gain_tile<true> instead of gain_tile2<true>, no T2 tiles
+  D  pass_mask(256, 128, "every"), host    ("persist", "sweep", "joseph"): gain_tile instead of gain_tile2<true>, no T2 tiles
 """
 import collections
 import ctypes as C
@@ -134,7 +134,7 @@ def targets(cid):
     the finished tile (mb + a, mb-1) itself -- so: every owner in one of uncovered_rows()."""
     roles, back, mb, nX = role_table(cid)
     assert mb == CASES[cid].mb
-    late = set(uncovered_rows(cid)) if CASES[cid].flow[2] == "t2" else set()  # (gain_tile<true> gathers no rows)
+    late = set(uncovered_rows(cid)) if CASES[cid].flow[2] == "t2" else set()  # (gain_tile gathers no rows)
     out, h = [], 0
     for b, (kind, i, j) in enumerate(roles):
         if kind != OWNER:

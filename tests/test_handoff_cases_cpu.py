@@ -46,7 +46,7 @@ def test_clustered_failures_spread_a_block_column_over_more_than_three_row_block
 
 def test_the_other_two_cases_have_no_uncovered_producer():
     """A: every block column's rows lie in at most three row blocks.  D: every second landmark measured spreads 64 rows over 192 state rows, four
-    row blocks -- but its flow forms the gain with gain_tile<true>, which gathers no rows of Y at all (the row gather belongs to the T2 flow's
+    row blocks -- but its flow forms the gain with gain_tile, which gathers no rows of Y at all (the row gather belongs to the T2 flow's
     gain_tile2), so nothing is read beyond the tile's own two panel blocks."""
     sp = H.spans(H.inputs("A")[4])
     assert len(sp) == 8 and all(0 <= ahi - alo <= 2 for alo, ahi in sp), sp

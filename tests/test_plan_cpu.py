@@ -36,7 +36,11 @@ def plan(N, m, cap=None, cus=CUS, m_on_device=False, sole=True, latched_off=Fals
     out = (C.c_int32 * 12)()
     rc = capi.load(hooks=True).ekfvio_test_plan(cus, cap or N, N, m, int(m_on_device), int(sole), int(latched_off), int(dense), next_dt, out)
     assert rc == capi.OK
-    return dict(zip(FIELDS, out))
+    p = dict(zip(FIELDS, out))
+    # every plan any test asks for: a gain tile of the T2 flow looks at n_pad / 64 + 2 flags in ONE look of a wavefront, a lane each, and lane 63
+    # is the abort word's (plan.h, PERSIST_POLL_FLAGS; chol_persist.inc, gain_tile2)
+    assert p["t2_skip"] < 0 or p["n_pad"] // 64 + 2 <= 63, (N, m, p)
+    return p
 
 
 def all_counts(**kw):
