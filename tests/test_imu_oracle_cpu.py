@@ -7,18 +7,9 @@ import numpy as np
 from ekf_vio_amd.sim import Scenario
 from oracle import OracleFilter
 
+from _imu_cases import np_imu_update, rot_t  # the independent evaluation lives with the IMU cases (tests/_imu_cases.py)
+
 G = np.array([0.0, 9.81, 0.0])
-
-
-def rot_t(q, v):
-    """R(q)^T v with the filter's rotation formula on the conjugate (q need not be normalised)."""
-    w, c = q[0], -np.asarray(q[1:])
-    uv = 2.0 * np.cross(c, v)
-    return v + w * uv + np.cross(c, uv)
-
-
-def h_imu(base):
-    return np.concatenate([base[10:13] + base[19:22], base[13:16] + base[16:19] - rot_t(base[3:7], G)])
 
 
 def converged_state(N=12, steps=6, seed=2):
@@ -59,19 +50,10 @@ def test_imu_update_matches_independent_numpy_evaluation():
     gv, av = 1e-4, 1e-2
     o.imu_update(gyro, acc, gv, av, G)
     out = o.get_state()
-    # independent evaluation
-    H = np.zeros((6, n))
-    for k in range(22):
-        d = np.zeros(22)
-        d[k] = 1e-6
-        H[:, k] = (h_imu(base + d) - h_imu(base - d)) / 2e-6
-    R = np.diag([gv] * 3 + [av] * 3)
-    S = H @ Sig @ H.T + R
-    K = Sig @ H.T @ np.linalg.inv(S)
-    I_KH = np.eye(n) - K @ H
-    Sig2 = I_KH @ Sig @ I_KH.T + K @ R @ K.T
-    mu = np.concatenate([base, st["feat_mu"].ravel()]) + K @ (np.concatenate([gyro, acc]) - h_imu(base))
-    mu[3:7] /= np.linalg.norm(mu[3:7])
+    # independent evaluation: H by central differences, K by numpy.linalg, Joseph form
+    ev = np_imu_update(base, st["feat_mu"], Sig, gyro, acc, gv, av, G)
+    mu, Sig2, H, R = ev["mu"], ev["Sigma"], ev["H"], ev["R"]
+    assert H.shape == (6, n)
     assert np.allclose(out["base_mu"], mu[:22], rtol=0, atol=1e-9)
     assert np.allclose(out["feat_mu"].ravel(), mu[22:], rtol=0, atol=1e-9)
     assert np.linalg.norm(out["Sigma"] - Sig2) / np.linalg.norm(Sig2) < 1e-8
