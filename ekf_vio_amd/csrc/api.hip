@@ -12,15 +12,6 @@
 
 #include "common.h"
 
-#define HIPC(f, expr)                                                                              \
-    do {                                                                                           \
-        hipError_t e__ = (expr);                                                                   \
-        if (e__ != hipSuccess) {                                                                   \
-            (f)->last_error = std::string(#expr) + ": " + hipGetErrorString(e__);                  \
-            return EKFVIO_EDEVICE;                                                                 \
-        }                                                                                          \
-    } while (0)
-
 namespace {
 // Allocation + zero fill ordered on the handle's (non-blocking) stream: nothing in this
 // library relies on the legacy null stream, which a non-blocking stream does not wait for.
@@ -86,7 +77,7 @@ int add_features_device(ekfvio_filter* f, int count) {
     hipLaunchKernelGGL(add_features_kernel, dim3(64), dim3(256), 0, f->stream, f->P, f->ldp, f->n, count,
                        f->cfg.default_point_homogenous_variance, f->cfg.default_point_depth_variance, f->mu,
                        f->last_klt, f->del_flag, f->zmeas, f->N, inv_depth, nullptr);
-    HIPC(f, hipStreamSynchronize(f->stream));
+    HIP_TRY(f, hipStreamSynchronize(f->stream));
     f->N += count;
     f->n += 3 * count;
     return EKFVIO_OK;
@@ -106,11 +97,7 @@ __global__ void copy_small_kernel(const float* __restrict__ src, float* __restri
     for (int i = threadIdx.x; i < n; i += blockDim.x) dst[i] = src[i];
     __threadfence_system();
     __syncthreads();
-    if (threadIdx.x == 0) {
-        host_word[0] = info[0];
-        host_word[2] = 0;
-        __hip_atomic_store(host_word + 1, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-    }
+    if (threadIdx.x == 0) publish_host_words(host_word, info, 0, seq);
 }
 
 // The host's wait at the end of a frame.  A one-thread kernel behind everything else on the stream writes the status
@@ -119,9 +106,7 @@ __global__ void copy_small_kernel(const float* __restrict__ src, float* __restri
 // per frame).  Polling is bounded: after 300 us (a long device-resident run is in flight) the host blocks in
 // hipStreamSynchronize like before.
 __global__ void publish_status_kernel(const int* __restrict__ info, int* host_word, int seq, const int* __restrict__ extra) {
-    host_word[0] = info[0];
-    host_word[2] = extra ? *extra : 0;
-    __hip_atomic_store(host_word + 1, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+    publish_host_words(host_word, info, extra ? *extra : 0, seq);
 }
 void launch_publish_status(ekfvio_filter* f, int seq) {
     hipLaunchKernelGGL(publish_status_kernel, dim3(1), dim3(1), 0, f->stream, f->info, f->d_hinfo, seq, (const int*)nullptr);
@@ -134,22 +119,22 @@ int wait_status(ekfvio_filter* f, int* status, const int* extra_dev, int* extra_
 // The polling half: for a caller whose own last kernel publishes sequence number `seq` (from next_status_seq).
 int next_status_seq(ekfvio_filter* f) { return ++f->status_seq; }
 int poll_status(ekfvio_filter* f, int seq, int* status, int* extra_out) {
-    HIPC(f, hipGetLastError());
+    HIP_TRY(f, hipGetLastError());
     volatile int* hw = f->h_info;
     const auto t0 = std::chrono::steady_clock::now();
     int spins = 0;
-    while (__atomic_load_n(&hw[1], __ATOMIC_ACQUIRE) != seq) {
+    while (__atomic_load_n(&hw[HW_SEQ], __ATOMIC_ACQUIRE) != seq) {
         if ((++spins & 1023) == 0 && std::chrono::steady_clock::now() - t0 > std::chrono::microseconds(300)) {
-            HIPC(f, hipStreamSynchronize(f->stream));
+            HIP_TRY(f, hipStreamSynchronize(f->stream));
             break;
         }
     }
-    if (__atomic_load_n(&hw[1], __ATOMIC_ACQUIRE) != seq) {
+    if (__atomic_load_n(&hw[HW_SEQ], __ATOMIC_ACQUIRE) != seq) {
         f->last_error = "status word not published";
         return EKFVIO_EDEVICE;
     }
-    *status = hw[0];
-    if (extra_out) *extra_out = hw[2];
+    *status = hw[HW_STATUS];
+    if (extra_out) *extra_out = hw[HW_EXTRA];
     return EKFVIO_OK;
 }
 
@@ -189,11 +174,11 @@ int ekfvio_default_config(ekfvio_config* c) {
 }
 
 static int create_body(ekfvio_filter* f, const ekfvio_config* cfg, int device, void* stream) {
-    HIPC(f, hipSetDevice(device));
+    HIP_TRY(f, hipSetDevice(device));
     if (stream) {
         f->stream = (hipStream_t)stream;
     } else {
-        HIPC(f, hipStreamCreateWithFlags(&f->stream, hipStreamNonBlocking));
+        HIP_TRY(f, hipStreamCreateWithFlags(&f->stream, hipStreamNonBlocking));
         f->own_stream = true;
     }
     const int maxf = cfg->max_features;
@@ -201,53 +186,53 @@ static int create_body(ekfvio_filter* f, const ekfvio_config* cfg, int device, v
     f->n_cap = dims.n_cap, f->ldp = dims.ldp, f->m_cap = dims.m_cap, f->ld_aug = dims.ld_aug, f->sweep_sync_words = dims.sweep_sync_words;
     f->tune = tuning_from_env();  // every switch, once per handle
     const size_t pp = (size_t)f->ldp * f->ldp, pm = (size_t)f->ldp * f->m_cap;
-    HIPC(f, dev_alloc(f->stream, &f->mu, f->ldp));
-    HIPC(f, dev_alloc(f->stream, &f->mu_next, f->ldp));
-    HIPC(f, dev_alloc(f->stream, &f->last_klt, 2 * (size_t)maxf));
-    HIPC(f, dev_alloc(f->stream, &f->del_flag, (size_t)maxf));
-    HIPC(f, dev_alloc(f->stream, &f->P, pp));
-    HIPC(f, dev_alloc(f->stream, &f->P2, pp));
-    HIPC(f, dev_alloc(f->stream, &f->FA, EKF_BASE * EKF_BASE));
-    HIPC(f, dev_alloc(f->stream, &f->FB, 27 * (size_t)maxf));
-    HIPC(f, dev_alloc(f->stream, &f->FD, 9 * (size_t)maxf));
-    HIPC(f, dev_alloc(f->stream, &f->Fdense, pp));
-    HIPC(f, dev_alloc(f->stream, &f->idx, (size_t)f->m_cap));
-    HIPC(f, dev_alloc(f->stream, &f->inv_idx, (size_t)f->ldp));
-    HIPC(f, dev_alloc(f->stream, &f->zmeas, 2 * (size_t)maxf));
-    HIPC(f, dev_alloc(f->stream, &f->Rmeas, 4 * (size_t)maxf));
-    HIPC(f, dev_alloc(f->stream, &f->pass, (size_t)maxf));
-    HIPC(f, dev_alloc(f->stream, &f->yres, (size_t)f->m_cap));
-    HIPC(f, dev_alloc(f->stream, &f->Rm, 2 * (size_t)f->m_cap));
-    HIPC(f, dev_alloc(f->stream, &f->Saug, (size_t)f->ld_aug * f->m_cap));
-    HIPC(f, dev_alloc(f->stream, &f->Laug, (size_t)f->ld_aug * f->m_cap));
-    HIPC(f, dev_alloc(f->stream, &f->Linv, 64 * (size_t)f->m_cap));
-    HIPC(f, dev_alloc(f->stream, &f->Lsign, (size_t)(f->m_cap / 64 > 256 ? f->m_cap / 64 : 256)));  // 256: the raw-solve test hook goes up to m = 16384
-    HIPC(f, dev_alloc(f->stream, &f->sweep_sync, f->sweep_sync_words));  // flags of the persistent sweeps (chol_persist.inc)
+    HIP_TRY(f, dev_alloc(f->stream, &f->mu, f->ldp));
+    HIP_TRY(f, dev_alloc(f->stream, &f->mu_next, f->ldp));
+    HIP_TRY(f, dev_alloc(f->stream, &f->last_klt, 2 * (size_t)maxf));
+    HIP_TRY(f, dev_alloc(f->stream, &f->del_flag, (size_t)maxf));
+    HIP_TRY(f, dev_alloc(f->stream, &f->P, pp));
+    HIP_TRY(f, dev_alloc(f->stream, &f->P2, pp));
+    HIP_TRY(f, dev_alloc(f->stream, &f->FA, EKF_BASE * EKF_BASE));
+    HIP_TRY(f, dev_alloc(f->stream, &f->FB, 27 * (size_t)maxf));
+    HIP_TRY(f, dev_alloc(f->stream, &f->FD, 9 * (size_t)maxf));
+    HIP_TRY(f, dev_alloc(f->stream, &f->Fdense, pp));
+    HIP_TRY(f, dev_alloc(f->stream, &f->idx, (size_t)f->m_cap));
+    HIP_TRY(f, dev_alloc(f->stream, &f->inv_idx, (size_t)f->ldp));
+    HIP_TRY(f, dev_alloc(f->stream, &f->zmeas, 2 * (size_t)maxf));
+    HIP_TRY(f, dev_alloc(f->stream, &f->Rmeas, 4 * (size_t)maxf));
+    HIP_TRY(f, dev_alloc(f->stream, &f->pass, (size_t)maxf));
+    HIP_TRY(f, dev_alloc(f->stream, &f->yres, (size_t)f->m_cap));
+    HIP_TRY(f, dev_alloc(f->stream, &f->Rm, 2 * (size_t)f->m_cap));
+    HIP_TRY(f, dev_alloc(f->stream, &f->Saug, (size_t)f->ld_aug * f->m_cap));
+    HIP_TRY(f, dev_alloc(f->stream, &f->Laug, (size_t)f->ld_aug * f->m_cap));
+    HIP_TRY(f, dev_alloc(f->stream, &f->Linv, 64 * (size_t)f->m_cap));
+    HIP_TRY(f, dev_alloc(f->stream, &f->Lsign, (size_t)(f->m_cap / 64 > 256 ? f->m_cap / 64 : 256)));  // 256: the raw-solve test hook goes up to m = 16384
+    HIP_TRY(f, dev_alloc(f->stream, &f->sweep_sync, f->sweep_sync_words));  // flags of the persistent sweeps (chol_persist.inc)
     {
         hipDeviceProp_t prop;
-        HIPC(f, hipGetDeviceProperties(&prop, device));
+        HIP_TRY(f, hipGetDeviceProperties(&prop, device));
         f->num_cus = prop.multiProcessorCount;
     }
-    HIPC(f, dev_alloc(f->stream, &f->Km, pm));
-    HIPC(f, dev_alloc(f->stream, &f->Wt, pm));
-    HIPC(f, dev_alloc(f->stream, &f->Gm, pm));
-    HIPC(f, dev_alloc(f->stream, &f->info, 4));
-    HIPC(f, dev_alloc(f->stream, &f->remove_words, 4));
-    HIPC(f, hipHostMalloc((void**)&f->h_info, 16 * sizeof(int), hipHostMallocMapped | hipHostMallocCoherent));
+    HIP_TRY(f, dev_alloc(f->stream, &f->Km, pm));
+    HIP_TRY(f, dev_alloc(f->stream, &f->Wt, pm));
+    HIP_TRY(f, dev_alloc(f->stream, &f->Gm, pm));
+    HIP_TRY(f, dev_alloc(f->stream, &f->info, 4));
+    HIP_TRY(f, dev_alloc(f->stream, &f->remove_words, 4));
+    HIP_TRY(f, hipHostMalloc((void**)&f->h_info, 16 * sizeof(int), hipHostMallocMapped | hipHostMallocCoherent));
     memset(f->h_info, 0, 16 * sizeof(int));
-    HIPC(f, hipHostGetDevicePointer((void**)&f->d_hinfo, f->h_info, 0));
+    HIP_TRY(f, hipHostGetDevicePointer((void**)&f->d_hinfo, f->h_info, 0));
     {
         const size_t words = EKF_BASE + 4 * (size_t)(f->cfg.max_features > 0 ? f->cfg.max_features : 1);
-        HIPC(f, hipHostMalloc((void**)&f->h_out, words * sizeof(float), hipHostMallocMapped | hipHostMallocCoherent));
-        HIPC(f, hipHostGetDevicePointer((void**)&f->d_out, f->h_out, 0));
+        HIP_TRY(f, hipHostMalloc((void**)&f->h_out, words * sizeof(float), hipHostMallocMapped | hipHostMallocCoherent));
+        HIP_TRY(f, hipHostGetDevicePointer((void**)&f->d_out, f->h_out, 0));
     }
     {
         const size_t cap = (size_t)(f->cfg.max_features > 0 ? f->cfg.max_features : 1);
-        HIPC(f, hipHostMalloc((void**)&f->h_meas, 25 * cap, hipHostMallocDefault));
-        HIPC(f, hipMalloc((void**)&f->d_meas, 25 * cap));
+        HIP_TRY(f, hipHostMalloc((void**)&f->h_meas, 25 * cap, hipHostMallocDefault));
+        HIP_TRY(f, hipMalloc((void**)&f->d_meas, 25 * cap));
     }
-    HIPC(f, hipEventCreate(&f->ev0));
-    HIPC(f, hipEventCreate(&f->ev1));
+    HIP_TRY(f, hipEventCreate(&f->ev0));
+    HIP_TRY(f, hipEventCreate(&f->ev1));
     int rc = klt_alloc(f);
     if (rc != EKFVIO_OK) return rc;
     rc = fast_alloc(f);
@@ -341,19 +326,19 @@ const char* ekfvio_last_error(const ekfvio_filter* f) {
 int ekfvio_reset(ekfvio_filter* f) {
     if (!f) return EKFVIO_EINVAL;
     f->out_fresh = false;
-    HIPC(f, hipSetDevice(f->device));
+    HIP_TRY(f, hipSetDevice(f->device));
     f->N = 0;
     f->n = EKF_BASE;
-    HIPC(f, hipMemsetAsync(f->P, 0, sizeof(float) * (size_t)f->ldp * f->ldp, f->stream));
-    HIPC(f, hipMemsetAsync(f->P2, 0, sizeof(float) * (size_t)f->ldp * f->ldp, f->stream));  // ping-pong partner: padding must be zero
-    HIPC(f, hipMemsetAsync(f->mu, 0, sizeof(float) * f->ldp, f->stream));
+    HIP_TRY(f, hipMemsetAsync(f->P, 0, sizeof(float) * (size_t)f->ldp * f->ldp, f->stream));
+    HIP_TRY(f, hipMemsetAsync(f->P2, 0, sizeof(float) * (size_t)f->ldp * f->ldp, f->stream));  // ping-pong partner: padding must be zero
+    HIP_TRY(f, hipMemsetAsync(f->mu, 0, sizeof(float) * f->ldp, f->stream));
     const float one = 1.f;
-    HIPC(f, hipMemcpyAsync(f->mu + 3, &one, sizeof(float), hipMemcpyHostToDevice, f->stream));
+    HIP_TRY(f, hipMemcpyAsync(f->mu + 3, &one, sizeof(float), hipMemcpyHostToDevice, f->stream));
     hipLaunchKernelGGL(init_sigma_kernel, dim3(1), dim3(32), 0, f->stream, f->P, f->ldp);
-    HIPC(f, hipMemsetAsync(f->info, 0, 4 * sizeof(int), f->stream));
-    if (f->gate_words) HIPC(f, hipMemsetAsync(f->gate_words, 0, 4 * sizeof(int), f->stream));  // the gate's counts start over; its threshold stays
-    if (f->fb_words) HIPC(f, hipMemsetAsync(f->fb_words, 0, 8 * sizeof(int), f->stream));  // ... and the forward-backward check's, likewise
-    HIPC(f, hipStreamSynchronize(f->stream));
+    HIP_TRY(f, hipMemsetAsync(f->info, 0, 4 * sizeof(int), f->stream));
+    if (f->gate_words) HIP_TRY(f, hipMemsetAsync(f->gate_words, 0, 4 * sizeof(int), f->stream));  // the gate's counts start over; its threshold stays
+    if (f->fb_words) HIP_TRY(f, hipMemsetAsync(f->fb_words, 0, 8 * sizeof(int), f->stream));  // ... and the forward-backward check's, likewise
+    HIP_TRY(f, hipStreamSynchronize(f->stream));
     f->have_stamp = false;
     f->frames[0].valid = f->frames[1].valid = false;
     return EKFVIO_OK;
@@ -364,29 +349,29 @@ int ekfvio_add_features(ekfvio_filter* f, const float* uv, int32_t count) {
     f->out_fresh = false;
     if (count == 0) return EKFVIO_OK;  // reference: early return (:59)
     if (f->N + count > f->cfg.max_features) return EKFVIO_ECAPACITY;
-    HIPC(f, hipSetDevice(f->device));
+    HIP_TRY(f, hipSetDevice(f->device));
     // stage uv through the (free between updates) zmeas buffer in chunks of max_features
-    HIPC(f, hipMemcpyAsync(f->zmeas, uv, sizeof(float) * 2 * count, hipMemcpyHostToDevice, f->stream));
+    HIP_TRY(f, hipMemcpyAsync(f->zmeas, uv, sizeof(float) * 2 * count, hipMemcpyHostToDevice, f->stream));
     return add_features_device(f, count);
 }
 
 int ekfvio_process(ekfvio_filter* f, float dt) {
     if (!f || !(dt >= 0.f)) return EKFVIO_EINVAL;  // ROS_ASSERT(dt >= 0) EKFVIO.cpp:162
     f->out_fresh = false;
-    HIPC(f, hipSetDevice(f->device));
+    HIP_TRY(f, hipSetDevice(f->device));
     launch_predict(f, dt);
-    HIPC(f, hipGetLastError());
+    HIP_TRY(f, hipGetLastError());
     return EKFVIO_OK;
 }
 
 int ekfvio_linearize(ekfvio_filter* f, float dt, float* F_dense) {
     if (!f || !F_dense) return EKFVIO_EINVAL;
-    HIPC(f, hipSetDevice(f->device));
+    HIP_TRY(f, hipSetDevice(f->device));
     launch_linearize(f, dt);
     launch_build_dense_F(f, f->Fdense);
-    HIPC(f, hipMemcpy2DAsync(F_dense, sizeof(float) * f->n, f->Fdense, sizeof(float) * f->ldp, sizeof(float) * f->n,
+    HIP_TRY(f, hipMemcpy2DAsync(F_dense, sizeof(float) * f->n, f->Fdense, sizeof(float) * f->ldp, sizeof(float) * f->n,
                              f->n, hipMemcpyDeviceToHost, f->stream));
-    HIPC(f, hipStreamSynchronize(f->stream));
+    HIP_TRY(f, hipStreamSynchronize(f->stream));
     return EKFVIO_OK;
 }
 
@@ -424,14 +409,17 @@ void sweep_maybe_retry(ekfvio_filter* f) {
 void sweep_clean_update(ekfvio_filter* f) {
     if (f->sweep_probation > 0 && f->tune.persist_sweep && !f->sweep_latched_off && --f->sweep_probation == 0) f->sweep_retry_pause_s = 0.0;
 }
-// Waits for the stream and reads the status word.  An aborted update is enqueued again by `rerun` (null: the caller cannot,
-// e.g. a graph replay of many steps: EKFVIO_EABORTED) with the per-step sweep and awaited: fresh launches, same inputs,
-// and the state comes out as if the per-step sweep had run in the first place.
-int finish_update_rerun(ekfvio_filter* f, void (*rerun)(ekfvio_filter*, void*), void* ctx, int published_seq) {
-    int bad = 0;
-    int rc = published_seq ? poll_status(f, published_seq, &bad, nullptr) : wait_status(f, &bad);  // (published_seq: the caller's launches publish it)
+// The host's end of an update (common.h).  read_status waits for the stream's work up to the publishing launch and reads the status
+// word; a word that was set is cleared on the device for the next update.
+int read_status(ekfvio_filter* f, int seq, const int* extra_dev, int* bad, int* extra) {
+    const int rc = seq ? poll_status(f, seq, bad, extra) : wait_status(f, bad, extra_dev, extra);  // (seq: the caller's launches publish it)
     if (rc != EKFVIO_OK) return rc;
-    if (bad) HIPC(f, hipMemsetAsync(f->info, 0, sizeof(int), f->stream));
+    if (*bad) HIP_TRY(f, hipMemsetAsync(f->info, 0, sizeof(int), f->stream));
+    return EKFVIO_OK;
+}
+// An aborted update is enqueued again by `rerun` (null: the caller cannot, e.g. a graph replay of many steps: EKFVIO_EABORTED) with
+// the per-step sweep and awaited: fresh launches, same inputs, and the state comes out as if the per-step sweep had run in the first place.
+int settle_update(ekfvio_filter* f, int bad, void (*rerun)(ekfvio_filter*, void*), void* ctx, bool counts_as_clean) {
     if (bad & 2) {
         sweep_abort_latch(f);
         if (!rerun) {
@@ -440,29 +428,27 @@ int finish_update_rerun(ekfvio_filter* f, void (*rerun)(ekfvio_filter*, void*), 
             return EKFVIO_EABORTED;
         }
         f->sweep_recoveries++;
+        f->out_fresh = false;  // (outputs that went out with the aborted update's status are the propagated state's)
         rerun(f, ctx);
-        HIPC(f, hipGetLastError());
-        rc = wait_status(f, &bad);
+        HIP_TRY(f, hipGetLastError());
+        const int rc = read_status(f, 0, nullptr, &bad, nullptr);
         if (rc != EKFVIO_OK) return rc;
-        if (bad) HIPC(f, hipMemsetAsync(f->info, 0, sizeof(int), f->stream));
         if (bad & 2) return EKFVIO_EABORTED;  // (cannot happen: the per-step sweep has no waits)
-    } else if (rerun) sweep_clean_update(f);
+    } else if (counts_as_clean) sweep_clean_update(f);
     return (bad & 1) ? EKFVIO_ENUMERIC : EKFVIO_OK;
 }
 
 extern "C" {
 
-static int finish_update(ekfvio_filter* f) { return finish_update_rerun(f, nullptr, nullptr, 0); }
-
 int ekfvio_update(ekfvio_filter* f, const float* z, const float* R, const uint8_t* pass, int32_t count) {
     if (!f || count != f->N) return EKFVIO_EINVAL;  // ROS_ASSERT :478
     f->out_fresh = false;
     if (count > 0 && (!z || !R || !pass)) return EKFVIO_EINVAL;
-    HIPC(f, hipSetDevice(f->device));
+    HIP_TRY(f, hipSetDevice(f->device));
     sweep_maybe_retry(f);
     const int m = count_rows(pass, count);
     // the frame's three host arrays travel as ONE copy from pinned memory (three pageable copies cost ~25 us per step);
-    // the previous call's synchronisation (finish_update) guarantees the staging buffer is free
+    // the previous call's synchronisation (read_status) guarantees the staging buffer is free
     const size_t cap = (size_t)(f->cfg.max_features > 0 ? f->cfg.max_features : 1);
     float* dz = reinterpret_cast<float*>(f->d_meas);
     float* dR = reinterpret_cast<float*>(f->d_meas + 8 * cap);
@@ -471,7 +457,7 @@ int ekfvio_update(ekfvio_filter* f, const float* z, const float* R, const uint8_
         memcpy(f->h_meas, z, sizeof(float) * 2 * count);
         memcpy(f->h_meas + 8 * cap, R, sizeof(float) * 4 * count);
         memcpy(f->h_meas + 24 * cap, pass, count);
-        HIPC(f, hipMemcpyAsync(f->d_meas, f->h_meas, 24 * cap + count, hipMemcpyHostToDevice, f->stream));
+        HIP_TRY(f, hipMemcpyAsync(f->d_meas, f->h_meas, 24 * cap + count, hipMemcpyHostToDevice, f->stream));
     }
     // The status of an update -- a non-positive pivot, a sweep that gave up -- is final when the Cholesky sweep is: the status word goes to
     // the host right behind the sweep, and the call returns while the two Joseph GEMMs are still running (everything the caller can do next
@@ -483,12 +469,15 @@ int ekfvio_update(ekfvio_filter* f, const float* z, const float* R, const uint8_
     in.m = m, in.z = dz, in.R = dR, in.pass = dp;
     in.publish_seq = early ? seq : 0;
     if (!launch_update(f, in).published) launch_publish_status(f, seq);  // (not early, or no sweep ran: nothing was published yet)
-    HIPC(f, hipGetLastError());
+    HIP_TRY(f, hipGetLastError());
     in.publish_seq = 0;
     in.gate_counted = true;  // (a re-run gates the same propagated state again: same verdicts, counted once)
-    return finish_update_rerun(f, [](ekfvio_filter* g, void* c) {
+    int bad = 0;
+    const int rc = read_status(f, seq, nullptr, &bad, nullptr);
+    if (rc != EKFVIO_OK) return rc;
+    return settle_update(f, bad, [](ekfvio_filter* g, void* c) {
         launch_update(g, *static_cast<const UpdateInputs*>(c));  // the staged measurement is still in d_meas; the bookkeeping is idempotent
-    }, &in, seq);
+    }, &in, true);  // (clean whenever it did not abort, an update without landmarks included)
 }
 
 int ekfvio_measurement_map(const ekfvio_filter* f, const uint8_t* measured, int32_t count, int32_t* idx, int32_t* rows) {
@@ -512,7 +501,7 @@ int ekfvio_get_base_mu(ekfvio_filter* f, float* base_mu) {
         memcpy(base_mu, f->h_out, sizeof(float) * EKF_BASE);
         return EKFVIO_OK;
     }
-    HIPC(f, hipSetDevice(f->device));
+    HIP_TRY(f, hipSetDevice(f->device));
     // 22 floats: written by a kernel straight into pinned host memory and awaited like the status word (the node reads
     // its odometry every frame: a device-to-host copy into pageable memory plus a synchronise cost three times as much)
     const int seq = next_status_seq(f);
@@ -526,52 +515,52 @@ int ekfvio_get_base_mu(ekfvio_filter* f, float* base_mu) {
 
 int ekfvio_get_features(ekfvio_filter* f, float* mu3N, float* last_klt2N, uint8_t* delN) {
     if (!f) return EKFVIO_EINVAL;
-    HIPC(f, hipSetDevice(f->device));
+    HIP_TRY(f, hipSetDevice(f->device));
     if (f->N > 0) {
-        if (mu3N) HIPC(f, hipMemcpyAsync(mu3N, f->mu + EKF_BASE, sizeof(float) * 3 * f->N, hipMemcpyDeviceToHost, f->stream));
-        if (last_klt2N) HIPC(f, hipMemcpyAsync(last_klt2N, f->last_klt, sizeof(float) * 2 * f->N, hipMemcpyDeviceToHost, f->stream));
-        if (delN) HIPC(f, hipMemcpyAsync(delN, f->del_flag, f->N, hipMemcpyDeviceToHost, f->stream));
+        if (mu3N) HIP_TRY(f, hipMemcpyAsync(mu3N, f->mu + EKF_BASE, sizeof(float) * 3 * f->N, hipMemcpyDeviceToHost, f->stream));
+        if (last_klt2N) HIP_TRY(f, hipMemcpyAsync(last_klt2N, f->last_klt, sizeof(float) * 2 * f->N, hipMemcpyDeviceToHost, f->stream));
+        if (delN) HIP_TRY(f, hipMemcpyAsync(delN, f->del_flag, f->N, hipMemcpyDeviceToHost, f->stream));
     }
-    HIPC(f, hipStreamSynchronize(f->stream));
+    HIP_TRY(f, hipStreamSynchronize(f->stream));
     return EKFVIO_OK;
 }
 
 int ekfvio_get_sigma(ekfvio_filter* f, float* sigma, int32_t ld) {
     if (!f || !sigma || ld < f->n) return EKFVIO_EINVAL;
-    HIPC(f, hipSetDevice(f->device));
-    HIPC(f, hipMemcpy2DAsync(sigma, sizeof(float) * ld, f->P, sizeof(float) * f->ldp, sizeof(float) * f->n, f->n,
+    HIP_TRY(f, hipSetDevice(f->device));
+    HIP_TRY(f, hipMemcpy2DAsync(sigma, sizeof(float) * ld, f->P, sizeof(float) * f->ldp, sizeof(float) * f->n, f->n,
                              hipMemcpyDeviceToHost, f->stream));
-    HIPC(f, hipStreamSynchronize(f->stream));
+    HIP_TRY(f, hipStreamSynchronize(f->stream));
     return EKFVIO_OK;
 }
 
 int ekfvio_get_feature_cov(ekfvio_filter* f, int32_t index, float cov[4]) {
     if (!f || !cov || index < 0 || index >= f->N) return EKFVIO_EINVAL;
-    HIPC(f, hipSetDevice(f->device));
+    HIP_TRY(f, hipSetDevice(f->device));
     const int s = EKF_BASE + 3 * index;  // Sigma.block(start,start,2,2), column-major out
-    HIPC(f, hipMemcpy2DAsync(cov, sizeof(float) * 2, f->P + (size_t)s * f->ldp + s, sizeof(float) * f->ldp,
+    HIP_TRY(f, hipMemcpy2DAsync(cov, sizeof(float) * 2, f->P + (size_t)s * f->ldp + s, sizeof(float) * f->ldp,
                              sizeof(float) * 2, 2, hipMemcpyDeviceToHost, f->stream));
-    HIPC(f, hipStreamSynchronize(f->stream));
+    HIP_TRY(f, hipStreamSynchronize(f->stream));
     return EKFVIO_OK;
 }
 
 int ekfvio_get_depth_variance(ekfvio_filter* f, int32_t index, float* var) {
     if (!f || !var || index < 0 || index >= f->N) return EKFVIO_EINVAL;
-    HIPC(f, hipSetDevice(f->device));
+    HIP_TRY(f, hipSetDevice(f->device));
     const int s = EKF_BASE + 3 * index + 2;
-    HIPC(f, hipMemcpyAsync(var, f->P + (size_t)s * f->ldp + s, sizeof(float), hipMemcpyDeviceToHost, f->stream));
-    HIPC(f, hipStreamSynchronize(f->stream));
+    HIP_TRY(f, hipMemcpyAsync(var, f->P + (size_t)s * f->ldp + s, sizeof(float), hipMemcpyDeviceToHost, f->stream));
+    HIP_TRY(f, hipStreamSynchronize(f->stream));
     return EKFVIO_OK;
 }
 
 // setFeatureHomogenousCovariance (TightlyCoupledEKF.cpp:668-676): the four coeffRef writes of the (u,v) block
 int ekfvio_set_feature_cov(ekfvio_filter* f, int32_t index, const float cov[4]) {
     if (!f || !cov || index < 0 || index >= f->N) return EKFVIO_EINVAL;
-    HIPC(f, hipSetDevice(f->device));
+    HIP_TRY(f, hipSetDevice(f->device));
     const int s = EKF_BASE + 3 * index;  // column-major in, column-major block of Sigma out
-    HIPC(f, hipMemcpy2DAsync(f->P + (size_t)s * f->ldp + s, sizeof(float) * f->ldp, cov, sizeof(float) * 2, sizeof(float) * 2, 2,
+    HIP_TRY(f, hipMemcpy2DAsync(f->P + (size_t)s * f->ldp + s, sizeof(float) * f->ldp, cov, sizeof(float) * 2, sizeof(float) * 2, 2,
                              hipMemcpyHostToDevice, f->stream));
-    HIPC(f, hipStreamSynchronize(f->stream));  // cov is the caller's memory
+    HIP_TRY(f, hipStreamSynchronize(f->stream));  // cov is the caller's memory
     return EKFVIO_OK;
 }
 
@@ -606,11 +595,11 @@ int ekfvio_get_odometry(ekfvio_filter* f, float position[3], float orientation_w
 
 int ekfvio_check_sigma(ekfvio_filter* f, float* min_diag, float* max_asym) {
     if (!f || !min_diag || !max_asym) return EKFVIO_EINVAL;
-    HIPC(f, hipSetDevice(f->device));
+    HIP_TRY(f, hipSetDevice(f->device));
     launch_check_sigma(f, f->yres);  // yres is free between updates
     float out[2];
-    HIPC(f, hipMemcpyAsync(out, f->yres, 2 * sizeof(float), hipMemcpyDeviceToHost, f->stream));
-    HIPC(f, hipStreamSynchronize(f->stream));
+    HIP_TRY(f, hipMemcpyAsync(out, f->yres, 2 * sizeof(float), hipMemcpyDeviceToHost, f->stream));
+    HIP_TRY(f, hipStreamSynchronize(f->stream));
     *min_diag = out[0];
     *max_asym = out[1];
     return EKFVIO_OK;
@@ -623,19 +612,19 @@ int ekfvio_set_state(ekfvio_filter* f, int32_t N, const float* base_mu, const fl
     if (N > f->cfg.max_features) return EKFVIO_ECAPACITY;
     const int n = EKF_BASE + 3 * N;
     if (ld < n || (N > 0 && (!mu3N || !last_klt2N || !delN))) return EKFVIO_EINVAL;
-    HIPC(f, hipSetDevice(f->device));
-    HIPC(f, hipMemsetAsync(f->P, 0, sizeof(float) * (size_t)f->ldp * f->ldp, f->stream));
-    HIPC(f, hipMemsetAsync(f->P2, 0, sizeof(float) * (size_t)f->ldp * f->ldp, f->stream));
-    HIPC(f, hipMemsetAsync(f->mu, 0, sizeof(float) * f->ldp, f->stream));
-    HIPC(f, hipMemcpyAsync(f->mu, base_mu, sizeof(float) * EKF_BASE, hipMemcpyHostToDevice, f->stream));
+    HIP_TRY(f, hipSetDevice(f->device));
+    HIP_TRY(f, hipMemsetAsync(f->P, 0, sizeof(float) * (size_t)f->ldp * f->ldp, f->stream));
+    HIP_TRY(f, hipMemsetAsync(f->P2, 0, sizeof(float) * (size_t)f->ldp * f->ldp, f->stream));
+    HIP_TRY(f, hipMemsetAsync(f->mu, 0, sizeof(float) * f->ldp, f->stream));
+    HIP_TRY(f, hipMemcpyAsync(f->mu, base_mu, sizeof(float) * EKF_BASE, hipMemcpyHostToDevice, f->stream));
     if (N > 0) {
-        HIPC(f, hipMemcpyAsync(f->mu + EKF_BASE, mu3N, sizeof(float) * 3 * N, hipMemcpyHostToDevice, f->stream));
-        HIPC(f, hipMemcpyAsync(f->last_klt, last_klt2N, sizeof(float) * 2 * N, hipMemcpyHostToDevice, f->stream));
-        HIPC(f, hipMemcpyAsync(f->del_flag, delN, N, hipMemcpyHostToDevice, f->stream));
+        HIP_TRY(f, hipMemcpyAsync(f->mu + EKF_BASE, mu3N, sizeof(float) * 3 * N, hipMemcpyHostToDevice, f->stream));
+        HIP_TRY(f, hipMemcpyAsync(f->last_klt, last_klt2N, sizeof(float) * 2 * N, hipMemcpyHostToDevice, f->stream));
+        HIP_TRY(f, hipMemcpyAsync(f->del_flag, delN, N, hipMemcpyHostToDevice, f->stream));
     }
-    HIPC(f, hipMemcpy2DAsync(f->P, sizeof(float) * f->ldp, sigma, sizeof(float) * ld, sizeof(float) * n, n,
+    HIP_TRY(f, hipMemcpy2DAsync(f->P, sizeof(float) * f->ldp, sigma, sizeof(float) * ld, sizeof(float) * n, n,
                              hipMemcpyHostToDevice, f->stream));
-    HIPC(f, hipStreamSynchronize(f->stream));
+    HIP_TRY(f, hipStreamSynchronize(f->stream));
     f->N = N;
     f->n = n;
     return EKFVIO_OK;
@@ -644,9 +633,9 @@ int ekfvio_set_state(ekfvio_filter* f, int32_t N, const float* base_mu, const fl
 int ekfvio_imu_update(ekfvio_filter* f, const float* gyro, const float* accel) {
     if (!f || !gyro || !accel) return EKFVIO_EINVAL;
     f->out_fresh = false;
-    HIPC(f, hipSetDevice(f->device));
+    HIP_TRY(f, hipSetDevice(f->device));
     launch_imu_update(f, gyro, accel);
-    HIPC(f, hipGetLastError());
+    HIP_TRY(f, hipGetLastError());
     return EKFVIO_OK;
 }
 
@@ -662,19 +651,19 @@ int ekfvio_imu(ekfvio_filter* f, double stamp, const float* gyro, const float* a
     }
     const double dt = stamp - f->t_stamp;
     if (!(dt >= 0)) return EKFVIO_EINVAL;
-    HIPC(f, hipSetDevice(f->device));
+    HIP_TRY(f, hipSetDevice(f->device));
     launch_predict(f, (float)dt);
     f->t_stamp = stamp;
     launch_imu_update(f, gyro, accel);
-    HIPC(f, hipGetLastError());
+    HIP_TRY(f, hipGetLastError());
     return EKFVIO_OK;
 }
 
 // ---- uploaded measurement sequences ---------------------------------------------------
 int ekfvio_upload_measurements(ekfvio_filter* f, int32_t frames, const float* z, const float* R, const uint8_t* pass) {
     if (!f || frames <= 0 || !z || !R || !pass || f->N <= 0) return EKFVIO_EINVAL;
-    HIPC(f, hipSetDevice(f->device));
-    HIPC(f, hipStreamSynchronize(f->stream));
+    HIP_TRY(f, hipSetDevice(f->device));
+    HIP_TRY(f, hipStreamSynchronize(f->stream));
     drop_graph(f);  // the captured launches hold pointers into the old sequence buffers
     if (f->seq_z) hipFree(f->seq_z);
     if (f->seq_R) hipFree(f->seq_R);
@@ -682,13 +671,13 @@ int ekfvio_upload_measurements(ekfvio_filter* f, int32_t frames, const float* z,
     f->seq_z = f->seq_R = nullptr;
     f->seq_pass = nullptr;
     const size_t N = f->N;
-    HIPC(f, dev_alloc(f->stream, &f->seq_z, frames * 2 * N));
-    HIPC(f, dev_alloc(f->stream, &f->seq_R, frames * 4 * N));
-    HIPC(f, dev_alloc(f->stream, &f->seq_pass, frames * N));
-    HIPC(f, hipMemcpyAsync(f->seq_z, z, sizeof(float) * frames * 2 * N, hipMemcpyHostToDevice, f->stream));
-    HIPC(f, hipMemcpyAsync(f->seq_R, R, sizeof(float) * frames * 4 * N, hipMemcpyHostToDevice, f->stream));
-    HIPC(f, hipMemcpyAsync(f->seq_pass, pass, frames * N, hipMemcpyHostToDevice, f->stream));
-    HIPC(f, hipStreamSynchronize(f->stream));
+    HIP_TRY(f, dev_alloc(f->stream, &f->seq_z, frames * 2 * N));
+    HIP_TRY(f, dev_alloc(f->stream, &f->seq_R, frames * 4 * N));
+    HIP_TRY(f, dev_alloc(f->stream, &f->seq_pass, frames * N));
+    HIP_TRY(f, hipMemcpyAsync(f->seq_z, z, sizeof(float) * frames * 2 * N, hipMemcpyHostToDevice, f->stream));
+    HIP_TRY(f, hipMemcpyAsync(f->seq_R, R, sizeof(float) * frames * 4 * N, hipMemcpyHostToDevice, f->stream));
+    HIP_TRY(f, hipMemcpyAsync(f->seq_pass, pass, frames * N, hipMemcpyHostToDevice, f->stream));
+    HIP_TRY(f, hipStreamSynchronize(f->stream));
     f->seq_frames = frames;
     f->seq_N = (int)N;
     f->seq_m.resize(frames);
@@ -732,7 +721,7 @@ static UpdateInputs uploaded_update(ekfvio_filter* f, int m, int i, int* counter
 // *pre_out: how many of its process(dt) launches were captured pre-linearised (counted per replay by ekfvio_run_uploaded).
 static int capture_steps(ekfvio_filter* f, int steps, int m, float dt, int* counter, hipGraphExec_t* out, int* pre_out) {
     hipGraph_t g = nullptr;
-    HIPC(f, hipStreamSynchronize(f->stream));
+    HIP_TRY(f, hipStreamSynchronize(f->stream));
     // sweep_flags_clean mirrors DEVICE state on the host, and a capture records launches without running them: the
     // graph must not inherit the mirror's value of the moment it was captured at -- its first sweep always zeroes the flags itself (one
     // memset node per replay) -- and the mirror must come out of the capture as it went in.  What a replay leaves behind is recorded
@@ -740,7 +729,7 @@ static int capture_steps(ekfvio_filter* f, int steps, int m, float dt, int* coun
     const bool mirror = f->sweep_flags_clean;
     f->sweep_flags_clean = false;
     const long long pre0 = f->prelinearized_steps;  // (nothing runs here either: launch_predict's counts of the capture go to *pre_out)
-    HIPC(f, hipStreamBeginCapture(f->stream, hipStreamCaptureModeThreadLocal));
+    HIP_TRY(f, hipStreamBeginCapture(f->stream, hipStreamCaptureModeThreadLocal));
     const bool gate = f->gate_chi2 > 0.f;
     for (int k = 0; k < steps; k++) {
         // the frame's measurement bookkeeping rides in the process(dt) launch -- unless the handle gates its measurements: the gate reads the
@@ -765,7 +754,7 @@ static int capture_steps(ekfvio_filter* f, int steps, int m, float dt, int* coun
         f->last_error = std::string("graph capture: ") + hipGetErrorString(ce);
         return EKFVIO_EDEVICE;
     }
-    HIPC(f, hipGraphInstantiate(out, g, nullptr, nullptr, 0));
+    HIP_TRY(f, hipGraphInstantiate(out, g, nullptr, nullptr, 0));
     (void)hipGraphDestroy(g);
     return EKFVIO_OK;
 }
@@ -773,7 +762,7 @@ static int capture_steps(ekfvio_filter* f, int steps, int m, float dt, int* coun
 int ekfvio_run_uploaded(ekfvio_filter* f, int32_t first, int32_t count, float dt) {
     if (!f || f->seq_frames <= 0 || f->seq_N != f->N || count < 0 || first < 0 || !(dt >= 0.f)) return EKFVIO_EINVAL;
     f->out_fresh = false;
-    HIPC(f, hipSetDevice(f->device));
+    HIP_TRY(f, hipSetDevice(f->device));
     // (no sweep_maybe_retry here -- ADVICE r05: a device-resident run cannot run an aborted update again, so a handle whose persistent
     // sweep once gave up keeps the per-step sweep for its graph replays until ekfvio_update / ekfvio_step_image, which CAN recover,
     // have tried the persistent launch again and it has come through; with a permanent obstacle (a compute-unit mask, a co-tenant
@@ -791,7 +780,7 @@ int ekfvio_run_uploaded(ekfvio_filter* f, int32_t first, int32_t count, float dt
         const int m = geometry(0);
         int* counter = f->info + 1;
         // by value (a copy from a host scalar could be overtaken by the next call's write to that scalar)
-        HIPC(f, hipMemsetD32Async((hipDeviceptr_t)counter, first % f->seq_frames, 1, f->stream));
+        HIP_TRY(f, hipMemsetD32Async((hipDeviceptr_t)counter, first % f->seq_frames, 1, f->stream));
         if (!f->step_graph || f->graph_N != f->N || f->graph_m != m || f->graph_dt != dt || f->graph_mu != f->mu || f->graph_P != f->P ||
             f->graph_seq != f->seq_z || f->graph_frames != f->seq_frames || f->graph_sole != (live_handles_on(f->device) <= 1)) {
             drop_graph(f);
@@ -817,15 +806,15 @@ int ekfvio_run_uploaded(ekfvio_filter* f, int32_t first, int32_t count, float dt
             return e;
         };
         if (f->step_graph_big)
-            while (s + EKF_GRAPH_STEPS_BIG <= count) HIPC(f, replay(f->step_graph_big, EKF_GRAPH_STEPS_BIG, f->graph_pre_big));
-        while (s + EKF_GRAPH_STEPS <= count) HIPC(f, replay(f->step_graph, EKF_GRAPH_STEPS, f->graph_pre));
-        while (s + 2 <= count) HIPC(f, replay(f->step_graph_pair, 2, f->graph_pre_pair));
+            while (s + EKF_GRAPH_STEPS_BIG <= count) HIP_TRY(f, replay(f->step_graph_big, EKF_GRAPH_STEPS_BIG, f->graph_pre_big));
+        while (s + EKF_GRAPH_STEPS <= count) HIP_TRY(f, replay(f->step_graph, EKF_GRAPH_STEPS, f->graph_pre));
+        while (s + 2 <= count) HIP_TRY(f, replay(f->step_graph_pair, 2, f->graph_pre_pair));
         if (s > 0) f->sweep_flags_clean = f->graph_leaves_flags_clean;  // what the last replayed step left in device memory
         for (; s < count; s++) {  // an odd last step, eager, same counter-driven bookkeeping
             launch_predict(f, dt);
             launch_update(f, uploaded_update(f, m, 0, counter));
         }
-        HIPC(f, hipGetLastError());
+        HIP_TRY(f, hipGetLastError());
         return EKFVIO_OK;
     }
     for (; s < count; s++) {
@@ -833,15 +822,18 @@ int ekfvio_run_uploaded(ekfvio_filter* f, int32_t first, int32_t count, float dt
         launch_predict(f, dt);
         launch_update(f, uploaded_update(f, f->seq_m[i], i, nullptr));
     }
-    HIPC(f, hipGetLastError());
+    HIP_TRY(f, hipGetLastError());
     return EKFVIO_OK;
 }
 
 int ekfvio_synchronize(ekfvio_filter* f) {
     if (!f) return EKFVIO_EINVAL;
-    HIPC(f, hipSetDevice(f->device));
+    HIP_TRY(f, hipSetDevice(f->device));
     // a non-positive pivot met by an asynchronous run (ekfvio_run_uploaded) surfaces here, once
-    return finish_update(f);
+    int bad = 0;
+    const int rc = read_status(f, 0, nullptr, &bad, nullptr);
+    if (rc != EKFVIO_OK) return rc;
+    return settle_update(f, bad, nullptr, nullptr, false);
 }
 
 // ---- instrumentation ------------------------------------------------------------------
@@ -871,30 +863,30 @@ int ekfvio_profile_enable(ekfvio_filter* f, int32_t on) {
 int ekfvio_profile_update_gemms(ekfvio_filter* f, int32_t reps, double* avg_launch_us, double* flops_per_launch) {
     if (!f || reps <= 0 || !avg_launch_us) return EKFVIO_EINVAL;
     if (f->last_m <= 0 || f->N <= 0) return EKFVIO_ESTATE;
-    HIPC(f, hipSetDevice(f->device));
-    HIPC(f, hipStreamSynchronize(f->stream));
+    HIP_TRY(f, hipSetDevice(f->device));
+    HIP_TRY(f, hipStreamSynchronize(f->stream));
     hipGraph_t g = nullptr;
     hipGraphExec_t ge = nullptr;
-    HIPC(f, hipStreamBeginCapture(f->stream, hipStreamCaptureModeThreadLocal));
+    HIP_TRY(f, hipStreamBeginCapture(f->stream, hipStreamCaptureModeThreadLocal));
     const int per_rep = launch_update_gemms_scratch(f, plan_update(f, f->last_m), reps);
     hipError_t ce = hipStreamEndCapture(f->stream, &g);
     if (ce != hipSuccess || !g) {
         f->last_error = std::string("graph capture: ") + hipGetErrorString(ce);
         return EKFVIO_EDEVICE;
     }
-    HIPC(f, hipGraphInstantiate(&ge, g, nullptr, nullptr, 0));
+    HIP_TRY(f, hipGraphInstantiate(&ge, g, nullptr, nullptr, 0));
     (void)hipGraphDestroy(g);
-    HIPC(f, hipGraphLaunch(ge, f->stream));  // warm-up
-    HIPC(f, hipEventRecord(f->ev0, f->stream));
-    HIPC(f, hipGraphLaunch(ge, f->stream));
-    HIPC(f, hipEventRecord(f->ev1, f->stream));
-    HIPC(f, hipEventSynchronize(f->ev1));
+    HIP_TRY(f, hipGraphLaunch(ge, f->stream));  // warm-up
+    HIP_TRY(f, hipEventRecord(f->ev0, f->stream));
+    HIP_TRY(f, hipGraphLaunch(ge, f->stream));
+    HIP_TRY(f, hipEventRecord(f->ev1, f->stream));
+    HIP_TRY(f, hipEventSynchronize(f->ev1));
     float ms = 0;
-    HIPC(f, hipEventElapsedTime(&ms, f->ev0, f->ev1));
+    HIP_TRY(f, hipEventElapsedTime(&ms, f->ev0, f->ev1));
     (void)hipGraphExecDestroy(ge);
     // P2 is the predict's scratch and must stay zero outside the live block
-    HIPC(f, hipMemsetAsync(f->P2, 0, sizeof(float) * (size_t)f->ldp * f->ldp, f->stream));
-    HIPC(f, hipStreamSynchronize(f->stream));
+    HIP_TRY(f, hipMemsetAsync(f->P2, 0, sizeof(float) * (size_t)f->ldp * f->ldp, f->stream));
+    HIP_TRY(f, hipStreamSynchronize(f->stream));
     *avg_launch_us = 1e3 * ms / ((double)per_rep * reps);
     const int m_pad = round_up(f->last_m, 64);
     if (flops_per_launch) {
@@ -929,10 +921,10 @@ int ekfvio_set_gate(ekfvio_filter* f, float chi2) {
     if (chi2 > 0.f && !f->gate_words) {
         // the gate's device memory, ONE allocation made when a handle first asks for the gate (a handle that never does launches and
         // allocates nothing it did not before): [4] words, then d2, verdicts and effective flags per landmark
-        HIPC(f, hipSetDevice(f->device));
+        HIP_TRY(f, hipSetDevice(f->device));
         const size_t maxf = (size_t)(f->cfg.max_features > 0 ? f->cfg.max_features : 1);
         unsigned char* buf = nullptr;
-        HIPC(f, dev_alloc(f->stream, &buf, 4 * sizeof(int) + maxf * (sizeof(float) + 2)));
+        HIP_TRY(f, dev_alloc(f->stream, &buf, 4 * sizeof(int) + maxf * (sizeof(float) + 2)));
         f->gate_words = reinterpret_cast<int*>(buf);
         f->gate_d2 = reinterpret_cast<float*>(buf + 4 * sizeof(int));
         f->gate_flag = buf + 4 * sizeof(int) + maxf * sizeof(float);
@@ -945,17 +937,17 @@ int ekfvio_set_gate(ekfvio_filter* f, float chi2) {
 
 int ekfvio_get_gate(ekfvio_filter* f, float* d2, uint8_t* gated, int32_t* n_landmarks, int32_t* gated_last, int64_t* gated_total) {
     if (!f) return EKFVIO_EINVAL;
-    HIPC(f, hipSetDevice(f->device));
+    HIP_TRY(f, hipSetDevice(f->device));
     int w[4] = {0, 0, 0, 0};
     if (f->gate_words) {  // (null: the handle never gated)
-        HIPC(f, hipMemcpyAsync(w, f->gate_words, sizeof(w), hipMemcpyDeviceToHost, f->stream));
-        HIPC(f, hipStreamSynchronize(f->stream));
+        HIP_TRY(f, hipMemcpyAsync(w, f->gate_words, sizeof(w), hipMemcpyDeviceToHost, f->stream));
+        HIP_TRY(f, hipStreamSynchronize(f->stream));
     }
     const int seen = std::min(std::max(w[1], 0), f->cfg.max_features);
     if (seen > 0) {
-        if (d2) HIPC(f, hipMemcpyAsync(d2, f->gate_d2, sizeof(float) * seen, hipMemcpyDeviceToHost, f->stream));
-        if (gated) HIPC(f, hipMemcpyAsync(gated, f->gate_flag, seen, hipMemcpyDeviceToHost, f->stream));
-        HIPC(f, hipStreamSynchronize(f->stream));
+        if (d2) HIP_TRY(f, hipMemcpyAsync(d2, f->gate_d2, sizeof(float) * seen, hipMemcpyDeviceToHost, f->stream));
+        if (gated) HIP_TRY(f, hipMemcpyAsync(gated, f->gate_flag, seen, hipMemcpyDeviceToHost, f->stream));
+        HIP_TRY(f, hipStreamSynchronize(f->stream));
     }
     if (n_landmarks) *n_landmarks = seen;
     if (gated_last) *gated_last = w[0];
@@ -972,17 +964,17 @@ int ekfvio_set_klt_fb(ekfvio_filter* f, float max_px) {
 
 int ekfvio_get_klt_fb(ekfvio_filter* f, float* err2, uint8_t* rejected, int32_t* n_landmarks, int32_t* rejected_last, int64_t* rejected_total) {
     if (!f) return EKFVIO_EINVAL;
-    HIPC(f, hipSetDevice(f->device));
+    HIP_TRY(f, hipSetDevice(f->device));
     int w[4] = {0, 0, 0, 0};
     if (f->fb_words) {  // (null: no track of this handle ran the check)
-        HIPC(f, hipMemcpyAsync(w, f->fb_words, sizeof(w), hipMemcpyDeviceToHost, f->stream));
-        HIPC(f, hipStreamSynchronize(f->stream));
+        HIP_TRY(f, hipMemcpyAsync(w, f->fb_words, sizeof(w), hipMemcpyDeviceToHost, f->stream));
+        HIP_TRY(f, hipStreamSynchronize(f->stream));
     }
     const int seen = std::min(std::max(w[1], 0), f->cfg.max_features);
     if (seen > 0) {
-        if (err2) HIPC(f, hipMemcpyAsync(err2, f->fb_err2, sizeof(float) * seen, hipMemcpyDeviceToHost, f->stream));
-        if (rejected) HIPC(f, hipMemcpyAsync(rejected, f->fb_flag, seen, hipMemcpyDeviceToHost, f->stream));
-        HIPC(f, hipStreamSynchronize(f->stream));
+        if (err2) HIP_TRY(f, hipMemcpyAsync(err2, f->fb_err2, sizeof(float) * seen, hipMemcpyDeviceToHost, f->stream));
+        if (rejected) HIP_TRY(f, hipMemcpyAsync(rejected, f->fb_flag, seen, hipMemcpyDeviceToHost, f->stream));
+        HIP_TRY(f, hipStreamSynchronize(f->stream));
     }
     if (n_landmarks) *n_landmarks = seen;
     if (rejected_last) *rejected_last = w[0];
@@ -1008,7 +1000,7 @@ int ekfvio_get_counters(ekfvio_filter* f, int64_t counters[8]) {
 int ekfvio_test_gemm(ekfvio_filter* f, int32_t transB, int32_t M, int32_t N, int32_t K, float alpha, const float* A,
                      int32_t lda, const float* B, int32_t ldb, float beta, float* C, int32_t ldc, int32_t variant) {
     if (!f || M <= 0 || N <= 0 || K <= 0 || !A || !B || !C) return EKFVIO_EINVAL;
-    HIPC(f, hipSetDevice(f->device));
+    HIP_TRY(f, hipSetDevice(f->device));
     // device copies padded to the kernels' contract (64-row/col slack, K to 64, zero fill);
     // packed on the host so that only flat copies are issued
     const int Mp = round_up(M, 64), Np = round_up(N, 64), Kp = round_up(K, 64);
@@ -1021,15 +1013,15 @@ int ekfvio_test_gemm(ekfvio_filter* f, int32_t transB, int32_t M, int32_t N, int
     for (int j = 0; j < N; j++)
         for (int i = 0; i < M; i++) hC[(size_t)j * Mp + i] = C[(size_t)j * ldc + i];
     float *dA, *dB, *dC;
-    HIPC(f, dev_alloc(f->stream, &dA, hA.size()));
-    HIPC(f, dev_alloc(f->stream, &dB, hB.size()));
-    HIPC(f, dev_alloc(f->stream, &dC, hC.size()));
-    HIPC(f, hipMemcpyAsync(dA, hA.data(), sizeof(float) * hA.size(), hipMemcpyHostToDevice, f->stream));
-    HIPC(f, hipMemcpyAsync(dB, hB.data(), sizeof(float) * hB.size(), hipMemcpyHostToDevice, f->stream));
-    HIPC(f, hipMemcpyAsync(dC, hC.data(), sizeof(float) * hC.size(), hipMemcpyHostToDevice, f->stream));
+    HIP_TRY(f, dev_alloc(f->stream, &dA, hA.size()));
+    HIP_TRY(f, dev_alloc(f->stream, &dB, hB.size()));
+    HIP_TRY(f, dev_alloc(f->stream, &dC, hC.size()));
+    HIP_TRY(f, hipMemcpyAsync(dA, hA.data(), sizeof(float) * hA.size(), hipMemcpyHostToDevice, f->stream));
+    HIP_TRY(f, hipMemcpyAsync(dB, hB.data(), sizeof(float) * hB.size(), hipMemcpyHostToDevice, f->stream));
+    HIP_TRY(f, hipMemcpyAsync(dC, hC.data(), sizeof(float) * hC.size(), hipMemcpyHostToDevice, f->stream));
     launch_gemm_variant(f, variant, transB, M, N, Kp, alpha, dA, Mp, dB, brows, beta, dC, Mp, dC, Mp, 0, 0);
-    HIPC(f, hipMemcpyAsync(hC.data(), dC, sizeof(float) * hC.size(), hipMemcpyDeviceToHost, f->stream));
-    HIPC(f, hipStreamSynchronize(f->stream));
+    HIP_TRY(f, hipMemcpyAsync(hC.data(), dC, sizeof(float) * hC.size(), hipMemcpyDeviceToHost, f->stream));
+    HIP_TRY(f, hipStreamSynchronize(f->stream));
     for (int j = 0; j < N; j++)
         for (int i = 0; i < M; i++) C[(size_t)j * ldc + i] = hC[(size_t)j * Mp + i];
     hipFree(dA);
@@ -1044,7 +1036,7 @@ int ekfvio_test_gemm(ekfvio_filter* f, int32_t transB, int32_t M, int32_t N, int
 int ekfvio_test_gemm_bench(ekfvio_filter* f, int32_t transB, int32_t lowerB, int32_t M, int32_t N, int32_t K,
                            int32_t reps, int32_t variant, double* mean_us) {
     if (!f || M <= 0 || N <= 0 || K <= 0 || reps <= 0 || !mean_us) return EKFVIO_EINVAL;
-    HIPC(f, hipSetDevice(f->device));
+    HIP_TRY(f, hipSetDevice(f->device));
     const int Mp = round_up(M, 128), Np = round_up(N, 128), Kp = round_up(K, 64);
     const int brows = transB ? Np : Kp, bcols = transB ? Kp : Np;
     std::vector<float> hA((size_t)Mp * Kp), hB((size_t)brows * bcols), hC((size_t)Mp * Np);
@@ -1054,32 +1046,32 @@ int ekfvio_test_gemm_bench(ekfvio_filter* f, int32_t transB, int32_t lowerB, int
     for (auto& v : hB) v = rnd();
     for (auto& v : hC) v = rnd();
     float *dA, *dB, *dC;
-    HIPC(f, dev_alloc(f->stream, &dA, hA.size()));
-    HIPC(f, dev_alloc(f->stream, &dB, hB.size()));
-    HIPC(f, dev_alloc(f->stream, &dC, hC.size()));
-    HIPC(f, hipMemcpyAsync(dA, hA.data(), sizeof(float) * hA.size(), hipMemcpyHostToDevice, f->stream));
-    HIPC(f, hipMemcpyAsync(dB, hB.data(), sizeof(float) * hB.size(), hipMemcpyHostToDevice, f->stream));
-    HIPC(f, hipMemcpyAsync(dC, hC.data(), sizeof(float) * hC.size(), hipMemcpyHostToDevice, f->stream));
+    HIP_TRY(f, dev_alloc(f->stream, &dA, hA.size()));
+    HIP_TRY(f, dev_alloc(f->stream, &dB, hB.size()));
+    HIP_TRY(f, dev_alloc(f->stream, &dC, hC.size()));
+    HIP_TRY(f, hipMemcpyAsync(dA, hA.data(), sizeof(float) * hA.size(), hipMemcpyHostToDevice, f->stream));
+    HIP_TRY(f, hipMemcpyAsync(dB, hB.data(), sizeof(float) * hB.size(), hipMemcpyHostToDevice, f->stream));
+    HIP_TRY(f, hipMemcpyAsync(dC, hC.data(), sizeof(float) * hC.size(), hipMemcpyHostToDevice, f->stream));
     const bool stamped = variant >= 10000;  // library built with -DEKF_GEMM_STAMPS
     variant %= 10000;
     for (int w = 0; w < 3; w++)
         launch_gemm_variant(f, variant, transB, M, N, Kp, -1e-3f, dA, Mp, dB, brows, 1.f, dC, Mp, dC, Mp, 0, lowerB);
-    HIPC(f, hipEventRecord(f->ev0, f->stream));
+    HIP_TRY(f, hipEventRecord(f->ev0, f->stream));
     for (int r = 0; r < reps; r++)
         launch_gemm_variant(f, variant, transB, M, N, Kp, -1e-3f, dA, Mp, dB, brows, 1.f, dC, Mp, dC, Mp, 0, lowerB);
-    HIPC(f, hipEventRecord(f->ev1, f->stream));
-    HIPC(f, hipEventSynchronize(f->ev1));
+    HIP_TRY(f, hipEventRecord(f->ev1, f->stream));
+    HIP_TRY(f, hipEventSynchronize(f->ev1));
     float ms = 0;
-    HIPC(f, hipEventElapsedTime(&ms, f->ev0, f->ev1));
+    HIP_TRY(f, hipEventElapsedTime(&ms, f->ev0, f->ev1));
     *mean_us = 1e3 * ms / reps;
     if (stamped) {  // diagnostic: one stamped launch, stamps returned through mean_us[1..40]
         long long* dst;
-        HIPC(f, dev_alloc(f->stream, &dst, 40));
+        HIP_TRY(f, dev_alloc(f->stream, &dst, 40));
         f->gemm_stamps = dst;
         launch_gemm_variant(f, variant, transB, M, N, Kp, -1e-3f, dA, Mp, dB, brows, 1.f, dC, Mp, dC, Mp, 0, lowerB);
         long long hst[40];
-        HIPC(f, hipMemcpyAsync(hst, dst, sizeof(hst), hipMemcpyDeviceToHost, f->stream));
-        HIPC(f, hipStreamSynchronize(f->stream));
+        HIP_TRY(f, hipMemcpyAsync(hst, dst, sizeof(hst), hipMemcpyDeviceToHost, f->stream));
+        HIP_TRY(f, hipStreamSynchronize(f->stream));
         f->gemm_stamps = nullptr;
         for (int i = 0; i < 40; i++) mean_us[1 + i] = (double)hst[i];
         hipFree(dst);
@@ -1096,24 +1088,24 @@ int ekfvio_test_gemm_bench(ekfvio_filter* f, int32_t transB, int32_t lowerB, int
 // phase i (2p: factor phase of panel p, 2p+1: column-update phase, 8: final phase).
 int ekfvio_test_potrf_stamps(ekfvio_filter* f, int64_t stamps[80]) {
     if (!f || !stamps) return EKFVIO_EINVAL;
-    HIPC(f, hipSetDevice(f->device));
+    HIP_TRY(f, hipSetDevice(f->device));
     std::vector<float> hs(64 * 64);
     for (int c = 0; c < 64; c++)
         for (int r = 0; r < 64; r++) hs[c * 64 + r] = (r == c ? 2.0f : 0.f) + 0.3f / (1.0f + (r > c ? r - c : c - r));
     float *dS, *dL, *dLi;
     long long* dst;
-    HIPC(f, dev_alloc(f->stream, &dS, hs.size()));
-    HIPC(f, dev_alloc(f->stream, &dL, hs.size()));
-    HIPC(f, dev_alloc(f->stream, &dLi, 4096));
-    HIPC(f, dev_alloc(f->stream, &dst, 80));
-    HIPC(f, hipMemsetAsync(dst, 0, sizeof(long long) * 80, f->stream));
-    HIPC(f, hipMemcpyAsync(dS, hs.data(), sizeof(float) * hs.size(), hipMemcpyHostToDevice, f->stream));
+    HIP_TRY(f, dev_alloc(f->stream, &dS, hs.size()));
+    HIP_TRY(f, dev_alloc(f->stream, &dL, hs.size()));
+    HIP_TRY(f, dev_alloc(f->stream, &dLi, 4096));
+    HIP_TRY(f, dev_alloc(f->stream, &dst, 80));
+    HIP_TRY(f, hipMemsetAsync(dst, 0, sizeof(long long) * 80, f->stream));
+    HIP_TRY(f, hipMemcpyAsync(dS, hs.data(), sizeof(float) * hs.size(), hipMemcpyHostToDevice, f->stream));
     for (int rep = 0; rep < 3; rep++) launch_potrf_stamps(f, dS, 64, dL, dLi, dst);
-    HIPC(f, hipMemcpyAsync(stamps, dst, sizeof(long long) * 80, hipMemcpyDeviceToHost, f->stream));
+    HIP_TRY(f, hipMemcpyAsync(stamps, dst, sizeof(long long) * 80, hipMemcpyDeviceToHost, f->stream));
     std::vector<uint32_t> hl(64 * 64), hi(4096);
-    HIPC(f, hipMemcpyAsync(hl.data(), dL, sizeof(float) * hl.size(), hipMemcpyDeviceToHost, f->stream));
-    HIPC(f, hipMemcpyAsync(hi.data(), dLi, sizeof(float) * hi.size(), hipMemcpyDeviceToHost, f->stream));
-    HIPC(f, hipStreamSynchronize(f->stream));
+    HIP_TRY(f, hipMemcpyAsync(hl.data(), dL, sizeof(float) * hl.size(), hipMemcpyDeviceToHost, f->stream));
+    HIP_TRY(f, hipMemcpyAsync(hi.data(), dLi, sizeof(float) * hi.size(), hipMemcpyDeviceToHost, f->stream));
+    HIP_TRY(f, hipStreamSynchronize(f->stream));
     // stamps[12], [13]: FNV-1a hashes of the bits of L and of the 16x16 inverses (variants must agree bit for bit)
     uint64_t h1 = 1469598103934665603ull, h2 = h1;
     for (uint32_t v : hl) h1 = (h1 ^ v) * 1099511628211ull;
@@ -1128,14 +1120,14 @@ int ekfvio_test_potrf_stamps(ekfvio_filter* f, int64_t stamps[80]) {
 // from [8]; first helper: 8 per block step from [256]).  enable != 0 allocates and arms the buffer.
 int ekfvio_test_sweep_stamps(ekfvio_filter* f, int enable, int64_t* stamps /* [1024] */) {
     if (!f) return EKFVIO_EINVAL;
-    HIPC(f, hipSetDevice(f->device));
+    HIP_TRY(f, hipSetDevice(f->device));
     if (enable && !f->sweep_dbg) {
-        HIPC(f, dev_alloc(f->stream, &f->sweep_dbg, 1024));
-        HIPC(f, hipMemsetAsync(f->sweep_dbg, 0, 1024 * sizeof(long long), f->stream));
+        HIP_TRY(f, dev_alloc(f->stream, &f->sweep_dbg, 1024));
+        HIP_TRY(f, hipMemsetAsync(f->sweep_dbg, 0, 1024 * sizeof(long long), f->stream));
     }
     if (stamps && f->sweep_dbg) {
-        HIPC(f, hipMemcpyAsync(stamps, f->sweep_dbg, 1024 * sizeof(long long), hipMemcpyDeviceToHost, f->stream));
-        HIPC(f, hipStreamSynchronize(f->stream));
+        HIP_TRY(f, hipMemcpyAsync(stamps, f->sweep_dbg, 1024 * sizeof(long long), hipMemcpyDeviceToHost, f->stream));
+        HIP_TRY(f, hipStreamSynchronize(f->stream));
     }
     return EKFVIO_OK;
 }
@@ -1164,7 +1156,7 @@ int ekfvio_test_cholesky_solve(ekfvio_filter* f, int32_t m, int32_t nrhs, const 
     // S: m x m (ld m) SPD; Crhs: nrhs x m (ld nrhs); L_out m x m; X_out = Crhs * S^-1 (nrhs x m).
     // Runs the production path: augmented sweep + gain GEMMs.
     if (!f || m <= 0 || nrhs <= 0 || !S || !Crhs) return EKFVIO_EINVAL;
-    HIPC(f, hipSetDevice(f->device));
+    HIP_TRY(f, hipSetDevice(f->device));
     const int mp = round_up(m, 64), rp = round_up(nrhs, 64);
     const int ld = mp + rp + mp;
     std::vector<float> hs((size_t)ld * mp, 0.f);
@@ -1175,32 +1167,32 @@ int ekfvio_test_cholesky_solve(ekfvio_filter* f, int32_t m, int32_t nrhs, const 
         hs[(size_t)c * ld + mp + rp + c] = 1.f;
     }
     float *dS, *dL, *dLi, *dK, *dW;
-    HIPC(f, dev_alloc(f->stream, &dS, hs.size()));
-    HIPC(f, dev_alloc(f->stream, &dL, hs.size()));
-    HIPC(f, dev_alloc(f->stream, &dLi, (size_t)64 * mp));
-    HIPC(f, dev_alloc(f->stream, &dK, (size_t)rp * mp));
-    HIPC(f, dev_alloc(f->stream, &dW, (size_t)rp * mp));
-    HIPC(f, hipMemcpyAsync(dS, hs.data(), sizeof(float) * hs.size(), hipMemcpyHostToDevice, f->stream));
+    HIP_TRY(f, dev_alloc(f->stream, &dS, hs.size()));
+    HIP_TRY(f, dev_alloc(f->stream, &dL, hs.size()));
+    HIP_TRY(f, dev_alloc(f->stream, &dLi, (size_t)64 * mp));
+    HIP_TRY(f, dev_alloc(f->stream, &dK, (size_t)rp * mp));
+    HIP_TRY(f, dev_alloc(f->stream, &dW, (size_t)rp * mp));
+    HIP_TRY(f, hipMemcpyAsync(dS, hs.data(), sizeof(float) * hs.size(), hipMemcpyHostToDevice, f->stream));
     // the flow the handle's knobs and the process's handle count select for this shape, as for an update of the filter (plan_raw_sweep)
     UpdatePlan plan = plan_raw_sweep(f->tune, plan_shape(f), mp, rp);
     launch_chol_sweep(f, plan, dS, dL, dLi, ld, plan.persistent() && !f->sweep_flags_clean);
     if (plan.persistent()) f->sweep_flags_clean = false;  // (no GEMM of an update behind this sweep zeroes its flags)
     // one step of residual refinement against L, unless a block went through the U S U^T path (K L = Y S then, not Y)
     std::vector<unsigned long long> hsign(mp / 64);
-    HIPC(f, hipMemcpyAsync(hsign.data(), f->Lsign, sizeof(unsigned long long) * hsign.size(), hipMemcpyDeviceToHost, f->stream));
-    HIPC(f, hipStreamSynchronize(f->stream));
+    HIP_TRY(f, hipMemcpyAsync(hsign.data(), f->Lsign, sizeof(unsigned long long) * hsign.size(), hipMemcpyDeviceToHost, f->stream));
+    HIP_TRY(f, hipStreamSynchronize(f->stream));
     int refine = 1;
     for (unsigned long long v : hsign) refine &= (v == 0ull);
     if (refine) plan.gain = GAIN_GEMM;
     launch_gain_from_sweep(f, plan, dL, ld, nrhs, dK, dW, rp, refine);
     std::vector<float> hl(hs.size()), hk((size_t)rp * mp);
-    HIPC(f, hipMemcpyAsync(hl.data(), dL, sizeof(float) * hl.size(), hipMemcpyDeviceToHost, f->stream));
-    HIPC(f, hipMemcpyAsync(hk.data(), dK, sizeof(float) * hk.size(), hipMemcpyDeviceToHost, f->stream));
+    HIP_TRY(f, hipMemcpyAsync(hl.data(), dL, sizeof(float) * hl.size(), hipMemcpyDeviceToHost, f->stream));
+    HIP_TRY(f, hipMemcpyAsync(hk.data(), dK, sizeof(float) * hk.size(), hipMemcpyDeviceToHost, f->stream));
     if (info) {
-        HIPC(f, hipMemcpyAsync(info, f->info, sizeof(int), hipMemcpyDeviceToHost, f->stream));
-        HIPC(f, hipMemsetAsync(f->info, 0, sizeof(int), f->stream));
+        HIP_TRY(f, hipMemcpyAsync(info, f->info, sizeof(int), hipMemcpyDeviceToHost, f->stream));
+        HIP_TRY(f, hipMemsetAsync(f->info, 0, sizeof(int), f->stream));
     }
-    HIPC(f, hipStreamSynchronize(f->stream));
+    HIP_TRY(f, hipStreamSynchronize(f->stream));
     if (const char* dp = getenv("EKFVIO_DEBUG_DUMP_LAUG")) {  // diagnostic: the whole swept matrix [L; Y; L^-T]
         if (FILE* fp = fopen(dp, "wb")) {
             const int hdr[3] = {ld, mp, rp};

@@ -25,7 +25,7 @@
 // itself, behind its own match.  Every wait is bounded: after PersistArgs::bound.wait_ticks of wall clock (3 ms; or bound.spin_limit looks, the
 // fault-injection hook's bound) the abort word is raised, every wait
 // falls through and info bit 1 reports it (the grid always drains); the kernels behind the sweep then leave Sigma and mu
-// untouched and the host runs the update again with one launch per block step (EKFVIO_EABORTED, api.hip finish_update).  Which workgroup does what,
+// untouched and the host runs the update again with one launch per block step (EKFVIO_EABORTED, api.hip settle_update).  Which workgroup does what,
 // the shapes whose grid is admitted and the flags' layout and zeroing: plan.h (PersistGrid, persist_shape / choose_sweep, PersistFlags).
 //
 // Bits: a tile receives its steps in ascending order, one subtraction of a k-ascending MFMA product per step, and the panel

@@ -21,6 +21,31 @@
 #endif
 #define EKF_FLUSH_THRESH (1e-8f * 1e-5f)
 
+// A HIP call inside a function that returns an ekfvio status: on failure the call's text and the runtime's message go to the handle's
+// last_error and the function returns EKFVIO_EDEVICE.
+#define HIP_TRY(f, expr)                                                           \
+    do {                                                                           \
+        hipError_t e__ = (expr);                                                   \
+        if (e__ != hipSuccess) {                                                   \
+            (f)->last_error = std::string(#expr) + ": " + hipGetErrorString(e__);  \
+            return EKFVIO_EDEVICE;                                                 \
+        }                                                                          \
+    } while (0)
+
+// The words of ekfvio_filter::h_info (pinned, device-mapped; d_hinfo on the device): what a kernel publishes and poll_status reads.
+enum HostWord {
+    HW_STATUS = 0,   // info[0]: bit 0 a non-positive pivot was met, bit 1 the persistent sweep gave up
+    HW_SEQ = 1,      // the sequence number of the launch that published (next_status_seq), stored last with release at system scope
+    HW_EXTRA = 2,    // one more device word for the caller (landmarks added, or added - removed; 0 where not asked)
+    HW_REMOVED = 3,  // landmarks the frame's removal kernel took out (remove.hip; written in front of the publishing launch)
+};
+// One thread, behind the launch's own writes and its __threadfence_system(): the host reads the other words once it sees `seq`.
+__device__ __forceinline__ void publish_host_words(int* host_word, const int* __restrict__ info, int extra, int seq) {
+    host_word[HW_STATUS] = info[0];
+    host_word[HW_EXTRA] = extra;
+    __hip_atomic_store(host_word + HW_SEQ, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+
 // Kernel classes for the built-in event profiler (ekfvio_profile_*).
 enum ProfClass {
     PC_LINEARIZE = 0,
@@ -154,7 +179,7 @@ struct ekfvio_filter {
     float* fb_pt_back = nullptr;  // points of ekfvio_klt_track_points_fb
     uint8_t* fb_pt_flag = nullptr;
     int* remove_words = nullptr;  // [4] device words of the removal kernel (remove.hip): [0] landmarks added - removed, [1] removed, [2] its ticket
-    int* h_info = nullptr;     // pinned, device-mapped: [0] status word, [1] sequence number (publish_status_kernel)
+    int* h_info = nullptr;     // pinned, device-mapped: the words of enum HostWord
     int* d_hinfo = nullptr;    // the device's address of h_info
     int status_seq = 0;
     // small per-frame outputs (odometry, point cloud): kernels write them straight into pinned host memory and the host
@@ -341,10 +366,22 @@ struct UpdateResult {
 };
 UpdateResult launch_update(ekfvio_filter* f, const UpdateInputs& in);
 void launch_check_sigma(ekfvio_filter* f, float* d_out);
-// klt.hip helpers shared with fast.hip
+// klt.hip helpers shared with fast.hip and frame.hip
 int klt_level_pitch(int w);
 int klt_border();
 void klt_intrinsics(const ekfvio_filter* f, const float* K, float* fx, float* fy, float* cx, float* cy);
+// Level 0 of the current frame as the frame's outputs and the replenishment see it: img = pixel (0,0) inside the border, pitch in
+// pixels, and the intrinsics of klt_intrinsics.  All zeros (img null) while no frame has been pushed.
+struct Level0View {
+    const uint8_t* img = nullptr;
+    int pitch = 0, w = 0, h = 0;
+    float fx = 0.f, fy = 0.f, cx = 0.f, cy = 0.f;
+};
+Level0View klt_level0(const ekfvio_filter* f);
+// what the frame loop (frame.hip) enqueues of the tracker's file
+int push_frame_check(ekfvio_filter* f, const uint8_t* image, int32_t width, int32_t height, int32_t stride, const float K[9]);
+int push_frame_enqueue(ekfvio_filter* f, const uint8_t* image, int32_t width, int32_t height, int32_t stride, const float K[9]);
+int klt_track_device(ekfvio_filter* f);  // the tracker over the current landmarks; results in f->zmeas / Rmeas / pass (device)
 // imu.hip
 void launch_imu_update(ekfvio_filter* f, const float gyro[3], const float accel[3]);
 // fast.hip
@@ -361,6 +398,13 @@ int next_status_seq(ekfvio_filter* f);
 // sweep for good and its captured graphs are dropped
 void sweep_abort_latch(ekfvio_filter* f);
 void sweep_clean_update(ekfvio_filter* f);  // an update whose persistent sweep came through (api.hip)
+// api.hip: the host's end of an update, in two halves so that a caller can act between them (ekfvio_step_image).
+// read_status: the status word into *bad (and HW_EXTRA into *extra, may be null) -- polled under `seq` where the caller's own launch
+// publishes it, published here (with *extra_dev, may be null) where seq == 0 -- and info[0] cleared on the device if it was set.
+int read_status(ekfvio_filter* f, int seq, const int* extra_dev, int* bad, int* extra);
+// settle_update: an aborted persistent sweep (bit 1) latches and the update runs again through `rerun` (null: EKFVIO_EABORTED); a clean
+// one counts towards the retry's probation where counts_as_clean; bit 0 of the last status read comes back as EKFVIO_ENUMERIC.
+int settle_update(ekfvio_filter* f, int bad, void (*rerun)(ekfvio_filter*, void*), void* ctx, bool counts_as_clean);
 void sweep_maybe_retry(ekfvio_filter* f);  // at the entry points that enqueue updates: the persistent sweep again, some time after an abort
 int poll_status(ekfvio_filter* f, int seq, int* status, int* extra_out);
 // api.hip: addNewFeatures with the k new (u,v) already in f->zmeas on the device
@@ -404,9 +448,9 @@ void launch_potrf_stamps(ekfvio_filter* f, const float* S, int ld, float* L, flo
 void launch_gain_from_sweep(ekfvio_filter* f, const UpdatePlan& p, const float* Laug, int ld, int n, float* K, float* scratch, int ldk, int refine);
 
 // remove.hip: Sigma, mu, last_klt, del_flag compacted in ONE launch over N + *added landmarks (added may be null); decision from
-// `remove` (device memory), null: del_flag; abort_aware: nothing removed behind an aborted persistent sweep; host_removed (may be
-// null): the count into pinned host memory too
-void launch_remove_features(ekfvio_filter* f, const uint8_t* remove, const int* added, bool abort_aware, int* host_removed);
+// `remove` (device memory), null: del_flag; abort_aware: nothing removed behind an aborted persistent sweep; host_removed: the
+// count into the pinned host word HW_REMOVED too
+void launch_remove_features(ekfvio_filter* f, const uint8_t* remove, const int* added, bool abort_aware, bool host_removed);
 size_t remove_lds_bytes(const ekfvio_filter* f);
 void remove_applied(ekfvio_filter* f, int delta, int removed);  // the host side behind a launch: pointer swaps, N, n, graphs
 // rectify.hip

@@ -16,15 +16,6 @@
 // wavefronts prepare the mask (existing landmarks' circles) before that.
 #include "common.h"
 
-#define HIPF(f, expr)                                                              \
-    do {                                                                           \
-        hipError_t e_ = (expr);                                                    \
-        if (e_ != hipSuccess) {                                                    \
-            (f)->last_error = std::string(#expr) + ": " + hipGetErrorString(e_);   \
-            return EKFVIO_EDEVICE;                                                 \
-        }                                                                          \
-    } while (0)
-
 namespace {
 
 // FAST-9/16 segment test + cornerScore<16> at pixel (x, y): -1 = no corner (or inside the 3-pixel frame cv::FAST skips).
@@ -396,7 +387,7 @@ int fast_ensure(ekfvio_filter* f, int w, int h) {
     const ekfvio_config& c = f->cfg;
     w = std::max(w, f->fast_cap_w);
     h = std::max(h, f->fast_cap_h);
-    if (f->stream) HIPF(f, hipStreamSynchronize(f->stream));  // nothing in flight may still read the old buffers
+    if (f->stream) HIP_TRY(f, hipStreamSynchronize(f->stream));  // nothing in flight may still read the old buffers
     void* old[] = {f->blurred, f->fast_row_kp, f->fast_kp_xy, f->fast_kp_score, f->occ_mask, f->fast_row_cnt};
     for (void* p : old)
         if (p) (void)hipFree(p);
@@ -404,13 +395,13 @@ int fast_ensure(ekfvio_filter* f, int w, int h) {
     f->fast_row_cnt = nullptr;
     f->fast_cap_w = f->fast_cap_h = 0;
     const size_t px = (size_t)w * h;
-    if (c.fast_blur_sigma != 0.f) HIPF(f, hipMalloc((void**)&f->blurred, px));
-    HIPF(f, hipMalloc((void**)&f->fast_row_kp, px * sizeof(unsigned)));  // per image row: its keypoints in x order, (score << 16) | x
+    if (c.fast_blur_sigma != 0.f) HIP_TRY(f, hipMalloc((void**)&f->blurred, px));
+    HIP_TRY(f, hipMalloc((void**)&f->fast_row_kp, px * sizeof(unsigned)));  // per image row: its keypoints in x order, (score << 16) | x
     f->fast_kp_cap = (int)(px / 4 + 1);
-    HIPF(f, hipMalloc((void**)&f->fast_kp_xy, (size_t)f->fast_kp_cap * 2 * sizeof(int)));
-    HIPF(f, hipMalloc((void**)&f->fast_kp_score, (size_t)f->fast_kp_cap * sizeof(short)));
-    HIPF(f, hipMalloc((void**)&f->occ_mask, ((size_t)(w + 31) / 32) * h * sizeof(unsigned)));
-    HIPF(f, hipMalloc((void**)&f->fast_row_cnt, (size_t)h * sizeof(int)));
+    HIP_TRY(f, hipMalloc((void**)&f->fast_kp_xy, (size_t)f->fast_kp_cap * 2 * sizeof(int)));
+    HIP_TRY(f, hipMalloc((void**)&f->fast_kp_score, (size_t)f->fast_kp_cap * sizeof(short)));
+    HIP_TRY(f, hipMalloc((void**)&f->occ_mask, ((size_t)(w + 31) / 32) * h * sizeof(unsigned)));
+    HIP_TRY(f, hipMalloc((void**)&f->fast_row_cnt, (size_t)h * sizeof(int)));
     f->fast_cap_w = w;
     f->fast_cap_h = h;
     return EKFVIO_OK;
@@ -428,8 +419,8 @@ int fast_alloc(ekfvio_filter* f) {
         return EKFVIO_EINVAL;
     }
     const int maxf = c.max_features > 0 ? c.max_features : 1;
-    HIPF(f, hipMalloc((void**)&f->new_xy, (size_t)maxf * 2 * sizeof(int)));
-    HIPF(f, hipMalloc((void**)&f->fast_counts, 4 * sizeof(int)));
+    HIP_TRY(f, hipMalloc((void**)&f->new_xy, (size_t)maxf * 2 * sizeof(int)));
+    HIP_TRY(f, hipMalloc((void**)&f->fast_counts, 4 * sizeof(int)));
     return fast_ensure(f, c.max_image_width, c.max_image_height);
 }
 
@@ -472,14 +463,13 @@ int replenish_enqueue(ekfvio_filter* f, int* enqueued) {
     *enqueued = 0;
     if (!f) return EKFVIO_EINVAL;
     // (fast_blur_sigma and min_new_feature_dist were validated by ekfvio_create: fast_alloc)
-    HIPF(f, hipSetDevice(f->device));
+    HIP_TRY(f, hipSetDevice(f->device));
     if (f->N >= f->cfg.max_features) return EKFVIO_OK;  // "if (tc_ekf.features.size() < NUM_FEATURES)" (:236)
     int rc = fast_detect_device(f, f->cfg.fast_threshold, 1, f->cfg.fast_blur_sigma != 0.f, false);
     if (rc != EKFVIO_OK) return rc;
-    const KltFrame& fr = f->frames[f->cur];
-    const int w = fr.w[0], h = fr.h[0];
-    float fx, fy, cx, cy;
-    klt_intrinsics(f, fr.K, &fx, &fy, &cx, &cy);
+    const Level0View v = klt_level0(f);
+    const int w = v.w, h = v.h;
+    const float fx = v.fx, fy = v.fy, cx = v.cx, cy = v.cy;
     const size_t mask_words = (size_t)((w + 31) / 32) * h;
     if (mask_words <= OCC_LDS_WORDS) {
         hipLaunchKernelGGL(replenish_select_kernel<true>, dim3(1), dim3(256), 0, f->stream, f->fast_kp_xy, f->fast_counts, f->fast_kp_cap,
@@ -487,7 +477,7 @@ int replenish_enqueue(ekfvio_filter* f, int* enqueued) {
                            (unsigned*)f->occ_mask, f->new_xy, f->zmeas, f->fast_counts + 1, f->fast_row_kp, f->fast_row_cnt, f->fast_kp_xy,
                            f->fast_kp_score, f->fast_counts);
     } else {
-        HIPF(f, hipMemsetAsync(f->occ_mask, 0, mask_words * sizeof(unsigned), f->stream));
+        HIP_TRY(f, hipMemsetAsync(f->occ_mask, 0, mask_words * sizeof(unsigned), f->stream));
         hipLaunchKernelGGL(replenish_select_kernel<false>, dim3(1), dim3(256), 0, f->stream, f->fast_kp_xy, f->fast_counts, f->fast_kp_cap,
                            f->mu, f->N, fx, fy, cx, cy, f->cfg.max_features, w, h, f->cfg.min_new_feature_dist, f->cfg.kill_pad,
                            (unsigned*)f->occ_mask, f->new_xy, f->zmeas, f->fast_counts + 1, f->fast_row_kp, f->fast_row_cnt, f->fast_kp_xy,
@@ -501,22 +491,22 @@ extern "C" {
 
 int ekfvio_fast_detect(ekfvio_filter* f, int32_t threshold, int32_t nonmax, int32_t cap, int32_t* xy, int32_t* score, int32_t* count) {
     if (!f || !count || cap < 0) return EKFVIO_EINVAL;
-    HIPF(f, hipSetDevice(f->device));
+    HIP_TRY(f, hipSetDevice(f->device));
     int rc = fast_detect_device(f, threshold, nonmax, f->cfg.fast_blur_sigma != 0.f);
     if (rc != EKFVIO_OK) return rc;
     int n = 0;
-    HIPF(f, hipMemcpyAsync(&n, f->fast_counts, sizeof(int), hipMemcpyDeviceToHost, f->stream));
-    HIPF(f, hipStreamSynchronize(f->stream));
+    HIP_TRY(f, hipMemcpyAsync(&n, f->fast_counts, sizeof(int), hipMemcpyDeviceToHost, f->stream));
+    HIP_TRY(f, hipStreamSynchronize(f->stream));
     *count = n;
     const int k = std::min(std::min(n, cap), f->fast_kp_cap);
-    if (k > 0 && xy) HIPF(f, hipMemcpyAsync(xy, f->fast_kp_xy, sizeof(int) * 2 * k, hipMemcpyDeviceToHost, f->stream));
+    if (k > 0 && xy) HIP_TRY(f, hipMemcpyAsync(xy, f->fast_kp_xy, sizeof(int) * 2 * k, hipMemcpyDeviceToHost, f->stream));
     if (k > 0 && score) {
         std::vector<short> hs(k);
-        HIPF(f, hipMemcpyAsync(hs.data(), f->fast_kp_score, sizeof(short) * k, hipMemcpyDeviceToHost, f->stream));
-        HIPF(f, hipStreamSynchronize(f->stream));
+        HIP_TRY(f, hipMemcpyAsync(hs.data(), f->fast_kp_score, sizeof(short) * k, hipMemcpyDeviceToHost, f->stream));
+        HIP_TRY(f, hipStreamSynchronize(f->stream));
         for (int i = 0; i < k; i++) score[i] = hs[i];
     }
-    HIPF(f, hipStreamSynchronize(f->stream));
+    HIP_TRY(f, hipStreamSynchronize(f->stream));
     return EKFVIO_OK;
 }
 
@@ -526,9 +516,9 @@ int ekfvio_test_blurred_level0(ekfvio_filter* f, uint8_t* out) {
     if (!f || !out) return EKFVIO_EINVAL;
     const KltFrame& fr = f->frames[f->cur];
     if (!fr.valid || !f->blurred) return EKFVIO_ESTATE;
-    HIPF(f, hipSetDevice(f->device));
-    HIPF(f, hipMemcpyAsync(out, f->blurred, (size_t)fr.w[0] * fr.h[0], hipMemcpyDeviceToHost, f->stream));
-    HIPF(f, hipStreamSynchronize(f->stream));
+    HIP_TRY(f, hipSetDevice(f->device));
+    HIP_TRY(f, hipMemcpyAsync(out, f->blurred, (size_t)fr.w[0] * fr.h[0], hipMemcpyDeviceToHost, f->stream));
+    HIP_TRY(f, hipStreamSynchronize(f->stream));
     return EKFVIO_OK;
 }
 #endif
@@ -544,12 +534,12 @@ int ekfvio_replenish(ekfvio_filter* f, int32_t* added, int32_t* new_px_xy) {
     int k = 0, bad = 0;
     rc = wait_status(f, &bad, f->fast_counts + 1, &k);  // the count through the polled host word (no pageable copy)
     if (rc != EKFVIO_OK) return rc;
-    if (k > 0 && new_px_xy) HIPF(f, hipMemcpyAsync(new_px_xy, f->new_xy, sizeof(int) * 2 * k, hipMemcpyDeviceToHost, f->stream));
+    if (k > 0 && new_px_xy) HIP_TRY(f, hipMemcpyAsync(new_px_xy, f->new_xy, sizeof(int) * 2 * k, hipMemcpyDeviceToHost, f->stream));
     if (k > 0) {
         rc = add_features_device(f, k);  // uv already in f->zmeas
         if (rc != EKFVIO_OK) return rc;
     }
-    HIPF(f, hipStreamSynchronize(f->stream));
+    HIP_TRY(f, hipStreamSynchronize(f->stream));
     if (added) *added = k;
     return EKFVIO_OK;
 }

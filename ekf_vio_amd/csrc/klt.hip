@@ -34,15 +34,6 @@
 #define KLT_RS (KLT_MAX_WIN + 1 + 2 * KLT_R)  // staged region edge (38)
 #define KLT_RP 40         // LDS row pitch of the staged region
 
-#define HIPK(f, expr)                                                              \
-    do {                                                                           \
-        hipError_t e__ = (expr);                                                   \
-        if (e__ != hipSuccess) {                                                   \
-            (f)->last_error = std::string(#expr) + ": " + hipGetErrorString(e__);  \
-            return EKFVIO_EDEVICE;                                                 \
-        }                                                                          \
-    } while (0)
-
 namespace {
 
 struct LevelView {
@@ -777,120 +768,6 @@ __global__ __launch_bounds__(64) void klt_track_kernel(PyrView P, PyrView Q, flo
 #undef KSTAMP
 
 
-// EKFVIO::publishPoints (EKFVIO.cpp:479-518): camera-frame point (u/rho, v/rho, 1/rho) per landmark -- p(2) = 1.0/p(2)
-// in double, narrowed, then two float products -- and the "intensity" channel f.img.at<uchar>(e.getPixel(f)): the byte
-// at the landmark's pixel (Feature::getPixel: K(0)*mu(0) + K(2), K(4)*mu(1) + K(5); cv::Point2f -> cv::Point rounds
-// to nearest even, cvRound).  The reference reads outside the image unchecked; here such a landmark gets intensity 0.
-// img = pixel (0,0) of level 0 of the current frame, or null when no frame has been pushed (intensity 0 then).
-__device__ inline void points_one(const float* __restrict__ mu, int i, const uint8_t* __restrict__ img, int pitch, int w, int h,
-                                  float fx, float fy, float cx, float cy, float* __restrict__ xyz, float* __restrict__ intensity) {
-    const float u = mu[EKF_BASE + 3 * i], v = mu[EKF_BASE + 3 * i + 1], rho = mu[EKF_BASE + 3 * i + 2];
-    const float z = (float)(1.0 / (double)rho);
-    xyz[3 * i] = u * z;
-    xyz[3 * i + 1] = v * z;
-    xyz[3 * i + 2] = z;
-    float in = 0.f;
-    if (img) {
-        const float px = fx * u + cx, py = fy * v + cy;
-        // cvRound; compared as floats first so that NaN / huge values never reach the conversion
-        if (px >= -0.5f && px < (float)w && py >= -0.5f && py < (float)h) {
-            const int ix = __float2int_rn(px), iy = __float2int_rn(py);
-            if (ix >= 0 && ix < w && iy >= 0 && iy < h) in = (float)img[(size_t)iy * pitch + ix];
-        }
-    }
-    intensity[i] = in;
-}
-// host_word != nullptr (single-workgroup launches only): the kernel publishes the status word itself behind its writes
-__global__ void points_kernel(const float* __restrict__ mu, int N, const uint8_t* __restrict__ img, int pitch, int w, int h,
-                              float fx, float fy, float cx, float cy, float* __restrict__ xyz, float* __restrict__ intensity,
-                              const int* __restrict__ info, int* host_word, int seq) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < N) points_one(mu, i, img, pitch, w, h, fx, fy, cx, cy, xyz, intensity);
-    if (host_word) {
-        __threadfence_system();
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            host_word[0] = info[0];
-            host_word[2] = 0;
-            __hip_atomic_store(host_word + 1, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-        }
-    }
-}
-
-// The last kernel of a frame (ekfvio_step_image): what the node publishes after addFrame -- publishOdometry's slices of
-// base_mu and publishPoints' cloud (EKFVIO.cpp:444-518) -- written into pinned host memory TOGETHER with the status word
-// the host is waiting for anyway.  ekfvio_get_odometry / ekfvio_get_points then cost a memcpy instead of a launch and a
-// wait each (the node's loop with outputs: 164 -> 140 us per frame at the node's defaults).  One workgroup; the number of
-// landmarks is N_old plus what the replenishment just added (added_dev, may be null).
-// Layout of out: base_mu[22], xyz[3 N], intensity[N].
-// Pcol != null (round 4): launched BETWEEN the update's two Joseph GEMMs.  The mean update mu += K y, quaternion renormalised, is the
-// second GEMM's (gemm.hip, mode 2, :600-609) from K y in column n of P, which the first one has just left there: the same sums are
-// formed here (into LDS, mu itself is not touched), so the frame's outputs and status reach the host while the second GEMM still runs
-// -- the host's next frame (copying the image, ~15 us) starts that much earlier.  Same values, same bits as behind the update.
-__global__ __launch_bounds__(256) void frame_outputs_kernel(const float* __restrict__ mu, int N_old, const int* __restrict__ added_dev,
-                                                            const uint8_t* __restrict__ img, int pitch, int w, int h, float fx, float fy,
-                                                            float cx, float cy, float* __restrict__ out, const int* __restrict__ info,
-                                                            int* host_word, int seq, const float* __restrict__ Pcol,
-                                                            const float* __restrict__ Kyp = nullptr, int kyp_blocks = 0, int kyp_ld = 0) {
-    extern __shared__ float s_mu[];  // Pcol / Kyp: the updated mean, EKF_BASE + 3 N floats
-    const int added = added_dev ? *added_dev : 0;
-    const int N = N_old + added;
-    if (Pcol || Kyp) {
-        const int n = EKF_BASE + 3 * N;
-        if (Kyp) {
-            // (round 6, T2 flow: K y as the gain tiles' partial sums, one row per block column, added as gemm16_finish_mean<3> adds them -- and requested as
-            // it requests them: up to four elements per thread and sixteen block columns each as ONE batch from clamped addresses.  The loop with a
-            // run-time bound it replaces was compiled load - wait - add: a memory round trip per block column and element, ~30 in a row at N = 256;
-            // image loop at N = 256, same box: 5 622 -> 5 798 frames/s.)
-            float v4[4];
-#pragma unroll
-            for (int u = 0; u < 4; u++) {
-                const int e = min((int)threadIdx.x + 256 * u, n - 1);
-                float pk[16];
-#pragma unroll
-                for (int cb = 0; cb < 16; cb++) pk[cb] = Kyp[(size_t)min(cb, kyp_blocks - 1) * kyp_ld + e];
-                const float m0 = mu[e];
-                float ky = pk[0];
-#pragma unroll
-                for (int cb = 1; cb < 16; cb++) ky = (cb < kyp_blocks) ? ky + pk[cb] : ky;
-                for (int cb = 16; cb < kyp_blocks; cb++) ky = ky + Kyp[(size_t)cb * kyp_ld + e];
-                v4[u] = m0 + ky;
-            }
-#pragma unroll
-            for (int u = 0; u < 4; u++) {
-                const int e = (int)threadIdx.x + 256 * u;
-                if (e < n) s_mu[e] = v4[u];
-            }
-            for (int e = threadIdx.x + 1024; e < n; e += 256) {
-                float ky = Kyp[e];
-                for (int cb = 1; cb < kyp_blocks; cb++) ky = ky + Kyp[(size_t)cb * kyp_ld + e];
-                s_mu[e] = mu[e] + ky;
-            }
-        } else {
-            for (int e = threadIdx.x; e < n; e += 256) s_mu[e] = mu[e] + Pcol[e];
-        }
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            const float q0 = s_mu[3], q1 = s_mu[4], q2 = s_mu[5], q3 = s_mu[6];
-            const float qn = sqrtf(q0 * q0 + q1 * q1 + q2 * q2 + q3 * q3);
-            s_mu[3] = q0 / qn, s_mu[4] = q1 / qn, s_mu[5] = q2 / qn, s_mu[6] = q3 / qn;
-        }
-        __syncthreads();
-        mu = s_mu;
-    }
-    if (threadIdx.x < EKF_BASE) out[threadIdx.x] = mu[threadIdx.x];
-    float* xyz = out + EKF_BASE;
-    float* inten = xyz + 3 * (size_t)N;
-    for (int i = threadIdx.x; i < N; i += 256) points_one(mu, i, img, pitch, w, h, fx, fy, cx, cy, xyz, inten);
-    __threadfence_system();
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        host_word[0] = info[0];
-        host_word[2] = added;
-        __hip_atomic_store(host_word + 1, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-    }
-}
-
 // ---- KLTTracker::estimateUncertaintySampleBased (KLTTracker.cpp:111-175) -------------------
 // cv::getRectSubPix(8-bit, Size(5,5), center, CV_32F) (OpenCV 3.x samplers.cpp, getRectSubPix_8u32f): one patch row.
 // Inside the image the horizontal interpolation is carried from pixel to pixel through a double factor
@@ -1035,7 +912,6 @@ PyrView make_view(const KltFrame& fr) {
 
 int klt_level_pitch(int w) { return level_pitch(w); }
 int klt_border() { return KLT_BORDER; }
-void klt_intrinsics(const ekfvio_filter* f, const float* K, float* fx, float* fy, float* cx, float* cy);
 
 // Planes of one frame for a level 0 of up to w x h pixels (every level the configuration allows).
 static int frame_planes_alloc(ekfvio_filter* f, KltFrame& fr, int w, int h) {
@@ -1051,10 +927,10 @@ static int frame_planes_alloc(ekfvio_filter* f, KltFrame& fr, int w, int h) {
     for (int l = 0; l <= f->cfg.klt_max_pyramid_level; l++) {
         // + one row of slack: the tracker's aligned 4-byte loads may touch up to 3 bytes past a row's last pixel
         const size_t px = (size_t)level_pitch(lw) * (lh + 2 * KLT_BORDER + 1);
-        HIPK(f, hipMalloc((void**)&fr.img[l], px));
-        HIPK(f, hipMalloc((void**)&fr.deriv[l], px * 2 * sizeof(short)));
-        HIPK(f, hipMemsetAsync(fr.img[l], 0, px, f->stream));
-        HIPK(f, hipMemsetAsync(fr.deriv[l], 0, px * 2 * sizeof(short), f->stream));
+        HIP_TRY(f, hipMalloc((void**)&fr.img[l], px));
+        HIP_TRY(f, hipMalloc((void**)&fr.deriv[l], px * 2 * sizeof(short)));
+        HIP_TRY(f, hipMemsetAsync(fr.img[l], 0, px, f->stream));
+        HIP_TRY(f, hipMemsetAsync(fr.deriv[l], 0, px * 2 * sizeof(short), f->stream));
         lw = (lw + 1) / 2;
         lh = (lh + 1) / 2;
     }
@@ -1072,14 +948,14 @@ static int ensure_frame_capacity(ekfvio_filter* f, int sw, int sh, int w, int h)
     KltFrame& fr = f->frames[f->cur ^ 1];
     const bool rect = f->rect_on && src > f->rect_cap;  // rectification on (ekfvio_set_distortion) and its buffers not there yet, or too small
     if (src <= f->src_cap && w <= fr.cap_w && h <= fr.cap_h && w <= f->fast_cap_w && h <= f->fast_cap_h && !rect) return EKFVIO_OK;
-    HIPK(f, hipSetDevice(f->device));
-    HIPK(f, hipStreamSynchronize(f->stream));
+    HIP_TRY(f, hipSetDevice(f->device));
+    HIP_TRY(f, hipStreamSynchronize(f->stream));
     if (src > f->src_cap) {
         if (f->staging) (void)hipFree(f->staging);
         if (f->h_image) (void)hipHostFree(f->h_image);
         f->staging = nullptr, f->h_image = nullptr, f->src_cap = 0;
-        HIPK(f, hipMalloc((void**)&f->staging, src + 16));  // (+16: the upload kernel moves whole 16-byte pieces)
-        HIPK(f, hipHostMalloc((void**)&f->h_image, src + 16, hipHostMallocMapped));
+        HIP_TRY(f, hipMalloc((void**)&f->staging, src + 16));  // (+16: the upload kernel moves whole 16-byte pieces)
+        HIP_TRY(f, hipHostMalloc((void**)&f->h_image, src + 16, hipHostMallocMapped));
         f->src_cap = src;
     }
     if (w > fr.cap_w || h > fr.cap_h) {
@@ -1105,13 +981,13 @@ int klt_alloc(ekfvio_filter* f) {
         if (rc != EKFVIO_OK) return rc;
     }
     const size_t maxf = f->cfg.max_features > 0 ? f->cfg.max_features : 1;
-    HIPK(f, hipMalloc((void**)&f->klt_prev_px, sizeof(float) * 2 * maxf));
-    HIPK(f, hipMalloc((void**)&f->klt_next_px, sizeof(float) * 2 * maxf));
-    HIPK(f, hipMalloc((void**)&f->klt_status, maxf));
-    HIPK(f, hipMalloc((void**)&f->klt_cov_px, sizeof(float) * 4 * maxf));
+    HIP_TRY(f, hipMalloc((void**)&f->klt_prev_px, sizeof(float) * 2 * maxf));
+    HIP_TRY(f, hipMalloc((void**)&f->klt_next_px, sizeof(float) * 2 * maxf));
+    HIP_TRY(f, hipMalloc((void**)&f->klt_status, maxf));
+    HIP_TRY(f, hipMalloc((void**)&f->klt_cov_px, sizeof(float) * 4 * maxf));
     f->src_cap = (size_t)c.max_image_width * c.max_image_height;
-    HIPK(f, hipMalloc((void**)&f->staging, f->src_cap + 16));
-    HIPK(f, hipHostMalloc((void**)&f->h_image, f->src_cap + 16, hipHostMallocMapped));
+    HIP_TRY(f, hipMalloc((void**)&f->staging, f->src_cap + 16));
+    HIP_TRY(f, hipHostMalloc((void**)&f->h_image, f->src_cap + 16, hipHostMallocMapped));
     return EKFVIO_OK;
 }
 
@@ -1166,11 +1042,7 @@ static int build_pyramid(ekfvio_filter* f, KltFrame& fr, const uint8_t* src, int
     return EKFVIO_OK;
 }
 
-static void intrinsics(const ekfvio_filter* f, const float* K, float* fx, float* fy, float* cx, float* cy);
 void klt_intrinsics(const ekfvio_filter* f, const float* K, float* fx, float* fy, float* cx, float* cy) {
-    intrinsics(f, K, fx, fy, cx, cy);
-}
-static void intrinsics(const ekfvio_filter* f, const float* K, float* fx, float* fy, float* cx, float* cy) {
     // CameraInfo.K is row-major [fx 0 cx; 0 fy cy; 0 0 1].  Feature.h:60-66 reads K(0), K(4)
     // and, for the offsets, K(2) and K(5) of a column-major Matrix3f = the zero entries K[2,0]
     // and K[2,1]: the principal point is ignored by the reference (self-consistently).
@@ -1180,18 +1052,30 @@ static void intrinsics(const ekfvio_filter* f, const float* K, float* fx, float*
     *cy = f->cfg.use_principal_point ? K[5] : 0.f;
 }
 
+Level0View klt_level0(const ekfvio_filter* f) {
+    Level0View v;
+    const KltFrame& fr = f->frames[f->cur];
+    if (!fr.valid) return v;
+    v.pitch = level_pitch(fr.w[0]);
+    v.img = fr.img[0] + (size_t)KLT_BORDER * v.pitch + KLT_BORDER;
+    v.w = fr.w[0];
+    v.h = fr.h[0];
+    klt_intrinsics(f, fr.K, &v.fx, &v.fy, &v.cx, &v.cy);
+    return v;
+}
+
 // The forward-backward check's device memory, ONE allocation made when a handle first needs it (a handle that never does allocates
 // nothing it did not before): [8] words; e2 per landmark; e2 and the backward result per point of ekfvio_klt_track_points_fb (which
 // leaves the landmarks' results of the last frame alone); then the verdict bytes of both.
 static int klt_fb_ensure(ekfvio_filter* f) {
     if (f->fb_words) return EKFVIO_OK;
-    HIPK(f, hipSetDevice(f->device));
+    HIP_TRY(f, hipSetDevice(f->device));
     const size_t maxf = (size_t)(f->cfg.max_features > 0 ? f->cfg.max_features : 1);
     const size_t bytes = 8 * sizeof(int) + maxf * (4 * sizeof(float) + 2);
     unsigned char* buf = nullptr;
-    HIPK(f, hipMalloc((void**)&buf, bytes));
+    HIP_TRY(f, hipMalloc((void**)&buf, bytes));
     f->fb_words = reinterpret_cast<int*>(buf);  // (from here on ekfvio_destroy releases it)
-    HIPK(f, hipMemsetAsync(buf, 0, bytes, f->stream));
+    HIP_TRY(f, hipMemsetAsync(buf, 0, bytes, f->stream));
     f->fb_err2 = reinterpret_cast<float*>(buf + 8 * sizeof(int));
     f->fb_pt_err2 = f->fb_err2 + maxf;
     f->fb_pt_back = f->fb_err2 + 2 * maxf;
@@ -1233,8 +1117,8 @@ int klt_track_device(ekfvio_filter* f) {
     const int N = f->N;
     if (N == 0) return EKFVIO_OK;
     float fxp, fyp, cxp, cyp, fxc, fyc, cxc, cyc;
-    intrinsics(f, prev.K, &fxp, &fyp, &cxp, &cyp);
-    intrinsics(f, cur.K, &fxc, &fyc, &cxc, &cyc);
+    klt_intrinsics(f, prev.K, &fxp, &fyp, &cxp, &cyp);
+    klt_intrinsics(f, cur.K, &fxc, &fyc, &cxc, &cyc);
     // estimateUncertainty (:100-106) = 1e-5 I; scale = pow(1.0/K(0,0), 2) in double, narrowed
     const float r0 = 0.00001f * (float)pow(1.0 / (double)cur.K[0], 2);
     const float r1 = 0.00001f * (float)pow(1.0 / (double)cur.K[4], 2);
@@ -1281,7 +1165,7 @@ __global__ __launch_bounds__(256) void upload_frame_kernel(const uint4* __restri
     if (i < n16) dst[i] = src[i];
 }
 
-static int push_frame_check(ekfvio_filter* f, const uint8_t* image, int32_t width, int32_t height, int32_t stride,
+int push_frame_check(ekfvio_filter* f, const uint8_t* image, int32_t width, int32_t height, int32_t stride,
                             const float K[9]) {
     if (!f || !image || !K || width < 1 || height < 1 || stride < width) return EKFVIO_EINVAL;
     if (width > 16384 || height > 16384) return EKFVIO_ECAPACITY;  // keypoints carry x in 16 bits (fast.hip)
@@ -1289,14 +1173,14 @@ static int push_frame_check(ekfvio_filter* f, const uint8_t* image, int32_t widt
     if (width / s < 1 || height / s < 1) return EKFVIO_EINVAL;
     return ensure_frame_capacity(f, width, height, width / s, height / s);
 }
-static int push_frame_enqueue(ekfvio_filter* f, const uint8_t* image, int32_t width, int32_t height, int32_t stride,
+int push_frame_enqueue(ekfvio_filter* f, const uint8_t* image, int32_t width, int32_t height, int32_t stride,
                               const float K[9]) {
     const int rcc = push_frame_check(f, image, width, height, stride, K);
     if (rcc != EKFVIO_OK) return rcc;
     // Frame::Frame (Frame.cpp:15-42): cv::resize to (cols / s, rows / s), K(0,0), K(0,2), K(1,1), K(1,2) divided by s
     const int s = f->cfg.inverse_image_scale > 1 ? f->cfg.inverse_image_scale : 1;
     const int w = width / s, h = height / s;
-    HIPK(f, hipSetDevice(f->device));
+    HIP_TRY(f, hipSetDevice(f->device));
     if (stride == width) {
         memcpy(f->h_image, image, (size_t)width * height);
     } else {
@@ -1307,11 +1191,11 @@ static int push_frame_enqueue(ekfvio_filter* f, const uint8_t* image, int32_t wi
     if (upload_kernel) {
         const int n16 = (int)(((size_t)width * height + 15) / 16);
         void* dsrc = nullptr;  // the device's address of the mapped buffer (the same pointer under unified addressing; asked for, not assumed)
-        HIPK(f, hipHostGetDevicePointer(&dsrc, f->h_image, 0));
+        HIP_TRY(f, hipHostGetDevicePointer(&dsrc, f->h_image, 0));
         hipLaunchKernelGGL(upload_frame_kernel, dim3((n16 + 255) / 256), dim3(256), 0, st, reinterpret_cast<const uint4*>(dsrc),
                            reinterpret_cast<uint4*>(f->staging), n16);
     } else {
-        HIPK(f, hipMemcpyAsync(f->staging, f->h_image, (size_t)width * height, hipMemcpyHostToDevice, st));
+        HIP_TRY(f, hipMemcpyAsync(f->staging, f->h_image, (size_t)width * height, hipMemcpyHostToDevice, st));
     }
     f->cur ^= 1;  // the former current frame becomes the previous one (frame_buffer depth 2)
     KltFrame& fr = f->frames[f->cur];
@@ -1326,7 +1210,7 @@ static int push_frame_enqueue(ekfvio_filter* f, const uint8_t* image, int32_t wi
     const uint8_t* full = f->rect_on ? rectify_enqueue(f, f->staging, width, height, K, st) : f->staging;
     build_pyramid(f, fr, full, width, height, w, h, st);
     fr.valid = true;
-    HIPK(f, hipGetLastError());
+    HIP_TRY(f, hipGetLastError());
     return EKFVIO_OK;
 }
 
@@ -1337,67 +1221,23 @@ int ekfvio_klt_push_frame(ekfvio_filter* f, const uint8_t* image, int32_t width,
     if (f) f->out_fresh = false;
     const int rc = push_frame_enqueue(f, image, width, height, stride, K);
     if (rc != EKFVIO_OK) return rc;
-    HIPK(f, hipStreamSynchronize(f->stream));
-    return EKFVIO_OK;
-}
-
-// publishPoints' payload (EKFVIO.cpp:479-518), formed on the device: xyz3N = (u/rho, v/rho, 1/rho) per landmark in the
-// camera frame, intensityN = the current (resized) frame's byte at the landmark's pixel (0 outside the image or before
-// the first frame).  Either pointer may be NULL.
-int ekfvio_get_points(ekfvio_filter* f, float* xyz3N, float* intensityN) {
-    if (!f) return EKFVIO_EINVAL;
-    const int N = f->N;
-    if (N == 0) return EKFVIO_OK;
-    if (f->out_fresh) {  // the frame's last kernel wrote them with the status word (frame_outputs_kernel)
-        if (xyz3N) memcpy(xyz3N, f->h_out + EKF_BASE, sizeof(float) * 3 * N);
-        if (intensityN) memcpy(intensityN, f->h_out + EKF_BASE + 3 * (size_t)N, sizeof(float) * N);
-        return EKFVIO_OK;
-    }
-    HIPK(f, hipSetDevice(f->device));
-    const KltFrame& fr = f->frames[f->cur];
-    const uint8_t* img = nullptr;
-    int pitch = 0, w = 0, h = 0;
-    float fx = 0.f, fy = 0.f, cx = 0.f, cy = 0.f;
-    if (fr.valid) {
-        pitch = level_pitch(fr.w[0]);
-        img = fr.img[0] + (size_t)KLT_BORDER * pitch + KLT_BORDER;
-        w = fr.w[0];
-        h = fr.h[0];
-        intrinsics(f, fr.K, &fx, &fy, &cx, &cy);
-    }
-    // the kernel writes into pinned host memory (behind the 22 floats ekfvio_get_base_mu uses): xyz, then the intensities
-    float* d_xyz = f->d_out + EKF_BASE;
-    float* d_int = d_xyz + 3 * (size_t)N;
-    int bad = 0, rc;
-    if (N <= 256) {  // one workgroup: it publishes the status word itself
-        const int seq = next_status_seq(f);
-        hipLaunchKernelGGL(points_kernel, dim3(1), dim3(256), 0, f->stream, f->mu, N, img, pitch, w, h, fx, fy, cx, cy, d_xyz, d_int,
-                           f->info, f->d_hinfo, seq);
-        rc = poll_status(f, seq, &bad, nullptr);
-    } else {
-        hipLaunchKernelGGL(points_kernel, dim3((N + 255) / 256), dim3(256), 0, f->stream, f->mu, N, img, pitch, w, h, fx, fy, cx, cy,
-                           d_xyz, d_int, nullptr, nullptr, 0);
-        rc = wait_status(f, &bad);
-    }
-    if (rc != EKFVIO_OK) return rc;
-    if (xyz3N) memcpy(xyz3N, f->h_out + EKF_BASE, sizeof(float) * 3 * N);
-    if (intensityN) memcpy(intensityN, f->h_out + EKF_BASE + 3 * (size_t)N, sizeof(float) * N);
+    HIP_TRY(f, hipStreamSynchronize(f->stream));
     return EKFVIO_OK;
 }
 
 int ekfvio_klt_track(ekfvio_filter* f, float* z2N, float* R4N, uint8_t* passN) {
     if (!f) return EKFVIO_EINVAL;
-    HIPK(f, hipSetDevice(f->device));
+    HIP_TRY(f, hipSetDevice(f->device));
     int rc = klt_track_device(f);
     if (rc != EKFVIO_OK) return rc;
     const int N = f->N;
     if (N > 0) {
-        if (z2N) HIPK(f, hipMemcpyAsync(z2N, f->zmeas, sizeof(float) * 2 * N, hipMemcpyDeviceToHost, f->stream));
-        if (R4N) HIPK(f, hipMemcpyAsync(R4N, f->Rmeas, sizeof(float) * 4 * N, hipMemcpyDeviceToHost, f->stream));
-        if (passN) HIPK(f, hipMemcpyAsync(passN, f->pass, N, hipMemcpyDeviceToHost, f->stream));
+        if (z2N) HIP_TRY(f, hipMemcpyAsync(z2N, f->zmeas, sizeof(float) * 2 * N, hipMemcpyDeviceToHost, f->stream));
+        if (R4N) HIP_TRY(f, hipMemcpyAsync(R4N, f->Rmeas, sizeof(float) * 4 * N, hipMemcpyDeviceToHost, f->stream));
+        if (passN) HIP_TRY(f, hipMemcpyAsync(passN, f->pass, N, hipMemcpyDeviceToHost, f->stream));
     }
-    HIPK(f, hipGetLastError());
-    HIPK(f, hipStreamSynchronize(f->stream));
+    HIP_TRY(f, hipGetLastError());
+    HIP_TRY(f, hipStreamSynchronize(f->stream));
     return EKFVIO_OK;
 }
 
@@ -1410,14 +1250,14 @@ int ekfvio_klt_track_points(ekfvio_filter* f, const float* prev_px, const float*
         return EKFVIO_ESTATE;
     }
     if (count == 0) return EKFVIO_OK;
-    HIPK(f, hipSetDevice(f->device));
-    HIPK(f, hipMemcpyAsync(f->klt_prev_px, prev_px, sizeof(float) * 2 * count, hipMemcpyHostToDevice, f->stream));
-    HIPK(f, hipMemcpyAsync(f->klt_next_px, init_px, sizeof(float) * 2 * count, hipMemcpyHostToDevice, f->stream));
+    HIP_TRY(f, hipSetDevice(f->device));
+    HIP_TRY(f, hipMemcpyAsync(f->klt_prev_px, prev_px, sizeof(float) * 2 * count, hipMemcpyHostToDevice, f->stream));
+    HIP_TRY(f, hipMemcpyAsync(f->klt_next_px, init_px, sizeof(float) * 2 * count, hipMemcpyHostToDevice, f->stream));
     track_points_device(f, count);
-    if (out_px) HIPK(f, hipMemcpyAsync(out_px, f->klt_next_px, sizeof(float) * 2 * count, hipMemcpyDeviceToHost, f->stream));
-    if (status) HIPK(f, hipMemcpyAsync(status, f->klt_status, count, hipMemcpyDeviceToHost, f->stream));
-    HIPK(f, hipGetLastError());
-    HIPK(f, hipStreamSynchronize(f->stream));
+    if (out_px) HIP_TRY(f, hipMemcpyAsync(out_px, f->klt_next_px, sizeof(float) * 2 * count, hipMemcpyDeviceToHost, f->stream));
+    if (status) HIP_TRY(f, hipMemcpyAsync(status, f->klt_status, count, hipMemcpyDeviceToHost, f->stream));
+    HIP_TRY(f, hipGetLastError());
+    HIP_TRY(f, hipStreamSynchronize(f->stream));
     return EKFVIO_OK;
 }
 
@@ -1430,11 +1270,11 @@ int ekfvio_klt_track_points_fb(ekfvio_filter* f, const float* prev_px, const flo
         return EKFVIO_ESTATE;
     }
     if (count == 0) return EKFVIO_OK;
-    HIPK(f, hipSetDevice(f->device));
+    HIP_TRY(f, hipSetDevice(f->device));
     const int rc = klt_fb_ensure(f);
     if (rc != EKFVIO_OK) return rc;
-    HIPK(f, hipMemcpyAsync(f->klt_prev_px, prev_px, sizeof(float) * 2 * count, hipMemcpyHostToDevice, f->stream));
-    HIPK(f, hipMemcpyAsync(f->klt_next_px, init_px, sizeof(float) * 2 * count, hipMemcpyHostToDevice, f->stream));
+    HIP_TRY(f, hipMemcpyAsync(f->klt_prev_px, prev_px, sizeof(float) * 2 * count, hipMemcpyHostToDevice, f->stream));
+    HIP_TRY(f, hipMemcpyAsync(f->klt_next_px, init_px, sizeof(float) * 2 * count, hipMemcpyHostToDevice, f->stream));
     TrackFuse tf;
     tf.fb = 2;  // the backward pass runs whatever the threshold; the landmarks' per-frame results (ekfvio_get_klt_fb) are not touched
     tf.fb_t2 = f->cfg.klt_fb_max_px * f->cfg.klt_fb_max_px;
@@ -1443,13 +1283,13 @@ int ekfvio_klt_track_points_fb(ekfvio_filter* f, const float* prev_px, const flo
     uint8_t* d_ok = f->fb_pt_flag;
     tf.fb_err2 = d_err2, tf.fb_back = d_back, tf.fb_flag = d_ok;
     track_points_device(f, count, tf);
-    if (out_px) HIPK(f, hipMemcpyAsync(out_px, f->klt_next_px, sizeof(float) * 2 * count, hipMemcpyDeviceToHost, f->stream));
-    if (status) HIPK(f, hipMemcpyAsync(status, f->klt_status, count, hipMemcpyDeviceToHost, f->stream));
-    if (back_px) HIPK(f, hipMemcpyAsync(back_px, d_back, sizeof(float) * 2 * count, hipMemcpyDeviceToHost, f->stream));
-    if (err2) HIPK(f, hipMemcpyAsync(err2, d_err2, sizeof(float) * count, hipMemcpyDeviceToHost, f->stream));
-    if (fb_ok) HIPK(f, hipMemcpyAsync(fb_ok, d_ok, count, hipMemcpyDeviceToHost, f->stream));
-    HIPK(f, hipGetLastError());
-    HIPK(f, hipStreamSynchronize(f->stream));
+    if (out_px) HIP_TRY(f, hipMemcpyAsync(out_px, f->klt_next_px, sizeof(float) * 2 * count, hipMemcpyDeviceToHost, f->stream));
+    if (status) HIP_TRY(f, hipMemcpyAsync(status, f->klt_status, count, hipMemcpyDeviceToHost, f->stream));
+    if (back_px) HIP_TRY(f, hipMemcpyAsync(back_px, d_back, sizeof(float) * 2 * count, hipMemcpyDeviceToHost, f->stream));
+    if (err2) HIP_TRY(f, hipMemcpyAsync(err2, d_err2, sizeof(float) * count, hipMemcpyDeviceToHost, f->stream));
+    if (fb_ok) HIP_TRY(f, hipMemcpyAsync(fb_ok, d_ok, count, hipMemcpyDeviceToHost, f->stream));
+    HIP_TRY(f, hipGetLastError());
+    HIP_TRY(f, hipStreamSynchronize(f->stream));
     return EKFVIO_OK;
 }
 
@@ -1461,13 +1301,13 @@ int ekfvio_klt_uncertainty_points(ekfvio_filter* f, const float* ref_px, const f
         return EKFVIO_ESTATE;
     }
     if (count == 0) return EKFVIO_OK;
-    HIPK(f, hipSetDevice(f->device));
-    HIPK(f, hipMemcpyAsync(f->klt_prev_px, ref_px, sizeof(float) * 2 * count, hipMemcpyHostToDevice, f->stream));
-    HIPK(f, hipMemcpyAsync(f->klt_next_px, cur_px, sizeof(float) * 2 * count, hipMemcpyHostToDevice, f->stream));
+    HIP_TRY(f, hipSetDevice(f->device));
+    HIP_TRY(f, hipMemcpyAsync(f->klt_prev_px, ref_px, sizeof(float) * 2 * count, hipMemcpyHostToDevice, f->stream));
+    HIP_TRY(f, hipMemcpyAsync(f->klt_next_px, cur_px, sizeof(float) * 2 * count, hipMemcpyHostToDevice, f->stream));
     uncertainty_device(f, count);
-    HIPK(f, hipMemcpyAsync(cov4, f->klt_cov_px, sizeof(float) * 4 * count, hipMemcpyDeviceToHost, f->stream));
-    HIPK(f, hipGetLastError());
-    HIPK(f, hipStreamSynchronize(f->stream));
+    HIP_TRY(f, hipMemcpyAsync(cov4, f->klt_cov_px, sizeof(float) * 4 * count, hipMemcpyDeviceToHost, f->stream));
+    HIP_TRY(f, hipGetLastError());
+    HIP_TRY(f, hipStreamSynchronize(f->stream));
     return EKFVIO_OK;
 }
 
@@ -1476,17 +1316,17 @@ int ekfvio_klt_get_level(ekfvio_filter* f, int32_t level, int32_t* w, int32_t* h
     if (!f || level < 0) return EKFVIO_EINVAL;
     const KltFrame& fr = f->frames[f->cur];
     if (!fr.valid || level >= fr.levels) return EKFVIO_ESTATE;
-    HIPK(f, hipSetDevice(f->device));
+    HIP_TRY(f, hipSetDevice(f->device));
     const int lw = fr.w[level], lh = fr.h[level], pitch = level_pitch(lw);
     if (w) *w = lw;
     if (h) *h = lh;
     if (img)
-        HIPK(f, hipMemcpy2DAsync(img, lw, fr.img[level] + (size_t)KLT_BORDER * pitch + KLT_BORDER, pitch, lw, lh,
+        HIP_TRY(f, hipMemcpy2DAsync(img, lw, fr.img[level] + (size_t)KLT_BORDER * pitch + KLT_BORDER, pitch, lw, lh,
                                  hipMemcpyDeviceToHost, f->stream));
     if (deriv)
-        HIPK(f, hipMemcpy2DAsync(deriv, (size_t)lw * 4, fr.deriv[level] + ((size_t)KLT_BORDER * pitch + KLT_BORDER) * 2,
+        HIP_TRY(f, hipMemcpy2DAsync(deriv, (size_t)lw * 4, fr.deriv[level] + ((size_t)KLT_BORDER * pitch + KLT_BORDER) * 2,
                                  (size_t)pitch * 4, (size_t)lw * 4, lh, hipMemcpyDeviceToHost, f->stream));
-    HIPK(f, hipStreamSynchronize(f->stream));
+    HIP_TRY(f, hipStreamSynchronize(f->stream));
     return EKFVIO_OK;
 }
 
@@ -1495,171 +1335,16 @@ int ekfvio_test_klt_padded_level(ekfvio_filter* f, int32_t level, int32_t* borde
     if (!f || level < 0) return EKFVIO_EINVAL;
     const KltFrame& fr = f->frames[f->cur];
     if (!fr.valid || level >= fr.levels) return EKFVIO_ESTATE;
-    HIPK(f, hipSetDevice(f->device));
+    HIP_TRY(f, hipSetDevice(f->device));
     const int pw = fr.w[level] + 2 * KLT_BORDER, ph = fr.h[level] + 2 * KLT_BORDER, pitch = level_pitch(fr.w[level]);
     if (border) *border = KLT_BORDER;
-    if (img) HIPK(f, hipMemcpy2DAsync(img, pw, fr.img[level], pitch, pw, ph, hipMemcpyDeviceToHost, f->stream));
+    if (img) HIP_TRY(f, hipMemcpy2DAsync(img, pw, fr.img[level], pitch, pw, ph, hipMemcpyDeviceToHost, f->stream));
     if (deriv)
-        HIPK(f, hipMemcpy2DAsync(deriv, (size_t)pw * 4, fr.deriv[level], (size_t)pitch * 4, (size_t)pw * 4, ph, hipMemcpyDeviceToHost,
+        HIP_TRY(f, hipMemcpy2DAsync(deriv, (size_t)pw * 4, fr.deriv[level], (size_t)pitch * 4, (size_t)pw * 4, ph, hipMemcpyDeviceToHost,
                                  f->stream));
-    HIPK(f, hipStreamSynchronize(f->stream));
+    HIP_TRY(f, hipStreamSynchronize(f->stream));
     return EKFVIO_OK;
 }
 #endif
-
-// EKFVIO::addFrame + updateStateWithNewImage (EKFVIO.cpp:139-219) minus ROS publishing; with
-// cfg.replenish the FAST replenishment of :154 / :172 runs on the device too (otherwise the caller
-// adds landmarks with ekfvio_add_features).
-int ekfvio_step_image(ekfvio_filter* f, double stamp, const uint8_t* image, int32_t width, int32_t height, int32_t stride,
-                      const float K[9]) {
-    if (!f) return EKFVIO_EINVAL;
-    f->out_fresh = false;
-    const bool first = !f->frames[f->cur].valid;
-    if (!first && f->have_stamp && !(stamp - f->t_stamp >= 0)) return EKFVIO_EINVAL;  // ROS_ASSERT(dt >= 0)
-    // nothing below waits for the device until the status word is read at the very end: process(dt), the frame
-    // upload, the pyramid, the tracker and the update are enqueued back to back.  process(dt) goes first: it does not
-    // depend on the image, so the device runs it while the host copies the frame into the pinned buffer.
-    // everything that can refuse the frame (sizes, capacity growth) comes before the first launch
-    int rc = push_frame_check(f, image, width, height, stride, K);
-    if (rc != EKFVIO_OK) return rc;
-    sweep_maybe_retry(f);
-    const float dt = first ? 0.f : (float)(stamp - f->t_stamp);
-    // an error return from here on has work enqueued behind it: wait for it (the pinned frame buffer is rewritten by the
-    // next call) and leave the stamp with the state it belongs to
-    auto fail = [&](int code) {
-        (void)hipStreamSynchronize(f->stream);
-        return code;
-    };
-    if (!first) {
-        HIPK(f, hipSetDevice(f->device));
-        launch_predict(f, dt);
-        f->t_stamp = stamp;  // tc_ekf.t = f.t (:164): the state now stands at this stamp whatever happens below
-        f->have_stamp = true;
-    }
-    rc = push_frame_enqueue(f, image, width, height, stride, K);
-    if (rc != EKFVIO_OK) return fail(rc);
-    if (first) {
-        // first frame: remember the stamp (tc_ekf.t = f.t) and return; the caller replenishes
-        if (!f->have_stamp) {
-            f->t_stamp = stamp;
-            f->have_stamp = true;
-        }
-        if (f->cfg.replenish) return ekfvio_replenish(f, nullptr, nullptr);  // replenishFeatures(first frame) (:154)
-        HIPK(f, hipStreamSynchronize(f->stream));
-        return EKFVIO_OK;
-    }
-    int status = EKFVIO_OK;
-    int early_seq = 0;
-    UpdateInputs in;  // the frame's update (and its re-run behind an aborted persistent sweep)
-    in.z = f->zmeas, in.R = f->Rmeas, in.pass = f->pass, in.m_on_device = true;
-    if (f->N > 0) {  // "run update if we have enough features" (EKFVIO.cpp:166)
-        rc = klt_track_device(f);
-        if (rc != EKFVIO_OK) return fail(rc);
-        // the pass flags stay on the device: the update is launched for m = 2N measurement rows and its kernels take
-        // the true count from the bookkeeping (rows beyond it are identity padding, exact zeros in every product)
-        // A frame that adds no landmarks publishes its outputs and its status BETWEEN the update's two Joseph GEMMs (frame_outputs_kernel,
-        // Pcol): launch_update calls back there.  (With landmarks to add the selection reads the updated mean and the outputs carry the count:
-        // behind the update, as before.  EKFVIO_EARLY_OUTPUTS=0: always behind.)
-        // (Nor with cfg.remove_lost: the frame's final landmark count is known only behind the removal, as with a replenishing frame.)
-        if (f->tune.early_outputs && f->tune.frame_outputs && !(f->cfg.replenish && f->N < f->cfg.max_features) && !f->cfg.remove_lost &&
-            sizeof(float) * (size_t)f->n <= 48 * 1024) {  // (the updated mean is formed in LDS)
-            in.between = [](ekfvio_filter* g, int kyp_blocks) {
-                const KltFrame& fr = g->frames[g->cur];
-                const int pitch = level_pitch(fr.w[0]);
-                float fx, fy, cx, cy;
-                intrinsics(g, fr.K, &fx, &fy, &cx, &cy);
-                const int seq = next_status_seq(g);
-                // (two-GEMM flow: K y is column n of P, left there by the first Joseph GEMM; T2 flow: the gain tiles' partial sums in Wt, and the
-                // outputs go out in front of the update's ONE GEMM)
-                const bool kyp = kyp_blocks > 0;
-                hipLaunchKernelGGL(frame_outputs_kernel, dim3(1), dim3(256), sizeof(float) * (size_t)g->n, g->stream, g->mu, g->N, (const int*)nullptr,
-                                   fr.img[0] + (size_t)KLT_BORDER * pitch + KLT_BORDER, pitch, fr.w[0], fr.h[0], fx, fy, cx, cy, g->d_out, g->info,
-                                   g->d_hinfo, seq, kyp ? (const float*)nullptr : (const float*)(g->P + (size_t)g->n * g->ldp),
-                                   kyp ? (const float*)g->Wt : (const float*)nullptr, kyp_blocks, g->ldp);
-                return seq;
-            };
-        }
-        early_seq = launch_update(f, in).between_seq;  // 0: the hook was not reached (no measurement, another flow of the update)
-        if (early_seq) f->early_output_frames++;
-    }
-    if (hipGetLastError() != hipSuccess) {
-        f->last_error = "launch failed in ekfvio_step_image";
-        return fail(EKFVIO_EDEVICE);
-    }
-    // "try to get more features if needed" (:172): detection, first-fit selection and the growth of the state are
-    // enqueued behind the update with the number of new landmarks left on the device; the host reads it with the status
-    // word, in the frame's single wait, and only then counts the landmarks in
-    int replenishing = 0;
-    if (f->cfg.replenish) {
-        rc = replenish_enqueue(f, &replenishing);
-        if (rc != EKFVIO_OK) return fail(rc);
-        if (replenishing) add_features_enqueue_device_count(f, f->fast_counts + 1);
-    }
-    // cfg.remove_lost: every flagged landmark leaves the state behind the replenishment (which still saw them), in front of the
-    // frame's outputs (remove.hip).  The kernel takes the landmark count from the device (N + what the replenishment added) and leaves
-    // `added - removed` in remove_words[0]: the outputs kernel counts the landmarks from it and the host reads it with the status word,
-    // so the frame keeps its single wait.  Flags only come from an update, and the flagged landmarks of earlier frames are gone: with
-    // no landmark before the frame there is nothing to remove.  Behind an aborted persistent sweep the kernel removes nothing (the
-    // update is run again below over the layout it was enqueued for); the flags stay and the next frame removes those landmarks.
-    const bool removing = f->cfg.remove_lost && f->N > 0;
-    const int* count_dev = replenishing ? f->fast_counts + 1 : nullptr;
-    if (removing) {
-        launch_remove_features(f, nullptr, count_dev, true, f->d_hinfo + 3);
-        count_dev = f->remove_words;
-    }
-    // the frame's one wait: the status word, the number of new landmarks and what the node publishes after addFrame
-    // (odometry, point cloud) arrive together in pinned host memory (frame_outputs_kernel)
-    int bad = 0, added = 0;
-    if (!f->tune.frame_outputs) {
-        rc = wait_status(f, &bad, count_dev, &added);
-    } else {
-        const KltFrame& fr = f->frames[f->cur];
-        const int pitch = level_pitch(fr.w[0]);
-        float fx, fy, cx, cy;
-        intrinsics(f, fr.K, &fx, &fy, &cx, &cy);
-        if (early_seq) {  // (the outputs went out between the Joseph GEMMs: launch_update's hook)
-            rc = poll_status(f, early_seq, &bad, &added);
-        } else {
-            const int seq = next_status_seq(f);
-            // (behind a removal the mean is in mu_next: the host swaps the two once it has the status word)
-            hipLaunchKernelGGL(frame_outputs_kernel, dim3(1), dim3(256), 0, f->stream, removing ? f->mu_next : f->mu, f->N, count_dev,
-                               fr.img[0] + (size_t)KLT_BORDER * pitch + KLT_BORDER, pitch, fr.w[0], fr.h[0], fx, fy, cx, cy, f->d_out, f->info,
-                               f->d_hinfo, seq, (const float*)nullptr);
-            rc = poll_status(f, seq, &bad, &added);
-        }
-    }
-    if (rc != EKFVIO_OK) return rc;
-    f->out_fresh = f->tune.frame_outputs != 0;
-    if (removing) remove_applied(f, 0, __atomic_load_n(&f->h_info[3], __ATOMIC_ACQUIRE));  // (the count of landmarks: below, with `added`)
-    if (bad) HIPK(f, hipMemsetAsync(f->info, 0, sizeof(int), f->stream));
-    if (bad & 2) {
-        // The persistent sweep gave up (chol_persist.inc): the Joseph GEMMs wrote nothing, the state is the propagated one.
-        // The update runs again now, with one launch per block step, over the landmarks it was enqueued for (the count is
-        // bumped below): idx, the measured coordinates per row, R and the row count are where the bookkeeping left them.
-        // Landmarks the replenishment has added meanwhile lie outside n, with ONE exception the re-run relies on an invariant for
-        // (ADVICE r04): the first Joseph GEMM writes n + 1 columns -- column n carries K y -- and the second zeroes rows 0 .. n-1 of
-        // column n again; column n is now the first new landmark's column.  addNewFeatures leaves a new landmark's cross-covariances
-        // exactly zero and its measurement-map entries at -1, so "zero before, K y in between, zero after" is what an update without
-        // new landmarks does to that padding column too (tests/test_gpu_sweep_abort.py, the replenishing-frame case).  (Those
-        // landmarks were picked around the predicted, not the updated, landmark pixels: a valid state, not bit for bit the
-        // frame an unshared GPU produces.)
-        sweep_abort_latch(f);
-        f->sweep_recoveries++;
-        f->out_fresh = false;
-        in.between = nullptr, in.bookkeeping_done = true;
-        launch_update(f, in);
-        HIPK(f, hipGetLastError());
-        rc = wait_status(f, &bad);
-        if (rc != EKFVIO_OK) return rc;
-        if (bad) HIPK(f, hipMemsetAsync(f->info, 0, sizeof(int), f->stream));
-        if (bad & 2) return EKFVIO_EABORTED;
-    } else if (f->N > 0) sweep_clean_update(f);
-    if (added != 0) {  // (added - removed with cfg.remove_lost)
-        f->N += added;
-        f->n += 3 * added;
-    }
-    if (bad & 1) status = EKFVIO_ENUMERIC;
-    return status;
-}
 
 }  // extern "C"

@@ -14,15 +14,6 @@
 
 #include "common.h"
 
-#define HIPR(f, expr)                                                              \
-    do {                                                                           \
-        hipError_t e__ = (expr);                                                   \
-        if (e__ != hipSuccess) {                                                   \
-            (f)->last_error = std::string(#expr) + ": " + hipGetErrorString(e__);  \
-            return EKFVIO_EDEVICE;                                                 \
-        }                                                                          \
-    } while (0)
-
 namespace {
 
 struct RectifyCam {
@@ -110,9 +101,9 @@ int rectify_ensure(ekfvio_filter* f, size_t src) {
     if (!f->rect_on || src <= f->rect_cap) return EKFVIO_OK;
     rectify_free(f);
     // (+16: the kernels move whole groups of four entries, and the pyramid's source has the slack of the upload staging)
-    HIPR(f, hipMalloc((void**)&f->rect_sx, sizeof(int) * (src + 16)));
-    HIPR(f, hipMalloc((void**)&f->rect_sy, sizeof(int) * (src + 16)));
-    HIPR(f, hipMalloc((void**)&f->rect_img, src + 16));
+    HIP_TRY(f, hipMalloc((void**)&f->rect_sx, sizeof(int) * (src + 16)));
+    HIP_TRY(f, hipMalloc((void**)&f->rect_sy, sizeof(int) * (src + 16)));
+    HIP_TRY(f, hipMalloc((void**)&f->rect_img, src + 16));
     f->rect_cap = src;
     return EKFVIO_OK;
 }

@@ -8,15 +8,6 @@
 
 #include "common.h"
 
-#define HIPC(f, expr)                                                                              \
-    do {                                                                                           \
-        hipError_t e__ = (expr);                                                                   \
-        if (e__ != hipSuccess) {                                                                   \
-            (f)->last_error = std::string(#expr) + ": " + hipGetErrorString(e__);                  \
-            return EKFVIO_EDEVICE;                                                                 \
-        }                                                                                          \
-    } while (0)
-
 namespace {
 
 constexpr int RM_THREADS = 256;
@@ -35,7 +26,7 @@ struct RemoveArgs {
     const int* added;        // ... plus these, from device memory (the replenishment's count; may be null)
     const int* info;         // non-null: info[0] bit 1 (the persistent sweep gave up) -> nothing is removed
     int* words;              // [0] added - removed, [1] removed, [2] ticket (zero between launches)
-    int* host_removed;       // may be null: the removed count, also into pinned host memory
+    int* host_removed;       // may be null: the removed count, also into pinned host memory (d_hinfo + HW_REMOVED)
 };
 
 // The decision and its prefix sum over the landmarks, formed by every workgroup in LDS: pre[i] = kept landmarks in front of i,
@@ -180,7 +171,7 @@ size_t remove_lds_bytes(const ekfvio_filter* f) {
 // Enqueues the removal.  N_host + *added (added may be null) landmarks; the decision from `remove` (device memory), where null
 // from del_flag.  abort_aware: nothing is removed behind an aborted persistent sweep (ekfvio_step_image).  The caller swaps
 // mu <-> mu_next after every launch, P <-> P2 when something was removed (words[1] > 0), and applies words[0] to N.
-void launch_remove_features(ekfvio_filter* f, const uint8_t* remove, const int* added, bool abort_aware, int* host_removed) {
+void launch_remove_features(ekfvio_filter* f, const uint8_t* remove, const int* added, bool abort_aware, bool host_removed) {
     RemoveArgs a;
     a.P = f->P;
     a.P2 = f->P2;
@@ -194,7 +185,7 @@ void launch_remove_features(ekfvio_filter* f, const uint8_t* remove, const int* 
     a.added = added;
     a.info = abort_aware ? f->info : nullptr;
     a.words = f->remove_words;
-    a.host_removed = host_removed;
+    a.host_removed = host_removed ? f->d_hinfo + HW_REMOVED : nullptr;
     const int n_bound = added ? f->n_cap : f->n;  // (the device count is at most max_features - N)
     const int grid = std::max(1, (n_bound + RM_COLS - 1) / RM_COLS);
     hipLaunchKernelGGL(remove_features_kernel, dim3(grid), dim3(RM_THREADS), remove_lds_bytes(f), f->stream, a);
@@ -222,17 +213,17 @@ int ekfvio_remove_features(ekfvio_filter* f, const uint8_t* remove, int32_t coun
         f->last_error = "ekfvio_remove_features: max_features too large for the removal kernel's LDS";
         return EKFVIO_ECAPACITY;
     }
-    HIPC(f, hipSetDevice(f->device));
+    HIP_TRY(f, hipSetDevice(f->device));
     if (remove) {
         int k = 0;
         for (int i = 0; i < count; i++) k += remove[i] ? 1 : 0;
         if (k == 0) return EKFVIO_OK;  // nothing launched, the state untouched
         f->out_fresh = false;
         // staged through the tracker's pass buffer (free between calls: ekfvio_step_image rewrites it before it reads it)
-        HIPC(f, hipMemcpyAsync(f->pass, remove, count, hipMemcpyHostToDevice, f->stream));
-        launch_remove_features(f, f->pass, nullptr, false, nullptr);
-        HIPC(f, hipGetLastError());
-        HIPC(f, hipStreamSynchronize(f->stream));  // (remove is the caller's memory)
+        HIP_TRY(f, hipMemcpyAsync(f->pass, remove, count, hipMemcpyHostToDevice, f->stream));
+        launch_remove_features(f, f->pass, nullptr, false, false);
+        HIP_TRY(f, hipGetLastError());
+        HIP_TRY(f, hipStreamSynchronize(f->stream));  // (remove is the caller's memory)
         remove_applied(f, -k, k);
         if (removed) *removed = k;
         return EKFVIO_OK;
@@ -240,7 +231,7 @@ int ekfvio_remove_features(ekfvio_filter* f, const uint8_t* remove, int32_t coun
     if (f->N == 0) return EKFVIO_OK;
     f->out_fresh = false;
     // the flags are on the device: one status poll brings the count back
-    launch_remove_features(f, nullptr, nullptr, false, nullptr);
+    launch_remove_features(f, nullptr, nullptr, false, false);
     int bad = 0, k = 0;
     const int rc = wait_status(f, &bad, f->remove_words + 1, &k);
     if (rc != EKFVIO_OK) return rc;
