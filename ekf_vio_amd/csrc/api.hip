@@ -868,7 +868,8 @@ int ekfvio_profile_update_gemms(ekfvio_filter* f, int32_t reps, double* avg_laun
     hipGraph_t g = nullptr;
     hipGraphExec_t ge = nullptr;
     HIP_TRY(f, hipStreamBeginCapture(f->stream, hipStreamCaptureModeThreadLocal));
-    const int per_rep = launch_update_gemms_scratch(f, plan_update(f, f->last_m), reps);
+    double last_flops = 0;
+    const int per_rep = launch_update_gemms_scratch(f, plan_update(f, f->last_m), reps, &last_flops);
     hipError_t ce = hipStreamEndCapture(f->stream, &g);
     if (ce != hipSuccess || !g) {
         f->last_error = std::string("graph capture: ") + hipGetErrorString(ce);
@@ -888,16 +889,9 @@ int ekfvio_profile_update_gemms(ekfvio_filter* f, int32_t reps, double* avg_laun
     HIP_TRY(f, hipMemsetAsync(f->P2, 0, sizeof(float) * (size_t)f->ldp * f->ldp, f->stream));
     HIP_TRY(f, hipStreamSynchronize(f->stream));
     *avg_launch_us = 1e3 * ms / ((double)per_rep * reps);
-    const int m_pad = round_up(f->last_m, 64);
-    if (flops_per_launch) {
-        // EXECUTED flops, averaged over the launches of one update: the second Joseph GEMM of the throughput regime forms the lower triangle's
-        // 64 x 64 tiles only (GemmEpi::sym)
-        const double full = 2.0 * f->n * (double)f->n * m_pad;
-        const int tn = (f->n + 63) / 64;
-        const bool half = per_rep == 2 && f->tune.sym_joseph && gemm_throughput_regime(f->num_cus, f->n, f->n, m_pad);
-        const double second = half ? 0.5 * tn * (tn + 1) * 2.0 * 64.0 * 64.0 * m_pad : full;
-        *flops_per_launch = per_rep == 2 ? 0.5 * (full + second) : full;
-    }
+    // EXECUTED flops, averaged over the launches of one update: the second Joseph GEMM of the throughput regime forms the lower triangle's
+    // 64 x 64 tiles only (GemmPlan::sym); the first is counted over n x n (its column n is the rider K y)
+    if (flops_per_launch) *flops_per_launch = per_rep == 2 ? 0.5 * (2.0 * f->n * (double)f->n * round_up(f->last_m, 64) + last_flops) : last_flops;
     return EKFVIO_OK;
 }
 int ekfvio_profile_reset(ekfvio_filter* f) {
@@ -1019,7 +1013,10 @@ int ekfvio_test_gemm(ekfvio_filter* f, int32_t transB, int32_t M, int32_t N, int
     HIP_TRY(f, hipMemcpyAsync(dA, hA.data(), sizeof(float) * hA.size(), hipMemcpyHostToDevice, f->stream));
     HIP_TRY(f, hipMemcpyAsync(dB, hB.data(), sizeof(float) * hB.size(), hipMemcpyHostToDevice, f->stream));
     HIP_TRY(f, hipMemcpyAsync(dC, hC.data(), sizeof(float) * hC.size(), hipMemcpyHostToDevice, f->stream));
-    launch_gemm_variant(f, variant, transB, M, N, Kp, alpha, dA, Mp, dB, brows, beta, dC, Mp, dC, Mp, 0, 0);
+    GemmCall g;
+    g.M = M, g.N = N, g.K = Kp, g.transB = transB != 0, g.alpha = alpha, g.A = dA, g.lda = Mp, g.B = dB, g.ldb = brows;
+    g.beta = beta, g.Cin = dC, g.ldcin = Mp, g.C = dC, g.ldc = Mp, g.variant = variant;
+    launch_gemm(f, g);
     HIP_TRY(f, hipMemcpyAsync(hC.data(), dC, sizeof(float) * hC.size(), hipMemcpyDeviceToHost, f->stream));
     HIP_TRY(f, hipStreamSynchronize(f->stream));
     for (int j = 0; j < N; j++)
@@ -1053,12 +1050,14 @@ int ekfvio_test_gemm_bench(ekfvio_filter* f, int32_t transB, int32_t lowerB, int
     HIP_TRY(f, hipMemcpyAsync(dB, hB.data(), sizeof(float) * hB.size(), hipMemcpyHostToDevice, f->stream));
     HIP_TRY(f, hipMemcpyAsync(dC, hC.data(), sizeof(float) * hC.size(), hipMemcpyHostToDevice, f->stream));
     const bool stamped = variant >= 10000;  // library built with -DEKF_GEMM_STAMPS
-    variant %= 10000;
+    GemmCall g;
+    g.M = M, g.N = N, g.K = Kp, g.transB = transB != 0, g.lowerB = lowerB != 0, g.alpha = -1e-3f, g.A = dA, g.lda = Mp, g.B = dB, g.ldb = brows;
+    g.beta = 1.f, g.Cin = dC, g.ldcin = Mp, g.C = dC, g.ldc = Mp, g.variant = variant % 10000;
     for (int w = 0; w < 3; w++)
-        launch_gemm_variant(f, variant, transB, M, N, Kp, -1e-3f, dA, Mp, dB, brows, 1.f, dC, Mp, dC, Mp, 0, lowerB);
+        launch_gemm(f, g);
     HIP_TRY(f, hipEventRecord(f->ev0, f->stream));
     for (int r = 0; r < reps; r++)
-        launch_gemm_variant(f, variant, transB, M, N, Kp, -1e-3f, dA, Mp, dB, brows, 1.f, dC, Mp, dC, Mp, 0, lowerB);
+        launch_gemm(f, g);
     HIP_TRY(f, hipEventRecord(f->ev1, f->stream));
     HIP_TRY(f, hipEventSynchronize(f->ev1));
     float ms = 0;
@@ -1068,7 +1067,7 @@ int ekfvio_test_gemm_bench(ekfvio_filter* f, int32_t transB, int32_t lowerB, int
         long long* dst;
         HIP_TRY(f, dev_alloc(f->stream, &dst, 40));
         f->gemm_stamps = dst;
-        launch_gemm_variant(f, variant, transB, M, N, Kp, -1e-3f, dA, Mp, dB, brows, 1.f, dC, Mp, dC, Mp, 0, lowerB);
+        launch_gemm(f, g);
         long long hst[40];
         HIP_TRY(f, hipMemcpyAsync(hst, dst, sizeof(hst), hipMemcpyDeviceToHost, f->stream));
         HIP_TRY(f, hipStreamSynchronize(f->stream));
@@ -1226,6 +1225,30 @@ int ekfvio_test_plan(int32_t num_cus, int32_t max_features, int32_t N, int32_t m
     const UpdatePlan p = plan_update(tuning_from_env(), s, m, m_on_device != 0, next_dt);
     const int32_t out[12] = {p.m, p.m_pad, p.n_pad, p.sweep, p.fused_gather, p.with_wt, p.gain, p.tail, p.t2_skip, p.t2_by_sweep, p.compact, p.lin_blocks};
     std::copy(out, out + 12, plan);
+    return EKFVIO_OK;
+}
+
+// ... plan_gemm for one shape; behind the GemmPlan's words: gemm_throughput_regime, gemm_tile_height
+int ekfvio_test_gemm_plan(int32_t num_cus, int32_t M, int32_t N, int32_t K, int32_t transB, int32_t lowerB, int32_t epi, int32_t mean,
+                          int32_t lin_blocks, int32_t sym, int32_t variant, int32_t plan[18]) {
+    if (!plan || M <= 0 || N <= 0 || K <= 0 || epi < EPI_NONE || epi > EPI_MEAN_PARTIAL) return EKFVIO_EINVAL;
+    GemmShape s;
+    s.M = M, s.N = N, s.K = K, s.transB = transB != 0, s.lowerB = lowerB != 0, s.epi = epi, s.mean = mean != 0;
+    s.lin_blocks = lin_blocks, s.sym = sym != 0, s.variant = variant;
+    const GemmPlan p = plan_gemm(tuning_from_env(), num_cus, s);
+    const int32_t out[18] = {p.k16, p.bm, p.wps, p.groups, p.threads(), p.tiles_x, p.tiles_y, p.tiles, p.grid_x, p.grid_y, p.mean_wg, p.lin_blocks,
+                             p.mean_keep, p.sym, p.sym_w, p.order2d, gemm_throughput_regime(num_cus, M, N, K), gemm_tile_height(num_cus, M, N, K, s.transB)};
+    std::copy(out, out + 18, plan);
+    return EKFVIO_OK;
+}
+// ... and plan_predict for a handle holding N landmarks
+int ekfvio_test_predict_plan(int32_t num_cus, int32_t N, int32_t dense_predict, int32_t prelinearized, int32_t bookkeeping, int32_t plan[8]) {
+    if (!plan || N < 0) return EKFVIO_EINVAL;
+    PlanShape s;
+    s.num_cus = num_cus, s.N = N, s.n = EKF_BASE + 3 * N, s.dense_predict = dense_predict != 0;
+    const PredictPlan p = plan_predict(tuning_from_env(), s, prelinearized != 0);
+    const int32_t out[8] = {p.dense, p.pre, p.lin_inside, p.lin_in_front, p.ts, p.chunks, p.book_rides(), p.grid(bookkeeping != 0)};
+    std::copy(out, out + 8, plan);
     return EKFVIO_OK;
 }
 

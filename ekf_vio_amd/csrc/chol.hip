@@ -1334,9 +1334,16 @@ void launch_gain_from_sweep(ekfvio_filter* f, const UpdatePlan& p, const float* 
     const float* Lf = Laug;
     const float* Y = Laug + m_pad;
     const float* LinvT = Laug + m_pad + n_pad;
-    launch_gemm(f, 1, n, m_pad, m_pad, 1.f, Y, ld, LinvT, ld, 0.f, nullptr, 0, K, ldk, refine ? 0 : 1, 1);
+    // K = Y L^-1, pruned unless the refinement follows
+    GemmCall g;
+    g.M = n, g.N = g.K = m_pad, g.transB = true, g.lowerB = true;
+    g.A = Y, g.lda = ld, g.B = LinvT, g.ldb = ld, g.C = K, g.ldc = ldk, g.flush = !refine;
+    launch_gemm(f, g);
     if (refine) {
-        launch_gemm(f, 0, n, m_pad, m_pad, -1.f, K, ldk, Lf, ld, 1.f, Y, ld, scratch, ldk, 0, 1);     // Y - K L
-        launch_gemm(f, 1, n, m_pad, m_pad, 1.f, scratch, ldk, LinvT, ld, 1.f, K, ldk, K, ldk, 1, 1);  // + prune
+        GemmCall r = g;  // Y - K L
+        r.transB = false, r.alpha = -1.f, r.A = K, r.lda = ldk, r.B = Lf, r.beta = 1.f, r.Cin = Y, r.ldcin = ld, r.C = scratch, r.flush = false;
+        launch_gemm(f, r);
+        g.A = scratch, g.lda = ldk, g.beta = 1.f, g.Cin = K, g.ldcin = ldk, g.flush = true;  // K + (Y - K L) L^-1, pruned
+        launch_gemm(f, g);
     }
 }

@@ -259,16 +259,18 @@ struct ekfvio_filter {
 // C[MxN] = beta*Cin + alpha * A[MxK] * op(B); all column-major.  transB: B is [NxK]
 // (op = transpose) else [KxN].  K must be a multiple of 32 and the K-padding of both
 // operands finite*0-safe (zero).  flush != 0 applies the reference's prune (|x|<=1e-13 -> 0).
-// Filter-specific epilogues of the two Joseph GEMMs (mode 0 = none):
-//  mode 1  T = Sigma - K (H Sigma): besides T, writes G = K R - T[:, idx] for the measured
-//          columns (inv_idx: state index -> measurement row or -1) so that no separate pass
-//          re-reads T; the residual rides as an extra row of (H Sigma)^T, so output column n
-//          receives K*y.
-//  mode 2  Sigma' = T + G K^T: workgroup (0,0) also finishes the mean: mu += column n,
-//          quaternion renormalised (:600-609), column n zeroed again, frame counter advanced.
-//  mode 3  the same, K y taken from per-column-block partial sums (Schur flow).
-//  (Round 4's symmetric Joseph flow -- `sym`, and mode 4, the gain GEMM that left K y as partial sums for it -- was measured, rejected on parity
-//  and left the product in round 5: scripts/experiments/joseph_sym.txt, profiles/r04_symmetric_joseph_experiment.txt.)
+// Filter-specific epilogues of the P-update GEMMs (GemmEpi::mode, a GemmEpiMode of plan.h):
+//  EPI_JOSEPH1 (1)       T = Sigma - K (H Sigma): besides T, writes G = K R - T[:, idx] for the measured columns (inv_idx: state
+//                        index -> measurement row or -1) so that no separate pass re-reads T; the residual rides as an extra row of
+//                        (H Sigma)^T, so output column n receives K*y.
+//  EPI_MEAN (2)          Sigma' = T + G K^T: with n > 0 one more workgroup (gemm16_kernel; workgroup (0,0) of the 64 x 64 kernel) also
+//                        finishes the mean: mu += column n, quaternion renormalised (:600-609), column n zeroed again, frame counter
+//                        advanced, the persistent sweep's flags zeroed.  In the throughput regime the product may be formed mirrored (sym).
+//  EPI_MEAN_PARTIAL (3)  Sigma' = T2 + K G'^T, the ONE GEMM of the T2 tail (the default where it applies) and of the Schur tail: the same
+//                        finish with K y taken from per-column-block partial sums (Kyp); the only mode the next process(dt)'s
+//                        linearisation rides in (lin_blocks).
+// The caller fills what the epilogue works on; how the launch is shaped (lin_blocks as kept, mean_keep, sym as heeded, sym_w, order2d) is
+// plan_gemm's answer (plan.h), written into the kernel's copy by launch_gemm.
 struct GemmEpi {
     int mode = 0;
     const int* inv_idx = nullptr;
@@ -285,7 +287,7 @@ struct GemmEpi {
     long long* stamps = nullptr;  // diagnostic s_memtime stamps (library built with -DEKF_GEMM_STAMPS), per handle
     int* zero_words = nullptr;    // modes 2-3: the persistent sweep's flags, zeroed by workgroup (0,0) for the NEXT update's sweep
     int n_zero = 0;               // (everything but the abort word, which only ever goes up and retires the persistent path)
-    int order2d = 0;              // gemm_f32_mfma_kernel: each XCD's run of tiles is a compact 2-D patch (launch_gemm_cfg decides)
+    int order2d = 0;              // gemm_f32_mfma_kernel: each XCD's run of tiles is a compact 2-D patch (GemmPlan::order2d)
     // round 6 (mode 3, gemm16_kernel): the linearisation of the NEXT process(dt) in `lin_blocks` workgroups behind the tiles' and the mean's -- a device-resident run
     // knows the next dt, and K y is final before the launch (Kyp), so numericallyLinearizeProcess (:176-325) and the mean propagation at mu + K y run while
     // this launch's tiles do, and the covariance propagation behind it only has the strips left (motion_model.inc, launch_update)
@@ -296,21 +298,31 @@ struct GemmEpi {
     float* lin_FB = nullptr;
     float* lin_FD = nullptr;
     float* lin_mu_next = nullptr;
-    int mean_keep = 0;            // (set by launch_gemm_cfg with lin_blocks) gemm16_finish_mean leaves mu alone
+    int mean_keep = 0;            // (GemmPlan::mean_keep, with lin_blocks) gemm16_finish_mean leaves mu alone
     int sym_w = 1;                // ... in strips of sym_w tile columns, each walked row by row
-    int sym = 0;                  // mode 2, gemm_f32_mfma_kernel: only the lower triangle's tiles are formed, each also writes its transpose
+    int sym = 0;                  // EPI_MEAN: the caller asks for the mirrored form; where plan_gemm heeds it (gemm_f32_mfma_kernel) only the lower triangle's tiles are formed, each also writes its transpose
     const int* abort = nullptr;   // modes 1-3: abort word of the persistent sweep in front (non-zero: the factor is unfinished) --
                                   // the kernel then writes nothing: Sigma, mu and the frame counter stay as process(dt) left them
 };
-void launch_gemm(ekfvio_filter* f, int transB, int M, int N, int K, float alpha, const float* A, int lda, const float* B,
-                 int ldb, float beta, const float* Cin, int ldcin, float* C, int ldc, int flush, int lowerB = 0,
-                 const GemmEpi* epi = nullptr);
-
-// same, selecting a tile configuration (0 = production default chosen by shape)
-void launch_gemm_variant(ekfvio_filter* f, int variant, int transB, int M, int N, int K, float alpha, const float* A, int lda,
-                         const float* B, int ldb, float beta, const float* Cin, int ldcin, float* C, int ldc, int flush,
-                         int lowerB);
-
+// One GEMM launch by name: operands with their leading dimensions, the scalars, and the epilogue
+struct GemmCall {
+    int M = 0, N = 0, K = 0;
+    bool transB = false;
+    bool flush = false, lowerB = false;  // the reference's prune on the way out; B is lower triangular (the contraction starts at the tile's column)
+    float alpha = 1.f, beta = 0.f;
+    const float *A = nullptr, *B = nullptr, *Cin = nullptr;  // Cin: read only with beta != 0
+    float* C = nullptr;
+    int lda = 0, ldb = 0, ldcin = 0, ldc = 0;
+    GemmEpi epi;
+    int variant = 0;  // GemmShape::variant (the two GEMM test hooks; no epilogue)
+};
+inline GemmShape gemm_shape(const GemmCall& c) {  // what plan_gemm (plan.h) may depend on
+    GemmShape s;
+    s.M = c.M, s.N = c.N, s.K = c.K, s.transB = c.transB, s.lowerB = c.lowerB;
+    s.epi = c.epi.mode, s.mean = c.epi.n > 0, s.lin_blocks = c.epi.lin_blocks, s.sym = c.epi.sym != 0, s.variant = c.variant;
+    return s;
+}
+void launch_gemm(ekfvio_filter* f, const GemmCall& c);  // plans (plan_gemm) and launches
 
 // Measurement bookkeeping of one update (device pointers); see bookkeeping_body in ekf_kernels.hip
 struct BookArgs {
@@ -429,7 +441,8 @@ inline UpdatePlan plan_update(const ekfvio_filter* f, int m, bool m_on_device = 
 }
 // The P-update GEMM launches of an update with plan p, `reps` times, into scratch (P2, Gm): the
 // filter state is not touched.  For timing the kernel under its production shape (ekfvio_profile_update_gemms).
-int launch_update_gemms_scratch(ekfvio_filter* f, const UpdatePlan& p, int reps);  // returns the GEMM launches per repetition (2 with the two-GEMM tail, else 1)
+// Returns the GEMM launches per repetition (2 with the two-GEMM tail, else 1); last_flops: the EXECUTED flops of the last of them (gemm_executed_flops)
+int launch_update_gemms_scratch(ekfvio_filter* f, const UpdatePlan& p, int reps, double* last_flops);
 // Augmented blocked Cholesky sweep (chol.hip): Saug = [A; X; I] (row blocks of 64; A is
 // m_pad x m_pad, X has n_pad rows) -> Laug = [L; X L^-T; L^-T], both ld x m_pad column-major.
 // zero_flags: a memset of the persistent sweep's flags goes in front.  Returns the abort word of the persistent launch (null: another sweep)

@@ -234,8 +234,8 @@ __device__ __forceinline__ void lin_base_test_point(const float* s_base, int q, 
     for (int i = 0; i < EKF_BASE; i++) out[i] = o[i];
 }
 
-#define PT 16  // landmarks per tile side (landmark x landmark tiles)
-#define PC 3   // landmarks per base-row / base-column workgroup (3*PC <= 64)
+#define PT PREDICT_PT  // landmarks per tile side (landmark x landmark tiles; plan.h)
+#define PC PREDICT_PC  // landmarks per base-row / base-column workgroup (3*PC <= 64)
 
 __device__ __forceinline__ float predict_finish(float acc, int i, int j, float dt) {
     if (i == j) acc = acc + process_noise(i, dt);
@@ -757,49 +757,80 @@ void launch_build_dense_F(ekfvio_filter* f, float* Fdense) {
                        Fdense);
 }
 
-// process(dt) (:96-121)
+// process(dt) (:96-121): executes a PredictPlan (plan.h, plan_predict)
 void launch_predict(ekfvio_filter* f, float dt, const BookArgs* book) {
-    // structured mode linearises inside the propagation kernel (predict_fused_kernel<true>); the dense mode and
-    // ekfvio_linearize keep the stand-alone linearize_kernel
-    // (while the landmark tiles are a few rounds of workgroups: with thousands of tiles, N = 1024, the Jacobian blocks
-    // formed 2 * 64 times over cost more than the launch they save)
-    const int tiles_side = (f->N + PT - 1) / PT;
-    // round 6: the previous update's last GEMM has linearised for this step already (launch_update, GemmEpi::lin_blocks): FA / FB / FD and the
-    // propagated mean are in place, the propagation kernel only carries the bookkeeping along
-    const bool pre = f->prelinearized && f->cfg.predict_mode != EKFVIO_PREDICT_DENSE;
+    // structured mode linearises inside the propagation kernel (predict_fused_kernel<true>) or in a launch in front; the dense mode and
+    // ekfvio_linearize keep the stand-alone linearize_kernel.  pre (round 6): the previous update's last GEMM has linearised for this step
+    // already (launch_update, GemmEpi::lin_blocks): FA / FB / FD and the propagated mean are in place, the propagation kernel only carries
+    // the bookkeeping along
+    const PredictPlan p = plan_predict(f->tune, plan_shape(f), f->prelinearized);
     f->prelinearized = false;
-    if (pre) f->prelinearized_steps++;  // (a capture takes its count back and adds it per replay: capture_steps)
-    const bool lin_in_predict = !pre && f->cfg.predict_mode != EKFVIO_PREDICT_DENSE && f->tune.fuse_linearize && tiles_side * tiles_side <= 4 * f->num_cus;
-    if (!lin_in_predict && !pre) launch_linearize(f, dt, book);
+    if (p.pre) f->prelinearized_steps++;  // (a capture takes its count back and adds it per replay: capture_steps)
+    if (p.lin_in_front) launch_linearize(f, dt, book);
     const int n = f->n, ld = f->ldp;
-    dim3 grid((n + 255) / 256, n);
-    if (f->cfg.predict_mode == EKFVIO_PREDICT_DENSE) {
+    if (p.dense) {
         launch_build_dense_F(f, f->Fdense);
-        const int np = round_up(n, 32);
         {
             ProfScope ps(f, PC_GEMM_PREDICT, 4.0 * n * (double)n * n);
             // X = F*P (B = P is [K x N]); P' = X*F^T (B = F is [N x K])
-            launch_gemm(f, 0, n, n, np, 1.f, f->Fdense, ld, f->P, ld, 0.f, nullptr, 0, f->P2, ld, 0);
-            launch_gemm(f, 1, n, n, np, 1.f, f->P2, ld, f->Fdense, ld, 0.f, nullptr, 0, f->P, ld, 0);
+            GemmCall g;
+            g.M = g.N = n, g.K = round_up(n, 32), g.A = f->Fdense, g.lda = ld, g.B = f->P, g.ldb = ld, g.C = f->P2, g.ldc = ld;
+            launch_gemm(f, g);
+            g.transB = true, g.A = f->P2, g.B = f->Fdense, g.C = f->P;
+            launch_gemm(f, g);
         }
         ProfScope ps(f, PC_PREDICT);
-        hipLaunchKernelGGL(add_noise_flush_kernel, grid, dim3(256), 0, f->stream, f->P, ld, n, dt);
+        hipLaunchKernelGGL(add_noise_flush_kernel, dim3((n + 255) / 256, n), dim3(256), 0, f->stream, f->P, ld, n, dt);
     } else {
         ProfScope ps(f, PC_PREDICT, 4.0 * n * (358.0 + 36.0 * f->N));
-        const int ts = (f->N + PT - 1) / PT;
-        const int chunks = (f->N + PC - 1) / PC;
         BookArgs b;
-        if (book && (lin_in_predict || pre)) b = *book;
-        if (lin_in_predict)
-            hipLaunchKernelGGL(predict_fused_kernel<true>, dim3(ts * ts + 1 + 2 * chunks + (b.enabled ? 1 : 0)), dim3(256), 0, f->stream,
-                               f->P, ld, f->N, n, f->FA, f->FB, f->FD, dt, f->P2, ts, chunks, f->mu, f->mu_next, b, f->sweep_dbg);
+        if (book && p.book_rides()) b = *book;
+        const dim3 grid(p.grid(b.enabled != 0));
+        if (p.lin_inside)
+            hipLaunchKernelGGL(predict_fused_kernel<true>, grid, dim3(256), 0, f->stream, f->P, ld, f->N, n, f->FA, f->FB, f->FD, dt, f->P2,
+                               p.ts, p.chunks, f->mu, f->mu_next, b, f->sweep_dbg);
         else
-            hipLaunchKernelGGL(predict_fused_kernel<false>, dim3(ts * ts + 1 + 2 * chunks + (b.enabled ? 1 : 0)), dim3(256), 0, f->stream, f->P, ld, f->N, n,
-                               f->FA, f->FB, f->FD, dt, f->P2, ts, chunks, f->mu, f->mu_next, b, f->sweep_dbg);
+            hipLaunchKernelGGL(predict_fused_kernel<false>, grid, dim3(256), 0, f->stream, f->P, ld, f->N, n, f->FA, f->FB, f->FD, dt, f->P2,
+                               p.ts, p.chunks, f->mu, f->mu_next, b, f->sweep_dbg);
         std::swap(f->P, f->P2);  // out of place; P2's padding is zero as well (never written outside n x n)
     }
     // the propagated mean becomes the state (landmarks used the OLD base state, :102-107)
     std::swap(f->mu, f->mu_next);
+}
+
+// The P-update GEMMs behind the sweep and the gain, described ONCE for the update itself and for the profiler's scratch launches.
+//   TAIL_JOSEPH, two GEMMs, both triangles:   T = Sigma - K*(H Sigma)   (I_KH * Sigma, :594) in place; also G and K*y (column n)
+//                                             Sigma' = T + G*K^T, pruned (:594-596, :625), mirrored in the throughput regime (plan_gemm)
+//   else ONE GEMM, the left Joseph factor applied to T2 = Sigma - X A^-1 X^T = Sigma (I - K H)^T, the RIGHT one (X = Sigma H^T; Sigma is symmetric
+//   only to rounding, so this is not the transpose of the reference's (I - K H) Sigma): Sigma' = (I - K H) T2 + K R K^T = T2 + K G'^T, which is the
+//   reference's (I - K H) Sigma (I - K H)^T + K R K^T (:594-596), pruned (:625).
+// `from` -> `to`: the covariance read and written (the two-GEMM tail passes through `to`).  What touches the filter's state -- the mean, the frame
+// counter, the sweep's flags and abort word, the riding linearisation -- is the update's to add (launch_update); as built here the last GEMM is
+// EPI_MEAN with nothing to finish.
+struct TailGemms {
+    int count;
+    GemmCall g[2];
+    GemmCall& last() { return g[count - 1]; }
+};
+static TailGemms update_tail_gemms(ekfvio_filter* f, const UpdatePlan& p, const float* from, float* to) {
+    const int n = f->n, ld = f->ldp;
+    TailGemms t;
+    GemmCall c;
+    c.M = c.N = n, c.K = p.m_pad, c.transB = true, c.lda = c.ldb = c.ldcin = c.ldc = ld, c.beta = 1.f, c.Cin = from, c.C = to;
+    t.g[0] = t.g[1] = c;
+    GemmCall& g2 = t.g[1];
+    if (p.tail != TAIL_JOSEPH) {
+        t.count = 1;
+        GemmCall& g = t.g[0];
+        g.A = f->Km, g.B = f->Gm, g.flush = true, g.epi.mode = EPI_MEAN;
+        return t;
+    }
+    t.count = 2;
+    GemmCall& g1 = t.g[0];
+    g1.N = n + 1, g1.alpha = -1.f, g1.A = f->Km, g1.B = f->Wt;
+    g1.epi.mode = EPI_JOSEPH1, g1.epi.inv_idx = f->inv_idx, g1.epi.Rm = f->Rm, g1.epi.G = f->Gm, g1.epi.ldg = ld;
+    g2.A = f->Gm, g2.B = f->Km, g2.Cin = to, g2.flush = true, g2.epi.mode = EPI_MEAN, g2.epi.sym = 1;
+    return t;
 }
 
 // updateWithFeaturePositions (:475-628) on device-resident z/R/pass; m = 2*(#passed) known to the host
@@ -846,10 +877,10 @@ UpdateResult launch_update(ekfvio_filter* f, const UpdateInputs& in) {
                                                       : launch_chol_sweep(f, p, f->Saug, f->Laug, f->Linv, f->ld_aug, zero_flags);
     // (ekfvio_update: the update's status is final here -- the host gets it now and returns while the GEMMs below run)
     if (in.publish_seq) launch_publish_status(f, in.publish_seq), out.published = true;
-    GemmEpi e2;  // of the update's last GEMM
-    e2.mode = 2, e2.mu = f->mu, e2.Pcol = f->P + (size_t)n * ld, e2.n = n;
+    TailGemms tail = update_tail_gemms(f, p, p.tail == TAIL_T2 ? t2_buffer(f) : f->P, f->P);
+    GemmEpi& e2 = tail.last().epi;  // the update's last GEMM finishes the mean
+    e2.mu = f->mu, e2.Pcol = f->P + (size_t)n * ld, e2.n = n;
     e2.frame_counter = in.frame_counter, e2.frames = in.frames;
-    e2.sym = f->tune.sym_joseph;  // (heeded by the throughput-regime kernel behind the two-GEMM flow: gemm.hip)
     e2.abort = abort;        // a persistent sweep that gave up: the GEMMs write nothing (T2, K, G' are scratch)
     if (p.persistent()) {    // ... and one that ran: the update's last GEMM leaves its flags zero for the next one
         e2.zero_words = f->sweep_sync, e2.n_zero = persist_zero_words(m_pad, n_pad);
@@ -861,55 +892,40 @@ UpdateResult launch_update(ekfvio_filter* f, const UpdateInputs& in) {
     else if (p.gain == GAIN2_T2_TILES) launch_gain2_tiles(f, p);  // (K, G', K y and T2 in one launch behind the per-step sweep)
     else if (p.gain != GAIN_SWEEP) launch_gain_from_sweep(f, p, f->Laug, f->ld_aug, n, f->Km, f->Gm, ld, 0);
     if (p.tail == TAIL_JOSEPH) {
-        GemmEpi e1;
-        e1.mode = 1, e1.inv_idx = f->inv_idx, e1.Rm = f->Rm, e1.G = f->Gm, e1.ldg = ld, e1.abort = abort;
-        // The two P-update GEMMs, back to back (one profiler scope, two launches), both triangles:
-        //   T = Sigma - K*(H Sigma)   (I_KH * Sigma, :594) in place; also G and K*y (column n)
-        //   Sigma' = T + G*K^T, pruned (:594-596, :625); workgroup (0,0) finishes the mean
+        // back to back (one profiler scope, two launches)
+        tail.g[0].epi.abort = abort;
         ProfScope ps(f, PC_GEMM_UPDATE, 2.0 * n * (double)(n + 1) * m_pad + 2.0 * n * (double)n * m_pad, 2);
-        launch_gemm(f, 1, n, n + 1, m_pad, -1.f, f->Km, ld, f->Wt, ld, 1.f, f->P, ld, f->P, ld, 0, 0, &e1);
+        launch_gemm(f, tail.g[0]);
         if (in.between) out.between_seq = in.between(f, 0);  // (ekfvio_step_image: the frame's outputs, from mu and K y in column n of P)
-        launch_gemm(f, 1, n, n, m_pad, 1.f, f->Gm, ld, f->Km, ld, 1.f, f->P, ld, f->P, ld, 1, 0, &e2);
+        launch_gemm(f, tail.g[1]);
         return out;
     }
-    // ONE P-update GEMM, the left Joseph factor applied to T2 = Sigma - X A^-1 X^T = Sigma (I - K H)^T, the RIGHT one (X = Sigma H^T; Sigma is symmetric
-    // only to rounding, so this is not the transpose of the reference's (I - K H) Sigma): Sigma' = (I - K H) T2 + K R K^T = T2 + K G'^T, which is the
-    // reference's (I - K H) Sigma (I - K H)^T + K R K^T (:594-596), pruned (:625), into f->P; its extra workgroup finishes the mean (:600-609).
     // TAIL_SCHUR: [A; Sigma H^T; I] was swept with Sigma and the gain as Schur tiles (chol.hip), T2 in place in f->P; joseph_g_kernel pruned K and left
     // G' = K R^T - (H T2)^T and K y.  TAIL_T2 (round 6): T2 came out of the persistent launch itself (freed owners, chol_persist.inc t2_tile; behind any
     // other sweep of such a shape gain2_t2_tiles_kernel forms the same T2 from the stored panel blocks), in the dense-F buffer; the gain tiles of the
     // same launch left K, G' and the partial sums of K y.
     if (p.tail == TAIL_T2 && in.between) out.between_seq = in.between(f, m_pad / 64);  // (ekfvio_step_image: the frame's outputs, from mu and the partial sums of K y)
     ProfScope ps(f, PC_GEMM_UPDATE, 2.0 * n * (double)n * m_pad, 1);
-    e2.mode = 3;  // the mean takes K y from the partial sums (joseph_g_kernel / gain_tile2: Kyp = Wt, one row of sums per block column)
+    // the mean takes K y from the partial sums (joseph_g_kernel / gain_tile2: Kyp = Wt, one row of sums per block column): plan.h, tail_gemm_shape
+    e2.mode = EPI_MEAN_PARTIAL;
     e2.Kyp = f->Wt, e2.kyp_blocks = m_pad / 64, e2.kyp_ld = ld;
     if (p.lin_blocks) {  // (plan_update: the next process(dt)'s linearisation rides in this launch)
         e2.lin_blocks = p.lin_blocks, e2.lin_N = f->N, e2.lin_dt = in.next_dt;
         e2.lin_FA = f->FA, e2.lin_FB = f->FB, e2.lin_FD = f->FD, e2.lin_mu_next = f->mu_next;
         f->prelinearized = true;
     }
-    launch_gemm(f, 1, n, n, m_pad, 1.f, f->Km, ld, f->Gm, ld, 1.f, p.tail == TAIL_T2 ? t2_buffer(f) : f->P, ld, f->P, ld, 1, 0, &e2);
+    launch_gemm(f, tail.last());
     return out;
 }
 
-int launch_update_gemms_scratch(ekfvio_filter* f, const UpdatePlan& p, int reps) {
-    const int n = f->n, ld = f->ldp, m_pad = p.m_pad;
-    GemmEpi e1, e2;
-    if (p.tail != TAIL_JOSEPH) {
-        // with the Schur sweep, and where T2 comes out of the persistent launch, the update has ONE P-update GEMM: Sigma' = T2 + K G'^T
-        e2.mode = 2;
-        for (int r = 0; r < reps; r++)
-            launch_gemm(f, 1, n, n, m_pad, 1.f, f->Km, ld, f->Gm, ld, 1.f, f->P, ld, f->P2, ld, 1, 0, &e2);
-        return 1;
-    }
-    e1.mode = 1, e1.inv_idx = f->inv_idx, e1.Rm = f->Rm, e1.G = f->Gm, e1.ldg = ld;
-    e2.mode = 2;  // n = 0: no mean update, no frame counter
-    e2.sym = f->tune.sym_joseph;
-    for (int r = 0; r < reps; r++) {
-        launch_gemm(f, 1, n, n + 1, m_pad, -1.f, f->Km, ld, f->Wt, ld, 1.f, f->P, ld, f->P2, ld, 0, 0, &e1);
-        launch_gemm(f, 1, n, n, m_pad, 1.f, f->Gm, ld, f->Km, ld, 1.f, f->P2, ld, f->P2, ld, 1, 0, &e2);
-    }
-    return 2;
+// into scratch (P2, Gm): no mean, no frame counter, no abort word, no flag zeroing -- the tail as update_tail_gemms builds it
+int launch_update_gemms_scratch(ekfvio_filter* f, const UpdatePlan& p, int reps, double* last_flops) {
+    TailGemms tail = update_tail_gemms(f, p, f->P, f->P2);
+    for (int r = 0; r < reps; r++)
+        for (int k = 0; k < tail.count; k++) launch_gemm(f, tail.g[k]);
+    const GemmShape sh = gemm_shape(tail.last());
+    *last_flops = gemm_executed_flops(sh, plan_gemm(f->tune, f->num_cus, sh));
+    return tail.count;
 }
 
 void launch_check_sigma(ekfvio_filter* f, float* d_out) {

@@ -873,91 +873,52 @@ __global__ __launch_bounds__(256 * WPS) void gemm16_kernel(int M, int N, int K, 
     GSTAMP(38);
 }
 
-// cfg: 0 = choose by shape; 1 / 2 = the 64x64 kernel with 256 / 512 threads; 32, 48, 64 = gemm16_kernel with that BM
-// (512 threads); +100 = the same with 256 threads
-static void launch_gemm_cfg(ekfvio_filter* f, int cfg, int transB, int M, int N, int K, float alpha, const float* A, int lda,
-                            const float* B, int ldb, float beta, const float* Cin, int ldcin, float* C, int ldc, int flush,
-                            int lowerB, const GemmEpi* epi) {
+// Executes a GemmPlan (plan.h, plan_gemm: kernel, tile height, grid, and how the epilogue's launch-shaped words are set)
+void launch_gemm(ekfvio_filter* f, const GemmCall& c) {
+    const int M = c.M, N = c.N, K = c.K;
     if (M <= 0 || N <= 0 || K <= 0) return;
-    GemmEpi e;
-    if (epi) e = *epi;
+    GemmEpi e = c.epi;
+    const GemmPlan p = plan_gemm(f->tune, f->num_cus, gemm_shape(c));  // per handle: handles on different devices may differ
     hipStream_t s = f->stream;
     e.stamps = f->gemm_stamps;
-    const int cus = f->num_cus > 0 ? f->num_cus : 256;  // per handle: handles on different devices may differ
-    const int ty = (N + 63) / 64;
-    if (cfg == 0) {  // latency regime: the smallest tile height whose grid is still a single wave of workgroups; else the 64 x 64 kernel (plan.h)
-        const int bm = gemm_tile_height(cus, M, N, K, transB != 0);
-        cfg = bm ? bm : 1;
-    }
-    if (cfg >= 32) {
-        const int wps = cfg >= 100 ? 1 : 2;  // 132 / 148 / 164: one wavefront per SIMD (micro-benchmark only)
-        const int bm = cfg % 100;
-        const int tx = (M + bm - 1) / bm;
-        if (!(e.mode == 3 && e.n > 0) || gemm_tiles(bm, M, N) + 1 + e.lin_blocks > cus) e.lin_blocks = 0;  // (a plan's lin_blocks fit: gemm_single_round_with, plan.h)
-        e.mean_keep = e.lin_blocks > 0 ? 1 : 0;
-        dim3 grid(gemm_tiles(bm, M, N) + ((e.mode == 2 || e.mode == 3) && e.n > 0 ? 1 : 0) + e.lin_blocks);  // (+1: gemm16_finish_mean; + the next step's linearisation)
-#define GEMM16_GO(BMv, W, EP)                                                                                           \
-    hipLaunchKernelGGL((gemm16_kernel<BMv, W, EP>), grid, dim3(256 * W), 0, s, M, N, K, alpha, A, lda, B, ldb, beta, Cin, ldcin, C, \
-                       ldc, flush, lowerB, e, tx, ty)
-#define GEMM16_BM(W, EP)                          \
-    do {                                          \
-        if (bm == 32) GEMM16_GO(32, W, EP);       \
-        else if (bm == 48) GEMM16_GO(48, W, EP);  \
-        else GEMM16_GO(64, W, EP);                \
+    e.lin_blocks = p.lin_blocks, e.mean_keep = p.mean_keep;
+    const dim3 grid(p.grid_x, p.grid_y), block(p.threads());
+    const int flush = c.flush, lowerB = c.lowerB;
+    if (p.k16) {
+#define GEMM16_GO(BMv, W, EP)                                                                                                     \
+    hipLaunchKernelGGL((gemm16_kernel<BMv, W, EP>), grid, block, 0, s, M, N, K, c.alpha, c.A, c.lda, c.B, c.ldb, c.beta, c.Cin, c.ldcin, \
+                       c.C, c.ldc, flush, lowerB, e, p.tiles_x, p.tiles_y)
+#define GEMM16_BM(W, EP)                            \
+    do {                                            \
+        if (p.bm == 32) GEMM16_GO(32, W, EP);       \
+        else if (p.bm == 48) GEMM16_GO(48, W, EP);  \
+        else GEMM16_GO(64, W, EP);                  \
     } while (0)
-        if (e.mode == 1) GEMM16_BM(2, 1);
-        else if (e.mode == 2) GEMM16_BM(2, 2);
-        else if (e.mode == 3) GEMM16_BM(2, 3);
-        else if (wps == 2) GEMM16_BM(2, 0);
+        if (e.mode == EPI_JOSEPH1) GEMM16_BM(2, 1);
+        else if (e.mode == EPI_MEAN) GEMM16_BM(2, 2);
+        else if (e.mode == EPI_MEAN_PARTIAL) GEMM16_BM(2, 3);
+        else if (p.wps == 2) GEMM16_BM(2, 0);
         else GEMM16_BM(1, 0);
 #undef GEMM16_BM
 #undef GEMM16_GO
         return;
     }
-    const int groups = cfg == 2 ? 2 : 1;
-    e.lin_blocks = 0, e.mean_keep = 0;  // (gemm16_kernel only)
-    dim3 grid((M + BM - 1) / BM, (N + BN - 1) / BN);
-    e.sym = (e.sym && e.mode == 2 && M == N && transB) ? 1 : 0;
-    if (e.sym) {
-        // strips of ceil(tn / 8) tile columns, as order2d's: measured at tn = 49 (FETCH_SIZE x 2 per launch, scripts/sym_w_sweep.sh) row by row 572 MB,
-        // strips of 12 / 7 / 4 / 3 columns 296 / 258 / 277 / 312 MB, the launch's duration the same within 0.5 % (it is MFMA-bound)
-        e.sym_w = ((int)grid.x + 7) >> 3;
-        grid = dim3(grid.x * (grid.x + 1) / 2);  // the lower triangle's tiles
-    }
-    // throughput regime (several tiles per compute unit and a full contraction per tile): compact 2-D patches per XCD.  Not for the
-    // triangular-aware gain GEMM: its tiles' work falls with the tile column, and strips of columns would load the XCDs unevenly.
-    e.order2d = (!e.sym && f->tune.gemm_order2d && !lowerB && (int)(grid.x * grid.y) >= 2 * cus) ? 1 : 0;
-#define GEMM_GO(TB, G, EP)                                                                                             \
-    hipLaunchKernelGGL((gemm_f32_mfma_kernel<TB, G, EP>), grid, dim3(256 * G), 0, s, M, N, K, alpha, A, lda, B, ldb, beta, \
-                       Cin, ldcin, C, ldc, flush, lowerB, e)
-    if (e.mode == 1) {
-        GEMM_GO(true, 1, 1);  // the Joseph GEMMs are always A * B^T
-    } else if (e.mode == 2) {
+    e.sym = p.sym, e.sym_w = p.sym_w, e.order2d = p.order2d;
+#define GEMM_GO(TB, G, EP)                                                                                                        \
+    hipLaunchKernelGGL((gemm_f32_mfma_kernel<TB, G, EP>), grid, block, 0, s, M, N, K, c.alpha, c.A, c.lda, c.B, c.ldb, c.beta, c.Cin, \
+                       c.ldcin, c.C, c.ldc, flush, lowerB, e)
+    if (e.mode == EPI_JOSEPH1) {
+        GEMM_GO(true, 1, 1);  // the P-update GEMMs are always A * B^T
+    } else if (e.mode == EPI_MEAN) {
         GEMM_GO(true, 1, 2);
-    } else if (e.mode == 3) {
+    } else if (e.mode == EPI_MEAN_PARTIAL) {
         GEMM_GO(true, 1, 3);
-    } else if (groups == 2) {
-        if (transB) GEMM_GO(true, 2, 0);
+    } else if (p.groups == 2) {
+        if (c.transB) GEMM_GO(true, 2, 0);
         else GEMM_GO(false, 2, 0);
     } else {
-        if (transB) GEMM_GO(true, 1, 0);
+        if (c.transB) GEMM_GO(true, 1, 0);
         else GEMM_GO(false, 1, 0);
     }
 #undef GEMM_GO
 }
-
-void launch_gemm(ekfvio_filter* f, int transB, int M, int N, int K, float alpha, const float* A, int lda, const float* B,
-                 int ldb, float beta, const float* Cin, int ldcin, float* C, int ldc, int flush, int lowerB,
-                 const GemmEpi* epi) {
-    launch_gemm_cfg(f, 0, transB, M, N, K, alpha, A, lda, B, ldb, beta, Cin, ldcin, C, ldc, flush, lowerB, epi);
-}
-
-// variant: 0 = production choice, 1 = 64x64 tiles / 256 threads, 2 = 64x64 / 512 threads, 32 / 48 / 64 = BM of gemm16_kernel
-void launch_gemm_variant(ekfvio_filter* f, int variant, int transB, int M, int N, int K, float alpha, const float* A, int lda,
-                         const float* B, int ldb, float beta, const float* Cin, int ldcin, float* C, int ldc, int flush,
-                         int lowerB) {
-    if (variant >= 32 && (!transB || K % 64 != 0)) variant = 1;
-    if (variant >= 32 && variant % 100 != 32 && variant % 100 != 48 && variant % 100 != 64) variant = 0;
-    launch_gemm_cfg(f, variant, transB, M, N, K, alpha, A, lda, B, ldb, beta, Cin, ldcin, C, ldc, flush, lowerB, nullptr);
-}
-

@@ -1,7 +1,9 @@
 // ekf_vio_amd/csrc/plan.h — everything that DECIDES: the run-time switches, the sizes a capacity implies, and the flow of one update.
 // Standard headers only (no HIP, no project header): integer arithmetic over a Tuning, a PlanShape and a row count, so the decision
-// table of the product is checked on a machine without a GPU (include/ekfvio_test_hooks.h, ekfvio_test_plan; tests/test_plan_cpu.py).
-// The launchers (chol.hip, ekf_kernels.hip, gemm.hip) execute an UpdatePlan; they do not decide.
+// table of the product is checked on a machine without a GPU (include/ekfvio_test_hooks.h: ekfvio_test_plan, ekfvio_test_gemm_plan,
+// ekfvio_test_predict_plan; tests/test_plan_cpu.py, tests/test_gemm_plan_cpu.py).
+// The launchers execute what is planned here, they do not decide: an UpdatePlan (chol.hip, ekf_kernels.hip: launch_update), a GemmPlan per GEMM
+// launch (gemm.hip: launch_gemm), a PredictPlan per process(dt) (ekf_kernels.hip: launch_predict).
 #ifndef EKFVIO_PLAN_H_
 #define EKFVIO_PLAN_H_
 #include <stddef.h>
@@ -150,9 +152,9 @@ struct PlanShape {
     bool latched_off = false;     // an aborted persistent sweep has retired the persistent launch for now (api.hip, sweep_abort_latch)
 };
 
-// ---- shared small decisions of the launchers -----------------------------------------------------------------------------------
-// The tile height launch_gemm forms C[MxN] = A * op(B) with: 32 / 48 / 64 = gemm16_kernel at the smallest height whose grid is still a
-// single wave of workgroups (latency regime; only A * B^T with K a multiple of 64), 0 = the 64 x 64 kernel (throughput regime).
+// ---- the launch of ONE GEMM, C[MxN] = beta Cin + alpha A op(B): decided HERE, executed by launch_gemm (gemm.hip) ---------------------
+// The tile height of A * op(B): 32 / 48 / 64 = gemm16_kernel at the smallest height whose grid is still a single wave of workgroups
+// (latency regime; only A * B^T with K a multiple of 64), 0 = the 64 x 64 kernel (throughput regime).
 inline int gemm_tiles(int bm, int M, int N) { return ((M + bm - 1) / bm) * ((N + 63) / 64); }
 inline int gemm_tile_height(int cus, int M, int N, int K, bool transB) {
     if (cus <= 0) cus = 256;
@@ -161,13 +163,105 @@ inline int gemm_tile_height(int cus, int M, int N, int K, bool transB) {
         if (gemm_tiles(bm, M, N) <= cus) return bm;
     return 0;
 }
-// true where launch_gemm forms A * B^T with the 64 x 64 kernel (more 64-row tiles than compute units): the regime in which GemmEpi::sym is heeded
+// true where A * B^T runs on the 64 x 64 kernel (more 64-row tiles than compute units): the regime in which GemmShape::sym is heeded
 inline bool gemm_throughput_regime(int cus, int M, int N, int K) { return gemm_tile_height(cus, M, N, K, true) == 0; }
-// would launch_gemm run A * B^T of this shape as ONE wave of gemm16_kernel workgroups with `extra` more workgroups still inside that wave?
-inline bool gemm_single_round_with(int cus, int M, int N, int K, int extra) {
-    const int bm = gemm_tile_height(cus, M, N, K, true);
-    return bm && gemm_tiles(bm, M, N) + extra <= (cus > 0 ? cus : 256);
+// What a GEMM does besides the product (GemmEpi::mode in common.h; the kernels' EPI template argument, so the values are fixed)
+enum GemmEpiMode { EPI_NONE = 0,
+                   EPI_JOSEPH1 = 1,        // T = Sigma - K (H Sigma), the first Joseph GEMM: also G = K R - T[:, idx]; output column n receives K y
+                   EPI_MEAN = 2,           // Sigma' = T + G K^T, the second Joseph GEMM: one more workgroup finishes the mean from column n of P
+                   EPI_MEAN_PARTIAL = 3 }; // Sigma' = T2 + K G'^T, the one GEMM of the T2 and Schur tails: the same with K y as per-block partial sums
+struct GemmShape {
+    int M = 0, N = 0, K = 0;
+    bool transB = false, lowerB = false;  // lowerB: B is lower triangular, the contraction starts at the tile's column
+    int epi = EPI_NONE;
+    bool mean = false;   // there is a mean to finish (GemmEpi::n > 0; the scratch launches of the profiler have none)
+    int lin_blocks = 0;  // asked for: workgroups that linearise for the next process(dt) (UpdatePlan::lin_blocks)
+    bool sym = false;    // asked for: the result is symmetric, its lower triangle's tiles may be formed alone and mirrored
+    int variant = 0;     // test hooks only: 0 = by shape, 1 / 2 = the 64 x 64 kernel with 256 / 512 threads, 32 / 48 / 64 = gemm16_kernel with that
+                         // tile height, + 100 = with one wavefront per SIMD
+};
+struct GemmPlan {
+    bool k16 = false;            // gemm16_kernel<bm, wps, epi>; false: gemm_f32_mfma_kernel<transB, groups, epi>
+    int bm = 64, wps = 2, groups = 1;
+    int tiles_x = 0, tiles_y = 0;  // tiles of bm x 64 over C
+    int tiles = 0;               // ... that the launch forms: tiles_x * tiles_y, or the lower triangle's with sym
+    int grid_x = 0, grid_y = 1;
+    bool mean_wg = false;        // gemm16_kernel: one workgroup behind the tiles' finishes the mean (gemm16_finish_mean)
+    int lin_blocks = 0;          // ... and this many behind it linearise: what was asked for where it fits one wave of workgroups, else 0
+    int mean_keep = 0;           // ... in which case the mean is left to them (GemmEpi::mean_keep)
+    int sym = 0, sym_w = 1;      // 64 x 64 kernel: sym as heeded, in strips of sym_w tile columns
+    int order2d = 0;             // 64 x 64 kernel: each XCD's run of tiles is a compact 2-D patch
+    int threads() const { return 256 * (k16 ? wps : groups); }
+};
+inline GemmPlan plan_gemm(const Tuning& t, int cus, const GemmShape& s) {
+    GemmPlan p;
+    if (cus <= 0) cus = 256;
+    int v = s.variant;
+    if (v >= 32 && (!s.transB || s.K % 64 != 0)) v = 1;  // gemm16_kernel is A * B^T over whole 64-deep K-tiles
+    if (v >= 32 && v % 100 != 32 && v % 100 != 48 && v % 100 != 64) v = 0;
+    if (v == 0) v = std::max(1, gemm_tile_height(cus, s.M, s.N, s.K, s.transB));
+    p.tiles_y = (s.N + 63) / 64;
+    if (v >= 32) {
+        p.k16 = true, p.bm = v % 100;
+        p.wps = (v >= 100 && s.epi == EPI_NONE) ? 1 : 2;  // (one wavefront per SIMD: micro-benchmark only)
+        p.tiles_x = (s.M + p.bm - 1) / p.bm;
+        p.tiles = p.tiles_x * p.tiles_y;
+        p.mean_wg = (s.epi == EPI_MEAN || s.epi == EPI_MEAN_PARTIAL) && s.mean;
+        // the ONE fit test of the riding linearisation (plan_update asks it through this function): tiles, mean and linearising workgroups are one wave
+        if (s.epi == EPI_MEAN_PARTIAL && s.mean && p.tiles + 1 + s.lin_blocks <= cus) p.lin_blocks = s.lin_blocks;
+        p.mean_keep = p.lin_blocks > 0 ? 1 : 0;
+        p.grid_x = p.tiles + (p.mean_wg ? 1 : 0) + p.lin_blocks;
+        return p;
+    }
+    p.bm = 64, p.wps = 1;
+    p.groups = (v == 2 && s.epi == EPI_NONE) ? 2 : 1;
+    p.tiles_x = (s.M + 63) / 64;
+    p.sym = (s.sym && t.sym_joseph && s.epi == EPI_MEAN && s.M == s.N && s.transB) ? 1 : 0;
+    if (p.sym) {
+        // strips of ceil(tn / 8) tile columns, as order2d's: measured at tn = 49 (FETCH_SIZE x 2 per launch, scripts/sym_w_sweep.sh) row by row 572 MB,
+        // strips of 12 / 7 / 4 / 3 columns 296 / 258 / 277 / 312 MB, the launch's duration the same within 0.5 % (it is MFMA-bound)
+        p.sym_w = (p.tiles_x + 7) >> 3;
+        p.tiles = p.grid_x = p.tiles_x * (p.tiles_x + 1) / 2;  // a 1-D grid over the lower triangle's tiles
+    } else {
+        p.grid_x = p.tiles_x, p.grid_y = p.tiles_y;
+        p.tiles = p.tiles_x * p.tiles_y;
+    }
+    // throughput regime (several tiles per compute unit and a full contraction per tile): compact 2-D patches per XCD.  Not for the
+    // triangular-aware gain GEMM: its tiles' work falls with the tile column, and strips of columns would load the XCDs unevenly.
+    p.order2d = (!p.sym && t.gemm_order2d && !s.lowerB && p.tiles >= 2 * cus) ? 1 : 0;
+    return p;
 }
+// EXECUTED flops of a planned GEMM: the mirrored form multiplies for the lower triangle's 64 x 64 tiles only
+inline double gemm_executed_flops(const GemmShape& s, const GemmPlan& p) {
+    return p.sym ? 2.0 * 64.0 * 64.0 * s.K * p.tiles : 2.0 * s.M * (double)s.N * s.K;
+}
+
+// ---- process(dt)'s launches: decided HERE, executed by launch_predict (ekf_kernels.hip) ---------------------------------------------
+#define PREDICT_PT 16  // landmarks per tile side of predict_fused_kernel (landmark x landmark tiles)
+#define PREDICT_PC 3   // landmarks per base-row / base-column workgroup (3 * PREDICT_PC <= 64)
+struct PredictPlan {
+    bool dense = false;         // F formed densely, two GEMMs and add_noise_flush_kernel; else predict_fused_kernel
+    bool pre = false;           // the previous update's last GEMM has linearised for this step (GemmEpi::lin_blocks): nothing linearises
+    bool lin_inside = false;    // predict_fused_kernel<true> forms the Jacobian blocks itself
+    bool lin_in_front = false;  // a linearize_kernel launch in front
+    int ts = 0, chunks = 0;     // predict_fused_kernel: tiles per side, base-row / base-column workgroups
+    // the measurement bookkeeping rides in predict_fused_kernel as one more workgroup (else in the linearize_kernel launch in front)
+    bool book_rides() const { return lin_inside || pre; }
+    int grid(bool bookkeeping) const { return ts * ts + 1 + 2 * chunks + (bookkeeping && book_rides() ? 1 : 0); }
+};
+// prelinearized: ekfvio_filter::prelinearized, the previous GEMM linearised
+inline PredictPlan plan_predict(const Tuning& t, const PlanShape& s, bool prelinearized) {
+    PredictPlan p;
+    p.dense = s.dense_predict;
+    p.pre = prelinearized && !p.dense;
+    p.ts = (s.N + PREDICT_PT - 1) / PREDICT_PT, p.chunks = (s.N + PREDICT_PC - 1) / PREDICT_PC;
+    // inside while the landmark tiles are a few rounds of workgroups: with thousands of tiles (N = 1024) the Jacobian blocks formed
+    // 2 * 64 times over cost more than the launch they save
+    p.lin_inside = !p.pre && !p.dense && t.fuse_linearize && p.ts * p.ts <= 4 * s.num_cus;
+    p.lin_in_front = !p.lin_inside && !p.pre;
+    return p;
+}
+
 // The gather's element workgroups (gather_body.inc): gx per GC*GCI measurement columns; the Wt tiles come behind them
 inline int gather_gx(int ldp, int m_pad) { return (std::max(ldp, m_pad) + 255) / 256; }
 inline int gather_element_wgs(int ldp, int m_pad) { return gather_gx(ldp, m_pad) * ((m_pad + GC * GCI - 1) / (GC * GCI)); }
@@ -335,6 +429,13 @@ inline UpdatePlan plan_raw_sweep(const Tuning& t, const PlanShape& s, int m_pad,
     return p;
 }
 
+// The one GEMM of the T2 and Schur tails, Sigma' = T2 + K G'^T over n x n x m_pad, as the update itself launches it: the mean is finished from the
+// partial sums of K y, and lin_blocks workgroups are asked to linearise (plan_update asks plan_gemm whether they fit; launch_update launches this shape)
+inline GemmShape tail_gemm_shape(int n, int m_pad, int lin_blocks) {
+    GemmShape g;
+    g.M = g.N = n, g.K = m_pad, g.transB = true, g.epi = EPI_MEAN_PARTIAL, g.mean = true, g.lin_blocks = lin_blocks;
+    return g;
+}
 // m_on_device: the host does not know the row count; next_dt >= 0: the next process(dt)'s dt of a device-resident run (UpdateInputs)
 inline UpdatePlan plan_update(const Tuning& t, const PlanShape& s, int m, bool m_on_device = false, float next_dt = -1.f, bool recoverable = true) {
     UpdatePlan p;
@@ -365,8 +466,8 @@ inline UpdatePlan plan_update(const Tuning& t, const PlanShape& s, int m, bool m
     // a device-resident run (capture_steps): the next process(dt)'s linearisation and mean propagation ride in the one GEMM's launch, in workgroups
     // of their own behind the tiles' (K y is final: the gain tiles' partial sums); launch_predict then only propagates Sigma
     const int lin_blocks = (s.N + LIN_LM - 1) / LIN_LM + 1;
-    if (next_dt >= 0.f && t.lin_overlap && !s.dense_predict && t.fuse_linearize && gemm_single_round_with(s.num_cus, n, n, m_pad, 1 + lin_blocks))
-        p.lin_blocks = lin_blocks;
+    if (next_dt >= 0.f && t.lin_overlap && !s.dense_predict && t.fuse_linearize)
+        p.lin_blocks = plan_gemm(t, s.num_cus, tail_gemm_shape(n, m_pad, lin_blocks)).lin_blocks;  // (all of them or none: they must fit the GEMM's one wave)
     return p;
 }
 #endif  // EKFVIO_PLAN_H_

@@ -48,6 +48,16 @@ EKFVIO_API int ekfvio_test_cholesky_solve(ekfvio_filter* f, int32_t m, int32_t n
  * fused_gather, with_wt, gain (GainBy), tail (UpdateTail), t2_skip, t2_by_sweep, compact, lin_blocks. */
 EKFVIO_API int ekfvio_test_plan(int32_t num_cus, int32_t max_features, int32_t N, int32_t m, int32_t m_on_device, int32_t sole_handle,
                                 int32_t latched_off, int32_t dense_predict, float next_dt, int32_t plan[12]);
+/* How ONE GEMM would be launched (csrc/plan.h, plan_gemm), likewise: epi is a GemmEpiMode (0 .. 3), mean: there is a mean to finish, lin_blocks
+ * and sym as asked for, variant as ekfvio_test_gemm's.  plan[18] = gemm16_kernel (0: the 64 x 64 kernel), bm, wavefronts per SIMD (gemm16_kernel),
+ * groups (64 x 64 kernel), threads, tiles_x, tiles_y, tiles formed, grid x, grid y, mean workgroup, lin_blocks kept, mean_keep, sym heeded, sym_w,
+ * order2d; and gemm_throughput_regime, gemm_tile_height of the shape. */
+EKFVIO_API int ekfvio_test_gemm_plan(int32_t num_cus, int32_t M, int32_t N, int32_t K, int32_t transB, int32_t lowerB, int32_t epi, int32_t mean,
+                                     int32_t lin_blocks, int32_t sym, int32_t variant, int32_t plan[18]);
+/* How process(dt) would be launched (csrc/plan.h, plan_predict) with N landmarks.  plan[8] = dense, pre, linearises inside predict_fused_kernel,
+ * linearize_kernel in front, ts, chunks, the bookkeeping rides in predict_fused_kernel, its grid (with the bookkeeping workgroup where asked). */
+EKFVIO_API int ekfvio_test_predict_plan(int32_t num_cus, int32_t N, int32_t dense_predict, int32_t prelinearized, int32_t bookkeeping,
+                                        int32_t plan[8]);
 /* The grid and the flag layout of the persistent sweep launch that plan selects (csrc/plan.h, PersistGrid / PersistFlags), likewise without a
  * handle or a device.  out[10] = total() (0: the planned sweep is not persistent, nothing else is filled), kind (PersistGridKind), owners,
  * the offsets of ready, fin, pan and the abort word, words(), zero_words(), FilterDims::sweep_sync_words.  roles (may be NULL; room for

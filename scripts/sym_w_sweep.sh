@@ -1,6 +1,6 @@
 #!/bin/bash
 # Tile order of the mirrored second Joseph GEMM (gemm.hip, GemmEpi::sym_w): steps/s, the kernel's mean duration and its FETCH_SIZE per strip width.
-# (needs the EKFVIO_SYM_W experiment switch of its commit in gemm.hip launch_gemm_cfg; kept as the record of how the strip width was chosen)
+# (needs the EKFVIO_SYM_W experiment switch of its commit in gemm.hip launch_gemm_cfg (today plan.h, plan_gemm); kept as the record of how the strip width was chosen)
 ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$ROOT/gpurun_out
 cd /tmp && export TMPDIR=/tmp
