@@ -62,8 +62,6 @@ int count_rows(const uint8_t* pass, int N) {
 }
 }  // namespace
 
-static void drop_graph(ekfvio_filter* f);
-
 static const char* kProfNames[PC_COUNT] = {"linearize",   "predict_structured", "gemm_predict", "gather",
                                            "cholesky",    "solve",              "gemm_update",  "update_misc",
                                            "klt_pyramid", "klt_track"};
@@ -268,6 +266,30 @@ static std::atomic<int>* live_registry() {
     return reg;
 }
 int live_handles_on(int device) { return (device >= 0 && device < 64) ? live_registry()[device].load(std::memory_order_relaxed) : 2; }
+
+void drop_graph(ekfvio_filter* f) {
+    for (GraphCache::Entry& e : f->graphs.g) {
+        if (e.exec) (void)hipGraphExecDestroy(e.exec);
+        e = GraphCache::Entry();
+    }
+}
+// What `body` enqueues on the handle's stream as an executable graph: the stream is drained, the launches are recorded (thread-local capture:
+// nothing runs) and instantiated.  Whatever host state the body's launchers mirror of the device is the caller's to put back.
+template <class Body>
+static int capture_graph(ekfvio_filter* f, hipGraphExec_t* out, Body body) {
+    hipGraph_t g = nullptr;
+    HIP_TRY(f, hipStreamSynchronize(f->stream));
+    HIP_TRY(f, hipStreamBeginCapture(f->stream, hipStreamCaptureModeThreadLocal));
+    body();
+    const hipError_t ce = hipStreamEndCapture(f->stream, &g);
+    if (ce != hipSuccess || !g) {
+        f->last_error = std::string("graph capture: ") + hipGetErrorString(ce);
+        return EKFVIO_EDEVICE;
+    }
+    HIP_TRY(f, hipGraphInstantiate(out, g, nullptr, nullptr, 0));
+    (void)hipGraphDestroy(g);
+    return EKFVIO_OK;
+}
 
 extern "C" {
 
@@ -685,28 +707,6 @@ int ekfvio_upload_measurements(ekfvio_filter* f, int32_t frames, const float* z,
     return EKFVIO_OK;
 }
 
-// steps per captured graph: even (the mean / covariance ping-pong is back in its starting orientation)
-// and large enough to amortise the ~8 us a hipGraphLaunch costs between replays
-#ifndef EKF_GRAPH_STEPS
-#define EKF_GRAPH_STEPS 8
-#endif
-#define EKF_GRAPH_STEPS_BIG 32  // second, longer graph for runs of at least two of them (+0.6 % steps/s at N=256)
-
-static void drop_graph(ekfvio_filter* f) {
-    if (f->step_graph) {
-        (void)hipGraphExecDestroy(f->step_graph);
-        f->step_graph = nullptr;
-    }
-    if (f->step_graph_big) {
-        (void)hipGraphExecDestroy(f->step_graph_big);
-        f->step_graph_big = nullptr;
-    }
-    if (f->step_graph_pair) {
-        (void)hipGraphExecDestroy(f->step_graph_pair);
-        f->step_graph_pair = nullptr;
-    }
-}
-
 // An update of ekfvio_run_uploaded: frame i of the uploaded sequence, or the one the device-side counter names.  These launches and captures
 // carry the long wait bound (plan.h, Tuning::sweep_wait_ticks): nothing can run their updates again
 static UpdateInputs uploaded_update(ekfvio_filter* f, int m, int i, int* counter) {
@@ -716,49 +716,56 @@ static UpdateInputs uploaded_update(ekfvio_filter* f, int m, int i, int* counter
     in.recoverable = false;
     return in;
 }
-// Captures `steps` filter steps (process + update with m measurement rows each, bookkeeping driven by the device-side
-// frame counter) into an executable graph.  `steps` is even: the mean / covariance ping-pong nets to zero.
-// *pre_out: how many of its process(dt) launches were captured pre-linearised (counted per replay by ekfvio_run_uploaded).
-static int capture_steps(ekfvio_filter* f, int steps, int m, float dt, int* counter, hipGraphExec_t* out, int* pre_out) {
-    hipGraph_t g = nullptr;
-    HIP_TRY(f, hipStreamSynchronize(f->stream));
+// One filter step of the uploaded sequence, enqueued or captured: process(dt) and the update with m measurement rows of frame i, or of the frame
+// the device-side counter names.  The three arguments behind it are a captured step's; an eager one leaves them alone.
+//   book_rides     the frame's measurement bookkeeping rides in the process(dt) launch
+//   prelinearized  the step in front of this one linearised for it (its StepDone::linearised_next)
+//   next_dt        >= 0: this step's update may linearise for the step behind it (round 6; plan_update decides whether the shape allows it)
+struct StepDone {
+    bool pre;              // process(dt) went out pre-linearised
+    bool linearised_next;  // the update's last GEMM linearised for the next process(dt)
+};
+static StepDone enqueue_uploaded_step(ekfvio_filter* f, float dt, int m, int i, int* counter, bool book_rides = false, bool prelinearized = false,
+                                      float next_dt = -1.f) {
+    BookArgs bk;
+    if (book_rides) bk = make_book_args(f, m, f->seq_z, f->seq_R, f->seq_pass, counter);
+    StepDone d;
+    d.pre = launch_predict(f, dt, book_rides ? &bk : nullptr, prelinearized);
+    UpdateInputs in = uploaded_update(f, m, i, counter);
+    in.bookkeeping_done = book_rides;
+    in.next_dt = next_dt;
+    d.linearised_next = launch_update(f, in).linearised_next;
+    return d;
+}
+// Captures `steps` filter steps (m measurement rows each, bookkeeping driven by the device-side frame counter) into entry e of the handle's
+// cache.  `steps` is even: the mean / covariance ping-pong nets to zero (the captured launches do not execute).
+static int capture_steps(ekfvio_filter* f, GraphCache::Entry* e, int steps, int m, float dt, int* counter) {
     // sweep_flags_clean mirrors DEVICE state on the host, and a capture records launches without running them: the
     // graph must not inherit the mirror's value of the moment it was captured at -- its first sweep always zeroes the flags itself (one
     // memset node per replay) -- and the mirror must come out of the capture as it went in.  What a replay leaves behind is recorded
-    // separately (graph_leaves_flags_clean) and applied after every hipGraphLaunch.
+    // with the cache (leaves_flags_clean) and applied after the replays.
     const bool mirror = f->sweep_flags_clean;
     f->sweep_flags_clean = false;
-    const long long pre0 = f->prelinearized_steps;  // (nothing runs here either: launch_predict's counts of the capture go to *pre_out)
-    HIP_TRY(f, hipStreamBeginCapture(f->stream, hipStreamCaptureModeThreadLocal));
+    // the bookkeeping rides in the process(dt) launch -- unless the handle gates its measurements: the gate reads the PROPAGATED state, so
+    // gate + bookkeeping are a launch of their own between process(dt) and the update (launch_update)
     const bool gate = f->gate_chi2 > 0.f;
-    for (int k = 0; k < steps; k++) {
-        // the frame's measurement bookkeeping rides in the process(dt) launch -- unless the handle gates its measurements: the gate reads the
-        // PROPAGATED state, so gate + bookkeeping are a launch of their own between process(dt) and the update (launch_update)
-        const BookArgs bk = make_book_args(f, m, f->seq_z, f->seq_R, f->seq_pass, counter);
-        launch_predict(f, dt, gate ? nullptr : &bk);
-        // round 6: inside a graph the next step's dt is known -- every update but the graph's last lets its last GEMM linearise for the step
-        // behind it (plan_update decides whether the shape allows it; the graph's last update leaves the next replay's first step to
-        // linearise for itself, so a graph needs nothing from whatever ran before it)
-        UpdateInputs in = uploaded_update(f, m, 0, counter);
-        in.bookkeeping_done = !gate;
-        in.next_dt = (k + 1 < steps) ? dt : -1.f;
-        launch_update(f, in);
-    }
-    f->prelinearized = false;
-    *pre_out = (int)(f->prelinearized_steps - pre0);
-    f->prelinearized_steps = pre0;
-    hipError_t ce = hipStreamEndCapture(f->stream, &g);
-    f->graph_leaves_flags_clean = f->sweep_flags_clean;  // (the same for every step count: the last update's last GEMM decides)
+    e->steps = steps, e->pre = 0;
+    const int rc = capture_graph(f, &e->exec, [&] {
+        // inside a graph the next step's dt is known: every update but the graph's last lets its last GEMM linearise for the step behind it
+        // (the graph's last update leaves the next replay's first step to linearise for itself, so a graph needs nothing from whatever ran
+        // before it)
+        StepDone d = {false, false};
+        for (int k = 0; k < steps; k++) {
+            d = enqueue_uploaded_step(f, dt, m, 0, counter, !gate, d.linearised_next, (k + 1 < steps) ? dt : -1.f);
+            e->pre += d.pre ? 1 : 0;
+        }
+    });
+    f->graphs.leaves_flags_clean = f->sweep_flags_clean;
     f->sweep_flags_clean = mirror;
-    if (ce != hipSuccess || !g) {
-        f->last_error = std::string("graph capture: ") + hipGetErrorString(ce);
-        return EKFVIO_EDEVICE;
-    }
-    HIP_TRY(f, hipGraphInstantiate(out, g, nullptr, nullptr, 0));
-    (void)hipGraphDestroy(g);
-    return EKFVIO_OK;
+    return rc;
 }
 
+// Executes a RunPlan (plan.h, plan_run): it does not decide
 int ekfvio_run_uploaded(ekfvio_filter* f, int32_t first, int32_t count, float dt) {
     if (!f || f->seq_frames <= 0 || f->seq_N != f->N || count < 0 || first < 0 || !(dt >= 0.f)) return EKFVIO_EINVAL;
     f->out_fresh = false;
@@ -767,61 +774,43 @@ int ekfvio_run_uploaded(ekfvio_filter* f, int32_t first, int32_t count, float dt
     // sweep once gave up keeps the per-step sweep for its graph replays until ekfvio_update / ekfvio_step_image, which CAN recover,
     // have tried the persistent launch again and it has come through; with a permanent obstacle (a compute-unit mask, a co-tenant
     // process) a retry from here would skip a replay's remaining updates every 2 .. 64 s for the handle's whole life)
-    int s = 0;
-    // hipGraph path: the same measurement-row count for every frame (one launch geometry),
-    // profiling off.  The bookkeeping kernel reads the frame index from a device counter.
-    // (count == 0 only prepares: the graphs are captured, nothing runs — callers that time a run call this first)
-    // (a gated handle's geometry is m = 2N, count on the device, for every frame in which any landmark passed: launch_update)
-    const bool gate = f->gate_chi2 > 0.f;
-    auto geometry = [&](int i) { return gate && f->seq_m[i] > 0 ? 2 * f->N : f->seq_m[i]; };
-    bool uniform = !f->prof_on && (count >= 2 || count == 0);
-    for (int i = 0; uniform && i < f->seq_frames; i++) uniform = geometry(i) == geometry(0);
-    if (uniform) {
-        const int m = geometry(0);
-        int* counter = f->info + 1;
-        // by value (a copy from a host scalar could be overtaken by the next call's write to that scalar)
-        HIP_TRY(f, hipMemsetD32Async((hipDeviceptr_t)counter, first % f->seq_frames, 1, f->stream));
-        if (!f->step_graph || f->graph_N != f->N || f->graph_m != m || f->graph_dt != dt || f->graph_mu != f->mu || f->graph_P != f->P ||
-            f->graph_seq != f->seq_z || f->graph_frames != f->seq_frames || f->graph_sole != (live_handles_on(f->device) <= 1)) {
-            drop_graph(f);
-            int rc = capture_steps(f, EKF_GRAPH_STEPS, m, dt, counter, &f->step_graph, &f->graph_pre);
-            if (rc != EKFVIO_OK) return rc;
-            rc = capture_steps(f, 2, m, dt, counter, &f->step_graph_pair, &f->graph_pre_pair);
-            if (rc != EKFVIO_OK) return rc;
-            f->graph_N = f->N; f->graph_m = m; f->graph_dt = dt; f->graph_mu = f->mu; f->graph_P = f->P; f->graph_seq = f->seq_z;
-            f->graph_frames = f->seq_frames;
-            f->graph_sole = live_handles_on(f->device) <= 1;  // (decides which sweep the captured steps contain)
-            // the captured launches did not execute: the pointer swaps of launch_predict netted to zero
-        }
-        // captured together with the short graph (i.e. in a caller's warm-up call) whenever the uploaded sequence is
-        // long enough to make runs of that length plausible, never lazily inside a long run
-        if (f->seq_frames >= 2 * EKF_GRAPH_STEPS_BIG && !f->step_graph_big) {
-            int rc = capture_steps(f, EKF_GRAPH_STEPS_BIG, m, dt, counter, &f->step_graph_big, &f->graph_pre_big);
-            if (rc != EKFVIO_OK) return rc;
-        }
-        // (a replay runs no host code: its steps and its pre-linearised ones are counted here, ekfvio_get_counters [6] and [7])
-        auto replay = [&](hipGraphExec_t g, int steps, int pre) {
-            const hipError_t e = hipGraphLaunch(g, f->stream);
-            if (e == hipSuccess) s += steps, f->graph_steps += steps, f->prelinearized_steps += pre;
-            return e;
-        };
-        if (f->step_graph_big)
-            while (s + EKF_GRAPH_STEPS_BIG <= count) HIP_TRY(f, replay(f->step_graph_big, EKF_GRAPH_STEPS_BIG, f->graph_pre_big));
-        while (s + EKF_GRAPH_STEPS <= count) HIP_TRY(f, replay(f->step_graph, EKF_GRAPH_STEPS, f->graph_pre));
-        while (s + 2 <= count) HIP_TRY(f, replay(f->step_graph_pair, 2, f->graph_pre_pair));
-        if (s > 0) f->sweep_flags_clean = f->graph_leaves_flags_clean;  // what the last replayed step left in device memory
-        for (; s < count; s++) {  // an odd last step, eager, same counter-driven bookkeeping
-            launch_predict(f, dt);
-            launch_update(f, uploaded_update(f, m, 0, counter));
+    const RunPlan run = plan_run(f->seq_m.data(), f->seq_frames, f->N, f->gate_chi2 > 0.f, f->prof_on, count);
+    if (!run.graphs) {
+        for (int s = 0; s < run.eager; s++) {
+            const int i = (first + s) % f->seq_frames;
+            enqueue_uploaded_step(f, dt, f->seq_m[i], i, nullptr);
         }
         HIP_TRY(f, hipGetLastError());
         return EKFVIO_OK;
     }
-    for (; s < count; s++) {
-        const int i = (first + s) % f->seq_frames;
-        launch_predict(f, dt);
-        launch_update(f, uploaded_update(f, f->seq_m[i], i, nullptr));
+    // the bookkeeping kernel reads the frame index from a device counter, set here
+    // by value (a copy from a host scalar could be overtaken by the next call's write to that scalar)
+    int* counter = f->info + 1;
+    HIP_TRY(f, hipMemsetD32Async((hipDeviceptr_t)counter, first % f->seq_frames, 1, f->stream));
+    GraphCache& c = f->graphs;
+    GraphKey key;
+    key.N = f->N, key.m = run.m, key.frames = f->seq_frames, key.dt = dt, key.mu = f->mu, key.P = f->P, key.seq = f->seq_z;
+    key.sole = live_handles_on(f->device) <= 1;
+    if (!(c.key == key)) {
+        drop_graph(f);
+        c.key = key;
     }
+    // whatever is missing is captured now, the long graph together with the others (i.e. in a caller's warm-up call), never lazily inside a long run
+    for (int g = 0; g < RUN_GRAPHS; g++)
+        if (run_graph_used(g, f->seq_frames) && !c.g[g].exec) {
+            const int rc = capture_steps(f, &c.g[g], run_graph_steps(g), run.m, dt, counter);
+            if (rc != EKFVIO_OK) return rc;
+        }
+    // (a replay runs no host code: its steps and its pre-linearised ones are counted here, ekfvio_get_counters [6] and [7])
+    bool replayed = false;
+    for (int g = 0; g < RUN_GRAPHS; g++)
+        for (int r = 0; r < run.replays[g]; r++) {
+            HIP_TRY(f, hipGraphLaunch(c.g[g].exec, f->stream));
+            f->graph_steps += c.g[g].steps, f->prelinearized_steps += c.g[g].pre;
+            replayed = true;
+        }
+    if (replayed) f->sweep_flags_clean = c.leaves_flags_clean;  // what the last replayed step left in device memory
+    for (int s = 0; s < run.eager; s++) enqueue_uploaded_step(f, dt, run.m, 0, counter);  // an odd last step, same counter-driven bookkeeping
     HIP_TRY(f, hipGetLastError());
     return EKFVIO_OK;
 }
@@ -864,19 +853,11 @@ int ekfvio_profile_update_gemms(ekfvio_filter* f, int32_t reps, double* avg_laun
     if (!f || reps <= 0 || !avg_launch_us) return EKFVIO_EINVAL;
     if (f->last_m <= 0 || f->N <= 0) return EKFVIO_ESTATE;
     HIP_TRY(f, hipSetDevice(f->device));
-    HIP_TRY(f, hipStreamSynchronize(f->stream));
-    hipGraph_t g = nullptr;
     hipGraphExec_t ge = nullptr;
-    HIP_TRY(f, hipStreamBeginCapture(f->stream, hipStreamCaptureModeThreadLocal));
     double last_flops = 0;
-    const int per_rep = launch_update_gemms_scratch(f, plan_update(f, f->last_m), reps, &last_flops);
-    hipError_t ce = hipStreamEndCapture(f->stream, &g);
-    if (ce != hipSuccess || !g) {
-        f->last_error = std::string("graph capture: ") + hipGetErrorString(ce);
-        return EKFVIO_EDEVICE;
-    }
-    HIP_TRY(f, hipGraphInstantiate(&ge, g, nullptr, nullptr, 0));
-    (void)hipGraphDestroy(g);
+    int per_rep = 0;
+    const int rc = capture_graph(f, &ge, [&] { per_rep = launch_update_gemms_scratch(f, plan_update(f, f->last_m), reps, &last_flops); });
+    if (rc != EKFVIO_OK) return rc;
     HIP_TRY(f, hipGraphLaunch(ge, f->stream));  // warm-up
     HIP_TRY(f, hipEventRecord(f->ev0, f->stream));
     HIP_TRY(f, hipGraphLaunch(ge, f->stream));
@@ -1249,6 +1230,14 @@ int ekfvio_test_predict_plan(int32_t num_cus, int32_t N, int32_t dense_predict, 
     const PredictPlan p = plan_predict(tuning_from_env(), s, prelinearized != 0);
     const int32_t out[8] = {p.dense, p.pre, p.lin_inside, p.lin_in_front, p.ts, p.chunks, p.book_rides(), p.grid(bookkeeping != 0)};
     std::copy(out, out + 8, plan);
+    return EKFVIO_OK;
+}
+// ... and plan_run for ekfvio_run_uploaded(first, count, dt) over `frames` uploaded frames of rows[i] measurement rows
+int ekfvio_test_run_plan(int32_t N, int32_t gated, int32_t profiling, int32_t frames, const int32_t* rows, int32_t count, int32_t out[6]) {
+    if (!out || !rows || N < 0 || frames <= 0 || count < 0) return EKFVIO_EINVAL;
+    const RunPlan p = plan_run(rows, frames, N, gated != 0, profiling != 0, count);
+    const int32_t res[6] = {p.graphs, p.m, p.replays[0], p.replays[1], p.replays[2], p.eager};
+    std::copy(res, res + 6, out);
     return EKFVIO_OK;
 }
 

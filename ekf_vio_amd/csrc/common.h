@@ -86,6 +86,31 @@ struct RectifyKey {
     int w, h;
 };
 
+// The captured step graphs of a device-resident run (api.hip, ekfvio_run_uploaded executes a RunPlan of plan.h with them).  A graph holds an
+// even number of filter steps: the mean / covariance ping-pong is back in its starting orientation behind a replay.
+// GraphKey: the VALUES the captured launches depend on; a run whose key differs drops all graphs and captures again.  Events that change a
+// captured launch -- the gate, the latch and its retry, a test hook's arguments, a new upload, a removal -- call drop_graph instead.
+struct GraphKey {
+    int N = -1, m = -1, frames = -1;  // landmarks, launch geometry (RunPlan::m), frames of the uploaded sequence
+    bool sole = true;                 // captured while this was the device's only handle (decides which sweep the captured steps contain)
+    float dt = -1.f;                  // compared exactly
+    const float *mu = nullptr, *P = nullptr;  // orientation of the mean / covariance ping-pong at capture time
+    const void* seq = nullptr;        // the uploaded sequence (seq_z)
+    bool operator==(const GraphKey& o) const {
+        return N == o.N && m == o.m && frames == o.frames && sole == o.sole && dt == o.dt && mu == o.mu && P == o.P && seq == o.seq;
+    }
+};
+struct GraphCache {
+    struct Entry {
+        hipGraphExec_t exec = nullptr;
+        int steps = 0;  // filter steps per replay (plan.h, run_graph_steps)
+        int pre = 0;    // ... of which this many process(dt) launches were captured pre-linearised: a replay runs no host code (prelinearized_steps)
+    };
+    GraphKey key;
+    Entry g[RUN_GRAPHS];  // longest first, as RunPlan::replays
+    bool leaves_flags_clean = false;  // ekfvio_filter::sweep_flags_clean as a replay leaves it (the same for every entry: the last update's last GEMM decides)
+};
+
 struct ekfvio_filter {
     ekfvio_config cfg;
     int device = 0;
@@ -130,8 +155,6 @@ struct ekfvio_filter {
     int* sweep_sync = nullptr; // flags of the persistent sweep, laid out by plan.h's PersistFlags (sweep_sync_words ints)
     size_t sweep_sync_words = 0;
     bool sweep_latched_off = false;  // an aborted persistent sweep has retired the persistent launch (sweep_abort_latch sets it, sweep_maybe_retry clears it)
-    bool prelinearized = false;   // the update's last GEMM linearised for the next process(dt) (UpdateInputs::next_dt): FA / FB / FD / mu_next hold its Jacobian
-                                  // blocks and propagated mean (launch_predict then skips its own); Tuning::lin_overlap
     long long persistent_sweeps = 0;  // sweeps enqueued (or captured) as chol_persist_kernel: ekfvio_test_persistent_sweeps
     long long schur_sweeps = 0;       // sweeps enqueued with Sigma and the gain as Schur tiles (EKFVIO_SCHUR=1): ekfvio_test_sweep_counts
     long long sweep_recoveries = 0;   // updates run again with the per-step sweep behind an aborted persistent launch
@@ -145,7 +168,6 @@ struct ekfvio_filter {
     double sweep_retry_pause_s = 0.0;  // (its first value: Tuning::sweep_retry_first_s)
     int sweep_probation = 0;           // > 0: clean persistent sweeps still to come behind a retry before sweep_retry_pause_s starts over (api.hip)
     std::chrono::steady_clock::time_point sweep_retry_at;
-    bool graph_leaves_flags_clean = false;  // sweep_flags_clean as a replay of the captured step graphs leaves it (api.hip, capture_steps)
     bool sweep_flags_clean = false;   // the persistent sweep's flags are zero for the launch enqueued next (zeroed by the last GEMM of the
                                       // previous update); otherwise gather_potrf_kernel zeroes them in front, or launch_update has a memset enqueued
     bool persist_attr_set = false;
@@ -153,7 +175,7 @@ struct ekfvio_filter {
     bool gather_attr_set = false;
     long long t2_updates = 0;  // updates enqueued (or captured) with the T2 flow: ONE P-update GEMM behind the sweep (ekfvio_get_counters [5])
     long long graph_steps = 0;          // filter steps enqueued as graph replays (ekfvio_run_uploaded; ekfvio_get_counters [6])
-    long long prelinearized_steps = 0;  // process(dt) launches, replayed or eager, that found their linearisation done by the previous update's GEMM ([7])
+    long long prelinearized_steps = 0;  // replayed process(dt) launches that found their linearisation done by the previous update's GEMM ([7]; GraphCache::Entry::pre)
     int num_cus = 0;
     int last_m = 0;            // measurement rows of the most recent update (shape of its GEMMs)
     long long* sweep_dbg = nullptr;  // [512] s_memtime stamps of the persistent sweep (diagnostic; null = off)
@@ -235,18 +257,7 @@ struct ekfvio_filter {
     double t_stamp = 0;
     bool have_stamp = false;
 
-    // --- hipGraph replay of device-resident sequences (an even number of steps per graph: the mean
-    //     ping-pong mu <-> mu_next is back in its starting orientation after an even count) ---
-    hipGraphExec_t step_graph = nullptr;      // EKF_GRAPH_STEPS filter steps
-    hipGraphExec_t step_graph_big = nullptr;  // EKF_GRAPH_STEPS_BIG filter steps (long runs: fewer graph launches)
-    hipGraphExec_t step_graph_pair = nullptr; // 2 filter steps (tails and short runs)
-    int graph_pre = 0, graph_pre_big = 0, graph_pre_pair = 0;  // steps of each graph captured pre-linearised: a replay runs no host code (prelinearized_steps)
-    int graph_N = -1, graph_m = -1, graph_frames = -1;
-    bool graph_sole = true;   // the graphs were captured while this was the device's only handle (persistent sweep inside)
-    float graph_dt = -1.f;
-    float* graph_mu = nullptr;      // orientation of the mean / covariance ping-pong at capture time
-    float* graph_P = nullptr;
-    const void* graph_seq = nullptr;
+    GraphCache graphs;  // hipGraph replay of device-resident sequences (ekfvio_run_uploaded)
 
     // --- profiler ---
     bool prof_on = false;
@@ -353,7 +364,9 @@ struct BookArgs {
 BookArgs make_book_args(ekfvio_filter* f, int m, const float* d_z, const float* d_R, const uint8_t* d_pass, const int* d_frame_counter);
 void launch_linearize(ekfvio_filter* f, float dt, const BookArgs* book = nullptr);
 void launch_build_dense_F(ekfvio_filter* f, float* Fdense);
-void launch_predict(ekfvio_filter* f, float dt, const BookArgs* book = nullptr);
+// prelinearized: the previous update's last GEMM linearised for this step (UpdateResult::linearised_next): FA / FB / FD / mu_next hold its Jacobian
+// blocks and propagated mean.  Returns whether the launch relied on that (PredictPlan::pre)
+bool launch_predict(ekfvio_filter* f, float dt, const BookArgs* book = nullptr, bool prelinearized = false);
 // m_on_device: the host does not know how many landmarks passed (no D2H of the flags): launches are sized for m = 2N,
 // the kernels read the true row count from f->info[2] (written by the bookkeeping) and treat the rest as padding
 struct UpdateInputs {
@@ -375,6 +388,7 @@ struct UpdateInputs {
 struct UpdateResult {
     bool published = false;  // the status went out behind the sweep (publish_seq; false: no sweep ran)
     int between_seq = 0;     // what `between` returned (0: not reached -- no measurement, or the Schur flow)
+    bool linearised_next = false;  // the last GEMM linearised for the next process(dt) (UpdateInputs::next_dt, Tuning::lin_overlap): hand it to that launch_predict
 };
 UpdateResult launch_update(ekfvio_filter* f, const UpdateInputs& in);
 void launch_check_sigma(ekfvio_filter* f, float* d_out);
@@ -425,9 +439,10 @@ void add_features_enqueue_device_count(ekfvio_filter* f, const int* count_dev); 
 int replenish_enqueue(ekfvio_filter* f, int* enqueued);  // fast.hip: FAST + first-fit selection, count left in f->fast_counts[1]
 
 int live_handles_on(int device);  // api.hip: handles alive on that device in this process
+void drop_graph(ekfvio_filter* f);  // api.hip: the ONE invalidation of ekfvio_filter::graphs (the next run captures again)
 // The flow of ONE update is decided in one place (plan.h, plan_update: a pure function of the handle's Tuning, a PlanShape and the row count) and handed
 // to the launchers as a value: they execute, they do not decide.  This is the ONE adapter from a handle to what a plan may depend on; the handle
-// count is asked per plan (capture_steps and ekfvio_run_uploaded re-capture on it: graph_sole), never cached.
+// count is asked per plan (ekfvio_run_uploaded re-captures on it: GraphKey::sole), never cached.
 inline PlanShape plan_shape(const ekfvio_filter* f) {
     PlanShape s;
     s.num_cus = f->num_cus, s.ldp = f->ldp, s.sweep_sync_words = f->sweep_sync_words, s.N = f->N, s.n = f->n;

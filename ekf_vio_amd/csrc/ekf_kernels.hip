@@ -758,14 +758,12 @@ void launch_build_dense_F(ekfvio_filter* f, float* Fdense) {
 }
 
 // process(dt) (:96-121): executes a PredictPlan (plan.h, plan_predict)
-void launch_predict(ekfvio_filter* f, float dt, const BookArgs* book) {
+bool launch_predict(ekfvio_filter* f, float dt, const BookArgs* book, bool prelinearized) {
     // structured mode linearises inside the propagation kernel (predict_fused_kernel<true>) or in a launch in front; the dense mode and
     // ekfvio_linearize keep the stand-alone linearize_kernel.  pre (round 6): the previous update's last GEMM has linearised for this step
     // already (launch_update, GemmEpi::lin_blocks): FA / FB / FD and the propagated mean are in place, the propagation kernel only carries
     // the bookkeeping along
-    const PredictPlan p = plan_predict(f->tune, plan_shape(f), f->prelinearized);
-    f->prelinearized = false;
-    if (p.pre) f->prelinearized_steps++;  // (a capture takes its count back and adds it per replay: capture_steps)
+    const PredictPlan p = plan_predict(f->tune, plan_shape(f), prelinearized);
     if (p.lin_in_front) launch_linearize(f, dt, book);
     const int n = f->n, ld = f->ldp;
     if (p.dense) {
@@ -796,6 +794,7 @@ void launch_predict(ekfvio_filter* f, float dt, const BookArgs* book) {
     }
     // the propagated mean becomes the state (landmarks used the OLD base state, :102-107)
     std::swap(f->mu, f->mu_next);
+    return p.pre;
 }
 
 // The P-update GEMMs behind the sweep and the gain, described ONCE for the update itself and for the profiler's scratch launches.
@@ -912,7 +911,7 @@ UpdateResult launch_update(ekfvio_filter* f, const UpdateInputs& in) {
     if (p.lin_blocks) {  // (plan_update: the next process(dt)'s linearisation rides in this launch)
         e2.lin_blocks = p.lin_blocks, e2.lin_N = f->N, e2.lin_dt = in.next_dt;
         e2.lin_FA = f->FA, e2.lin_FB = f->FB, e2.lin_FD = f->FD, e2.lin_mu_next = f->mu_next;
-        f->prelinearized = true;
+        out.linearised_next = true;
     }
     launch_gemm(f, tail.last());
     return out;

@@ -1,9 +1,10 @@
 // ekf_vio_amd/csrc/plan.h — everything that DECIDES: the run-time switches, the sizes a capacity implies, and the flow of one update.
 // Standard headers only (no HIP, no project header): integer arithmetic over a Tuning, a PlanShape and a row count, so the decision
 // table of the product is checked on a machine without a GPU (include/ekfvio_test_hooks.h: ekfvio_test_plan, ekfvio_test_gemm_plan,
-// ekfvio_test_predict_plan; tests/test_plan_cpu.py, tests/test_gemm_plan_cpu.py).
+// ekfvio_test_predict_plan, ekfvio_test_run_plan; tests/test_plan_cpu.py, tests/test_gemm_plan_cpu.py, tests/test_resident_cases_cpu.py).
 // The launchers execute what is planned here, they do not decide: an UpdatePlan (chol.hip, ekf_kernels.hip: launch_update), a GemmPlan per GEMM
-// launch (gemm.hip: launch_gemm), a PredictPlan per process(dt) (ekf_kernels.hip: launch_predict).
+// launch (gemm.hip: launch_gemm), a PredictPlan per process(dt) (ekf_kernels.hip: launch_predict), a RunPlan per device-resident run (api.hip:
+// ekfvio_run_uploaded).
 #ifndef EKFVIO_PLAN_H_
 #define EKFVIO_PLAN_H_
 #include <stddef.h>
@@ -249,7 +250,7 @@ struct PredictPlan {
     bool book_rides() const { return lin_inside || pre; }
     int grid(bool bookkeeping) const { return ts * ts + 1 + 2 * chunks + (bookkeeping && book_rides() ? 1 : 0); }
 };
-// prelinearized: ekfvio_filter::prelinearized, the previous GEMM linearised
+// prelinearized: the previous update's last GEMM linearised for this step (UpdateResult::linearised_next; only inside a captured graph)
 inline PredictPlan plan_predict(const Tuning& t, const PlanShape& s, bool prelinearized) {
     PredictPlan p;
     p.dense = s.dense_predict;
@@ -468,6 +469,44 @@ inline UpdatePlan plan_update(const Tuning& t, const PlanShape& s, int m, bool m
     const int lin_blocks = (s.N + LIN_LM - 1) / LIN_LM + 1;
     if (next_dt >= 0.f && t.lin_overlap && !s.dense_predict && t.fuse_linearize)
         p.lin_blocks = plan_gemm(t, s.num_cus, tail_gemm_shape(n, m_pad, lin_blocks)).lin_blocks;  // (all of them or none: they must fit the GEMM's one wave)
+    return p;
+}
+
+// ---- the device-resident run: decided HERE, executed by ekfvio_run_uploaded (api.hip) ---------------------------------------------------
+// Steps per captured graph: even (the mean / covariance ping-pong is back in its starting orientation) and large enough to amortise the
+// ~8 us a hipGraphLaunch costs between replays
+#ifndef EKF_GRAPH_STEPS
+#define EKF_GRAPH_STEPS 8
+#endif
+#define EKF_GRAPH_STEPS_BIG 32  // second, longer graph for runs of at least two of them (+0.6 % steps/s at N=256)
+#define EKF_GRAPH_STEPS_PAIR 2  // tails and short runs
+// ... of which the long one exists only for sequences long enough to make runs of that length plausible
+#define EKF_GRAPH_BIG_FROM_FRAMES (2 * EKF_GRAPH_STEPS_BIG)
+#define RUN_GRAPHS 3
+// The graphs of a run, longest first: the order of the greedy cut, and of the cache's table (common.h, GraphCache)
+inline int run_graph_steps(int g) { return g == 0 ? EKF_GRAPH_STEPS_BIG : g == 1 ? EKF_GRAPH_STEPS : EKF_GRAPH_STEPS_PAIR; }
+inline bool run_graph_used(int g, int frames) { return g != 0 || frames >= EKF_GRAPH_BIG_FROM_FRAMES; }
+struct RunPlan {
+    bool graphs = false;  // the steps are replays of captured graphs (bookkeeping driven by the device-side frame counter); else every step is eager
+    int m = 0;            // with graphs: the one launch geometry of the sequence
+    int replays[RUN_GRAPHS] = {0, 0, 0};  // of the graph of run_graph_steps(g) steps
+    int eager = 0;        // with graphs: the odd last step, counter-driven like the replays; without: all `count` steps, each with its own frame's rows
+};
+// The launch geometry of uploaded frame i: its measurement rows as the host counted them; on a gated handle 2N for every frame in which any
+// landmark passed (the count is then on the device: launch_update)
+inline int run_geometry(const int* seq_m, int i, int N, bool gated) { return gated && seq_m[i] > 0 ? 2 * N : seq_m[i]; }
+// ekfvio_run_uploaded(first, count, dt) over `frames` uploaded frames of seq_m[i] rows.  Graphs need one launch geometry for every frame and
+// profiling off; a single step runs eager; count == 0 only prepares: the graphs are captured, nothing runs (callers that time a run call
+// this first)
+inline RunPlan plan_run(const int* seq_m, int frames, int N, bool gated, bool profiling, int count) {
+    RunPlan p;
+    p.eager = count;
+    p.graphs = !profiling && (count >= 2 || count == 0);
+    for (int i = 0; p.graphs && i < frames; i++) p.graphs = run_geometry(seq_m, i, N, gated) == run_geometry(seq_m, 0, N, gated);
+    if (!p.graphs) return p;
+    p.m = run_geometry(seq_m, 0, N, gated);
+    for (int g = 0; g < RUN_GRAPHS; g++)
+        if (run_graph_used(g, frames)) p.replays[g] = p.eager / run_graph_steps(g), p.eager %= run_graph_steps(g);
     return p;
 }
 #endif  // EKFVIO_PLAN_H_

@@ -196,9 +196,8 @@ void remove_applied(ekfvio_filter* f, int delta, int removed) {
     std::swap(f->mu, f->mu_next);
     if (removed > 0) {
         std::swap(f->P, f->P2);
-        f->graph_N = -1;  // captured step graphs are for the old shape: recaptured at the next run
+        drop_graph(f);  // captured step graphs are for the old shape: recaptured at the next run
     }
-    f->prelinearized = false;
     f->N += delta;
     f->n = EKF_BASE + 3 * f->N;
 }

@@ -58,6 +58,10 @@ EKFVIO_API int ekfvio_test_gemm_plan(int32_t num_cus, int32_t M, int32_t N, int3
  * linearize_kernel in front, ts, chunks, the bookkeeping rides in predict_fused_kernel, its grid (with the bookkeeping workgroup where asked). */
 EKFVIO_API int ekfvio_test_predict_plan(int32_t num_cus, int32_t N, int32_t dense_predict, int32_t prelinearized, int32_t bookkeeping,
                                         int32_t plan[8]);
+/* How ekfvio_run_uploaded(first, count, dt) would cut its steps (csrc/plan.h, plan_run) on a handle of N landmarks, gate and profiler on or off,
+ * over `frames` uploaded frames of rows[i] measurement rows as the host counts them.  out[6] = graphs are used, their launch geometry m, replays of
+ * the 32-, 8- and 2-step graph, eager steps. */
+EKFVIO_API int ekfvio_test_run_plan(int32_t N, int32_t gated, int32_t profiling, int32_t frames, const int32_t* rows, int32_t count, int32_t out[6]);
 /* The grid and the flag layout of the persistent sweep launch that plan selects (csrc/plan.h, PersistGrid / PersistFlags), likewise without a
  * handle or a device.  out[10] = total() (0: the planned sweep is not persistent, nothing else is filled), kind (PersistGridKind), owners,
  * the offsets of ready, fin, pan and the abort word, words(), zero_words(), FilterDims::sweep_sync_words.  roles (may be NULL; room for

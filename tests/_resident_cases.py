@@ -3,7 +3,7 @@ _update_cases.py): the device-resident run, ekfvio_run_uploaded, where its captu
 
 Nothing here looks at what a run returns.  What a run is EXPECTED to do is written down twice, independently of the library's control flow:
   * replays(): how ekfvio_run_uploaded cuts `count` steps into replays of its 32-, 8- and 2-step graphs and eager steps -- the rule of
-    api.hip restated (the 32-step graph exists only for sequences of at least 64 frames; greedy 32, 8, 2; an odd last step is eager; a
+    plan.h's plan_run restated (the 32-step graph exists only for sequences of at least 64 frames; greedy 32, 8, 2; an odd last step is eager; a
     single step, or a sequence whose frames do not all have one launch geometry, runs eager throughout);
   * expected_counters(): the deltas of the handle's counters `graph_steps` and `prelinearized_steps` that follow from it.  Whether a graph's
     steps are pre-linearised is the PLANNER's decision (plan.h, plan_update: lin_blocks), asked of ekfvio_test_plan with the compute-unit
@@ -15,6 +15,7 @@ A case is a small script of operations that the GPU test applies to a device-res
   ("step", i)                       one ekfvio_process + ekfvio_update with frame i of the uploaded sequence, on both
   ("reset",)                        ekfvio_set_state back to the start state, on both
   ("upload", shift, frames)         upload frames shift .. shift + frames of the scenario (the per-call twin indexes the new sequence)
+  ("gemms", reps)                   ekfvio_profile_update_gemms(reps) on the device-resident handle (a capture of its own, into scratch) | nothing
 """
 import collections
 import ctypes as C
@@ -148,13 +149,15 @@ def _cases():
     out.append(_case("wrap-count136", 256, 256, [_run(136)], "overlap", frames=64))                  # more than two laps
     # calls in sequence
     out.append(_case("seq-odd-then-even", 256, 256, [_run(9), _run(34, first=9)], "overlap"))  # the eager ninth step flips the ping-pong
-    # ... and with the dense predict, which flips the mean's ping-pong alone (Sigma is propagated in place): graph_mu is the only key that sees it
+    # ... and with the dense predict, which flips the mean's ping-pong alone (Sigma is propagated in place): GraphKey::mu is the only key that sees it
     out.append(_case("seq-odd-then-even-dense-predict", 30, 30, [_run(9), _run(34, first=9)], "one block column", dense=True))
     out.append(_case("seq-run-step-run", 256, 256, [_run(10), ("step", 10), _run(16, first=11)], "overlap"))
     out.append(_case("seq-dt-changed", 256, 256, [_run(10), _run(10, first=10, dt_scale=0.5)], "overlap"))
     out.append(_case("seq-dt-zero", 256, 256, [_run(10, dt_scale=0.0)], "overlap"))
     out.append(_case("seq-set-state", 256, 256, [_run(9), ("reset",), _run(16, first=9)], "overlap"))
     out.append(_case("seq-second-upload", 256, 256, [_run(10), ("upload", 8, 64), _run(40, first=2)], "overlap"))
+    # the profiler's capture between two runs (the capture helper the step graphs share): the graphs and the host's mirror of the sweep's flags stand
+    out.append(_case("seq-run-gemms-run", 100, 100, [_run(10), ("gemms", 2), _run(16, first=10)], "overlap"))
     # a second, idle handle alive on the device: per-step sweep in the graphs, the T2 shape and the overlap stay
     out.append(_case("second-handle", 256, 256, [_run(FRAMES)], "overlap", second=True))
     # one frame with two failed landmarks: eager throughout with the gate off; with the gate on the geometry is 2N for every frame

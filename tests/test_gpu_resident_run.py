@@ -11,7 +11,7 @@ A. Against the per-call path, bit for bit: every case is a script applied to one
    handle's counters `graph_steps` and `prelinearized_steps` to what the host rule and the planner say the run must have done, so that
    no case can fall back to the eager loop (or lose the overlap) and still pass.  Covered: every sweep the graphs can contain, every cut of a
    count into graphs, the device counter's wrap inside a 32-step graph and over several laps, runs behind runs (the ping-pong flipped by an
-   odd step, a per-call step in between, the same with the dense predict, another dt, dt = 0, ekfvio_set_state, another uploaded sequence), a second live handle, a ragged
+   odd step, a per-call step in between, the same with the dense predict, another dt, dt = 0, ekfvio_set_state, another uploaded sequence, the profiler's own capture), a second live handle, a ragged
    sequence with the gate off (the eager fallback, named) and on (graphs), and EKFVIO_LIN_OVERLAP=0.
 B. Against the fp64 oracle, independently of the per-call path: the two-step graph is the smallest run with a pre-linearised process(dt).
 
@@ -97,6 +97,9 @@ def drive(case, resident):
                 z, R, p = sequence(case, op[1], op[2])
                 if resident:
                     g.upload_measurements(z, R, p)
+            elif op[0] == "gemms":
+                if resident:
+                    g.profile_update_gemms(op[1])
             else:
                 raise ValueError(op)
         c1 = g.counters()

@@ -1,6 +1,8 @@
 """The expectations tests/test_gpu_resident_run.py holds the device-resident run to (tests/_resident_cases.py), checked without a GPU: the
-replay decomposition on hand-written examples, the labels of the case table against the planner at 256 compute units, and the host rule
+replay decomposition on hand-written examples and against the library's own rule (plan.h, plan_run through ekfvio_test_run_plan), the labels of the case table against the planner at 256 compute units, and the host rule
 that sends a sequence with one ragged frame through the eager loop."""
+import ctypes as C
+
 import numpy as np
 import pytest
 
@@ -31,6 +33,57 @@ def test_replay_decomposition_on_hand_written_examples():
         for frames in (2, 63, 64, 72):
             n32, n8, n2, eager = RC.replays(count, frames)
             assert 32 * n32 + 8 * n8 + 2 * n2 + eager == count and n8 < 4 + 100 * (frames < 64) and n2 < 4 and eager < 2
+
+
+def run_plan(rows, N, gated, profiling, count):
+    """plan_run (plan.h) through ekfvio_test_run_plan: what ekfvio_run_uploaded executes.  rows: measurement rows per uploaded frame."""
+    from ekf_vio_amd import capi
+    rows = np.ascontiguousarray(rows, np.int32)
+    out = (C.c_int32 * 6)()
+    rc = capi.load(hooks=True).ekfvio_test_run_plan(int(N), int(gated), int(profiling), len(rows), rows.ctypes.data_as(C.POINTER(C.c_int32)), int(count), out)
+    assert rc == capi.OK
+    return bool(out[0]), out[1], tuple(out[2:6])
+
+
+def layouts(N, k, frames):
+    """The four sequence layouts: uniform, one ragged frame, one frame without any measurement, all frames empty."""
+    ragged = RC.passes_for(N, k, frames, ragged=(frames // 2, np.flatnonzero(RC.passes_for(N, k, frames)[frames // 2])[:2]))
+    none_once = RC.passes_for(N, k, frames)
+    none_once[frames // 3] = 0
+    return dict(uniform=RC.passes_for(N, k, frames), ragged=ragged, none_once=none_once, empty=np.zeros((frames, N), np.uint8))
+
+
+def test_the_librarys_run_plan_is_the_restated_rule():
+    """plan_run against replays(), geometry() and is_uniform(): graphs iff the geometry is uniform, profiling is off and count is not 1; the cut;
+    and the geometry the graphs are captured for.  (The profiler is not part of the restatement: with it on, the rule is the non-uniform one.)"""
+    N, k = 16, 12
+    for frames in (1, 2, 63, 64, 72, 144):
+        for name, p in layouts(N, k, frames).items():
+            rows = 2 * p.astype(np.int64).sum(axis=1)
+            assert (name == "uniform") == bool((rows == 2 * k).all()) and (name != "empty" or not rows.any()), (name, frames)
+            for gated in (False, True):
+                uniform, geom = RC.is_uniform(p, gated), RC.geometry(p, gated)
+                for profiling in (False, True):
+                    for count in range(0, 201):
+                        graphs, m, cut = run_plan(rows, N, gated, profiling, count)
+                        what = (frames, name, gated, profiling, count)
+                        assert graphs == (uniform and not profiling and count != 1), what
+                        assert cut == RC.replays(count, frames, uniform and not profiling), what
+                        assert sum(s * c for s, c in zip((RC.GRAPH_BIG, RC.GRAPH, RC.GRAPH_PAIR, 1), cut)) == count, what
+                        if graphs:
+                            assert m == int(geom[0]), what
+                        else:
+                            assert cut[:3] == (0, 0, 0), what
+
+
+def test_the_librarys_run_plan_cuts_the_cases_as_restated():
+    for c in RC.CASES:
+        for p, first, count, scale in RC.walk(c):
+            uniform = RC.is_uniform(p, c.gated)
+            graphs, m, cut = run_plan(2 * p.astype(np.int64).sum(axis=1), c.N, c.gated, False, count)
+            assert cut == RC.replays(count, p.shape[0], uniform), (c.id, cut)
+            assert graphs == (uniform and count != 1) and (not graphs or m == int(RC.geometry(p, c.gated)[0])), (c.id, graphs, m)
+    assert RC.case_counters(next(c for c in RC.CASES if c.id == "seq-run-gemms-run"), CUS)[1] == [(0, 1, 1, 0), (0, 2, 0, 0)]
 
 
 def test_uniform_sequences_measure_k_landmarks_at_moving_positions():
@@ -94,7 +147,7 @@ def test_expected_counters_of_the_cases():
     want = {"shape-N256-cap256-k256": (72, 69), "shape-N256-cap256-k160": (72, 0), "shape-N600-cap600-k600": (10, 0), "count-0": (0, 0),
             "count-1": (0, 0), "count-2": (2, 1), "count-3": (2, 1), "count-9": (8, 7), "count-43": (42, 39),  # 72 frames: 32 + 8 + 2 + 1
             "wrap-first50-count43": (42, 39), "wrap-first63-count2": (2, 1), "wrap-count136": (136, 4 * 31 + 7),
-            "seq-odd-then-even": (8 + 34, 7 + 31 + 1), "seq-odd-then-even-dense-predict": (8 + 34, 0), "seq-run-step-run": (26, 8 + 14), "seq-second-upload": (10 + 40, 8 + 31 + 7),
+            "seq-odd-then-even": (8 + 34, 7 + 31 + 1), "seq-odd-then-even-dense-predict": (8 + 34, 0), "seq-run-step-run": (26, 8 + 14), "seq-run-gemms-run": (26, 8 + 14), "seq-second-upload": (10 + 40, 8 + 31 + 7),
             "second-handle": (72, 69), "ragged": (0, 0), "ragged-gated": (72, 69), "overlap-off": (72, 69)}
     for c in RC.CASES:
         total, cuts = RC.case_counters(c, CUS)
