@@ -220,7 +220,7 @@ static int create_body(ekfvio_filter* f, const ekfvio_config* cfg, int device, v
     memset(f->h_info, 0, 16 * sizeof(int));
     HIP_TRY(f, hipHostGetDevicePointer((void**)&f->d_hinfo, f->h_info, 0));
     {
-        const size_t words = EKF_BASE + 4 * (size_t)(f->cfg.max_features > 0 ? f->cfg.max_features : 1);
+        const size_t words = out_words(f);
         HIP_TRY(f, hipHostMalloc((void**)&f->h_out, words * sizeof(float), hipHostMallocMapped | hipHostMallocCoherent));
         HIP_TRY(f, hipHostGetDevicePointer((void**)&f->d_out, f->h_out, 0));
     }
@@ -578,6 +578,7 @@ int ekfvio_get_depth_variance(ekfvio_filter* f, int32_t index, float* var) {
 // setFeatureHomogenousCovariance (TightlyCoupledEKF.cpp:668-676): the four coeffRef writes of the (u,v) block
 int ekfvio_set_feature_cov(ekfvio_filter* f, int32_t index, const float cov[4]) {
     if (!f || !cov || index < 0 || index >= f->N) return EKFVIO_EINVAL;
+    f->out_cov_fresh = false;  // (the mean and the cloud stay what they are: out_fresh is kept)
     HIP_TRY(f, hipSetDevice(f->device));
     const int s = EKF_BASE + 3 * index;  // column-major in, column-major block of Sigma out
     HIP_TRY(f, hipMemcpy2DAsync(f->P + (size_t)s * f->ldp + s, sizeof(float) * f->ldp, cov, sizeof(float) * 2, sizeof(float) * 2, 2,

@@ -206,11 +206,14 @@ struct ekfvio_filter {
     int status_seq = 0;
     // small per-frame outputs (odometry, point cloud): kernels write them straight into pinned host memory and the host
     // waits with wait_status: no device-to-host copy into pageable memory, no interrupt-driven synchronise
-    float* h_out = nullptr;    // pinned, device-mapped: EKF_BASE + 4 * max_features floats
+    float* h_out = nullptr;    // pinned, device-mapped: base_mu[22], xyz[3 N], intensity[N] in the first EKF_BASE + 4 * max_features floats, then
+                               // at fixed offsets (out_cov_offset) pose_cov[36], twist_cov[36], cov[9 N]: EKF_BASE + 72 + 13 * max_features floats
     float* d_out = nullptr;    // the device's address of h_out
     bool out_fresh = false;    // h_out holds base_mu and the point cloud of the CURRENT state and frame: ekfvio_step_image's last
                                // kernel writes them with the status word, and every call that changes the state or the frame
                                // clears the flag; while it is set the node's getters cost a memcpy
+    bool output_cov = false;   // ekfvio_set_output_covariance: the frame's outputs include the covariances of include/ekfvio.h (and never go out early)
+    bool out_cov_fresh = false;  // ... and the fresh outputs (out_fresh) do include them: cleared, besides, by what changes Sigma alone (ekfvio_set_feature_cov)
     unsigned char* h_meas = nullptr;  // pinned staging for one frame's (z, R, pass): one H2D copy per ekfvio_update
     unsigned char* d_meas = nullptr;  // its device image: z at 0, R at 8N_cap, pass at 24N_cap bytes
     // uploaded measurement sequences
@@ -404,6 +407,9 @@ struct Level0View {
     float fx = 0.f, fy = 0.f, cx = 0.f, cy = 0.f;
 };
 Level0View klt_level0(const ekfvio_filter* f);
+// Where the covariances lie in h_out / d_out (frame.hip): pose_cov[36], twist_cov[36], then 9 floats per landmark; out_words: the whole allocation
+inline size_t out_cov_offset(const ekfvio_filter* f) { return EKF_BASE + 4 * (size_t)(f->cfg.max_features > 0 ? f->cfg.max_features : 1); }
+inline size_t out_words(const ekfvio_filter* f) { return out_cov_offset(f) + 72 + 9 * (size_t)(f->cfg.max_features > 0 ? f->cfg.max_features : 1); }
 // what the frame loop (frame.hip) enqueues of the tracker's file
 int push_frame_check(ekfvio_filter* f, const uint8_t* image, int32_t width, int32_t height, int32_t stride, const float K[9]);
 int push_frame_enqueue(ekfvio_filter* f, const uint8_t* image, int32_t width, int32_t height, int32_t stride, const float K[9]);

@@ -4,7 +4,8 @@
 // (ekf_kernels.hip, chol.hip, gemm.hip), the replenishment (fast.hip), the removal of lost landmarks (remove.hip) and the frame's
 // outputs, enqueued back to back with ONE host wait at the end (read_status / settle_update, api.hip).  The outputs -- odometry and
 // point cloud -- are written by frame_outputs_kernel into pinned host memory together with the status word; ekfvio_get_points is the
-// getter that launches points_kernel when they are not fresh.
+// getter that launches points_kernel when they are not fresh.  The covariances of those outputs (include/ekfvio.h) are formed here too:
+// by the getters' own kernels, or, with ekfvio_set_output_covariance, by frame_outputs_kernel with everything else.
 #include <string.h>
 
 #include "common.h"
@@ -47,6 +48,90 @@ __global__ void points_kernel(const float* __restrict__ mu, int N, const uint8_t
     }
 }
 
+// ---- covariances of the outputs (include/ekfvio.h, "covariances of the published outputs": the lines there are the specification, the
+// functions below are those lines; fp32, no contraction, sums ascending and left-associated) ------------------------------------------
+// S(i,j): Sigma's lower-triangle element
+__device__ inline float cov_S(const float* __restrict__ P, int ld, int i, int j) {
+    const int r = i > j ? i : j, c = i > j ? j : i;
+    return P[(size_t)c * ld + r];
+}
+// Row r of J = 2 [[-qx, qw, -qz, qy], [-qy, qz, qw, -qx], [-qz, -qy, qx, qw]] (columns w, x, y, z); compiled for the host too
+// (ekfvio_rotation_error_jacobian).  Selections, not an indexed table: a lane's row stays in registers
+__host__ __device__ inline void rot_err_jacobian_row(const float* q, int r, float* Jr) {
+    const float w = q[0], x = q[1], y = q[2], z = q[3];
+    Jr[0] = 2.f * -(r == 0 ? x : r == 1 ? y : z);
+    Jr[1] = 2.f * (r == 0 ? w : r == 1 ? z : -y);
+    Jr[2] = 2.f * (r == 0 ? -z : r == 1 ? w : x);
+    Jr[3] = 2.f * (r == 0 ? y : r == 1 ? -x : w);
+}
+// T[3+r][j] of the specification from row r of J
+__device__ inline float cov_T(const float* __restrict__ P, int ld, const float* Jr, int j) {
+    return ((Jr[0] * cov_S(P, ld, 3, j) + Jr[1] * cov_S(P, ld, 4, j)) + Jr[2] * cov_S(P, ld, 5, j)) + Jr[3] * cov_S(P, ld, 6, j);
+}
+// Element e (0 .. 71) of out72 = pose_cov[36], twist_cov[36]: one lane per element; the lane of (a,b) forms the lower triangle's
+// element (max, min), so both halves hold the same bits
+__device__ inline void odom_cov_one(const float* __restrict__ mu, const float* __restrict__ P, int ld, int e, float* __restrict__ out72) {
+    const int blk = e / 36, k = e - 36 * blk, r0 = k / 6, c0 = k - 6 * r0;
+    const int a = r0 > c0 ? r0 : c0, b = r0 > c0 ? c0 : r0;
+    float v;
+    if (blk == 1) {
+        v = cov_S(P, ld, 7 + a, 7 + b);
+    } else if (a < 3) {
+        v = cov_S(P, ld, a, b);
+    } else {
+        float Ja[4], Jb[4];
+        rot_err_jacobian_row(mu + 3, a - 3, Ja);
+        if (b < 3) {
+            v = cov_T(P, ld, Ja, b);
+        } else {
+            rot_err_jacobian_row(mu + 3, b - 3, Jb);
+            v = ((cov_T(P, ld, Ja, 3) * Jb[0] + cov_T(P, ld, Ja, 4) * Jb[1]) + cov_T(P, ld, Ja, 5) * Jb[2]) + cov_T(P, ld, Ja, 6) * Jb[3];
+        }
+    }
+    out72[e] = v;
+}
+// Landmark i's 3x3 into out9N[9 i ..]: one lane per landmark; its six Sigma entries lie in three columns
+__device__ inline void points_cov_one(const float* __restrict__ mu, const float* __restrict__ P, int ld, int i, float* __restrict__ out9N) {
+    const int s = EKF_BASE + 3 * i;
+    const float u = mu[s], v = mu[s + 1], rho = mu[s + 2];
+    const float z = (float)(1.0 / (double)rho);
+    const float x = u * z, y = v * z;
+    const float jx = -(x * z), jy = -(y * z), jz = -(z * z);
+    const float* c0 = P + (size_t)s * ld + s;  // column s from its diagonal element down
+    const float* c1 = c0 + ld + 1;
+    const float L00 = c0[0], L10 = c0[1], L20 = c0[2], L11 = c1[0], L21 = c1[1], L22 = c1[ld + 1];
+    const float M00 = z * L00 + jx * L20, M02 = z * L20 + jx * L22;
+    const float M10 = z * L10 + jy * L20, M11 = z * L11 + jy * L21, M12 = z * L21 + jy * L22;
+    const float M20 = jz * L20, M21 = jz * L21, M22 = jz * L22;
+    const float C00 = M00 * z + M02 * jx;
+    const float C10 = M10 * z + M12 * jx, C11 = M11 * z + M12 * jy;
+    const float C20 = M20 * z + M22 * jx, C21 = M21 * z + M22 * jy, C22 = M22 * jz;
+    float* o = out9N + 9 * (size_t)i;
+    o[0] = C00, o[1] = C10, o[2] = C20;
+    o[3] = C10, o[4] = C11, o[5] = C21;
+    o[6] = C20, o[7] = C21, o[8] = C22;
+}
+// The on-demand road (ekfvio_get_odometry_covariance / ekfvio_get_points_covariance), in the shape of points_kernel.
+// One workgroup; it publishes the status word itself
+__global__ __launch_bounds__(128) void odom_cov_kernel(const float* __restrict__ mu, const float* __restrict__ P, int ld, float* __restrict__ out72,
+                                                       const int* __restrict__ info, int* host_word, int seq) {
+    if (threadIdx.x < 72) odom_cov_one(mu, P, ld, threadIdx.x, out72);
+    __threadfence_system();
+    __syncthreads();
+    if (threadIdx.x == 0) publish_host_words(host_word, info, 0, seq);
+}
+// host_word != nullptr (single-workgroup launches only): as points_kernel
+__global__ __launch_bounds__(256) void points_cov_kernel(const float* __restrict__ mu, const float* __restrict__ P, int ld, int N,
+                                                         float* __restrict__ out9N, const int* __restrict__ info, int* host_word, int seq) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < N) points_cov_one(mu, P, ld, i, out9N);
+    if (host_word) {
+        __threadfence_system();
+        __syncthreads();
+        if (threadIdx.x == 0) publish_host_words(host_word, info, 0, seq);
+    }
+}
+
 // The last kernel of a frame (ekfvio_step_image): what the node publishes after addFrame -- publishOdometry's slices of
 // base_mu and publishPoints' cloud (EKFVIO.cpp:444-518) -- written into pinned host memory TOGETHER with the status word
 // the host is waiting for anyway.  ekfvio_get_odometry / ekfvio_get_points then cost a memcpy instead of a launch and a
@@ -57,11 +142,20 @@ __global__ void points_kernel(const float* __restrict__ mu, int N, const uint8_t
 // second GEMM's (gemm.hip, mode 2, :600-609) from K y in column n of P, which the first one has just left there: the same sums are
 // formed here (into LDS, mu itself is not touched), so the frame's outputs and status reach the host while the second GEMM still runs
 // -- the host's next frame (copying the image, ~15 us) starts that much earlier.  Same values, same bits as behind the update.
+// cov.S != null (ekfvio_set_output_covariance; never with Pcol / Kyp: Sigma' does not exist in front of the last GEMM): pose_cov[36], twist_cov[36] and
+// cov[9 N] of the frame's FINAL Sigma go out too, at cov.out.  Behind a removal that took landmarks out that Sigma is the buffer the removal wrote.
+struct FrameCovOut {
+    const float* S = nullptr;          // Sigma (null: no covariances, today's path)
+    const float* S_removed = nullptr;  // ... or this one where removed_dev[1] > 0 (remove.hip: words[1], the removed count)
+    const int* removed_dev = nullptr;
+    int ld = 0;
+    float* out = nullptr;
+};
 __global__ __launch_bounds__(256) void frame_outputs_kernel(const float* __restrict__ mu, int N_old, const int* __restrict__ added_dev,
                                                             const uint8_t* __restrict__ img, int pitch, int w, int h, float fx, float fy,
                                                             float cx, float cy, float* __restrict__ out, const int* __restrict__ info,
                                                             int* host_word, int seq, const float* __restrict__ Pcol,
-                                                            const float* __restrict__ Kyp = nullptr, int kyp_blocks = 0, int kyp_ld = 0) {
+                                                            const float* __restrict__ Kyp, int kyp_blocks, int kyp_ld, FrameCovOut cov) {
     extern __shared__ float s_mu[];  // Pcol / Kyp: the updated mean, EKF_BASE + 3 N floats
     const int added = added_dev ? *added_dev : 0;
     const int N = N_old + added;
@@ -112,6 +206,11 @@ __global__ __launch_bounds__(256) void frame_outputs_kernel(const float* __restr
     float* xyz = out + EKF_BASE;
     float* inten = xyz + 3 * (size_t)N;
     for (int i = threadIdx.x; i < N; i += 256) points_one(mu, i, img, pitch, w, h, fx, fy, cx, cy, xyz, inten);
+    if (cov.S) {
+        const float* S = (cov.removed_dev && cov.removed_dev[1] > 0) ? cov.S_removed : cov.S;
+        if (threadIdx.x < 72) odom_cov_one(mu, S, cov.ld, threadIdx.x, cov.out);
+        for (int i = threadIdx.x; i < N; i += 256) points_cov_one(mu, S, cov.ld, i, cov.out + 72);
+    }
     __threadfence_system();
     __syncthreads();
     if (threadIdx.x == 0) publish_host_words(host_word, info, added, seq);
@@ -122,14 +221,19 @@ __global__ __launch_bounds__(256) void frame_outputs_kernel(const float* __restr
 // Enqueues frame_outputs_kernel over level 0 of the current frame and returns the status sequence number it publishes.
 // early: between the update's two Joseph GEMMs, or in front of the T2 flow's one -- the updated mean is formed in LDS (n floats) from
 // `mu` and K y, which is column n of P or, with kyp_blocks > 0, Wt's first rows.  Otherwise behind the frame's last launch: `mu` is
-// final, and count_dev (may be null) holds the landmarks added meanwhile.
-static int launch_frame_outputs(ekfvio_filter* f, const float* mu, const int* count_dev, int kyp_blocks, bool early) {
+// final, and count_dev (may be null) holds the landmarks added meanwhile.  removed: a removal is enqueued in front (its words say whether Sigma moved).
+static int launch_frame_outputs(ekfvio_filter* f, const float* mu, const int* count_dev, int kyp_blocks, bool early, bool removed = false) {
     const Level0View v = klt_level0(f);
     const int seq = next_status_seq(f);
     const float* Pcol = early && kyp_blocks == 0 ? f->P + (size_t)f->n * f->ldp : nullptr;
     const float* Kyp = early && kyp_blocks > 0 ? f->Wt : nullptr;
+    FrameCovOut cov;
+    if (f->output_cov && !early) {
+        cov.S = f->P, cov.ld = f->ldp, cov.out = f->d_out + out_cov_offset(f);
+        if (removed) cov.S_removed = f->P2, cov.removed_dev = f->remove_words;
+    }
     hipLaunchKernelGGL(frame_outputs_kernel, dim3(1), dim3(256), early ? sizeof(float) * (size_t)f->n : 0, f->stream, mu, f->N, count_dev, v.img,
-                       v.pitch, v.w, v.h, v.fx, v.fy, v.cx, v.cy, f->d_out, f->info, f->d_hinfo, seq, Pcol, Kyp, kyp_blocks, early ? f->ldp : 0);
+                       v.pitch, v.w, v.h, v.fx, v.fy, v.cx, v.cy, f->d_out, f->info, f->d_hinfo, seq, Pcol, Kyp, kyp_blocks, early ? f->ldp : 0, cov);
     return seq;
 }
 
@@ -169,13 +273,67 @@ int ekfvio_get_points(ekfvio_filter* f, float* xyz3N, float* intensityN) {
     return EKFVIO_OK;
 }
 
+// The covariances of the outputs (include/ekfvio.h): a memcpy while the frame's outputs are fresh and include them, else one launch on the
+// handle's stream -- behind whatever is still running there, an update's Joseph GEMM included -- and one wait.
+int ekfvio_set_output_covariance(ekfvio_filter* f, int32_t on) {
+    if (!f || (on != 0 && on != 1)) return EKFVIO_EINVAL;
+    f->output_cov = on != 0;  // (read by the next ekfvio_step_image; the frame loop is in no captured graph)
+    if (!on) f->out_cov_fresh = false;
+    return EKFVIO_OK;
+}
+
+int ekfvio_get_odometry_covariance(ekfvio_filter* f, float pose_cov[36], float twist_cov[36]) {
+    if (!f) return EKFVIO_EINVAL;
+    const size_t off = out_cov_offset(f);
+    if (!(f->out_fresh && f->out_cov_fresh)) {
+        HIP_TRY(f, hipSetDevice(f->device));
+        const int seq = next_status_seq(f);
+        hipLaunchKernelGGL(odom_cov_kernel, dim3(1), dim3(128), 0, f->stream, f->mu, f->P, f->ldp, f->d_out + off, f->info, f->d_hinfo, seq);
+        int bad = 0;
+        const int rc = poll_status(f, seq, &bad, nullptr);
+        if (rc != EKFVIO_OK) return rc;
+    }
+    if (pose_cov) memcpy(pose_cov, f->h_out + off, sizeof(float) * 36);
+    if (twist_cov) memcpy(twist_cov, f->h_out + off + 36, sizeof(float) * 36);
+    return EKFVIO_OK;
+}
+
+int ekfvio_get_points_covariance(ekfvio_filter* f, float* cov9N) {
+    if (!f) return EKFVIO_EINVAL;
+    const int N = f->N;
+    if (N == 0) return EKFVIO_OK;
+    if (!cov9N) return EKFVIO_EINVAL;
+    const size_t off = out_cov_offset(f) + 72;
+    if (!(f->out_fresh && f->out_cov_fresh)) {
+        HIP_TRY(f, hipSetDevice(f->device));
+        int bad = 0, rc;
+        if (N <= 256) {  // one workgroup: it publishes the status word itself
+            const int seq = next_status_seq(f);
+            hipLaunchKernelGGL(points_cov_kernel, dim3(1), dim3(256), 0, f->stream, f->mu, f->P, f->ldp, N, f->d_out + off, f->info, f->d_hinfo, seq);
+            rc = poll_status(f, seq, &bad, nullptr);
+        } else {
+            hipLaunchKernelGGL(points_cov_kernel, dim3((N + 255) / 256), dim3(256), 0, f->stream, f->mu, f->P, f->ldp, N, f->d_out + off, nullptr, nullptr, 0);
+            rc = wait_status(f, &bad);
+        }
+        if (rc != EKFVIO_OK) return rc;
+    }
+    memcpy(cov9N, f->h_out + off, sizeof(float) * 9 * (size_t)N);
+    return EKFVIO_OK;
+}
+
+int ekfvio_rotation_error_jacobian(const float q_wxyz[4], float J3x4[12]) {
+    if (!q_wxyz || !J3x4) return EKFVIO_EINVAL;
+    for (int r = 0; r < 3; r++) rot_err_jacobian_row(q_wxyz, r, J3x4 + 4 * r);
+    return EKFVIO_OK;
+}
+
 // EKFVIO::addFrame + updateStateWithNewImage (EKFVIO.cpp:139-219) minus ROS publishing; with
 // cfg.replenish the FAST replenishment of :154 / :172 runs on the device too (otherwise the caller
 // adds landmarks with ekfvio_add_features).
 int ekfvio_step_image(ekfvio_filter* f, double stamp, const uint8_t* image, int32_t width, int32_t height, int32_t stride,
                       const float K[9]) {
     if (!f) return EKFVIO_EINVAL;
-    f->out_fresh = false;
+    f->out_fresh = f->out_cov_fresh = false;
     const bool first = !f->frames[f->cur].valid;
     if (!first && f->have_stamp && !(stamp - f->t_stamp >= 0)) return EKFVIO_EINVAL;  // ROS_ASSERT(dt >= 0)
     // nothing below waits for the device until the status word is read at the very end: process(dt), the frame
@@ -222,7 +380,8 @@ int ekfvio_step_image(ekfvio_filter* f, double stamp, const uint8_t* image, int3
         // Pcol): launch_update calls back there.  (With landmarks to add the selection reads the updated mean and the outputs carry the count:
         // behind the update, as before.  EKFVIO_EARLY_OUTPUTS=0: always behind.)
         // (Nor with cfg.remove_lost: the frame's final landmark count is known only behind the removal, as with a replenishing frame.)
-        if (f->tune.early_outputs && f->tune.frame_outputs && !(f->cfg.replenish && f->N < f->cfg.max_features) && !f->cfg.remove_lost &&
+        // (Nor with ekfvio_set_output_covariance: the outputs then include covariances of Sigma', which the last GEMM is still to write.)
+        if (f->tune.early_outputs && f->tune.frame_outputs && !(f->cfg.replenish && f->N < f->cfg.max_features) && !f->cfg.remove_lost && !f->output_cov &&
             sizeof(float) * (size_t)f->n <= 48 * 1024) {  // (the updated mean is formed in LDS)
             // (two-GEMM flow: K y is column n of P, left there by the first Joseph GEMM; T2 flow: the gain tiles' partial sums in Wt, and the
             // outputs go out in front of the update's ONE GEMM)
@@ -261,11 +420,12 @@ int ekfvio_step_image(ekfvio_filter* f, double stamp, const uint8_t* image, int3
     // (EKFVIO_FRAME_OUTPUTS=0: the status word and the count alone, published by read_status itself)
     int seq = early_seq;  // (non-zero: the outputs went out between the Joseph GEMMs, launch_update's hook)
     // (behind a removal the mean is in mu_next: the host swaps the two once it has the status word)
-    if (!seq && f->tune.frame_outputs) seq = launch_frame_outputs(f, removing ? f->mu_next : f->mu, count_dev, 0, false);
+    if (!seq && f->tune.frame_outputs) seq = launch_frame_outputs(f, removing ? f->mu_next : f->mu, count_dev, 0, false, removing);
     int bad = 0, added = 0;
     rc = read_status(f, seq, count_dev, &bad, &added);
     if (rc != EKFVIO_OK) return rc;
     f->out_fresh = f->tune.frame_outputs != 0;
+    f->out_cov_fresh = f->out_fresh && f->output_cov;
     // (in front of a re-run, which reads f->mu and f->P as the swap leaves them; the count of landmarks: below, with `added`)
     if (removing) remove_applied(f, 0, __atomic_load_n(&f->h_info[HW_REMOVED], __ATOMIC_ACQUIRE));
     // Bit 1: the persistent sweep gave up (chol_persist.inc), the Joseph GEMMs wrote nothing, the state is the propagated one.

@@ -25,7 +25,8 @@ def _u8(a):
 class TightlyCoupledEKF:
     def __init__(self, max_features=100, device=0, stream=None, predict_mode=capi.PREDICT_STRUCTURED,
                  default_point_depth=0.5, default_point_depth_variance=100.0,
-                 default_point_homogenous_variance=1e-5, hooks=False, gate_chi2=0.0, klt_fb_max_px=0.0, distortion=None, **cfg_overrides):
+                 default_point_homogenous_variance=1e-5, hooks=False, gate_chi2=0.0, klt_fb_max_px=0.0, distortion=None, output_covariance=False,
+                 **cfg_overrides):
         # hooks=True: this handle lives in libekfvio_hip_hooks.so, the build that also has include/ekfvio_test_hooks.h (tests, profiling scripts)
         self.hooks = bool(hooks)
         self.lib = capi.load(hooks=self.hooks)
@@ -53,6 +54,8 @@ class TightlyCoupledEKF:
             self.setGate(gate_chi2)
         if distortion is not None:  # likewise a property of the handle (ekfvio_set_distortion)
             self.setDistortion(distortion)
+        if output_covariance:  # likewise (ekfvio_set_output_covariance)
+            self.setOutputCovariance(True)
 
     def _chk(self, rc, allow=()):
         if rc != capi.OK and rc not in allow:
@@ -191,6 +194,25 @@ class TightlyCoupledEKF:
         None, () or all zeros: off."""
         d = np.ascontiguousarray([] if D is None else D, dtype=np.float64).reshape(-1)
         self._chk(self.lib.ekfvio_set_distortion(self.h, d.ctypes.data_as(C.POINTER(C.c_double)) if d.size else None, int(d.size)))
+
+    def setOutputCovariance(self, on):
+        """Not in the reference (EKFVIO.cpp:473 "TODO add convariance computation"): with it on, every frame of ekfvio_step_image carries the
+        covariances of its odometry and its point cloud with its other outputs (ekfvio_set_output_covariance), and odometry_covariance() /
+        points_covariance() cost a memcpy behind a frame.  Such a frame's outputs never go out in front of the update's last GEMM."""
+        self._chk(self.lib.ekfvio_set_output_covariance(self.h, int(on)))
+
+    def odometry_covariance(self):
+        """ekfvio_get_odometry_covariance: (pose 6x6 over (x, y, z, rotation about X, Y, Z) in the world frame, twist 6x6 over (linear, angular) in
+        the body frame), float32, exactly symmetric."""
+        c = np.empty((2, 6, 6), np.float32)
+        self._chk(self.lib.ekfvio_get_odometry_covariance(self.h, _fp(c[0]), _fp(c[1])))
+        return c[0], c[1]
+
+    def points_covariance(self):
+        """ekfvio_get_points_covariance: (N, 3, 3) float32, the covariance of the camera-frame point (u/rho, v/rho, 1/rho) of every landmark."""
+        cov = np.empty((self.num_features, 3, 3), np.float32)
+        self._chk(self.lib.ekfvio_get_points_covariance(self.h, _fp(cov)))
+        return cov
 
     def checkSigma(self):
         a, b = C.c_float(0), C.c_float(0)
@@ -412,6 +434,17 @@ def _ip(a):
     return a.ctypes.data_as(C.POINTER(C.c_int32))
 
 
+def rotation_error_jacobian(q_wxyz):
+    """ekfvio_rotation_error_jacobian: the 3x4 J with dtheta = J dq for q_true = [1, dtheta/2] (x) q (include/ekfvio.h).  A host function: no GPU involved."""
+    lib = capi.load()
+    q = np.ascontiguousarray(q_wxyz, dtype=np.float32).reshape(4)
+    J = np.zeros((3, 4), np.float32)
+    rc = lib.ekfvio_rotation_error_jacobian(_fp(q), _fp(J))
+    if rc != capi.OK:
+        raise capi.EkfvioError(rc, "ekfvio_rotation_error_jacobian")
+    return J
+
+
 def rectify_map(K, D, width, height):
     """ekfvio_rectify_map: the fixed-point map (sx, sy), int32 [height, width] each, that a handle with the coefficients D (k1, k2, p1, p2[, k3])
     rectifies a width x height frame with intrinsics K through; INT32_MIN where no source pixel exists.  A host function: no GPU involved."""
@@ -432,7 +465,9 @@ class EKFVIO:
     on the device; otherwise call replenishFeatures() (or addNewFeatures) yourself."""
 
     def __init__(self, **kw):
-        self.tc_ekf = TightlyCoupledEKF(**kw)  # (distortion=(k1, k2, p1, p2[, k3]): raw frames are rectified on the device, setDistortion below)
+        # (distortion=(k1, k2, p1, p2[, k3]): raw frames are rectified on the device, setDistortion below; output_covariance=True: every frame's
+        # outputs carry their covariances, setOutputCovariance below)
+        self.tc_ekf = TightlyCoupledEKF(**kw)
         self.tracker = KLTTracker(self.tc_ekf)
         self._imu_queue = []      # (stamp, gyro, accel), kept in stamp order; only used with use_imu = 1
         self._t_filter = None     # the stamp the device state stands at
@@ -456,6 +491,19 @@ class EKFVIO:
     def setDistortion(self, D):
         """The camera's plumb_bob coefficients (TightlyCoupledEKF.setDistortion): from the next frame on addFrame takes raw frames."""
         self.tc_ekf.setDistortion(D)
+
+    def setOutputCovariance(self, on):
+        """TightlyCoupledEKF.setOutputCovariance: from the next frame on addFrame delivers the covariances with the frame's outputs."""
+        self.tc_ekf.setOutputCovariance(on)
+
+    def odometry_covariance(self):
+        """The covariances nav_msgs/Odometry asks for: (pose 6x6 in the world frame, twist 6x6 in the body frame); a memcpy behind a frame with
+        output_covariance on, a launch and a wait otherwise."""
+        return self.tc_ekf.odometry_covariance()
+
+    def points_covariance(self):
+        """(N, 3, 3): the covariance of every point of points()."""
+        return self.tc_ekf.points_covariance()
 
     def replenishFeatures(self):
         """EKFVIO::replenishFeatures (EKFVIO.cpp:224-311) on the current frame, on the device: FAST-9/16 with

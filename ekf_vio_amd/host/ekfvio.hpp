@@ -51,6 +51,9 @@ struct Params {
     // CameraInfo.D (the ROS node) or from the distortion_* parameters (a caller without CameraInfo, the replay driver); all zero = off.
     int rectify = 0;
     std::array<double, 5> distortion{};
+    // Not in the reference, which publishes all-zero covariances (EKFVIO.cpp:473): with publish_covariance = 1 every frame carries the covariances of
+    // its odometry and point cloud (ekfvio_set_output_covariance) and the node fills nav_msgs/Odometry's two 6x6 blocks from them.
+    int publish_covariance = 0;
     std::map<std::string, std::string> node;  // odom_topic, camera_topic, base_frame, use_imu, publish_insight, ...
 
     Params() {
@@ -102,6 +105,7 @@ struct Params {
             if (cfg.klt_fb_max_px < 0.f) throw Error(EKFVIO_EINVAL, "parameter klt_fb_max_px: negative: " + value);
         }
         else if (key == "rectify") rectify = (value == "true" || value == "1") ? 1 : 0;
+        else if (key == "publish_covariance") publish_covariance = (value == "true" || value == "1") ? 1 : 0;
         else if (key == "distortion_k1") distortion[0] = number(key, value);
         else if (key == "distortion_k2") distortion[1] = number(key, value);
         else if (key == "distortion_p1") distortion[2] = number(key, value);
@@ -126,7 +130,7 @@ struct Params {
                                         "default_point_depth", "default_point_depth_variance",
                                         "default_point_homogenous_variance", "frame_buffer_size", "imu_update",
                                         "imu_gyro_variance", "imu_accel_variance", "gravity_x", "gravity_y", "gravity_z", "remove_lost", "gate_chi2",
-                                        "klt_fb_max_px", "rectify", "distortion_k1", "distortion_k2", "distortion_p1", "distortion_p2", "distortion_k3"};
+                                        "klt_fb_max_px", "rectify", "publish_covariance", "distortion_k1", "distortion_k2", "distortion_p1", "distortion_p2", "distortion_k3"};
         for (const auto& e : Params().node) out.push_back(e.first);
         for (const auto& e : ignored()) out.push_back(e.first);
         return out;
@@ -262,6 +266,25 @@ class TightlyCoupledEKF {
     // Not in the reference, which assumes a pinhole image (Frame.h:31): the camera's plumb_bob coefficients k1 k2 p1 p2 [k3] (ekfvio_set_distortion).
     // From the next frame on, frames are rectified on the device between the upload and the pyramid; empty or all zero: off.
     void setDistortion(const std::vector<double>& D) { chk(ekfvio_set_distortion(h_, D.empty() ? nullptr : D.data(), (int32_t)D.size())); }
+    // Not in the reference (EKFVIO.cpp:473 "TODO add convariance computation"): the covariances of the published outputs (include/ekfvio.h).
+    // setOutputCovariance(true): every frame of addFrame carries them with its other outputs, and the two getters cost a memcpy behind a frame
+    // (such a frame's outputs never go out in front of the update's last GEMM); otherwise each getter is one launch and one wait.
+    void setOutputCovariance(bool on) { chk(ekfvio_set_output_covariance(h_, on ? 1 : 0)); }
+    struct OdometryCovariance {
+        std::array<float, 36> pose{};   // row-major 6x6 over (x, y, z, rotation about X, Y, Z), world frame: nav_msgs/Odometry.pose.covariance
+        std::array<float, 36> twist{};  // row-major 6x6 over (linear, angular), body frame: twist.covariance
+    };
+    OdometryCovariance getOdometryCovariance() {
+        OdometryCovariance c;
+        chk(ekfvio_get_odometry_covariance(h_, c.pose.data(), c.twist.data()));
+        return c;
+    }
+    // one row-major 3x3 per landmark: the covariance of the camera-frame point (u/rho, v/rho, 1/rho) of the point cloud
+    std::vector<std::array<float, 9>> getPointsCovariance() {
+        std::vector<std::array<float, 9>> out(numFeatures());
+        chk(ekfvio_get_points_covariance(h_, out.empty() ? nullptr : out[0].data()));
+        return out;
+    }
     // Not in the reference (it flags lost landmarks, TightlyCoupledEKF.cpp:528, and keeps them): removes the landmarks whose byte
     // of `remove` is nonzero (one per landmark), or, with no mask, those flagged for deletion.  Returns the number removed.
     int removeFeatures(const std::vector<uint8_t>* remove = nullptr) {
@@ -411,6 +434,7 @@ class EKFVIO {
           scale_(p.cfg.inverse_image_scale > 1 ? p.cfg.inverse_image_scale : 1) {
         if (p.gate_chi2 > 0.f) tc_ekf.setGate(p.gate_chi2);  // (behind ekfvio_create: the gate is a property of the handle)
         if (p.rectify) tc_ekf.setDistortion(std::vector<double>(p.distortion.begin(), p.distortion.end()));  // (likewise; a node replaces them with CameraInfo.D)
+        if (p.publish_covariance) tc_ekf.setOutputCovariance(true);  // (likewise)
     }
     TightlyCoupledEKF tc_ekf;
     KLTTracker tracker;

@@ -6,7 +6,7 @@
 // final odometry next to the ground truth, the checkSigma numbers and the step rate.
 // Usage: ekfvio_replay [landmarks=256] [frames=300] [seed=0] [dt=0.0333333]
 //        ekfvio_replay --print-config [params.yaml]   (no GPU work: the node's parameter file -> ekfvio_config as JSON)
-//        ekfvio_replay --records <dir> [--out <dir>] [--params params.yaml] [--device n] [--insight]
+//        ekfvio_replay --records <dir> [--out <dir>] [--params params.yaml] [--device n] [--insight] [--covariance]
 //
 // --records replays what the node's two subscriptions deliver (EKFVIO.cpp:69-81) and writes what its two publishers
 // send (EKFVIO.cpp:444-518), with no ROS in between.  <dir>/records.txt holds one record per line, in arrival order:
@@ -18,7 +18,9 @@
 //     <out>/points.txt   "cloud <stamp> <n>" followed by n lines "x y z intensity"
 // (floats printed with %.9g: exact).  IMU records go to imu_callback, a logging stub in the reference (with imu_update: 1 in
 // the parameter file they are queued and applied in stamp order in front of the next frame).  --insight also writes what
-// publishInsight sends, <out>/insight_NNN.ppm.
+// publishInsight sends, <out>/insight_NNN.ppm.  --covariance turns on the covariances of the outputs (ekfvio_set_output_covariance) and
+// prints, per frame, the diagonals of the pose and twist covariances the node would put into nav_msgs/Odometry:
+//     cov <stamp> <6 pose variances: x y z rotX rotY rotZ> <6 twist variances: linear, angular>
 #include <cctype>
 #include <chrono>
 #include <cmath>
@@ -72,12 +74,12 @@ static int print_config(const char* path) {
                     "\"kill_pad\": %d, \"klt_min_eigen\": %.9g, \"min_new_feature_dist\": %d, \"klt_max_pyramid_level\": %d, "
                     "\"klt_window_size\": %d, \"default_point_depth\": %.9g, \"default_point_depth_variance\": %.9g, "
                     "\"default_point_homogenous_variance\": %.9g, \"sample_based_uncertainty\": %d, \"gate_chi2\": %.9g, "
-                    "\"klt_fb_max_px\": %.9g, \"rectify\": %d, \"distortion\": [%.17g, %.17g, %.17g, %.17g, %.17g], \"node\": {",
+                    "\"klt_fb_max_px\": %.9g, \"rectify\": %d, \"publish_covariance\": %d, \"distortion\": [%.17g, %.17g, %.17g, %.17g, %.17g], \"node\": {",
                     c.max_features, c.fast_threshold, (double)c.fast_blur_sigma, c.inverse_image_scale, c.kill_pad,
                     (double)c.klt_min_eigen, c.min_new_feature_dist, c.klt_max_pyramid_level, c.klt_window_size,
                     (double)c.default_point_depth, (double)c.default_point_depth_variance,
                     (double)c.default_point_homogenous_variance, c.sample_based_uncertainty, (double)p.gate_chi2,
-                    (double)c.klt_fb_max_px, p.rectify, p.distortion[0], p.distortion[1], p.distortion[2], p.distortion[3], p.distortion[4]);
+                    (double)c.klt_fb_max_px, p.rectify, p.publish_covariance, p.distortion[0], p.distortion[1], p.distortion[2], p.distortion[3], p.distortion[4]);
         bool first = true;
         for (const auto& e : p.node) {
             std::printf("%s\"%s\": \"%s\"", first ? "" : ", ", e.first.c_str(), e.second.c_str());
@@ -120,11 +122,12 @@ static bool read_pgm(const std::string& path, std::vector<uint8_t>& px, int& w, 
     return (size_t)in.gcount() == px.size();
 }
 
-static int replay_records(const std::string& dir, const std::string& out_dir, const char* params_path, int device, bool insight) {
+static int replay_records(const std::string& dir, const std::string& out_dir, const char* params_path, int device, bool insight, bool covariance) {
     try {
         ekfvio::Params p = params_path ? ekfvio::Params::fromFile(params_path) : ekfvio::Params();
         if (!params_path) p.cfg.inverse_image_scale = 1;  // no parameter file: frames are used as recorded
         p.cfg.replenish = 1;                              // addFrame runs replenishFeatures itself (EKFVIO.cpp:154, :172)
+        if (covariance) p.publish_covariance = 1;
         std::ifstream rec(dir + "/records.txt");
         if (!rec) throw ekfvio::Error(EKFVIO_EINVAL, "cannot open " + dir + "/records.txt");
         // no image size anywhere: the device planes grow with the first frame that needs it (Frame::Frame takes any image)
@@ -172,6 +175,13 @@ static int replay_records(const std::string& dir, const std::string& out_dir, co
                 std::fprintf(fp, "cloud %.9f %zu\n", pc.stamp, pc.points.size());
                 for (size_t i = 0; i < pc.points.size(); i++)
                     std::fprintf(fp, "%.9g %.9g %.9g %.9g\n", pc.points[i][0], pc.points[i][1], pc.points[i][2], pc.intensity[i]);
+                if (covariance) {  // what the node fills pose.covariance / twist.covariance from: a memcpy behind the frame
+                    const ekfvio::TightlyCoupledEKF::OdometryCovariance oc = node.tc_ekf.getOdometryCovariance();
+                    std::printf("cov %.9f", od.stamp);
+                    for (int i = 0; i < 6; i++) std::printf(" %.9g", oc.pose[7 * i]);
+                    for (int i = 0; i < 6; i++) std::printf(" %.9g", oc.twist[7 * i]);
+                    std::printf("\n");
+                }
                 if (insight) {  // publishInsight (EKFVIO.cpp:379-442) as a binary PPM (RGB order on disk)
                     const ekfvio::Insight in = node.insight();
                     char name[64];
@@ -210,10 +220,10 @@ int main(int argc, char** argv) {
         std::string dir = argv[2], out = argv[2];
         const char* params = nullptr;
         int device = 0;
-        bool insight = false;
+        bool insight = false, covariance = false;
         for (int i = 3; i < argc; i += 2) {
-            if (std::strcmp(argv[i], "--insight") == 0) {
-                insight = true;
+            if (std::strcmp(argv[i], "--insight") == 0 || std::strcmp(argv[i], "--covariance") == 0) {
+                (std::strcmp(argv[i], "--insight") == 0 ? insight : covariance) = true;
                 i--;
                 continue;
             }
@@ -229,7 +239,7 @@ int main(int argc, char** argv) {
                 return 2;
             }
         }
-        return replay_records(dir, out, params, device, insight);
+        return replay_records(dir, out, params, device, insight, covariance);
     }
     const int N = argc > 1 ? std::atoi(argv[1]) : 256;
     const int frames = argc > 2 ? std::atoi(argv[2]) : 300;

@@ -82,12 +82,26 @@ std::string distortion_model_of(const Info&, long) {
     return "plumb_bob";
 }
 
+// pose.covariance / twist.covariance (row-major 6x6, float64) where the message type carries them (geometry_msgs/PoseWithCovariance and
+// TwistWithCovariance of every ROS release do; a declaration-only stand-in for the header may not, and then has nothing to fill)
+template <class WithCovariance>
+auto fill_covariance(WithCovariance& m, const std::array<float, 36>& c, int) -> decltype((void)(m.covariance[0] = 0.0)) {
+    for (size_t i = 0; i < 36; i++) m.covariance[i] = (double)c[i];  // widened, never recomputed
+}
+template <class WithCovariance>
+void fill_covariance(WithCovariance&, const std::array<float, 36>&, long) {}
+#ifdef EKFVIO_NODE_REQUIRE_COVARIANCE  // for a build that must not lose the covariances to the fallback above (tests/test_gpu_host_shim_covout.py)
+static_assert(sizeof(nav_msgs::Odometry().pose.covariance) == 36 * sizeof(double) && sizeof(nav_msgs::Odometry().twist.covariance) == 36 * sizeof(double),
+              "nav_msgs/Odometry without pose.covariance / twist.covariance");
+#endif
+
 class EkfvioNode {
    public:
     EkfvioNode() : it_(nh_) {
         // the ~48 private parameters of EKFVIO::EKFVIO (EKFVIO.cpp:20-67) by the reference's names
         // (and this backend's own: imu_update, remove_lost, gate_chi2, klt_fb_max_px -- the tracker's forward-backward threshold in pixels of
-        // the resized frame, which reaches the handle inside ekfvio_config)
+        // the resized frame, which reaches the handle inside ekfvio_config -- and publish_covariance, default false: with it the handle is
+        // told at start-up, by ekfvio::EKFVIO's constructor, to deliver the covariances with every frame's outputs)
         for (const std::string& name : ekfvio::Params::names()) {
             XmlRpc::XmlRpcValue v;
             if (ros::param::get("~" + name, v)) params_.set(name, to_text(v));
@@ -205,7 +219,15 @@ class EkfvioNode {
         msg.twist.twist.angular.x = o.angular[0];
         msg.twist.twist.angular.y = o.angular[1];
         msg.twist.twist.angular.z = o.angular[2];
-        odom_pub_.publish(msg);  // no covariance, as in the reference (:473)
+        // the reference leaves both covariances zero (:473 "TODO add convariance computation"), and so does publish_covariance = false: the
+        // message is then byte for byte what it was.  With it on: pose in the world frame over (x, y, z, rotation about X, Y, Z), twist in the
+        // child frame over (linear, angular) -- the frame's own outputs, a memcpy behind addFrame
+        if (params_.publish_covariance) {
+            const ekfvio::TightlyCoupledEKF::OdometryCovariance c = vio_->tc_ekf.getOdometryCovariance();
+            fill_covariance(msg.pose, c.pose, 0);
+            fill_covariance(msg.twist, c.twist, 0);
+        }
+        odom_pub_.publish(msg);
     }
 
     // EKFVIO.cpp:479-518

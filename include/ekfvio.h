@@ -117,7 +117,7 @@ EKFVIO_API int ekfvio_create(const ekfvio_config* cfg, int device, void* stream,
 EKFVIO_API int ekfvio_destroy(ekfvio_filter* f);
 /* initializeBaseState(): back to mu = [0,0,0,1,0...], Sigma diag [0x7,30x9,0.5x6], no landmarks.  (The innovation gate's counts start
  * over; its threshold stays.  The same holds for the tracker's forward-backward check.  The distortion coefficients of
- * ekfvio_set_distortion stay too.) */
+ * ekfvio_set_distortion stay too, and so does the setting of ekfvio_set_output_covariance.) */
 EKFVIO_API int ekfvio_reset(ekfvio_filter* f);
 EKFVIO_API const char* ekfvio_last_error(const ekfvio_filter* f);
 
@@ -249,6 +249,70 @@ EKFVIO_API int ekfvio_set_distortion(ekfvio_filter* f, const double* D, int32_t 
  * (a tap outside the frame means no data there).  D, count as above (count = 0: the identity map). */
 EKFVIO_API int ekfvio_rectify_map(const float K[9], const double* D, int32_t count, int32_t width, int32_t height, int32_t* sx,
                                   int32_t* sy);
+
+/* ---- covariances of the published outputs (not in the reference: EKFVIO.cpp:473 "TODO add convariance computation"; its Odometry
+ * message carries two all-zero 6x6 covariances) -----------------------------------------------------------------------------------------
+ * The covariance of what ekfvio_get_odometry and ekfvio_get_points return, formed on the device from the dense Sigma.  The lines below
+ * are the specification: everything in fp32, without fused multiply-add; a sum runs over an ascending index and associates to the left;
+ * a NumPy float32 restatement of them (tests/_covout.py) is what the device is held to, bit for bit.  S(i,j) always means Sigma's
+ * LOWER-triangle element P(max(i,j), min(i,j)), as the gate reads it (both triangles agree only up to rounding, and the mirrored Joseph
+ * GEMM writes one of them).  Of every result the lower triangle is computed and then mirrored: the outputs are exactly symmetric.
+ *
+ * Pose covariance: 6x6, row-major, ordered (x, y, z, rotation about X, Y, Z), in the filter's world frame with fixed axes -- what
+ * nav_msgs/Odometry.pose.covariance asks for.  The rotation error is dtheta with q_true = [1, dtheta/2] (x) q; the state's quaternion is
+ * body-to-world, so this left perturbation is in world axes.  With (qw, qx, qy, qz) = mu[3..6]:
+ *
+ *     J = 2 * [ -qx   qw  -qz   qy ]
+ *             [ -qy   qz   qw  -qx ]          3x4, columns w, x, y, z (the doubling and the negation are exact)
+ *             [ -qz  -qy   qx   qw ]
+ *     A = blkdiag(I3, J)   (6x7)              C = A S[0:7, 0:7] A^T
+ *
+ *     T[r][j]   = S(r,j)                                                                      r < 3      (a copy, not a product)
+ *     T[3+r][j] = ((J[r][0]*S(3,j) + J[r][1]*S(4,j)) + J[r][2]*S(5,j)) + J[r][3]*S(6,j)       r = 0..2, j = 0..6
+ *     for a >= b:
+ *         C[a][b] = S(a,b)                                                                    a < 3
+ *         C[a][b] = T[a][b]                                                                   a >= 3 > b
+ *         C[a][b] = ((T[a][3]*J[b-3][0] + T[a][4]*J[b-3][1]) + T[a][5]*J[b-3][2]) + T[a][6]*J[b-3][3]     otherwise
+ *     C[b][a] = C[a][b]
+ *
+ * J q = 0: the direction of the quaternion's norm drops out by itself.  At q = (1,0,0,0) the rotation block is 4 S[4:7, 4:7].
+ *
+ * Twist covariance: 6x6, row-major, ordered (linear, angular): S[7:13, 7:13], copied and mirrored.  Both are body-frame quantities in this
+ * motion model (the position advances by q * (dt vel + ...), omega is the body rate): what twist.covariance means for the child frame.
+ *
+ * Landmark covariance: one 3x3 per landmark, row-major, 9 floats: the covariance of the camera-frame point (u/rho, v/rho, 1/rho) that
+ * ekfvio_get_points returns.  For landmark i with s = 22 + 3i, (u, v, rho) = mu[s..s+2]:
+ *
+ *     z = (float)(1.0 / (double)rho)     x = u*z     y = v*z                   (the very values of the point cloud)
+ *     jx = -(x*z)     jy = -(y*z)     jz = -(z*z)                              Jl = [[z, 0, jx], [0, z, jy], [0, 0, jz]]
+ *     L(a,b) = S(s+a, s+b)                                                     M = Jl L,  Cl = M Jl^T, structural zeros skipped:
+ *     M00 = z*L(0,0) + jx*L(2,0)     M02 = z*L(0,2) + jx*L(2,2)
+ *     M10 = z*L(1,0) + jy*L(2,0)     M11 = z*L(1,1) + jy*L(2,1)     M12 = z*L(1,2) + jy*L(2,2)
+ *     M20 = jz*L(2,0)     M21 = jz*L(2,1)     M22 = jz*L(2,2)
+ *     Cl[0][0] = M00*z + M02*jx
+ *     Cl[1][0] = M10*z + M12*jx          Cl[1][1] = M11*z + M12*jy
+ *     Cl[2][0] = M20*z + M22*jx          Cl[2][1] = M21*z + M22*jy          Cl[2][2] = M22*jz
+ *     Cl[0][1] = Cl[1][0]     Cl[0][2] = Cl[2][0]     Cl[1][2] = Cl[2][1]
+ *
+ * A landmark no update has measured yet has L = diag(hv, hv, dv) (addNewFeatures), for which these lines give Jl diag(hv, hv, dv) Jl^T.
+ * Cross-covariances between landmarks, or between a landmark and the pose, are not reported.
+ *
+ * Two roads.  On demand: the getters below launch their own kernel on the handle's stream (so behind an update's Joseph GEMM that is
+ * still running) and wait for it -- one launch for all landmarks.  In the frame: with ekfvio_set_output_covariance(f, 1),
+ * ekfvio_step_image writes the three results with the frame's other outputs and the status word, and the getters cost a memcpy until
+ * the state changes.  Such a frame cannot publish in front of the update's last GEMM (Sigma' does not exist yet): its outputs go out
+ * behind the frame's last launch, as those of a frame that replenishes or removes already do.  The setting changes WHEN a frame's
+ * outputs are published, never what the filter computes.  Off by default (then no launch differs and every output keeps its bits).
+ * A property of the handle: it survives ekfvio_reset.  Values other than 0 and 1: EKFVIO_EINVAL. */
+EKFVIO_API int ekfvio_set_output_covariance(ekfvio_filter* f, int32_t on);
+/* Either pointer may be NULL. */
+EKFVIO_API int ekfvio_get_odometry_covariance(ekfvio_filter* f, float pose_cov[36], float twist_cov[36]);
+/* cov9N: room for 9 floats per landmark (ekfvio_num_features), in landmark order. */
+EKFVIO_API int ekfvio_get_points_covariance(ekfvio_filter* f, float* cov9N);
+/* The J above for a quaternion (w, x, y, z), row-major 3x4: a pure host function (no handle, no device) that compiles the very inline
+ * function the kernels compile.  For a caller that keeps its own Sigma, or wants the body-frame (right-perturbation) convention:
+ * R(q)^T J is that convention's Jacobian. */
+EKFVIO_API int ekfvio_rotation_error_jacobian(const float q_wxyz[4], float J3x4[12]);
 
 /* ---- KLT (KLTTracker::findNewFeaturePositions, KLTTracker.cpp:29-95) ----------------- */
 /* Uploads a frame (Frame.h:25-41: image + intrinsics K row-major 3x3 as in CameraInfo.K),
