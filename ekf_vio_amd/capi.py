@@ -50,7 +50,7 @@ SYMBOLS = ["ekfvio_default_config", "ekfvio_create", "ekfvio_destroy", "ekfvio_r
 # every symbol include/ekfvio_test_hooks.h declares (libekfvio_hip_hooks.so only)
 HOOK_SYMBOLS = ["ekfvio_test_klt_padded_level", "ekfvio_test_blurred_level0", "ekfvio_test_gemm", "ekfvio_test_gemm_bench", "ekfvio_test_potrf_stamps",
                 "ekfvio_test_sweep_stamps", "ekfvio_test_sweep_fault", "ekfvio_test_sweep_delay", "ekfvio_test_cholesky_solve", "ekfvio_test_plan", "ekfvio_test_persist_grid", "ekfvio_test_t2_pair",
-                "ekfvio_test_gemm_plan", "ekfvio_test_predict_plan", "ekfvio_test_run_plan"]
+                "ekfvio_test_gemm_plan", "ekfvio_test_predict_plan", "ekfvio_test_run_plan", "ekfvio_test_mem", "ekfvio_test_mem_fail"]
 
 _libs = {}
 
@@ -121,6 +121,8 @@ def load(build_if_missing=True, hooks=False):
             "ekfvio_test_gemm_plan": [i32] * 11 + [ip],  # ... plan_gemm and plan_predict
             "ekfvio_test_predict_plan": [i32] * 5 + [ip],
             "ekfvio_test_run_plan": [i32] * 4 + [ip, i32, ip],  # ... and plan_run
+            "ekfvio_test_mem": [vp, C.POINTER(C.c_int64)],  # csrc/mem.h: what a handle's ledger holds (None: the whole library copy)
+            "ekfvio_test_mem_fail": [vp, i32],
         })
     for name, args in sig.items():
         fn = getattr(lib, name)

@@ -12,15 +12,36 @@
 
 #include "common.h"
 
+// ---- the library's memory backend (mem.h): the ONLY calls of the runtime's allocation functions under csrc/ -------------------
+static_assert((int)hipErrorOutOfMemory == MEM_ERR_OUT_OF_MEMORY && (int)hipSuccess == MEM_OK, "mem.h's codes are the runtime's");
 namespace {
-// Allocation + zero fill ordered on the handle's (non-blocking) stream: nothing in this
-// library relies on the legacy null stream, which a non-blocking stream does not wait for.
-template <class T>
-hipError_t dev_alloc(hipStream_t s, T** p, size_t count) {
-    hipError_t e = hipMalloc((void**)p, sizeof(T) * (count ? count : 1));
-    if (e == hipSuccess) e = hipMemsetAsync(*p, 0, sizeof(T) * (count ? count : 1), s);
-    return e;
+// what this copy of the library holds through every ledger, handles' and test hooks' alike (ekfvio_test_mem with a null handle)
+struct MemTotal {
+    std::atomic<int64_t> live{0}, live_bytes{0}, acquired{0}, released{0};
+} g_mem_total[MEM_KINDS];
+int hip_mem_allocate(MemKind kind, size_t bytes, void** out) {
+    static const unsigned host_flags[MEM_KINDS] = {0, hipHostMallocDefault, hipHostMallocMapped, hipHostMallocMapped | hipHostMallocCoherent};
+    void* p = nullptr;
+    const hipError_t e = kind == MEM_DEVICE ? hipMalloc(&p, bytes) : hipHostMalloc(&p, bytes, host_flags[kind]);
+    if (e != hipSuccess) return (int)e;
+    g_mem_total[kind].live++, g_mem_total[kind].live_bytes += (int64_t)bytes, g_mem_total[kind].acquired++;
+    *out = p;
+    return MEM_OK;
 }
+void hip_mem_free(MemKind kind, void* p, size_t bytes) {
+    (void)(kind == MEM_DEVICE ? hipFree(p) : hipHostFree(p));
+    g_mem_total[kind].live--, g_mem_total[kind].live_bytes -= (int64_t)bytes, g_mem_total[kind].released++;
+}
+#ifdef EKFVIO_TEST_HOOKS
+std::atomic<int> g_next_create_fail{0};  // ekfvio_test_mem_fail(NULL, k): armed on the ledger of the next ekfvio_create
+#endif
+}  // namespace
+const MemBackend& hip_mem_backend() {
+    static const MemBackend b = {hip_mem_allocate, hip_mem_free};
+    return b;
+}
+
+namespace {
 
 __global__ void init_sigma_kernel(float* P, int ld) {
     // initializeBaseState (TightlyCoupledEKF.cpp:23-56): diag [0x7, 30x9, 0.5x6]
@@ -184,50 +205,50 @@ static int create_body(ekfvio_filter* f, const ekfvio_config* cfg, int device, v
     f->n_cap = dims.n_cap, f->ldp = dims.ldp, f->m_cap = dims.m_cap, f->ld_aug = dims.ld_aug, f->sweep_sync_words = dims.sweep_sync_words;
     f->tune = tuning_from_env();  // every switch, once per handle
     const size_t pp = (size_t)f->ldp * f->ldp, pm = (size_t)f->ldp * f->m_cap;
-    HIP_TRY(f, dev_alloc(f->stream, &f->mu, f->ldp));
-    HIP_TRY(f, dev_alloc(f->stream, &f->mu_next, f->ldp));
-    HIP_TRY(f, dev_alloc(f->stream, &f->last_klt, 2 * (size_t)maxf));
-    HIP_TRY(f, dev_alloc(f->stream, &f->del_flag, (size_t)maxf));
-    HIP_TRY(f, dev_alloc(f->stream, &f->P, pp));
-    HIP_TRY(f, dev_alloc(f->stream, &f->P2, pp));
-    HIP_TRY(f, dev_alloc(f->stream, &f->FA, EKF_BASE * EKF_BASE));
-    HIP_TRY(f, dev_alloc(f->stream, &f->FB, 27 * (size_t)maxf));
-    HIP_TRY(f, dev_alloc(f->stream, &f->FD, 9 * (size_t)maxf));
-    HIP_TRY(f, dev_alloc(f->stream, &f->Fdense, pp));
-    HIP_TRY(f, dev_alloc(f->stream, &f->idx, (size_t)f->m_cap));
-    HIP_TRY(f, dev_alloc(f->stream, &f->inv_idx, (size_t)f->ldp));
-    HIP_TRY(f, dev_alloc(f->stream, &f->zmeas, 2 * (size_t)maxf));
-    HIP_TRY(f, dev_alloc(f->stream, &f->Rmeas, 4 * (size_t)maxf));
-    HIP_TRY(f, dev_alloc(f->stream, &f->pass, (size_t)maxf));
-    HIP_TRY(f, dev_alloc(f->stream, &f->yres, (size_t)f->m_cap));
-    HIP_TRY(f, dev_alloc(f->stream, &f->Rm, 2 * (size_t)f->m_cap));
-    HIP_TRY(f, dev_alloc(f->stream, &f->Saug, (size_t)f->ld_aug * f->m_cap));
-    HIP_TRY(f, dev_alloc(f->stream, &f->Laug, (size_t)f->ld_aug * f->m_cap));
-    HIP_TRY(f, dev_alloc(f->stream, &f->Linv, 64 * (size_t)f->m_cap));
-    HIP_TRY(f, dev_alloc(f->stream, &f->Lsign, (size_t)(f->m_cap / 64 > 256 ? f->m_cap / 64 : 256)));  // 256: the raw-solve test hook goes up to m = 16384
-    HIP_TRY(f, dev_alloc(f->stream, &f->sweep_sync, f->sweep_sync_words));  // flags of the persistent sweeps (chol_persist.inc)
+    HIP_TRY(f, dev_alloc(f, &f->mu, f->ldp));
+    HIP_TRY(f, dev_alloc(f, &f->mu_next, f->ldp));
+    HIP_TRY(f, dev_alloc(f, &f->last_klt, 2 * (size_t)maxf));
+    HIP_TRY(f, dev_alloc(f, &f->del_flag, (size_t)maxf));
+    HIP_TRY(f, dev_alloc(f, &f->P, pp));
+    HIP_TRY(f, dev_alloc(f, &f->P2, pp));
+    HIP_TRY(f, dev_alloc(f, &f->FA, EKF_BASE * EKF_BASE));
+    HIP_TRY(f, dev_alloc(f, &f->FB, 27 * (size_t)maxf));
+    HIP_TRY(f, dev_alloc(f, &f->FD, 9 * (size_t)maxf));
+    HIP_TRY(f, dev_alloc(f, &f->Fdense, pp));
+    HIP_TRY(f, dev_alloc(f, &f->idx, (size_t)f->m_cap));
+    HIP_TRY(f, dev_alloc(f, &f->inv_idx, (size_t)f->ldp));
+    HIP_TRY(f, dev_alloc(f, &f->zmeas, 2 * (size_t)maxf));
+    HIP_TRY(f, dev_alloc(f, &f->Rmeas, 4 * (size_t)maxf));
+    HIP_TRY(f, dev_alloc(f, &f->pass, (size_t)maxf));
+    HIP_TRY(f, dev_alloc(f, &f->yres, (size_t)f->m_cap));
+    HIP_TRY(f, dev_alloc(f, &f->Rm, 2 * (size_t)f->m_cap));
+    HIP_TRY(f, dev_alloc(f, &f->Saug, (size_t)f->ld_aug * f->m_cap));
+    HIP_TRY(f, dev_alloc(f, &f->Laug, (size_t)f->ld_aug * f->m_cap));
+    HIP_TRY(f, dev_alloc(f, &f->Linv, 64 * (size_t)f->m_cap));
+    HIP_TRY(f, dev_alloc(f, &f->Lsign, (size_t)(f->m_cap / 64 > 256 ? f->m_cap / 64 : 256)));  // 256: the raw-solve test hook goes up to m = 16384
+    HIP_TRY(f, dev_alloc(f, &f->sweep_sync, f->sweep_sync_words));  // flags of the persistent sweeps (chol_persist.inc)
     {
         hipDeviceProp_t prop;
         HIP_TRY(f, hipGetDeviceProperties(&prop, device));
         f->num_cus = prop.multiProcessorCount;
     }
-    HIP_TRY(f, dev_alloc(f->stream, &f->Km, pm));
-    HIP_TRY(f, dev_alloc(f->stream, &f->Wt, pm));
-    HIP_TRY(f, dev_alloc(f->stream, &f->Gm, pm));
-    HIP_TRY(f, dev_alloc(f->stream, &f->info, 4));
-    HIP_TRY(f, dev_alloc(f->stream, &f->remove_words, 4));
-    HIP_TRY(f, hipHostMalloc((void**)&f->h_info, 16 * sizeof(int), hipHostMallocMapped | hipHostMallocCoherent));
+    HIP_TRY(f, dev_alloc(f, &f->Km, pm));
+    HIP_TRY(f, dev_alloc(f, &f->Wt, pm));
+    HIP_TRY(f, dev_alloc(f, &f->Gm, pm));
+    HIP_TRY(f, dev_alloc(f, &f->info, 4));
+    HIP_TRY(f, dev_alloc(f, &f->remove_words, 4));
+    HIP_TRY(f, host_alloc(f, &f->h_info, 16 * sizeof(int), MEM_PINNED_COHERENT));
     memset(f->h_info, 0, 16 * sizeof(int));
     HIP_TRY(f, hipHostGetDevicePointer((void**)&f->d_hinfo, f->h_info, 0));
     {
         const size_t words = out_words(f);
-        HIP_TRY(f, hipHostMalloc((void**)&f->h_out, words * sizeof(float), hipHostMallocMapped | hipHostMallocCoherent));
+        HIP_TRY(f, host_alloc(f, &f->h_out, words * sizeof(float), MEM_PINNED_COHERENT));
         HIP_TRY(f, hipHostGetDevicePointer((void**)&f->d_out, f->h_out, 0));
     }
     {
         const size_t cap = (size_t)(f->cfg.max_features > 0 ? f->cfg.max_features : 1);
-        HIP_TRY(f, hipHostMalloc((void**)&f->h_meas, 25 * cap, hipHostMallocDefault));
-        HIP_TRY(f, hipMalloc((void**)&f->d_meas, 25 * cap));
+        HIP_TRY(f, host_alloc(f, &f->h_meas, 25 * cap, MEM_PINNED));
+        HIP_TRY(f, dev_alloc_bare(f, &f->d_meas, 25 * cap));
     }
     HIP_TRY(f, hipEventCreate(&f->ev0));
     HIP_TRY(f, hipEventCreate(&f->ev1));
@@ -303,12 +324,15 @@ int ekfvio_create(const ekfvio_config* cfg, int device, void* stream, ekfvio_fil
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return EKFVIO_EDEVICE;
     ekfvio_filter* f = new ekfvio_filter();
+#ifdef EKFVIO_TEST_HOOKS
+    f->mem.fail_nth(g_next_create_fail.exchange(0));
+#endif
     f->cfg = *cfg;
     f->device = device;
     if (device < 64) live_registry()[device].fetch_add(1, std::memory_order_relaxed);
     const int rc = create_body(f, cfg, device, stream);
     if (rc != EKFVIO_OK) {
-        // a half-built handle never leaves the library: whatever was allocated is released here
+        // a half-built handle never leaves the library: whatever its ledger holds is released here
         fprintf(stderr, "ekfvio_create: %s\n", f->last_error.c_str());
         (void)ekfvio_destroy(f);
         return rc;
@@ -321,18 +345,8 @@ int ekfvio_destroy(ekfvio_filter* f) {
     if (!f) return EKFVIO_EINVAL;
     (void)hipSetDevice(f->device);
     if (f->stream) (void)hipStreamSynchronize(f->stream);
-    void* ptrs[] = {f->mu, f->mu_next, f->last_klt, f->del_flag, f->P,  f->P2, f->FA, f->FB, f->FD,   f->Fdense,
-                    f->idx, f->inv_idx, f->zmeas,  f->Rmeas,    f->pass,     f->yres, f->Rm, f->Saug,  f->Laug,  f->Linv, f->Lsign, f->Km, f->sweep_sync, f->sweep_dbg,
-                    f->Wt,  f->Gm,     f->info,     f->remove_words, f->seq_z,    f->seq_R, f->seq_pass, f->gate_words, f->fb_words};
-    for (void* p : ptrs)
-        if (p) hipFree(p);
-    if (f->h_info) hipHostFree(f->h_info);
-    if (f->h_out) hipHostFree(f->h_out);
-    if (f->h_meas) hipHostFree(f->h_meas);
-    if (f->d_meas) (void)hipFree(f->d_meas);
-    klt_free(f);
-    fast_free(f);
     drop_graph(f);
+    f->mem.release_all();  // every buffer of the handle, whichever file acquired it and whichever field holds it now
     if (f->ev0) hipEventDestroy(f->ev0);
     if (f->ev1) hipEventDestroy(f->ev1);
     if (f->own_stream && f->stream) hipStreamDestroy(f->stream);
@@ -683,24 +697,32 @@ int ekfvio_imu(ekfvio_filter* f, double stamp, const float* gyro, const float* a
 }
 
 // ---- uploaded measurement sequences ---------------------------------------------------
+// the three buffers of a sequence (the previous upload's are released as each is acquired) and their contents, waited for
+static int upload_sequence(ekfvio_filter* f, int32_t frames, const float* z, const float* R, const uint8_t* pass) {
+    const size_t N = f->N;
+    HIP_TRY(f, dev_alloc(f, &f->seq_z, frames * 2 * N));
+    HIP_TRY(f, dev_alloc(f, &f->seq_R, frames * 4 * N));
+    HIP_TRY(f, dev_alloc(f, &f->seq_pass, frames * N));
+    HIP_TRY(f, hipMemcpyAsync(f->seq_z, z, sizeof(float) * frames * 2 * N, hipMemcpyHostToDevice, f->stream));
+    HIP_TRY(f, hipMemcpyAsync(f->seq_R, R, sizeof(float) * frames * 4 * N, hipMemcpyHostToDevice, f->stream));
+    HIP_TRY(f, hipMemcpyAsync(f->seq_pass, pass, frames * N, hipMemcpyHostToDevice, f->stream));
+    HIP_TRY(f, hipStreamSynchronize(f->stream));
+    return EKFVIO_OK;
+}
 int ekfvio_upload_measurements(ekfvio_filter* f, int32_t frames, const float* z, const float* R, const uint8_t* pass) {
     if (!f || frames <= 0 || !z || !R || !pass || f->N <= 0) return EKFVIO_EINVAL;
     HIP_TRY(f, hipSetDevice(f->device));
     HIP_TRY(f, hipStreamSynchronize(f->stream));
     drop_graph(f);  // the captured launches hold pointers into the old sequence buffers
-    if (f->seq_z) hipFree(f->seq_z);
-    if (f->seq_R) hipFree(f->seq_R);
-    if (f->seq_pass) hipFree(f->seq_pass);
-    f->seq_z = f->seq_R = nullptr;
-    f->seq_pass = nullptr;
+    // no sequence while this one is on its way: an upload that fails leaves a handle ekfvio_run_uploaded refuses, holding no sequence memory
+    f->seq_frames = 0, f->seq_N = 0;
+    f->seq_m.clear();
+    const int rc = upload_sequence(f, frames, z, R, pass);
+    if (rc != EKFVIO_OK) {
+        f->mem.release(&f->seq_z), f->mem.release(&f->seq_R), f->mem.release(&f->seq_pass);
+        return rc;
+    }
     const size_t N = f->N;
-    HIP_TRY(f, dev_alloc(f->stream, &f->seq_z, frames * 2 * N));
-    HIP_TRY(f, dev_alloc(f->stream, &f->seq_R, frames * 4 * N));
-    HIP_TRY(f, dev_alloc(f->stream, &f->seq_pass, frames * N));
-    HIP_TRY(f, hipMemcpyAsync(f->seq_z, z, sizeof(float) * frames * 2 * N, hipMemcpyHostToDevice, f->stream));
-    HIP_TRY(f, hipMemcpyAsync(f->seq_R, R, sizeof(float) * frames * 4 * N, hipMemcpyHostToDevice, f->stream));
-    HIP_TRY(f, hipMemcpyAsync(f->seq_pass, pass, frames * N, hipMemcpyHostToDevice, f->stream));
-    HIP_TRY(f, hipStreamSynchronize(f->stream));
     f->seq_frames = frames;
     f->seq_N = (int)N;
     f->seq_m.resize(frames);
@@ -900,7 +922,7 @@ int ekfvio_set_gate(ekfvio_filter* f, float chi2) {
         HIP_TRY(f, hipSetDevice(f->device));
         const size_t maxf = (size_t)(f->cfg.max_features > 0 ? f->cfg.max_features : 1);
         unsigned char* buf = nullptr;
-        HIP_TRY(f, dev_alloc(f->stream, &buf, 4 * sizeof(int) + maxf * (sizeof(float) + 2)));
+        HIP_TRY(f, dev_alloc(f, &buf, 4 * sizeof(int) + maxf * (sizeof(float) + 2)));
         f->gate_words = reinterpret_cast<int*>(buf);
         f->gate_d2 = reinterpret_cast<float*>(buf + 4 * sizeof(int));
         f->gate_flag = buf + 4 * sizeof(int) + maxf * sizeof(float);
@@ -988,10 +1010,11 @@ int ekfvio_test_gemm(ekfvio_filter* f, int32_t transB, int32_t M, int32_t N, int
         for (int r = 0; r < (transB ? N : K); r++) hB[(size_t)c * brows + r] = B[(size_t)c * ldb + r];
     for (int j = 0; j < N; j++)
         for (int i = 0; i < M; i++) hC[(size_t)j * Mp + i] = C[(size_t)j * ldc + i];
-    float *dA, *dB, *dC;
-    HIP_TRY(f, dev_alloc(f->stream, &dA, hA.size()));
-    HIP_TRY(f, dev_alloc(f->stream, &dB, hB.size()));
-    HIP_TRY(f, dev_alloc(f->stream, &dC, hC.size()));
+    MemLedger tmp(hip_mem_backend());  // the call's own device memory: released on every return
+    float *dA = nullptr, *dB = nullptr, *dC = nullptr;
+    HIP_TRY(f, dev_alloc(tmp, f->stream, &dA, hA.size()));
+    HIP_TRY(f, dev_alloc(tmp, f->stream, &dB, hB.size()));
+    HIP_TRY(f, dev_alloc(tmp, f->stream, &dC, hC.size()));
     HIP_TRY(f, hipMemcpyAsync(dA, hA.data(), sizeof(float) * hA.size(), hipMemcpyHostToDevice, f->stream));
     HIP_TRY(f, hipMemcpyAsync(dB, hB.data(), sizeof(float) * hB.size(), hipMemcpyHostToDevice, f->stream));
     HIP_TRY(f, hipMemcpyAsync(dC, hC.data(), sizeof(float) * hC.size(), hipMemcpyHostToDevice, f->stream));
@@ -1003,9 +1026,6 @@ int ekfvio_test_gemm(ekfvio_filter* f, int32_t transB, int32_t M, int32_t N, int
     HIP_TRY(f, hipStreamSynchronize(f->stream));
     for (int j = 0; j < N; j++)
         for (int i = 0; i < M; i++) C[(size_t)j * ldc + i] = hC[(size_t)j * Mp + i];
-    hipFree(dA);
-    hipFree(dB);
-    hipFree(dC);
     return EKFVIO_OK;
 }
 
@@ -1024,10 +1044,11 @@ int ekfvio_test_gemm_bench(ekfvio_filter* f, int32_t transB, int32_t lowerB, int
     for (auto& v : hA) v = rnd();
     for (auto& v : hB) v = rnd();
     for (auto& v : hC) v = rnd();
-    float *dA, *dB, *dC;
-    HIP_TRY(f, dev_alloc(f->stream, &dA, hA.size()));
-    HIP_TRY(f, dev_alloc(f->stream, &dB, hB.size()));
-    HIP_TRY(f, dev_alloc(f->stream, &dC, hC.size()));
+    MemLedger tmp(hip_mem_backend());  // the call's own device memory: released on every return
+    float *dA = nullptr, *dB = nullptr, *dC = nullptr;
+    HIP_TRY(f, dev_alloc(tmp, f->stream, &dA, hA.size()));
+    HIP_TRY(f, dev_alloc(tmp, f->stream, &dB, hB.size()));
+    HIP_TRY(f, dev_alloc(tmp, f->stream, &dC, hC.size()));
     HIP_TRY(f, hipMemcpyAsync(dA, hA.data(), sizeof(float) * hA.size(), hipMemcpyHostToDevice, f->stream));
     HIP_TRY(f, hipMemcpyAsync(dB, hB.data(), sizeof(float) * hB.size(), hipMemcpyHostToDevice, f->stream));
     HIP_TRY(f, hipMemcpyAsync(dC, hC.data(), sizeof(float) * hC.size(), hipMemcpyHostToDevice, f->stream));
@@ -1046,20 +1067,16 @@ int ekfvio_test_gemm_bench(ekfvio_filter* f, int32_t transB, int32_t lowerB, int
     HIP_TRY(f, hipEventElapsedTime(&ms, f->ev0, f->ev1));
     *mean_us = 1e3 * ms / reps;
     if (stamped) {  // diagnostic: one stamped launch, stamps returned through mean_us[1..40]
-        long long* dst;
-        HIP_TRY(f, dev_alloc(f->stream, &dst, 40));
-        f->gemm_stamps = dst;
+        long long* dst = nullptr;
+        HIP_TRY(f, dev_alloc(tmp, f->stream, &dst, 40));
+        f->gemm_stamps = dst;  // (no return between set and reset: the handle's next GEMM launch must not find a temporary here)
         launch_gemm(f, g);
+        f->gemm_stamps = nullptr;
         long long hst[40];
         HIP_TRY(f, hipMemcpyAsync(hst, dst, sizeof(hst), hipMemcpyDeviceToHost, f->stream));
         HIP_TRY(f, hipStreamSynchronize(f->stream));
-        f->gemm_stamps = nullptr;
         for (int i = 0; i < 40; i++) mean_us[1 + i] = (double)hst[i];
-        hipFree(dst);
     }
-    hipFree(dA);
-    hipFree(dB);
-    hipFree(dC);
     return EKFVIO_OK;
 }
 
@@ -1073,12 +1090,13 @@ int ekfvio_test_potrf_stamps(ekfvio_filter* f, int64_t stamps[80]) {
     std::vector<float> hs(64 * 64);
     for (int c = 0; c < 64; c++)
         for (int r = 0; r < 64; r++) hs[c * 64 + r] = (r == c ? 2.0f : 0.f) + 0.3f / (1.0f + (r > c ? r - c : c - r));
-    float *dS, *dL, *dLi;
-    long long* dst;
-    HIP_TRY(f, dev_alloc(f->stream, &dS, hs.size()));
-    HIP_TRY(f, dev_alloc(f->stream, &dL, hs.size()));
-    HIP_TRY(f, dev_alloc(f->stream, &dLi, 4096));
-    HIP_TRY(f, dev_alloc(f->stream, &dst, 80));
+    MemLedger tmp(hip_mem_backend());
+    float *dS = nullptr, *dL = nullptr, *dLi = nullptr;
+    long long* dst = nullptr;
+    HIP_TRY(f, dev_alloc(tmp, f->stream, &dS, hs.size()));
+    HIP_TRY(f, dev_alloc(tmp, f->stream, &dL, hs.size()));
+    HIP_TRY(f, dev_alloc(tmp, f->stream, &dLi, 4096));
+    HIP_TRY(f, dev_alloc(tmp, f->stream, &dst, 80));
     HIP_TRY(f, hipMemsetAsync(dst, 0, sizeof(long long) * 80, f->stream));
     HIP_TRY(f, hipMemcpyAsync(dS, hs.data(), sizeof(float) * hs.size(), hipMemcpyHostToDevice, f->stream));
     for (int rep = 0; rep < 3; rep++) launch_potrf_stamps(f, dS, 64, dL, dLi, dst);
@@ -1093,7 +1111,6 @@ int ekfvio_test_potrf_stamps(ekfvio_filter* f, int64_t stamps[80]) {
     for (uint32_t v : hi) h2 = (h2 ^ v) * 1099511628211ull;
     stamps[12] = (int64_t)h1;
     stamps[13] = (int64_t)h2;
-    hipFree(dS); hipFree(dL); hipFree(dLi); hipFree(dst);
     return EKFVIO_OK;
 }
 
@@ -1103,7 +1120,7 @@ int ekfvio_test_sweep_stamps(ekfvio_filter* f, int enable, int64_t* stamps /* [1
     if (!f) return EKFVIO_EINVAL;
     HIP_TRY(f, hipSetDevice(f->device));
     if (enable && !f->sweep_dbg) {
-        HIP_TRY(f, dev_alloc(f->stream, &f->sweep_dbg, 1024));
+        HIP_TRY(f, dev_alloc(f, &f->sweep_dbg, 1024));
         HIP_TRY(f, hipMemsetAsync(f->sweep_dbg, 0, 1024 * sizeof(long long), f->stream));
     }
     if (stamps && f->sweep_dbg) {
@@ -1147,12 +1164,13 @@ int ekfvio_test_cholesky_solve(ekfvio_filter* f, int32_t m, int32_t nrhs, const 
             for (int r = 0; r < nrhs; r++) hs[(size_t)c * ld + mp + r] = Crhs[(size_t)c * nrhs + r];
         hs[(size_t)c * ld + mp + rp + c] = 1.f;
     }
-    float *dS, *dL, *dLi, *dK, *dW;
-    HIP_TRY(f, dev_alloc(f->stream, &dS, hs.size()));
-    HIP_TRY(f, dev_alloc(f->stream, &dL, hs.size()));
-    HIP_TRY(f, dev_alloc(f->stream, &dLi, (size_t)64 * mp));
-    HIP_TRY(f, dev_alloc(f->stream, &dK, (size_t)rp * mp));
-    HIP_TRY(f, dev_alloc(f->stream, &dW, (size_t)rp * mp));
+    MemLedger tmp(hip_mem_backend());
+    float *dS = nullptr, *dL = nullptr, *dLi = nullptr, *dK = nullptr, *dW = nullptr;
+    HIP_TRY(f, dev_alloc(tmp, f->stream, &dS, hs.size()));
+    HIP_TRY(f, dev_alloc(tmp, f->stream, &dL, hs.size()));
+    HIP_TRY(f, dev_alloc(tmp, f->stream, &dLi, (size_t)64 * mp));
+    HIP_TRY(f, dev_alloc(tmp, f->stream, &dK, (size_t)rp * mp));
+    HIP_TRY(f, dev_alloc(tmp, f->stream, &dW, (size_t)rp * mp));
     HIP_TRY(f, hipMemcpyAsync(dS, hs.data(), sizeof(float) * hs.size(), hipMemcpyHostToDevice, f->stream));
     // the flow the handle's knobs and the process's handle count select for this shape, as for an update of the filter (plan_raw_sweep)
     UpdatePlan plan = plan_raw_sweep(f->tune, plan_shape(f), mp, rp);
@@ -1188,11 +1206,29 @@ int ekfvio_test_cholesky_solve(ekfvio_filter* f, int32_t m, int32_t nrhs, const 
     if (X_out)
         for (int c = 0; c < m; c++)
             for (int r = 0; r < nrhs; r++) X_out[(size_t)c * nrhs + r] = hk[(size_t)c * rp + r];
-    hipFree(dS);
-    hipFree(dL);
-    hipFree(dLi);
-    hipFree(dK);
-    hipFree(dW);
+    return EKFVIO_OK;
+}
+
+// What a ledger holds (mem.h): the handle's, or with a null handle everything this copy of the library holds, the test hooks' scratch included
+int ekfvio_test_mem(ekfvio_filter* f, int64_t out[8]) {
+    if (!out) return EKFVIO_EINVAL;
+    MemCounts c[2];  // device; pinned, whatever its flags
+    for (int k = 0; k < MEM_KINDS; k++) {
+        MemCounts& d = c[k == MEM_DEVICE ? 0 : 1];
+        const MemTotal& t = g_mem_total[k];
+        const MemCounts s = f ? f->mem.counts((MemKind)k) : MemCounts{t.live.load(), t.live_bytes.load(), t.acquired.load(), t.released.load()};
+        d.live += s.live, d.live_bytes += s.live_bytes, d.acquired += s.acquired, d.released += s.released;
+    }
+    const int64_t res[8] = {c[0].live, c[0].live_bytes, c[1].live, c[1].live_bytes, c[0].acquired, c[0].released, c[1].acquired, c[1].released};
+    std::copy(res, res + 8, out);
+    return EKFVIO_OK;
+}
+int ekfvio_test_mem_fail(ekfvio_filter* f, int32_t nth) {
+    if (nth < 0) return EKFVIO_EINVAL;
+    if (f)
+        f->mem.fail_nth(nth);
+    else
+        g_next_create_fail.store(nth);
     return EKFVIO_OK;
 }
 

@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "../../include/ekfvio.h"
+#include "mem.h"   // HIP-free: MemLedger, what owns a handle's device and pinned memory
 #include "plan.h"  // HIP-free: the switches (Tuning), the sizes a capacity implies, the flow of an update (UpdatePlan, plan_update)
 #ifdef EKFVIO_TEST_HOOKS
 #include "../../include/ekfvio_test_hooks.h"
@@ -111,12 +112,15 @@ struct GraphCache {
     bool leaves_flags_clean = false;  // ekfvio_filter::sweep_flags_clean as a replay leaves it (the same for every entry: the last update's last GEMM decides)
 };
 
+const MemBackend& hip_mem_backend();  // api.hip: the runtime's device and pinned allocation, the only place that calls it
+
 struct ekfvio_filter {
     ekfvio_config cfg;
     int device = 0;
     hipStream_t stream = nullptr;
     bool own_stream = false;
     std::string last_error;
+    MemLedger mem{hip_mem_backend()};  // owns every device and pinned buffer below, the lazily allocated ones included: ekfvio_destroy releases the ledger, no list of fields
 
     int N = 0;      // landmarks
     int n = EKF_BASE;
@@ -269,6 +273,24 @@ struct ekfvio_filter {
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
 };
 
+// ---- memory: every allocation of the library is an acquire on a ledger (mem.h) ---------
+// A non-null *p is released first (a grow); on failure *p is null.  dev_alloc: `count` elements, zero-filled on stream s -- nothing in this
+// library relies on the legacy null stream, which a non-blocking stream does not wait for; dev_alloc_bare: `bytes` as they come.
+inline hipError_t mem_error(int rc) { return rc == MEM_ERR_FOREIGN ? hipErrorInvalidDevicePointer : (hipError_t)rc; }
+template <class T>
+hipError_t dev_alloc(MemLedger& mem, hipStream_t s, T** p, size_t count) {
+    const size_t bytes = sizeof(T) * (count ? count : 1);
+    hipError_t e = mem_error(mem.acquire(p, bytes, MEM_DEVICE));
+    if (e == hipSuccess) e = hipMemsetAsync(*p, 0, bytes, s);
+    return e;
+}
+template <class T>
+hipError_t dev_alloc(ekfvio_filter* f, T** p, size_t count) { return dev_alloc(f->mem, f->stream, p, count); }
+template <class T>
+hipError_t dev_alloc_bare(ekfvio_filter* f, T** p, size_t bytes) { return mem_error(f->mem.acquire(p, bytes, MEM_DEVICE)); }
+template <class T>
+hipError_t host_alloc(ekfvio_filter* f, T** p, size_t bytes, MemKind kind) { return mem_error(f->mem.acquire(p, bytes, kind)); }
+
 // ---- launchers implemented across the translation units -------------------------------
 // C[MxN] = beta*Cin + alpha * A[MxK] * op(B); all column-major.  transB: B is [NxK]
 // (op = transpose) else [KxN].  K must be a multiple of 32 and the K-padding of both
@@ -418,7 +440,6 @@ int klt_track_device(ekfvio_filter* f);  // the tracker over the current landmar
 void launch_imu_update(ekfvio_filter* f, const float gyro[3], const float accel[3]);
 // fast.hip
 int fast_alloc(ekfvio_filter* f);
-void fast_free(ekfvio_filter* f);
 int fast_ensure(ekfvio_filter* f, int w, int h);  // grows the detector's per-pixel buffers to a w x h level 0 (synchronises if it must)
 // Waits for everything on the handle's stream and returns the factorisation's status word through *status (api.hip).
 // extra_dev (may be null): one more device word delivered with it through *extra_out.
@@ -489,10 +510,8 @@ size_t remove_lds_bytes(const ekfvio_filter* f);
 void remove_applied(ekfvio_filter* f, int delta, int removed);  // the host side behind a launch: pointer swaps, N, n, graphs
 // rectify.hip
 int rectify_ensure(ekfvio_filter* f, size_t src);  // the map planes and the second staging buffer for a frame of src pixels (the caller has waited for the stream)
-void rectify_free(ekfvio_filter* f);
 const uint8_t* rectify_enqueue(ekfvio_filter* f, const uint8_t* src, int w, int h, const float K[9], hipStream_t st);  // returns the rectified frame
 int klt_alloc(ekfvio_filter* f);  // klt.hip
-void klt_free(ekfvio_filter* f);
 
 struct ProfScope {
     ekfvio_filter* f;

@@ -388,20 +388,15 @@ int fast_ensure(ekfvio_filter* f, int w, int h) {
     w = std::max(w, f->fast_cap_w);
     h = std::max(h, f->fast_cap_h);
     if (f->stream) HIP_TRY(f, hipStreamSynchronize(f->stream));  // nothing in flight may still read the old buffers
-    void* old[] = {f->blurred, f->fast_row_kp, f->fast_kp_xy, f->fast_kp_score, f->occ_mask, f->fast_row_cnt};
-    for (void* p : old)
-        if (p) (void)hipFree(p);
-    f->blurred = nullptr, f->fast_row_kp = nullptr, f->fast_kp_xy = nullptr, f->fast_kp_score = nullptr, f->occ_mask = nullptr,
-    f->fast_row_cnt = nullptr;
     f->fast_cap_w = f->fast_cap_h = 0;
     const size_t px = (size_t)w * h;
-    if (c.fast_blur_sigma != 0.f) HIP_TRY(f, hipMalloc((void**)&f->blurred, px));
-    HIP_TRY(f, hipMalloc((void**)&f->fast_row_kp, px * sizeof(unsigned)));  // per image row: its keypoints in x order, (score << 16) | x
+    if (c.fast_blur_sigma != 0.f) HIP_TRY(f, dev_alloc_bare(f, &f->blurred, px));
+    HIP_TRY(f, dev_alloc_bare(f, &f->fast_row_kp, px * sizeof(unsigned)));  // per image row: its keypoints in x order, (score << 16) | x
     f->fast_kp_cap = (int)(px / 4 + 1);
-    HIP_TRY(f, hipMalloc((void**)&f->fast_kp_xy, (size_t)f->fast_kp_cap * 2 * sizeof(int)));
-    HIP_TRY(f, hipMalloc((void**)&f->fast_kp_score, (size_t)f->fast_kp_cap * sizeof(short)));
-    HIP_TRY(f, hipMalloc((void**)&f->occ_mask, ((size_t)(w + 31) / 32) * h * sizeof(unsigned)));
-    HIP_TRY(f, hipMalloc((void**)&f->fast_row_cnt, (size_t)h * sizeof(int)));
+    HIP_TRY(f, dev_alloc_bare(f, &f->fast_kp_xy, (size_t)f->fast_kp_cap * 2 * sizeof(int)));
+    HIP_TRY(f, dev_alloc_bare(f, &f->fast_kp_score, (size_t)f->fast_kp_cap * sizeof(short)));
+    HIP_TRY(f, dev_alloc_bare(f, &f->occ_mask, ((size_t)(w + 31) / 32) * h * sizeof(unsigned)));
+    HIP_TRY(f, dev_alloc_bare(f, &f->fast_row_cnt, (size_t)h * sizeof(int)));
     f->fast_cap_w = w;
     f->fast_cap_h = h;
     return EKFVIO_OK;
@@ -419,15 +414,9 @@ int fast_alloc(ekfvio_filter* f) {
         return EKFVIO_EINVAL;
     }
     const int maxf = c.max_features > 0 ? c.max_features : 1;
-    HIP_TRY(f, hipMalloc((void**)&f->new_xy, (size_t)maxf * 2 * sizeof(int)));
-    HIP_TRY(f, hipMalloc((void**)&f->fast_counts, 4 * sizeof(int)));
+    HIP_TRY(f, dev_alloc_bare(f, &f->new_xy, (size_t)maxf * 2 * sizeof(int)));
+    HIP_TRY(f, dev_alloc_bare(f, &f->fast_counts, 4 * sizeof(int)));
     return fast_ensure(f, c.max_image_width, c.max_image_height);
-}
-
-void fast_free(ekfvio_filter* f) {
-    void* ptrs[] = {f->blurred, f->fast_row_kp, f->fast_kp_xy, f->fast_kp_score, f->occ_mask, f->new_xy, f->fast_counts, f->fast_row_cnt};
-    for (void* p : ptrs)
-        if (p) (void)hipFree(p);
 }
 
 // cv::FAST on level 0 of the current frame -> f->fast_kp_* (raster order), count in f->fast_counts[0]

@@ -913,24 +913,16 @@ PyrView make_view(const KltFrame& fr) {
 int klt_level_pitch(int w) { return level_pitch(w); }
 int klt_border() { return KLT_BORDER; }
 
-// Planes of one frame for a level 0 of up to w x h pixels (every level the configuration allows).
+// Planes of one frame for a level 0 of up to w x h pixels (every level the configuration allows); a frame that has planes grows them.
 static int frame_planes_alloc(ekfvio_filter* f, KltFrame& fr, int w, int h) {
-    for (int l = 0; l < 8; l++) {
-        if (fr.img[l]) (void)hipFree(fr.img[l]);
-        if (fr.deriv[l]) (void)hipFree(fr.deriv[l]);
-        fr.img[l] = nullptr;
-        fr.deriv[l] = nullptr;
-    }
     fr.cap_w = fr.cap_h = 0;
     fr.valid = false;
     int lw = w, lh = h;
     for (int l = 0; l <= f->cfg.klt_max_pyramid_level; l++) {
         // + one row of slack: the tracker's aligned 4-byte loads may touch up to 3 bytes past a row's last pixel
         const size_t px = (size_t)level_pitch(lw) * (lh + 2 * KLT_BORDER + 1);
-        HIP_TRY(f, hipMalloc((void**)&fr.img[l], px));
-        HIP_TRY(f, hipMalloc((void**)&fr.deriv[l], px * 2 * sizeof(short)));
-        HIP_TRY(f, hipMemsetAsync(fr.img[l], 0, px, f->stream));
-        HIP_TRY(f, hipMemsetAsync(fr.deriv[l], 0, px * 2 * sizeof(short), f->stream));
+        HIP_TRY(f, dev_alloc(f, &fr.img[l], px));  // (zero-filled, the borders with them)
+        HIP_TRY(f, dev_alloc(f, &fr.deriv[l], px * 2));
         lw = (lw + 1) / 2;
         lh = (lh + 1) / 2;
     }
@@ -951,11 +943,9 @@ static int ensure_frame_capacity(ekfvio_filter* f, int sw, int sh, int w, int h)
     HIP_TRY(f, hipSetDevice(f->device));
     HIP_TRY(f, hipStreamSynchronize(f->stream));
     if (src > f->src_cap) {
-        if (f->staging) (void)hipFree(f->staging);
-        if (f->h_image) (void)hipHostFree(f->h_image);
-        f->staging = nullptr, f->h_image = nullptr, f->src_cap = 0;
-        HIP_TRY(f, hipMalloc((void**)&f->staging, src + 16));  // (+16: the upload kernel moves whole 16-byte pieces)
-        HIP_TRY(f, hipHostMalloc((void**)&f->h_image, src + 16, hipHostMallocMapped));
+        f->src_cap = 0;
+        HIP_TRY(f, dev_alloc_bare(f, &f->staging, src + 16));  // (+16: the upload kernel moves whole 16-byte pieces)
+        HIP_TRY(f, host_alloc(f, &f->h_image, src + 16, MEM_PINNED_MAPPED));
         f->src_cap = src;
     }
     if (w > fr.cap_w || h > fr.cap_h) {
@@ -981,29 +971,15 @@ int klt_alloc(ekfvio_filter* f) {
         if (rc != EKFVIO_OK) return rc;
     }
     const size_t maxf = f->cfg.max_features > 0 ? f->cfg.max_features : 1;
-    HIP_TRY(f, hipMalloc((void**)&f->klt_prev_px, sizeof(float) * 2 * maxf));
-    HIP_TRY(f, hipMalloc((void**)&f->klt_next_px, sizeof(float) * 2 * maxf));
-    HIP_TRY(f, hipMalloc((void**)&f->klt_status, maxf));
-    HIP_TRY(f, hipMalloc((void**)&f->klt_cov_px, sizeof(float) * 4 * maxf));
-    f->src_cap = (size_t)c.max_image_width * c.max_image_height;
-    HIP_TRY(f, hipMalloc((void**)&f->staging, f->src_cap + 16));
-    HIP_TRY(f, hipHostMalloc((void**)&f->h_image, f->src_cap + 16, hipHostMallocMapped));
+    HIP_TRY(f, dev_alloc_bare(f, &f->klt_prev_px, sizeof(float) * 2 * maxf));
+    HIP_TRY(f, dev_alloc_bare(f, &f->klt_next_px, sizeof(float) * 2 * maxf));
+    HIP_TRY(f, dev_alloc_bare(f, &f->klt_status, maxf));
+    HIP_TRY(f, dev_alloc_bare(f, &f->klt_cov_px, sizeof(float) * 4 * maxf));
+    const size_t src = (size_t)c.max_image_width * c.max_image_height;
+    HIP_TRY(f, dev_alloc_bare(f, &f->staging, src + 16));
+    HIP_TRY(f, host_alloc(f, &f->h_image, src + 16, MEM_PINNED_MAPPED));
+    f->src_cap = src;
     return EKFVIO_OK;
-}
-
-void klt_free(ekfvio_filter* f) {
-    for (int fr = 0; fr < 2; fr++)
-        for (int l = 0; l < 8; l++) {
-            if (f->frames[fr].img[l]) (void)hipFree(f->frames[fr].img[l]);
-            if (f->frames[fr].deriv[l]) (void)hipFree(f->frames[fr].deriv[l]);
-        }
-    if (f->klt_prev_px) (void)hipFree(f->klt_prev_px);
-    if (f->klt_next_px) (void)hipFree(f->klt_next_px);
-    if (f->klt_status) (void)hipFree(f->klt_status);
-    if (f->klt_cov_px) (void)hipFree(f->klt_cov_px);
-    if (f->staging) (void)hipFree(f->staging);
-    if (f->h_image) (void)hipHostFree(f->h_image);
-    rectify_free(f);
 }
 
 // Device-side part of klt_push_frame: staging -> pyramid + derivatives of frames[cur]
@@ -1073,9 +1049,8 @@ static int klt_fb_ensure(ekfvio_filter* f) {
     const size_t maxf = (size_t)(f->cfg.max_features > 0 ? f->cfg.max_features : 1);
     const size_t bytes = 8 * sizeof(int) + maxf * (4 * sizeof(float) + 2);
     unsigned char* buf = nullptr;
-    HIP_TRY(f, hipMalloc((void**)&buf, bytes));
-    f->fb_words = reinterpret_cast<int*>(buf);  // (from here on ekfvio_destroy releases it)
-    HIP_TRY(f, hipMemsetAsync(buf, 0, bytes, f->stream));
+    HIP_TRY(f, dev_alloc(f, &buf, bytes));
+    f->fb_words = reinterpret_cast<int*>(buf);
     f->fb_err2 = reinterpret_cast<float*>(buf + 8 * sizeof(int));
     f->fb_pt_err2 = f->fb_err2 + maxf;
     f->fb_pt_back = f->fb_err2 + 2 * maxf;

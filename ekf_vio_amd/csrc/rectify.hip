@@ -99,23 +99,16 @@ __global__ __launch_bounds__(256) void rectify_kernel(const uint8_t* __restrict_
 // for the stream): allocated when the first frame arrives with distortion on, regrown with a larger frame.
 int rectify_ensure(ekfvio_filter* f, size_t src) {
     if (!f->rect_on || src <= f->rect_cap) return EKFVIO_OK;
-    rectify_free(f);
-    // (+16: the kernels move whole groups of four entries, and the pyramid's source has the slack of the upload staging)
-    HIP_TRY(f, hipMalloc((void**)&f->rect_sx, sizeof(int) * (src + 16)));
-    HIP_TRY(f, hipMalloc((void**)&f->rect_sy, sizeof(int) * (src + 16)));
-    HIP_TRY(f, hipMalloc((void**)&f->rect_img, src + 16));
-    f->rect_cap = src;
-    return EKFVIO_OK;
-}
-
-void rectify_free(ekfvio_filter* f) {
-    if (f->rect_sx) (void)hipFree(f->rect_sx);
-    if (f->rect_sy) (void)hipFree(f->rect_sy);
-    if (f->rect_img) (void)hipFree(f->rect_img);
-    f->rect_sx = f->rect_sy = nullptr;
-    f->rect_img = nullptr;
+    // the old planes go before the new ones come, and with them the map they held
+    f->mem.release(&f->rect_sx), f->mem.release(&f->rect_sy), f->mem.release(&f->rect_img);
     f->rect_cap = 0;
     f->rect_key_valid = false;
+    // (+16: the kernels move whole groups of four entries, and the pyramid's source has the slack of the upload staging)
+    HIP_TRY(f, dev_alloc_bare(f, &f->rect_sx, sizeof(int) * (src + 16)));
+    HIP_TRY(f, dev_alloc_bare(f, &f->rect_sy, sizeof(int) * (src + 16)));
+    HIP_TRY(f, dev_alloc_bare(f, &f->rect_img, src + 16));
+    f->rect_cap = src;
+    return EKFVIO_OK;
 }
 
 // staging (w x h, tightly packed) -> the rectified frame, which is returned: what build_pyramid reads in its place.  The map is

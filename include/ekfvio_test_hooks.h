@@ -72,6 +72,14 @@ EKFVIO_API int ekfvio_test_persist_grid(int32_t num_cus, int32_t max_features, i
                                         int32_t out[10]);
 /* Tile pair p of T2's (csrc/plan.h, t2_pair): pair[2] = ta, tb. */
 EKFVIO_API int ekfvio_test_t2_pair(int32_t p, int32_t pair[2]);
+/* What the handle's memory ledger holds (csrc/mem.h).  out[8] = device: live allocations, live bytes; pinned host memory (mapped or not):
+ * live allocations, live bytes; then device: acquisitions ever, releases ever; pinned: acquisitions ever, releases ever (successful
+ * acquisitions only: live = acquired - released).  f == NULL: the totals over every ledger of this copy of the library, the scratch
+ * ledgers of the hooks above included. */
+EKFVIO_API int ekfvio_test_mem(ekfvio_filter* f, int64_t out[8]);
+/* Failure injection for the ledger: the handle's nth acquisition from now reports out-of-memory WITHOUT calling the runtime, once; 0 disarms.
+ * f == NULL arms the ledger of the next ekfvio_create of this copy of the library. */
+EKFVIO_API int ekfvio_test_mem_fail(ekfvio_filter* f, int32_t nth);
 
 #ifdef __cplusplus
 }
