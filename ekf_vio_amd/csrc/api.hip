@@ -377,6 +377,7 @@ int ekfvio_reset(ekfvio_filter* f) {
     HIP_TRY(f, hipStreamSynchronize(f->stream));
     f->have_stamp = false;
     f->frames[0].valid = f->frames[1].valid = false;
+    f->mask_hits_n = 0;  // the mask's hits of the last track go with the landmarks; the mask itself stays (ekfvio_set_mask)
     return EKFVIO_OK;
 }
 

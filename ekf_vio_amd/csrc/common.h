@@ -87,6 +87,14 @@ struct RectifyKey {
     int w, h;
 };
 
+// What the blocked map of a handle was formed for (mask.hip): compared as bits
+struct MaskKey {
+    RectifyKey rect;    // the rectification key where the border term is live (flag set and distortion on), else zeros
+    int rect_live;
+    unsigned user_gen;  // generation of the caller's mask (0: none)
+    int s, pad, w, h, flags;
+};
+
 // The captured step graphs of a device-resident run (api.hip, ekfvio_run_uploaded executes a RunPlan of plan.h with them).  A graph holds an
 // even number of filter steps: the mean / covariance ping-pong is back in its starting orientation behind a replay.
 // GraphKey: the VALUES the captured launches depend on; a run whose key differs drops all graphs and captures again.  Events that change a
@@ -250,6 +258,21 @@ struct ekfvio_filter {
     size_t rect_cap = 0;           // pixels the three were allocated for
     RectifyKey rect_key;           // what the map in rect_sx / rect_sy was formed for
     bool rect_key_valid = false;
+    // --- no-data mask (ekfvio_set_mask; mask.hip): the blocked map B of include/ekfvio.h, read by the detector and the tracker ---
+    bool mask_on = false;          // a caller's mask or a flag is set: B is formed (once per MaskKey) behind the rectification of a pushed frame
+    int mask_flags = 0;            // EKFVIO_MASK_*
+    // (device memory: the caller's copy is allocated by ekfvio_set_mask, the rest with the first frame pushed while mask_on, mask_ensure)
+    uint8_t* mask_user = nullptr;  // [mask_uw * mask_uh] the caller's mask, tightly packed (null: none)
+    int mask_uw = 0, mask_uh = 0;  // its size: the FULL frame size every pushed frame must then have
+    unsigned mask_user_gen = 0;    // counts the caller's masks this handle has been given
+    unsigned* mask_nodata = nullptr;   // [mask_cap_words] N, in OccMask's layout (fast.hip): (W + 31) / 32 words per row, tail bits 1
+    unsigned* mask_blocked = nullptr;  // [mask_cap_words] B, likewise
+    size_t mask_cap_words = 0;
+    MaskKey mask_key;              // what B was formed for
+    bool mask_key_valid = false;
+    int mask_bw = 0, mask_bh = 0;  // level-0 size of the B the device holds (0: none -- no frame pushed with the mask on, or off since)
+    uint8_t* mask_hit = nullptr;   // [max_features] 1: the most recent track's landmark was let through by everything else and masked
+    int mask_hits_n = 0;           // the landmark count that track saw
     // --- frame ingest + replenishment (fast.hip) ---
     uint8_t* blurred = nullptr;    // replenishFeatures' cv::GaussianBlur output (only with cfg.fast_blur_sigma != 0)
     unsigned* fast_row_kp = nullptr;  // [w*h] per image row its keypoints in x order, (score << 16) | x
@@ -511,6 +534,14 @@ void remove_applied(ekfvio_filter* f, int delta, int removed);  // the host side
 // rectify.hip
 int rectify_ensure(ekfvio_filter* f, size_t src);  // the map planes and the second staging buffer for a frame of src pixels (the caller has waited for the stream)
 const uint8_t* rectify_enqueue(ekfvio_filter* f, const uint8_t* src, int w, int h, const float K[9], hipStream_t st);  // returns the rectified frame
+// mask.hip
+int mask_check_frame(ekfvio_filter* f, int width, int height);  // EKFVIO_EINVAL (and last_error) for a frame that is not the caller's mask's size
+int mask_ensure(ekfvio_filter* f, int w, int h);  // the bit planes for a w x h level 0 and the hit flags (waits for the stream if it must allocate)
+void mask_enqueue(ekfvio_filter* f, int width, int height, int w, int h, int s, hipStream_t st);  // forms B if its key changed; behind rectify_enqueue
+// B for a w x h level 0 as the device holds it (words per row: (w + 31) / 32), or null: the mask is off, or was formed for another size
+inline const unsigned* mask_blocked_for(const ekfvio_filter* f, int w, int h) {
+    return (f->mask_bw == w && f->mask_bh == h && w > 0) ? f->mask_blocked : nullptr;
+}
 int klt_alloc(ekfvio_filter* f);  // klt.hip
 
 struct ProfScope {

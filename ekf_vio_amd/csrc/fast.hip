@@ -249,14 +249,15 @@ __device__ inline void stamp_circle(const OccMask<LDSMASK>& mask, int w, int h, 
 
 // replenishFeatures' selection.  Four wavefronts clear the mask and stamp the existing landmarks' circles (order-free:
 // bit ORs; every wavefront fetches 64 landmark pixels at once and takes every fourth); the first fit itself is sequential
-// by definition and stays with wavefront 0.  The global mask (LDSMASK = false) is zeroed by the caller.
+// by definition and stays with wavefront 0.  The global mask (LDSMASK = false) is zeroed, or filled with the no-data mask's B, by the caller.
 template <bool LDSMASK>
 __global__ __launch_bounds__(256) void replenish_select_kernel(const int* kp_xy, const int* kp_count, int cap_kp,
                                                               const float* __restrict__ mu, int N_old, float fx, float fy, float cx,
                                                               float cy, int num_features, int w, int h, int radius, int kill_pad,
                                                               unsigned* gmask, int* new_xy, float* new_uv, int* new_count,
                                                               const unsigned* __restrict__ row_kp, const int* __restrict__ row_cnt,
-                                                              int* kp_xy_out, short* kp_score_out, int* kp_total_out) {
+                                                              int* kp_xy_out, short* kp_score_out, int* kp_total_out,
+                                                              const unsigned* __restrict__ blocked) {
     __shared__ unsigned lmask[LDSMASK ? OCC_LDS_WORDS : 1];
     __shared__ int s_gw[4];
     __shared__ int s_gcarry;
@@ -274,7 +275,8 @@ __global__ __launch_bounds__(256) void replenish_select_kernel(const int* kp_xy,
     mask.wpr = (w + 31) / 32;
     mask.words = LDSMASK ? lmask : gmask;
     if (LDSMASK) {
-        for (int i = threadIdx.x; i < mask.wpr * h; i += 256) lmask[i] = 0u;
+        // (blocked: the no-data mask's B, mask.hip, in this layout -- a blocked keypoint is then skipped exactly as an occupied one is; null: off)
+        for (int i = threadIdx.x; i < mask.wpr * h; i += 256) lmask[i] = blocked ? blocked[i] : 0u;
         __syncthreads();
     }
     int hw[OCC_PASSES];
@@ -460,17 +462,19 @@ int replenish_enqueue(ekfvio_filter* f, int* enqueued) {
     const int w = v.w, h = v.h;
     const float fx = v.fx, fy = v.fy, cx = v.cx, cy = v.cy;
     const size_t mask_words = (size_t)((w + 31) / 32) * h;
+    const unsigned* blocked = mask_blocked_for(f, w, h);  // ekfvio_set_mask: the occupancy image starts as B instead of empty (null: off)
     if (mask_words <= OCC_LDS_WORDS) {
         hipLaunchKernelGGL(replenish_select_kernel<true>, dim3(1), dim3(256), 0, f->stream, f->fast_kp_xy, f->fast_counts, f->fast_kp_cap,
                            f->mu, f->N, fx, fy, cx, cy, f->cfg.max_features, w, h, f->cfg.min_new_feature_dist, f->cfg.kill_pad,
                            (unsigned*)f->occ_mask, f->new_xy, f->zmeas, f->fast_counts + 1, f->fast_row_kp, f->fast_row_cnt, f->fast_kp_xy,
-                           f->fast_kp_score, f->fast_counts);
+                           f->fast_kp_score, f->fast_counts, blocked);
     } else {
-        HIP_TRY(f, hipMemsetAsync(f->occ_mask, 0, mask_words * sizeof(unsigned), f->stream));
+        if (blocked) HIP_TRY(f, hipMemcpyAsync(f->occ_mask, blocked, mask_words * sizeof(unsigned), hipMemcpyDeviceToDevice, f->stream));
+        else HIP_TRY(f, hipMemsetAsync(f->occ_mask, 0, mask_words * sizeof(unsigned), f->stream));
         hipLaunchKernelGGL(replenish_select_kernel<false>, dim3(1), dim3(256), 0, f->stream, f->fast_kp_xy, f->fast_counts, f->fast_kp_cap,
                            f->mu, f->N, fx, fy, cx, cy, f->cfg.max_features, w, h, f->cfg.min_new_feature_dist, f->cfg.kill_pad,
                            (unsigned*)f->occ_mask, f->new_xy, f->zmeas, f->fast_counts + 1, f->fast_row_kp, f->fast_row_cnt, f->fast_kp_xy,
-                           f->fast_kp_score, f->fast_counts);
+                           f->fast_kp_score, f->fast_counts, (const unsigned*)nullptr);
     }
     *enqueued = 1;
     return EKFVIO_OK;

@@ -3,7 +3,7 @@
 // What a deployment of the reference runs in front of the node (image_proc/rectify: cv::initUndistortRectifyMap with R = I and the new
 // camera matrix = K, then cv::remap(INTER_LINEAR, BORDER_CONSTANT 0)); the reference itself assumes a pinhole image (Frame.h:31, its D at
 // :32 is never read; EKFVIO.cpp:429 "TODO add distortion coeffs").  The arithmetic is specified line by line in include/ekfvio.h
-// (ekfvio_set_distortion): rectify_map_entry below is that block, compiled for the host (ekfvio_rectify_map) and for the device
+// (ekfvio_set_distortion): rectify_map_entry (rectify_map.h) is that block, compiled for the host (ekfvio_rectify_map) and for the device
 // (rectify_map_kernel) out of the same lines, in fp64 without contraction, so that both give the bits of a NumPy restatement.
 //
 // Kernels: rectify_map_kernel writes the two fixed-point planes (once per camera: the host keeps the key it was formed for);
@@ -13,42 +13,9 @@
 #include <string.h>
 
 #include "common.h"
+#include "rectify_map.h"  // RectifyCam, rectify_map_entry: the specification's fp64 block, shared with mask.hip
 
 namespace {
-
-struct RectifyCam {
-    double fx, cx, fy, cy;
-    double k1, k2, p1, p2, k3;
-};
-
-// include/ekfvio.h, rectification: the fp64 block, line by line
-__host__ __device__ inline void rectify_map_entry(const RectifyCam& c, int x, int y, int* sx, int* sy) {
-    const double xn = ((double)x - c.cx) / c.fx, yn = ((double)y - c.cy) / c.fy;
-    const double xx = xn * xn, yy = yn * yn, xy = xn * yn, r2 = xx + yy;
-    const double rad = 1.0 + ((c.k3 * r2 + c.k2) * r2 + c.k1) * r2;
-    const double xd = (xn * rad + (2.0 * c.p1) * xy) + c.p2 * (r2 + 2.0 * xx);
-    const double yd = (yn * rad + c.p1 * (r2 + 2.0 * yy)) + (2.0 * c.p2) * xy;
-    const double u = c.fx * xd + c.cx, v = c.fy * yd + c.cy;
-    const bool valid = fabs(u) <= 1048576.0 && fabs(v) <= 1048576.0;  // (a NaN compares false)
-    *sx = valid ? (int)rint(u * 32.0) : INT32_MIN;  // |u * 32| <= 2^25: the conversion is exact
-    *sy = valid ? (int)rint(v * 32.0) : INT32_MIN;
-}
-
-RectifyCam rectify_cam(const float K[9], const double D[5]) {
-    RectifyCam c;
-    c.fx = (double)K[0], c.cx = (double)K[2], c.fy = (double)K[4], c.cy = (double)K[5];
-    c.k1 = D[0], c.k2 = D[1], c.p1 = D[2], c.p2 = D[3], c.k3 = D[4];
-    return c;
-}
-
-// D, count of the two entry points -> five coefficients; false: EKFVIO_EINVAL
-bool rectify_coefficients(const double* D, int32_t count, double out[5]) {
-    if (!(count == 0 || count == 4 || count == 5) || (count > 0 && !D)) return false;
-    for (int i = 0; i < 5; i++) out[i] = i < count ? D[i] : 0.0;
-    for (int i = 0; i < 5; i++)
-        if (!__builtin_isfinite(out[i])) return false;
-    return true;
-}
 
 // The frame as ONE run of w * h pixels, the planes likewise (no pitch: every row of four entries is 16-byte aligned whatever the
 // width).  n4 = ceil(w h / 4) lanes' worth of entries are written; those behind the frame's last pixel hold the sentinel.

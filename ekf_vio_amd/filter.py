@@ -26,7 +26,7 @@ class TightlyCoupledEKF:
     def __init__(self, max_features=100, device=0, stream=None, predict_mode=capi.PREDICT_STRUCTURED,
                  default_point_depth=0.5, default_point_depth_variance=100.0,
                  default_point_homogenous_variance=1e-5, hooks=False, gate_chi2=0.0, klt_fb_max_px=0.0, distortion=None, output_covariance=False,
-                 **cfg_overrides):
+                 mask=None, mask_rectify_border=False, **cfg_overrides):
         # hooks=True: this handle lives in libekfvio_hip_hooks.so, the build that also has include/ekfvio_test_hooks.h (tests, profiling scripts)
         self.hooks = bool(hooks)
         self.lib = capi.load(hooks=self.hooks)
@@ -56,6 +56,8 @@ class TightlyCoupledEKF:
             self.setDistortion(distortion)
         if output_covariance:  # likewise (ekfvio_set_output_covariance)
             self.setOutputCovariance(True)
+        if mask is not None or mask_rectify_border:  # likewise (ekfvio_set_mask)
+            self.setMask(mask, rectify_border=mask_rectify_border)
 
     def _chk(self, rc, allow=()):
         if rc != capi.OK and rc not in allow:
@@ -194,6 +196,39 @@ class TightlyCoupledEKF:
         None, () or all zeros: off."""
         d = np.ascontiguousarray([] if D is None else D, dtype=np.float64).reshape(-1)
         self._chk(self.lib.ekfvio_set_distortion(self.h, d.ctypes.data_as(C.POINTER(C.c_double)) if d.size else None, int(d.size)))
+
+    def setMask(self, mask, rectify_border=False):
+        """Not in the reference, which passes no mask to cv::FAST: the no-data mask (ekfvio_set_mask).  mask: uint8 [height, width] at the FULL
+        frame size, nonzero = scene, or None; rectify_border: the black border that rectification leaves is no-data too.  From the next pushed
+        frame on the detector takes no landmark, and the tracker passes none, within the kill-pad window of a no-data pixel; None and False:
+        off.  While a mask is set, frames of another size are refused."""
+        flags = capi.MASK_RECTIFY_BORDER if rectify_border else 0
+        if mask is None:
+            self._chk(self.lib.ekfvio_set_mask(self.h, None, 0, 0, 0, flags))
+            return
+        m = np.asarray(mask)
+        if m.ndim != 2:
+            raise capi.EkfvioError(capi.EINVAL, "the mask is a 2-D array")
+        m = np.ascontiguousarray(m != 0 if m.dtype != np.uint8 else m, dtype=np.uint8)
+        self._chk(self.lib.ekfvio_set_mask(self.h, _u8(m), m.shape[1], m.shape[0], m.shape[1], flags))
+
+    def mask_blocked(self):
+        """ekfvio_get_mask: the blocked map B as the device holds it, uint8 [H, W] of level 0 (1 = blocked); shape (0, 0) before the first
+        frame pushed with the mask on."""
+        w, h = C.c_int32(0), C.c_int32(0)
+        self._chk(self.lib.ekfvio_get_mask(self.h, None, 0, C.byref(w), C.byref(h)))
+        b = np.zeros((h.value, w.value), np.uint8)
+        if b.size:
+            self._chk(self.lib.ekfvio_get_mask(self.h, _u8(b), b.size, C.byref(w), C.byref(h)))
+        return b
+
+    def mask_hits(self):
+        """ekfvio_get_mask_hits: dict(masked[n], n_landmarks, masked_last) of the most recent track of the landmarks with the mask on."""
+        cap = max(int(self.cfg.max_features), 1)
+        m = np.zeros(cap, np.uint8)
+        n, last = C.c_int32(0), C.c_int32(0)
+        self._chk(self.lib.ekfvio_get_mask_hits(self.h, _u8(m), C.byref(n), C.byref(last)))
+        return dict(masked=m[:n.value].copy(), n_landmarks=int(n.value), masked_last=int(last.value))
 
     def setOutputCovariance(self, on):
         """Not in the reference (EKFVIO.cpp:473 "TODO add convariance computation"): with it on, every frame of ekfvio_step_image carries the
@@ -458,6 +493,28 @@ def rectify_map(K, D, width, height):
     return sx, sy
 
 
+def mask_blocked(K, D, mask, width, height, inverse_image_scale, kill_pad, flags):
+    """ekfvio_mask_blocked: the blocked map B (include/ekfvio.h, ekfvio_set_mask), uint8 [height // s, width // s], that a handle with these
+    settings holds for width x height frames: K, D as rectify_map takes them, mask uint8 [height, width] or None (any row stride of the array is
+    passed on), flags = capi.MASK_RECTIFY_BORDER or 0.  A host function: no GPU involved."""
+    lib = capi.load()
+    Kp = None if K is None else _fp(np.ascontiguousarray(K, dtype=np.float32).reshape(9))
+    d = np.ascontiguousarray([] if D is None else D, dtype=np.float64).reshape(-1)
+    mp, stride = None, 0
+    if mask is not None:
+        m = np.asarray(mask)
+        if m.dtype != np.uint8 or m.ndim != 2 or m.strides[1] != 1 or m.shape != (int(height), int(width)):
+            m = np.ascontiguousarray(m, dtype=np.uint8).reshape(int(height), int(width))
+        mp, stride = C.cast(m.ctypes.data, C.POINTER(C.c_uint8)), int(m.strides[0])
+    s = max(int(inverse_image_scale), 1)
+    out = np.zeros((max(int(height) // s, 0), max(int(width) // s, 0)), np.uint8)
+    rc = lib.ekfvio_mask_blocked(Kp, d.ctypes.data_as(C.POINTER(C.c_double)) if d.size else None, int(d.size), mp, int(width), int(height), stride,
+                                 int(inverse_image_scale), int(kill_pad), int(flags), _u8(out) if out.size else None)
+    if rc != capi.OK:
+        raise capi.EkfvioError(rc, "ekfvio_mask_blocked")
+    return out
+
+
 class EKFVIO:
     """Host mirror of the step sequence of EKFVIO::addFrame / updateStateWithNewImage
     (include/ekf_vio/EKFVIO.cpp:139-219) without ROS: frames in, odometry + landmark cloud out.
@@ -466,7 +523,7 @@ class EKFVIO:
 
     def __init__(self, **kw):
         # (distortion=(k1, k2, p1, p2[, k3]): raw frames are rectified on the device, setDistortion below; output_covariance=True: every frame's
-        # outputs carry their covariances, setOutputCovariance below)
+        # outputs carry their covariances, setOutputCovariance below; mask=uint8 [h, w] and / or mask_rectify_border=True: the no-data mask, setMask below)
         self.tc_ekf = TightlyCoupledEKF(**kw)
         self.tracker = KLTTracker(self.tc_ekf)
         self._imu_queue = []      # (stamp, gyro, accel), kept in stamp order; only used with use_imu = 1
@@ -491,6 +548,10 @@ class EKFVIO:
     def setDistortion(self, D):
         """The camera's plumb_bob coefficients (TightlyCoupledEKF.setDistortion): from the next frame on addFrame takes raw frames."""
         self.tc_ekf.setDistortion(D)
+
+    def setMask(self, mask, rectify_border=False):
+        """TightlyCoupledEKF.setMask: from the next frame on no landmark is taken or passed within the kill-pad window of a no-data pixel."""
+        self.tc_ekf.setMask(mask, rectify_border=rectify_border)
 
     def setOutputCovariance(self, on):
         """TightlyCoupledEKF.setOutputCovariance: from the next frame on addFrame delivers the covariances with the frame's outputs."""

@@ -54,6 +54,9 @@ struct Params {
     // Not in the reference, which publishes all-zero covariances (EKFVIO.cpp:473): with publish_covariance = 1 every frame carries the covariances of
     // its odometry and point cloud (ekfvio_set_output_covariance) and the node fills nav_msgs/Odometry's two 6x6 blocks from them.
     int publish_covariance = 0;
+    // Not in the reference, which passes no mask to cv::FAST: with mask_rectify_border = 1 the black border that rectification leaves is no-data
+    // (ekfvio_set_mask, EKFVIO_MASK_RECTIFY_BORDER): no landmark is detected or passed within the kill-pad window of it.  Nothing to mask while rectify = 0.
+    int mask_rectify_border = 0;
     std::map<std::string, std::string> node;  // odom_topic, camera_topic, base_frame, use_imu, publish_insight, ...
 
     Params() {
@@ -106,6 +109,7 @@ struct Params {
         }
         else if (key == "rectify") rectify = (value == "true" || value == "1") ? 1 : 0;
         else if (key == "publish_covariance") publish_covariance = (value == "true" || value == "1") ? 1 : 0;
+        else if (key == "mask_rectify_border") mask_rectify_border = (value == "true" || value == "1") ? 1 : 0;
         else if (key == "distortion_k1") distortion[0] = number(key, value);
         else if (key == "distortion_k2") distortion[1] = number(key, value);
         else if (key == "distortion_p1") distortion[2] = number(key, value);
@@ -130,7 +134,7 @@ struct Params {
                                         "default_point_depth", "default_point_depth_variance",
                                         "default_point_homogenous_variance", "frame_buffer_size", "imu_update",
                                         "imu_gyro_variance", "imu_accel_variance", "gravity_x", "gravity_y", "gravity_z", "remove_lost", "gate_chi2",
-                                        "klt_fb_max_px", "rectify", "publish_covariance", "distortion_k1", "distortion_k2", "distortion_p1", "distortion_p2", "distortion_k3"};
+                                        "klt_fb_max_px", "rectify", "publish_covariance", "mask_rectify_border", "distortion_k1", "distortion_k2", "distortion_p1", "distortion_p2", "distortion_k3"};
         for (const auto& e : Params().node) out.push_back(e.first);
         for (const auto& e : ignored()) out.push_back(e.first);
         return out;
@@ -266,6 +270,35 @@ class TightlyCoupledEKF {
     // Not in the reference, which assumes a pinhole image (Frame.h:31): the camera's plumb_bob coefficients k1 k2 p1 p2 [k3] (ekfvio_set_distortion).
     // From the next frame on, frames are rectified on the device between the upload and the pyramid; empty or all zero: off.
     void setDistortion(const std::vector<double>& D) { chk(ekfvio_set_distortion(h_, D.empty() ? nullptr : D.data(), (int32_t)D.size())); }
+    // Not in the reference, which passes no mask to cv::FAST: the no-data mask (ekfvio_set_mask).  mask: w x h bytes at the FULL frame size with a row
+    // stride, nonzero = scene, or nullptr (w = h = stride = 0); flags: EKFVIO_MASK_RECTIFY_BORDER or 0.  From the next frame on no landmark is
+    // detected or passed within the kill-pad window of a no-data pixel; nullptr and 0: off.  While a mask is set, frames of another size are refused.
+    void setMask(const uint8_t* mask, int w, int h, int stride, int flags) { chk(ekfvio_set_mask(h_, mask, w, h, stride, flags)); }
+    struct Mask {
+        int width = 0, height = 0;     // level 0; 0 x 0 before the first frame pushed with the mask on
+        std::vector<uint8_t> blocked;  // height x width, 1 = blocked
+    };
+    Mask getMask() {
+        Mask m;
+        int32_t w = 0, h = 0;
+        chk(ekfvio_get_mask(h_, nullptr, 0, &w, &h));
+        m.blocked.assign((size_t)w * (size_t)h, 0);
+        if (!m.blocked.empty()) chk(ekfvio_get_mask(h_, m.blocked.data(), (int32_t)m.blocked.size(), &w, &h));
+        m.width = w, m.height = h;
+        return m;
+    }
+    struct MaskHits {
+        std::vector<uint8_t> masked;  // per landmark of the most recent track: let through by everything else, and on a blocked pixel
+        int32_t masked_last = 0;
+    };
+    MaskHits getMaskHits() {
+        MaskHits r;
+        r.masked.assign((size_t)(max_features_ > 0 ? max_features_ : 1), 0);
+        int32_t n = 0;
+        chk(ekfvio_get_mask_hits(h_, r.masked.data(), &n, &r.masked_last));
+        r.masked.resize((size_t)n);
+        return r;
+    }
     // Not in the reference (EKFVIO.cpp:473 "TODO add convariance computation"): the covariances of the published outputs (include/ekfvio.h).
     // setOutputCovariance(true): every frame of addFrame carries them with its other outputs, and the two getters cost a memcpy behind a frame
     // (such a frame's outputs never go out in front of the update's last GEMM); otherwise each getter is one launch and one wait.
@@ -435,6 +468,7 @@ class EKFVIO {
         if (p.gate_chi2 > 0.f) tc_ekf.setGate(p.gate_chi2);  // (behind ekfvio_create: the gate is a property of the handle)
         if (p.rectify) tc_ekf.setDistortion(std::vector<double>(p.distortion.begin(), p.distortion.end()));  // (likewise; a node replaces them with CameraInfo.D)
         if (p.publish_covariance) tc_ekf.setOutputCovariance(true);  // (likewise)
+        if (p.mask_rectify_border) tc_ekf.setMask(nullptr, 0, 0, 0, EKFVIO_MASK_RECTIFY_BORDER);  // (likewise; live once the coefficients are nonzero)
     }
     TightlyCoupledEKF tc_ekf;
     KLTTracker tracker;

@@ -101,7 +101,8 @@ class EkfvioNode {
         // the ~48 private parameters of EKFVIO::EKFVIO (EKFVIO.cpp:20-67) by the reference's names
         // (and this backend's own: imu_update, remove_lost, gate_chi2, klt_fb_max_px -- the tracker's forward-backward threshold in pixels of
         // the resized frame, which reaches the handle inside ekfvio_config -- and publish_covariance, default false: with it the handle is
-        // told at start-up, by ekfvio::EKFVIO's constructor, to deliver the covariances with every frame's outputs)
+        // told at start-up, by ekfvio::EKFVIO's constructor, to deliver the covariances with every frame's outputs; mask_rectify_border, default
+        // false: with it, and rectify = 1, the black border that rectification leaves is no-data for the detector and the tracker, ekfvio_set_mask)
         for (const std::string& name : ekfvio::Params::names()) {
             XmlRpc::XmlRpcValue v;
             if (ros::param::get("~" + name, v)) params_.set(name, to_text(v));

@@ -117,7 +117,7 @@ EKFVIO_API int ekfvio_create(const ekfvio_config* cfg, int device, void* stream,
 EKFVIO_API int ekfvio_destroy(ekfvio_filter* f);
 /* initializeBaseState(): back to mu = [0,0,0,1,0...], Sigma diag [0x7,30x9,0.5x6], no landmarks.  (The innovation gate's counts start
  * over; its threshold stays.  The same holds for the tracker's forward-backward check.  The distortion coefficients of
- * ekfvio_set_distortion stay too, and so does the setting of ekfvio_set_output_covariance.) */
+ * ekfvio_set_distortion stay too, and so does the setting of ekfvio_set_output_covariance.  The mask of ekfvio_set_mask stays as well.) */
 EKFVIO_API int ekfvio_reset(ekfvio_filter* f);
 EKFVIO_API const char* ekfvio_last_error(const ekfvio_filter* f);
 
@@ -237,8 +237,8 @@ EKFVIO_API int ekfvio_get_gate(ekfvio_filter* f, float* d2, uint8_t* gated, int3
  * contributes 0 (so the sentinel gives 0 by itself); out = (sum + 512) >> 10.  With D = 0 the map is exactly (32x, 32y) and the frame
  * keeps every byte.  The rectified full-size frame then takes the road of an uploaded one: the resize and the pyramid read it, K is
  * unchanged, and the intensity channel of ekfvio_get_points reads it.  The map is formed on the device once per (fx, cx, fy, cy, D, w, h)
- * and kept.  Out of scope: the equidistant and rational models, a new camera matrix or alpha crop, and a mask that keeps the detector
- * away from the black border (image_proc/rectify leaves the same border).
+ * and kept.  Out of scope: the equidistant and rational models, and a new camera matrix or alpha crop.  (The black border these lines
+ * leave, as image_proc/rectify does, is kept away from the detector and the tracker by ekfvio_set_mask, below.)
  *
  * count = 5: D as above; count = 4: k3 = 0; count = 0 (D may be NULL) or all coefficients zero: off (default; then no launch differs and
  * every output keeps its bits).  A non-finite coefficient, any other count, NULL with count > 0: EKFVIO_EINVAL, and the setting stays
@@ -249,6 +249,61 @@ EKFVIO_API int ekfvio_set_distortion(ekfvio_filter* f, const double* D, int32_t 
  * (a tap outside the frame means no data there).  D, count as above (count = 0: the identity map). */
 EKFVIO_API int ekfvio_rectify_map(const float K[9], const double* D, int32_t count, int32_t width, int32_t height, int32_t* sx,
                                   int32_t* sy);
+
+/* ---- no-data mask (not in the reference, which passes no mask to cv::FAST, EKFVIO.cpp:224-311) ----------------------------------------
+ * Keeps the detector and the tracker off pixels that hold no scene.  Two sources: the black border that rectification leaves (FAST fires on
+ * its edge, and the corners it finds there are fixed in the image: landmarks that contradict every camera motion, which neither the gate
+ * nor the forward-backward check can see), and regions the caller knows are not scene (a bonnet, a gimbal arm, a burnt-in timestamp).  The
+ * lines below are the specification; a NumPy restatement of them (tests/_mask.py) is what the device is held to, bit for bit.
+ *
+ * A pushed frame is w x h at full size; s = max(cfg.inverse_image_scale, 1); W = w / s, H = h / s (integer division: the size of level 0);
+ * pad = max(cfg.kill_pad, 0).
+ *
+ *  1. Full-size no-data n(x, y), the OR of two terms.
+ *     Caller's mask: a mask is set and mask[y * stride + x] == 0.
+ *     Rectification border: EKFVIO_MASK_RECTIFY_BORDER is set and distortion is on.  With (sx, sy) the map entry of (x, y) (ekfvio_set_distortion,
+ *     above), ix = sx >> 5, ax = sx & 31, iy = sy >> 5, ay = sy & 31 as there: no-data if any of the four taps (ix, iy), (ix+1, iy), (ix, iy+1),
+ *     (ix+1, iy+1) with the weights (32-ax)(32-ay), ax(32-ay), (32-ax)ay, ax*ay has a non-zero weight and lies outside [0, w) x [0, h).  (The
+ *     sentinel entry needs no special case: its first tap has weight 1024 and lies outside.  Nor does the identity map: its taps outside the
+ *     frame have weight 0.)
+ *  2. Level-0 no-data N(X, Y): the OR of n(x, y) over x in [s X, s X + s), y in [s Y, s Y + s).  Outside [0, W) x [0, H): N = 1.  (Every pixel the
+ *     resize reads for (X, Y) lies in that block.)
+ *  3. Blocked B(X, Y): the OR of N(X', Y') over X' in [X - pad, X + max(pad - 1, 0)] and Y' in the same window around Y.  The window is
+ *     asymmetric by one on purpose: with no no-data pixel inside the frame, B is exactly the complement of Frame::isPixelInBox, whose test is
+ *     x < pad || w - x < pad.  The mask generalises the kill box; it has no margin parameter of its own.
+ *
+ * Detector (ekfvio_replenish; ekfvio_step_image with cfg.replenish = 1): the occupancy image starts as B instead of empty; a blocked keypoint is
+ * skipped exactly as an occupied one is.  The kill-box test stays.
+ * Tracker (ekfvio_klt_track, ekfvio_step_image; with the constant R and with the sample-based R): pass additionally requires
+ * B(cvRound(ox), cvRound(oy)) == 0 for the tracked pixel (ox, oy); cvRound is round-half-to-even, as Feature::getPixel's conversion; a rounded
+ * pixel outside level 0 counts as blocked.  The order of verdicts: forward status, forward-backward check, kill box, mask: masked[i] = 1 only
+ * for a landmark that everything before the mask let through.  A masked landmark takes in every respect the road of one the tracker lost:
+ * pass = 0, z and R zero, no measurement rows, last_klt kept, delete flag set by the update -- and with cfg.remove_lost = 1 ekfvio_step_image
+ * removes it in the same frame.  The innovation gate never sees it.  ekfvio_klt_track_points and ekfvio_klt_track_points_fb work in pixel
+ * space, have no pass test and do not change.  ekfvio_add_features stays unchecked: a caller's own detector is the caller's business.
+ *
+ * B is formed on the device once per (rectification key where the border term is live, caller's mask, s, pad, w, h, flags), behind the
+ * rectification of the frame that first needs it, and kept as bit words; per frame the detector copies it into its occupancy image and the
+ * tracker reads one bit per landmark.
+ *
+ * ekfvio_set_mask.  mask: w x h bytes at the FULL frame size with a row stride, nonzero = scene; NULL (width = height = stride = 0): no caller's
+ * mask.  mask == NULL and flags == 0: off (default; then no launch differs, nothing is allocated and every output keeps its bits).  The mask is
+ * copied before the call returns (the call waits for the handle's stream first).  A property of the handle: it holds from the next pushed frame
+ * and survives ekfvio_reset.  Unknown flag bits, NULL with a non-zero size, stride < width, a size outside [1, 16384]: EKFVIO_EINVAL, and the
+ * setting stays what it was.  While a caller's mask is set, a frame pushed with another size is refused (EKFVIO_EINVAL, ekfvio_last_error has
+ * the sizes) and not ingested.  The border flag with distortion off contributes nothing; it is not an error. */
+enum { EKFVIO_MASK_RECTIFY_BORDER = 1 };
+EKFVIO_API int ekfvio_set_mask(ekfvio_filter* f, const uint8_t* mask, int32_t width, int32_t height, int32_t stride, int32_t flags);
+/* B as the device holds it, one byte (0/1) per level-0 pixel, row-major *w x *h, and its size; *w = *h = 0 before the first frame pushed with
+ * the mask on (and again once a frame has been pushed with it off).  blocked may be NULL (the size alone); cap < *w * *h: EKFVIO_EINVAL. */
+EKFVIO_API int ekfvio_get_mask(ekfvio_filter* f, uint8_t* blocked, int32_t cap, int32_t* w, int32_t* h);
+/* Per landmark of the most recent track of the landmarks with the mask on: masked flag (room for max_features), the landmark count that
+ * track saw (indices are its indices; 0 before the first such track), number masked.  Any pointer may be NULL. */
+EKFVIO_API int ekfvio_get_mask_hits(ekfvio_filter* f, uint8_t* masked, int32_t* n_landmarks, int32_t* masked_last);
+/* B on the host, width / s x height / s bytes: a pure host function (no handle, no device) that compiles the very inline functions the
+ * kernels compile, as ekfvio_rectify_map does.  K, D, count as there (K may be NULL where the border term is not live); mask may be NULL. */
+EKFVIO_API int ekfvio_mask_blocked(const float K[9], const double* D, int32_t count, const uint8_t* mask, int32_t width, int32_t height,
+                                   int32_t stride, int32_t inverse_image_scale, int32_t kill_pad, int32_t flags, uint8_t* blocked);
 
 /* ---- covariances of the published outputs (not in the reference: EKFVIO.cpp:473 "TODO add convariance computation"; its Odometry
  * message carries two all-zero 6x6 covariances) -----------------------------------------------------------------------------------------
