@@ -273,6 +273,13 @@ struct ekfvio_filter {
     int mask_bw = 0, mask_bh = 0;  // level-0 size of the B the device holds (0: none -- no frame pushed with the mask on, or off since)
     uint8_t* mask_hit = nullptr;   // [max_features] 1: the most recent track's landmark was let through by everything else and masked
     int mask_hits_n = 0;           // the landmark count that track saw
+    // --- equalisation of pushed frames (ekfvio_set_equalize; equalize.hip): clip-limited tile histograms, in place on the full-size frame ---
+    bool eq_on = false;            // clip limit > 0: frames pass the two equalize kernels between the rectification and the pyramid
+    float eq_clip = 0.f;           // the setting as given
+    int eq_tx = 0, eq_ty = 0;
+    // (device memory: allocated with the first frame pushed while eq_on, ensure_frame_capacity in klt.hip)
+    uint8_t* eq_lut = nullptr;     // [eq_lut_cap] one 256-byte table per tile, row-major tiles
+    size_t eq_lut_cap = 0;
     // --- frame ingest + replenishment (fast.hip) ---
     uint8_t* blurred = nullptr;    // replenishFeatures' cv::GaussianBlur output (only with cfg.fast_blur_sigma != 0)
     unsigned* fast_row_kp = nullptr;  // [w*h] per image row its keypoints in x order, (score << 16) | x
@@ -542,6 +549,10 @@ void mask_enqueue(ekfvio_filter* f, int width, int height, int w, int h, int s, 
 inline const unsigned* mask_blocked_for(const ekfvio_filter* f, int w, int h) {
     return (f->mask_bw == w && f->mask_bh == h && w > 0) ? f->mask_blocked : nullptr;
 }
+// equalize.hip
+int equalize_check_frame(ekfvio_filter* f, int width, int height);  // EKFVIO_EINVAL (and last_error) for a frame with fewer columns or rows than tiles
+int equalize_ensure(ekfvio_filter* f);  // the tables for the current setting (the caller has waited for the stream)
+void equalize_enqueue(ekfvio_filter* f, uint8_t* full, int w, int h, hipStream_t st);  // equalises the full-size frame in place; behind rectify_enqueue
 int klt_alloc(ekfvio_filter* f);  // klt.hip
 
 struct ProfScope {

@@ -952,7 +952,8 @@ static int ensure_frame_capacity(ekfvio_filter* f, int sw, int sh, int w, int h)
     const size_t src = (size_t)sw * sh;
     KltFrame& fr = f->frames[f->cur ^ 1];
     const bool rect = f->rect_on && src > f->rect_cap;  // rectification on (ekfvio_set_distortion) and its buffers not there yet, or too small
-    if (src <= f->src_cap && w <= fr.cap_w && h <= fr.cap_h && w <= f->fast_cap_w && h <= f->fast_cap_h && !rect) return EKFVIO_OK;
+    const bool eq = f->eq_on && (size_t)f->eq_tx * f->eq_ty * 256 > f->eq_lut_cap;  // equalisation on (ekfvio_set_equalize) and its tables not there yet, or too few
+    if (src <= f->src_cap && w <= fr.cap_w && h <= fr.cap_h && w <= f->fast_cap_w && h <= f->fast_cap_h && !rect && !eq) return EKFVIO_OK;
     HIP_TRY(f, hipSetDevice(f->device));
     HIP_TRY(f, hipStreamSynchronize(f->stream));
     if (src > f->src_cap) {
@@ -967,6 +968,10 @@ static int ensure_frame_capacity(ekfvio_filter* f, int sw, int sh, int w, int h)
     }
     if (rect) {
         const int rc = rectify_ensure(f, src);
+        if (rc != EKFVIO_OK) return rc;
+    }
+    if (eq) {
+        const int rc = equalize_ensure(f);
         if (rc != EKFVIO_OK) return rc;
     }
     return fast_ensure(f, w, h);
@@ -1173,6 +1178,8 @@ int push_frame_check(ekfvio_filter* f, const uint8_t* image, int32_t width, int3
     if (width / s < 1 || height / s < 1) return EKFVIO_EINVAL;
     int rc = mask_check_frame(f, width, height);  // ekfvio_set_mask: a caller's mask is as large as the frames it is for
     if (rc != EKFVIO_OK) return rc;
+    rc = equalize_check_frame(f, width, height);  // ekfvio_set_equalize: every tile needs a column and a row of the frame
+    if (rc != EKFVIO_OK) return rc;
     rc = ensure_frame_capacity(f, width, height, width / s, height / s);
     return rc != EKFVIO_OK ? rc : mask_ensure(f, width / s, height / s);
 }
@@ -1211,6 +1218,8 @@ int push_frame_enqueue(ekfvio_filter* f, const uint8_t* image, int32_t width, in
     }
     // ekfvio_set_distortion: the full-size frame is rectified first (with the K as passed), and the pyramid reads that plane instead
     const uint8_t* full = f->rect_on ? rectify_enqueue(f, f->staging, width, height, K, st) : f->staging;
+    // ekfvio_set_equalize: that plane (both are the handle's own) is equalised in place, and everything behind sees the equalised frame
+    if (f->eq_on) equalize_enqueue(f, f->rect_on ? f->rect_img : f->staging, width, height, st);
     mask_enqueue(f, width, height, w, h, s, st);  // ekfvio_set_mask: the blocked map for this frame, formed only if its key changed
     build_pyramid(f, fr, full, width, height, w, h, st);
     fr.valid = true;

@@ -26,7 +26,7 @@ class TightlyCoupledEKF:
     def __init__(self, max_features=100, device=0, stream=None, predict_mode=capi.PREDICT_STRUCTURED,
                  default_point_depth=0.5, default_point_depth_variance=100.0,
                  default_point_homogenous_variance=1e-5, hooks=False, gate_chi2=0.0, klt_fb_max_px=0.0, distortion=None, output_covariance=False,
-                 mask=None, mask_rectify_border=False, **cfg_overrides):
+                 mask=None, mask_rectify_border=False, equalize=None, **cfg_overrides):
         # hooks=True: this handle lives in libekfvio_hip_hooks.so, the build that also has include/ekfvio_test_hooks.h (tests, profiling scripts)
         self.hooks = bool(hooks)
         self.lib = capi.load(hooks=self.hooks)
@@ -58,6 +58,8 @@ class TightlyCoupledEKF:
             self.setOutputCovariance(True)
         if mask is not None or mask_rectify_border:  # likewise (ekfvio_set_mask)
             self.setMask(mask, rectify_border=mask_rectify_border)
+        if equalize is not None:  # likewise (ekfvio_set_equalize)
+            self.setEqualize(*equalize)
 
     def _chk(self, rc, allow=()):
         if rc != capi.OK and rc not in allow:
@@ -211,6 +213,12 @@ class TightlyCoupledEKF:
             raise capi.EkfvioError(capi.EINVAL, "the mask is a 2-D array")
         m = np.ascontiguousarray(m != 0 if m.dtype != np.uint8 else m, dtype=np.uint8)
         self._chk(self.lib.ekfvio_set_mask(self.h, _u8(m), m.shape[1], m.shape[0], m.shape[1], flags))
+
+    def setEqualize(self, clip_limit, tiles_x=8, tiles_y=8):
+        """Not in the reference, whose detector has a fixed contrast threshold and whose tracker assumes brightness constancy: clip-limited tile
+        histogram equalisation of every pushed frame on the device, between the rectification and the pyramid (ekfvio_set_equalize).
+        clip_limit > 0 with tiles in [1, 16]: on from the next pushed frame; clip_limit == 0: off."""
+        self._chk(self.lib.ekfvio_set_equalize(self.h, float(clip_limit), int(tiles_x), int(tiles_y)))
 
     def mask_blocked(self):
         """ekfvio_get_mask: the blocked map B as the device holds it, uint8 [H, W] of level 0 (1 = blocked); shape (0, 0) before the first
@@ -515,6 +523,23 @@ def mask_blocked(K, D, mask, width, height, inverse_image_scale, kill_pad, flags
     return out
 
 
+def equalize(image, clip_limit, tiles_x=8, tiles_y=8):
+    """ekfvio_equalize: the frame a handle with ekfvio_set_equalize(clip_limit, tiles_x, tiles_y) makes of `image` (uint8 [height, width]; any row
+    stride of the array is passed on) before its pyramid, uint8 [height, width].  A host function: no GPU involved."""
+    lib = capi.load()
+    m = np.asarray(image)
+    if m.ndim != 2:
+        raise capi.EkfvioError(capi.EINVAL, "the image is a 2-D array")
+    if m.dtype != np.uint8 or m.strides[1] != 1 or m.strides[0] < m.shape[1]:
+        m = np.ascontiguousarray(m, dtype=np.uint8)
+    out = np.zeros(m.shape, np.uint8)
+    rc = lib.ekfvio_equalize(C.cast(m.ctypes.data, C.POINTER(C.c_uint8)) if m.size else None, int(m.shape[1]), int(m.shape[0]), int(m.strides[0]),
+                             float(clip_limit), int(tiles_x), int(tiles_y), _u8(out) if out.size else None)
+    if rc != capi.OK:
+        raise capi.EkfvioError(rc, "ekfvio_equalize")
+    return out
+
+
 class EKFVIO:
     """Host mirror of the step sequence of EKFVIO::addFrame / updateStateWithNewImage
     (include/ekf_vio/EKFVIO.cpp:139-219) without ROS: frames in, odometry + landmark cloud out.
@@ -523,7 +548,8 @@ class EKFVIO:
 
     def __init__(self, **kw):
         # (distortion=(k1, k2, p1, p2[, k3]): raw frames are rectified on the device, setDistortion below; output_covariance=True: every frame's
-        # outputs carry their covariances, setOutputCovariance below; mask=uint8 [h, w] and / or mask_rectify_border=True: the no-data mask, setMask below)
+        # outputs carry their covariances, setOutputCovariance below; mask=uint8 [h, w] and / or mask_rectify_border=True: the no-data mask, setMask below;
+        # equalize=(clip_limit, tiles_x, tiles_y): every frame is equalised on the device before its pyramid, setEqualize below)
         self.tc_ekf = TightlyCoupledEKF(**kw)
         self.tracker = KLTTracker(self.tc_ekf)
         self._imu_queue = []      # (stamp, gyro, accel), kept in stamp order; only used with use_imu = 1
@@ -552,6 +578,10 @@ class EKFVIO:
     def setMask(self, mask, rectify_border=False):
         """TightlyCoupledEKF.setMask: from the next frame on no landmark is taken or passed within the kill-pad window of a no-data pixel."""
         self.tc_ekf.setMask(mask, rectify_border=rectify_border)
+
+    def setEqualize(self, clip_limit, tiles_x=8, tiles_y=8):
+        """TightlyCoupledEKF.setEqualize: from the next frame on the detector and the tracker see the equalised frame (clip_limit 0: off)."""
+        self.tc_ekf.setEqualize(clip_limit, tiles_x, tiles_y)
 
     def setOutputCovariance(self, on):
         """TightlyCoupledEKF.setOutputCovariance: from the next frame on addFrame delivers the covariances with the frame's outputs."""

@@ -57,6 +57,11 @@ struct Params {
     // Not in the reference, which passes no mask to cv::FAST: with mask_rectify_border = 1 the black border that rectification leaves is no-data
     // (ekfvio_set_mask, EKFVIO_MASK_RECTIFY_BORDER): no landmark is detected or passed within the kill-pad window of it.  Nothing to mask while rectify = 0.
     int mask_rectify_border = 0;
+    // Not in the reference, whose detector has a fixed contrast threshold and whose tracker assumes brightness constancy: with equalize_clip_limit > 0
+    // every frame is equalised on the device between its rectification and the pyramid (ekfvio_set_equalize: clip-limited histograms over
+    // equalize_tiles_x x equalize_tiles_y tiles, each in [1, 16]); 0 = off.
+    float equalize_clip_limit = 0.f;
+    int equalize_tiles_x = 8, equalize_tiles_y = 8;
     std::map<std::string, std::string> node;  // odom_topic, camera_topic, base_frame, use_imu, publish_insight, ...
 
     Params() {
@@ -110,6 +115,15 @@ struct Params {
         else if (key == "rectify") rectify = (value == "true" || value == "1") ? 1 : 0;
         else if (key == "publish_covariance") publish_covariance = (value == "true" || value == "1") ? 1 : 0;
         else if (key == "mask_rectify_border") mask_rectify_border = (value == "true" || value == "1") ? 1 : 0;
+        else if (key == "equalize_clip_limit") {
+            equalize_clip_limit = (float)number(key, value);
+            if (equalize_clip_limit < 0.f) throw Error(EKFVIO_EINVAL, "parameter equalize_clip_limit: negative: " + value);
+        }
+        else if (key == "equalize_tiles_x" || key == "equalize_tiles_y") {
+            const int t = integer(key, value);
+            if (t < 1 || t > 16) throw Error(EKFVIO_EINVAL, "parameter " + key + ": not in [1, 16]: " + value);
+            (key == "equalize_tiles_x" ? equalize_tiles_x : equalize_tiles_y) = t;
+        }
         else if (key == "distortion_k1") distortion[0] = number(key, value);
         else if (key == "distortion_k2") distortion[1] = number(key, value);
         else if (key == "distortion_p1") distortion[2] = number(key, value);
@@ -134,7 +148,7 @@ struct Params {
                                         "default_point_depth", "default_point_depth_variance",
                                         "default_point_homogenous_variance", "frame_buffer_size", "imu_update",
                                         "imu_gyro_variance", "imu_accel_variance", "gravity_x", "gravity_y", "gravity_z", "remove_lost", "gate_chi2",
-                                        "klt_fb_max_px", "rectify", "publish_covariance", "mask_rectify_border", "distortion_k1", "distortion_k2", "distortion_p1", "distortion_p2", "distortion_k3"};
+                                        "klt_fb_max_px", "rectify", "publish_covariance", "mask_rectify_border", "equalize_clip_limit", "equalize_tiles_x", "equalize_tiles_y", "distortion_k1", "distortion_k2", "distortion_p1", "distortion_p2", "distortion_k3"};
         for (const auto& e : Params().node) out.push_back(e.first);
         for (const auto& e : ignored()) out.push_back(e.first);
         return out;
@@ -274,6 +288,9 @@ class TightlyCoupledEKF {
     // stride, nonzero = scene, or nullptr (w = h = stride = 0); flags: EKFVIO_MASK_RECTIFY_BORDER or 0.  From the next frame on no landmark is
     // detected or passed within the kill-pad window of a no-data pixel; nullptr and 0: off.  While a mask is set, frames of another size are refused.
     void setMask(const uint8_t* mask, int w, int h, int stride, int flags) { chk(ekfvio_set_mask(h_, mask, w, h, stride, flags)); }
+    // Not in the reference: clip-limited tile histogram equalisation of every pushed frame on the device, between the rectification and the pyramid
+    // (ekfvio_set_equalize).  clip_limit > 0 with tiles in [1, 16]: on from the next frame; clip_limit == 0: off.
+    void setEqualize(float clip_limit, int tiles_x = 8, int tiles_y = 8) { chk(ekfvio_set_equalize(h_, clip_limit, tiles_x, tiles_y)); }
     struct Mask {
         int width = 0, height = 0;     // level 0; 0 x 0 before the first frame pushed with the mask on
         std::vector<uint8_t> blocked;  // height x width, 1 = blocked
@@ -469,6 +486,7 @@ class EKFVIO {
         if (p.rectify) tc_ekf.setDistortion(std::vector<double>(p.distortion.begin(), p.distortion.end()));  // (likewise; a node replaces them with CameraInfo.D)
         if (p.publish_covariance) tc_ekf.setOutputCovariance(true);  // (likewise)
         if (p.mask_rectify_border) tc_ekf.setMask(nullptr, 0, 0, 0, EKFVIO_MASK_RECTIFY_BORDER);  // (likewise; live once the coefficients are nonzero)
+        if (p.equalize_clip_limit > 0.f) tc_ekf.setEqualize(p.equalize_clip_limit, p.equalize_tiles_x, p.equalize_tiles_y);  // (likewise)
     }
     TightlyCoupledEKF tc_ekf;
     KLTTracker tracker;

@@ -7,6 +7,7 @@
 // Usage: ekfvio_replay [landmarks=256] [frames=300] [seed=0] [dt=0.0333333]
 //        ekfvio_replay --print-config [params.yaml]   (no GPU work: the node's parameter file -> ekfvio_config as JSON)
 //        ekfvio_replay --records <dir> [--out <dir>] [--params params.yaml] [--device n] [--insight] [--covariance]
+//                                [--equalize-clip-limit c] [--equalize-tiles-x n] [--equalize-tiles-y n]
 //
 // --records replays what the node's two subscriptions deliver (EKFVIO.cpp:69-81) and writes what its two publishers
 // send (EKFVIO.cpp:444-518), with no ROS in between.  <dir>/records.txt holds one record per line, in arrival order:
@@ -21,6 +22,8 @@
 // publishInsight sends, <out>/insight_NNN.ppm.  --covariance turns on the covariances of the outputs (ekfvio_set_output_covariance) and
 // prints, per frame, the diagonals of the pose and twist covariances the node would put into nav_msgs/Odometry:
 //     cov <stamp> <6 pose variances: x y z rotX rotY rotZ> <6 twist variances: linear, angular>
+// --equalize-clip-limit / --equalize-tiles-x / --equalize-tiles-y are the node parameters of the same names (ekfvio_set_equalize), applied
+// behind the parameter file.
 #include <cctype>
 #include <chrono>
 #include <cmath>
@@ -74,12 +77,12 @@ static int print_config(const char* path) {
                     "\"kill_pad\": %d, \"klt_min_eigen\": %.9g, \"min_new_feature_dist\": %d, \"klt_max_pyramid_level\": %d, "
                     "\"klt_window_size\": %d, \"default_point_depth\": %.9g, \"default_point_depth_variance\": %.9g, "
                     "\"default_point_homogenous_variance\": %.9g, \"sample_based_uncertainty\": %d, \"gate_chi2\": %.9g, "
-                    "\"klt_fb_max_px\": %.9g, \"rectify\": %d, \"publish_covariance\": %d, \"mask_rectify_border\": %d, \"distortion\": [%.17g, %.17g, %.17g, %.17g, %.17g], \"node\": {",
+                    "\"klt_fb_max_px\": %.9g, \"rectify\": %d, \"publish_covariance\": %d, \"mask_rectify_border\": %d, \"equalize_clip_limit\": %.9g, \"equalize_tiles_x\": %d, \"equalize_tiles_y\": %d, \"distortion\": [%.17g, %.17g, %.17g, %.17g, %.17g], \"node\": {",
                     c.max_features, c.fast_threshold, (double)c.fast_blur_sigma, c.inverse_image_scale, c.kill_pad,
                     (double)c.klt_min_eigen, c.min_new_feature_dist, c.klt_max_pyramid_level, c.klt_window_size,
                     (double)c.default_point_depth, (double)c.default_point_depth_variance,
                     (double)c.default_point_homogenous_variance, c.sample_based_uncertainty, (double)p.gate_chi2,
-                    (double)c.klt_fb_max_px, p.rectify, p.publish_covariance, p.mask_rectify_border, p.distortion[0], p.distortion[1], p.distortion[2], p.distortion[3], p.distortion[4]);
+                    (double)c.klt_fb_max_px, p.rectify, p.publish_covariance, p.mask_rectify_border, (double)p.equalize_clip_limit, p.equalize_tiles_x, p.equalize_tiles_y, p.distortion[0], p.distortion[1], p.distortion[2], p.distortion[3], p.distortion[4]);
         bool first = true;
         for (const auto& e : p.node) {
             std::printf("%s\"%s\": \"%s\"", first ? "" : ", ", e.first.c_str(), e.second.c_str());
@@ -122,9 +125,11 @@ static bool read_pgm(const std::string& path, std::vector<uint8_t>& px, int& w, 
     return (size_t)in.gcount() == px.size();
 }
 
-static int replay_records(const std::string& dir, const std::string& out_dir, const char* params_path, int device, bool insight, bool covariance) {
+static int replay_records(const std::string& dir, const std::string& out_dir, const char* params_path, int device, bool insight, bool covariance,
+                          const std::vector<std::pair<std::string, std::string>>& overrides) {
     try {
         ekfvio::Params p = params_path ? ekfvio::Params::fromFile(params_path) : ekfvio::Params();
+        for (const auto& kv : overrides) p.set(kv.first, kv.second);
         if (!params_path) p.cfg.inverse_image_scale = 1;  // no parameter file: frames are used as recorded
         p.cfg.replenish = 1;                              // addFrame runs replenishFeatures itself (EKFVIO.cpp:154, :172)
         if (covariance) p.publish_covariance = 1;
@@ -221,6 +226,7 @@ int main(int argc, char** argv) {
         const char* params = nullptr;
         int device = 0;
         bool insight = false, covariance = false;
+        std::vector<std::pair<std::string, std::string>> overrides;  // options that are node parameters, by the parameter's name
         for (int i = 3; i < argc; i += 2) {
             if (std::strcmp(argv[i], "--insight") == 0 || std::strcmp(argv[i], "--covariance") == 0) {
                 (std::strcmp(argv[i], "--insight") == 0 ? insight : covariance) = true;
@@ -234,12 +240,15 @@ int main(int argc, char** argv) {
             if (std::strcmp(argv[i], "--out") == 0) out = argv[i + 1];
             else if (std::strcmp(argv[i], "--params") == 0) params = argv[i + 1];
             else if (std::strcmp(argv[i], "--device") == 0) device = std::atoi(argv[i + 1]);
+            else if (std::strcmp(argv[i], "--equalize-clip-limit") == 0) overrides.emplace_back("equalize_clip_limit", argv[i + 1]);
+            else if (std::strcmp(argv[i], "--equalize-tiles-x") == 0) overrides.emplace_back("equalize_tiles_x", argv[i + 1]);
+            else if (std::strcmp(argv[i], "--equalize-tiles-y") == 0) overrides.emplace_back("equalize_tiles_y", argv[i + 1]);
             else {
                 std::fprintf(stderr, "unknown option %s\n", argv[i]);
                 return 2;
             }
         }
-        return replay_records(dir, out, params, device, insight, covariance);
+        return replay_records(dir, out, params, device, insight, covariance, overrides);
     }
     const int N = argc > 1 ? std::atoi(argv[1]) : 256;
     const int frames = argc > 2 ? std::atoi(argv[2]) : 300;

@@ -102,7 +102,9 @@ class EkfvioNode {
         // (and this backend's own: imu_update, remove_lost, gate_chi2, klt_fb_max_px -- the tracker's forward-backward threshold in pixels of
         // the resized frame, which reaches the handle inside ekfvio_config -- and publish_covariance, default false: with it the handle is
         // told at start-up, by ekfvio::EKFVIO's constructor, to deliver the covariances with every frame's outputs; mask_rectify_border, default
-        // false: with it, and rectify = 1, the black border that rectification leaves is no-data for the detector and the tracker, ekfvio_set_mask)
+        // false: with it, and rectify = 1, the black border that rectification leaves is no-data for the detector and the tracker, ekfvio_set_mask;
+        // equalize_clip_limit, default 0 = off, with equalize_tiles_x / equalize_tiles_y, default 8: every frame is equalised on the device in front
+        // of its pyramid, ekfvio_set_equalize)
         for (const std::string& name : ekfvio::Params::names()) {
             XmlRpc::XmlRpcValue v;
             if (ros::param::get("~" + name, v)) params_.set(name, to_text(v));

@@ -117,7 +117,7 @@ EKFVIO_API int ekfvio_create(const ekfvio_config* cfg, int device, void* stream,
 EKFVIO_API int ekfvio_destroy(ekfvio_filter* f);
 /* initializeBaseState(): back to mu = [0,0,0,1,0...], Sigma diag [0x7,30x9,0.5x6], no landmarks.  (The innovation gate's counts start
  * over; its threshold stays.  The same holds for the tracker's forward-backward check.  The distortion coefficients of
- * ekfvio_set_distortion stay too, and so does the setting of ekfvio_set_output_covariance.  The mask of ekfvio_set_mask stays as well.) */
+ * ekfvio_set_distortion stay too, and so does the setting of ekfvio_set_output_covariance.  The mask of ekfvio_set_mask stays as well, and the setting of ekfvio_set_equalize.) */
 EKFVIO_API int ekfvio_reset(ekfvio_filter* f);
 EKFVIO_API const char* ekfvio_last_error(const ekfvio_filter* f);
 
@@ -304,6 +304,54 @@ EKFVIO_API int ekfvio_get_mask_hits(ekfvio_filter* f, uint8_t* masked, int32_t* 
  * kernels compile, as ekfvio_rectify_map does.  K, D, count as there (K may be NULL where the border term is not live); mask may be NULL. */
 EKFVIO_API int ekfvio_mask_blocked(const float K[9], const double* D, int32_t count, const uint8_t* mask, int32_t width, int32_t height,
                                    int32_t stride, int32_t inverse_image_scale, int32_t kill_pad, int32_t flags, uint8_t* blocked);
+
+/* ---- equalisation of pushed frames (not in the reference, whose detector runs at a fixed contrast threshold, EKFVIO.cpp:224-311, and whose
+ * tracker assumes brightness constancy; VINS-style front ends run a cv::CLAHE pass on the host in front of the tracker) ----------------------
+ * With the setting on, every pushed frame (ekfvio_klt_push_frame, ekfvio_step_image) is equalised on the device between its upload -- or its
+ * rectification, where distortion is on -- and the pyramid: clip-limited histograms per tile, one table per tile, every pixel blended from the
+ * four tables around it.  The lines below are the specification, restated from memory of cv::CLAHE, not from its source; a NumPy restatement of
+ * them (tests/_equalize.py) is what the device is held to, bit for bit.
+ *
+ * Inputs: the full-size w x h frame (the rectified one where distortion is on), tiles tx x ty, clip_limit as fp32.
+ * Host values, formed once and passed to the kernels as arguments:
+ *
+ *     tw = ceil(w / tx)    th = ceil(h / ty)    A = tw * th
+ *     clip = max((int)floor((double)clip_limit * A / 256.0), 1)        (a value above A is taken as A: no bin holds more, the result is the same)
+ *     scale = 255.0f / (float)A    inv_tw = 1.0f / (float)tw    inv_th = 1.0f / (float)th                                             (fp32)
+ *
+ *  1. Padded source.  Tile (i, j) covers X in [i tw, (i+1) tw) and Y in [j th, (j+1) th) of the padded frame and reads
+ *     src(X >= w ? 2(w-1) - X : X,  Y >= h ? 2(h-1) - Y : Y)  (reflect-101; one reflection suffices because tx <= w and ty <= h are required:
+ *     tx tw <= w + tx - 1 <= 2w - 1).  Every tile therefore has exactly A pixels.
+ *  2. Histogram.  hist[256] of the tile, in integers.
+ *  3. Clip and redistribute.  excess = sum max(hist[b] - clip, 0), then hist[b] = min(hist[b], clip).  batch = excess / 256,
+ *     res = excess - 256 batch, then hist[b] += batch.  If res > 0: step = max(256 / res, 1), and bin b gets +1 iff b % step == 0 and
+ *     b / step < res.  The sum stays A.
+ *  4. Table.  lut[b] = saturate_u8(rint((float)(hist[0] + ... + hist[b]) * scale)): the integer sum converted to fp32 round-to-nearest, rint
+ *     half to even.  So lut[255] = 255.
+ *  5. Interpolation.  Per pixel (x, y) with value v, in fp32, without fused multiply-add:
+ *         fx = (float)x * inv_tw - 0.5f    t = floorf(fx)    xa = fx - t    xa1 = 1.0f - xa
+ *         i1 = max((int)t, 0)    i2 = min((int)t + 1, tx - 1)
+ *     the same for y with inv_th, giving ya, ya1, j1, j2, and
+ *         out = saturate_u8(rint((lut[j1][i1][v]*xa1 + lut[j1][i2][v]*xa)*ya1 + (lut[j2][i1][v]*xa1 + lut[j2][i2][v]*xa)*ya))
+ *
+ * The equalised full-size frame then takes the road of an uploaded one: the resize, the pyramid, FAST, the sample-based R and the intensity
+ * channel of ekfvio_get_points all see it.  K, the rectification map and the mask's B do not change.  Two limits.  The black rectification
+ * border and a caller's masked region are counted in the histograms; the clip bounds their influence to one bin's worth, and leaving no-data
+ * pixels out is out of scope.  And cfg.fast_threshold now acts on stretched contrast, so the detector finds more.  Equalisation is no full
+ * repair of a gain change either: the tracks it does not save are what the forward-backward check and the gate are for.
+ *
+ * ekfvio_set_equalize.  clip_limit == 0: off (default; then no launch differs, nothing is allocated and every output keeps its bits; the tile
+ * counts are not looked at).  clip_limit > 0 and finite with tiles_x, tiles_y in [1, 16]: on from the next pushed frame.  A negative, NaN or
+ * infinite clip_limit, tiles out of range: EKFVIO_EINVAL, and the setting stays what it was.  A property of the handle: it survives
+ * ekfvio_reset.  While it is on, a frame with width < tiles_x or height < tiles_y is refused (EKFVIO_EINVAL, ekfvio_last_error has the sizes)
+ * and not ingested.  The frame is equalised in place in the handle's own staging plane; the setting costs tiles_x * tiles_y * 256 bytes of
+ * device memory, taken when the first frame arrives with it on. */
+EKFVIO_API int ekfvio_set_equalize(ekfvio_filter* f, float clip_limit, int32_t tiles_x, int32_t tiles_y);
+/* The equalised frame itself, width x height bytes tightly packed into out: a pure host function (no handle, no device) that compiles the very
+ * inline functions the kernels compile, as ekfvio_rectify_map does.  image: width x height bytes with a row stride.  clip_limit > 0 and finite,
+ * tiles in [1, 16] and not above the frame's size, a size in [1, 16384], stride >= width; anything else: EKFVIO_EINVAL. */
+EKFVIO_API int ekfvio_equalize(const uint8_t* image, int32_t width, int32_t height, int32_t stride, float clip_limit, int32_t tiles_x,
+                               int32_t tiles_y, uint8_t* out);
 
 /* ---- covariances of the published outputs (not in the reference: EKFVIO.cpp:473 "TODO add convariance computation"; its Odometry
  * message carries two all-zero 6x6 covariances) -----------------------------------------------------------------------------------------
