@@ -47,7 +47,8 @@ SYMBOLS = ["ekfvio_default_config", "ekfvio_create", "ekfvio_destroy", "ekfvio_r
            "ekfvio_profile_update_gemms", "ekfvio_get_counters", "ekfvio_set_gate", "ekfvio_get_gate",
            "ekfvio_set_klt_fb", "ekfvio_get_klt_fb", "ekfvio_klt_track_points_fb", "ekfvio_set_distortion", "ekfvio_rectify_map",
            "ekfvio_set_output_covariance", "ekfvio_get_odometry_covariance", "ekfvio_get_points_covariance", "ekfvio_rotation_error_jacobian",
-           "ekfvio_set_mask", "ekfvio_get_mask", "ekfvio_get_mask_hits", "ekfvio_mask_blocked", "ekfvio_set_equalize", "ekfvio_equalize"]
+           "ekfvio_set_mask", "ekfvio_get_mask", "ekfvio_get_mask_hits", "ekfvio_mask_blocked", "ekfvio_set_equalize", "ekfvio_equalize",
+           "ekfvio_set_klt_photometric", "ekfvio_klt_project_gradients"]
 MASK_RECTIFY_BORDER = 1  # EKFVIO_MASK_RECTIFY_BORDER
 # every symbol include/ekfvio_test_hooks.h declares (libekfvio_hip_hooks.so only)
 HOOK_SYMBOLS = ["ekfvio_test_klt_padded_level", "ekfvio_test_blurred_level0", "ekfvio_test_gemm", "ekfvio_test_gemm_bench", "ekfvio_test_potrf_stamps",
@@ -109,6 +110,8 @@ def load(build_if_missing=True, hooks=False):
         "ekfvio_mask_blocked": [fp, C.POINTER(C.c_double), i32, u8p, i32, i32, i32, i32, i32, i32, u8p],  # no handle, no device
         "ekfvio_set_equalize": [vp, f32, i32, i32],
         "ekfvio_equalize": [u8p, i32, i32, i32, f32, i32, i32, u8p],  # no handle, no device
+        "ekfvio_set_klt_photometric": [vp, i32],
+        "ekfvio_klt_project_gradients": [ip, ip, ip, i32, ip, ip],  # no handle, no device
     }
     if hooks:
         sig.update({

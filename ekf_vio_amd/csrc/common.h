@@ -245,6 +245,7 @@ struct ekfvio_filter {
     float* klt_next_px = nullptr;  // [2*max_features]
     uint8_t* klt_status = nullptr; // [max_features]
     float* klt_cov_px = nullptr;   // [4*max_features] sample-based pixel covariances (cfg.sample_based_uncertainty)
+    bool klt_photo = false;        // ekfvio_set_klt_photometric: the tracker's launches take klt_track_kernel<true> (gain/offset term; klt_photo.h)
     uint8_t* staging = nullptr;    // device staging for the uploaded image
     uint8_t* h_image = nullptr;    // pinned host staging: the caller's frame is copied here, so its buffer is free on return without a stream sync
     size_t src_cap = 0;            // bytes of staging / h_image (the uploaded, un-resized frame)

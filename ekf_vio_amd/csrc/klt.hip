@@ -26,6 +26,7 @@
 #include <string.h>
 
 #include "common.h"
+#include "klt_photo.h"
 
 #define KLT_BORDER 24     // >= window size (21); multiple of 8
 #define KLT_MAX_WIN 21
@@ -411,6 +412,11 @@ __device__ inline void wave_sum2_i32_as_float(int a, int b, float& fa, float& fb
     fa = (float)((double)s1 * 65536.0 + (double)s0);
     fb = (float)((double)s3 * 65536.0 + (double)s2);
 }
+// The exact sum as a 64-bit integer, for per-lane partials of any size: the two halves put together in integers.
+__device__ inline long long wave_sum_i32_as_i64(int v) {
+    const int lo = wave_sum_small_i32(v & 0xffff), hi = wave_sum_small_i32(v >> 16);
+    return (long long)hi * 65536 + (long long)lo;
+}
 __device__ inline int descale(int x, int n) { return (x + (1 << (n - 1))) >> n; }
 
 // Copies `rows` rows of `nbytes` bytes starting at byte address src (row stride `pitch`, a multiple of 4) into LDS
@@ -490,6 +496,10 @@ struct TrackFuse {
 // work then runs out of LDS.  The staging buffers belong to the pass that is running: every level opens with a barrier behind the
 // LDS readers before it, which is also what separates the backward pass from the forward one.  Inlined at both call sites, with
 // the views as the kernel's own arguments: nothing of a pass lives in scratch.  dbg: the forward pass's diagnostic stamps.
+// PHOTO (include/ekfvio.h, ekfvio_set_klt_photometric): span{1, Iv} is projected out of the template's two gradient images, once per
+// level, and everything behind runs on the projected gradients; the iteration loop is the same code.  A template parameter and no
+// argument: the kernel is at its scalar budget (profiles/mask_resources.txt), and the instance without the term is the kernel it was.
+template <bool PHOTO>
 __device__ __forceinline__ bool klt_lk_pass(const PyrView& P, const PyrView& Q, const float ppx0, const float ppy0, float& ox, float& oy,
                                             const int win, const int max_iter, const float eps2, const float min_eig, const int lane,
                                             long long* dbg, unsigned& itpack) {
@@ -595,6 +605,34 @@ __device__ __forceinline__ bool klt_lk_pass(const PyrView& P, const PyrView& Q, 
                 Iy[t] = descale(__mul24((short)(d00 >> 16), iw00) + __mul24((short)(d01 >> 16), iw01) +
                                     __mul24((short)(d10 >> 16), iw10) + __mul24((short)(d11 >> 16), iw11), W_BITS);
                 if (!sv[t]) Iv[t] = Ix[t] = Iy[t] = 0;
+                if constexpr (!PHOTO) {
+                    pA11 += __mul24(Ix[t], Ix[t]);
+                    pA12 += __mul24(Ix[t], Iy[t]);
+                    pA22 += __mul24(Iy[t], Iy[t]);
+                }
+            }
+        }
+        if constexpr (PHOTO) {
+            // the six sums over the window (slots past it hold zeros); per-lane partials: 7 terms of at most 8160^2 each, inside int32;
+            // sI, sX, sY fit int32 as totals, the three products reach 2.9e10 and are summed as 16-bit halves
+            int pI = 0, pX = 0, pY = 0, pII = 0, pIX = 0, pIY = 0;
+#pragma unroll
+            for (int t = 0; t < KLT_SLOTS; t++) {
+                pI += Iv[t];
+                pX += Ix[t];
+                pY += Iy[t];
+                pII += __mul24(Iv[t], Iv[t]);
+                pIX += __mul24(Iv[t], Ix[t]);
+                pIY += __mul24(Iv[t], Iy[t]);
+            }
+            KltPhotoSums ps;
+            ps.sI = wave_sum_small_i32(pI), ps.sX = wave_sum_small_i32(pX), ps.sY = wave_sum_small_i32(pY);
+            ps.sII = wave_sum_i32_as_i64(pII), ps.sIX = wave_sum_i32_as_i64(pIX), ps.sIY = wave_sum_i32_as_i64(pIY);
+            const KltPhotoCoef pc = klt_photo_coef(ps, win * win);
+#pragma unroll
+            for (int t = 0; t < KLT_SLOTS; t++) {
+                Ix[t] = sv[t] ? klt_photo_project(Ix[t], Iv[t], pc.mX, pc.cx, pc.mI) : 0;
+                Iy[t] = sv[t] ? klt_photo_project(Iy[t], Iv[t], pc.mY, pc.cy, pc.mI) : 0;
                 pA11 += __mul24(Ix[t], Ix[t]);
                 pA12 += __mul24(Ix[t], Iy[t]);
                 pA22 += __mul24(Iy[t], Iy[t]);
@@ -682,7 +720,8 @@ __device__ __forceinline__ bool klt_lk_pass(const PyrView& P, const PyrView& Q, 
 }
 
 // One wavefront per point: the forward pass from the previous frame (P) into the current one (Q) and, with the forward-backward
-// check on, the pass back from its result.
+// check on, the pass back from its result.  PHOTO: both passes with the gain/offset term.
+template <bool PHOTO>
 __global__ __launch_bounds__(64) void klt_track_kernel(PyrView P, PyrView Q, float* prev_px, float* next_px, uint8_t* status, int n,
                                                        int win, int max_iter, float eps2, float min_eig, long long* dbg, TrackFuse tf) {
     KSTAMP(0);
@@ -707,7 +746,7 @@ __global__ __launch_bounds__(64) void klt_track_kernel(PyrView P, PyrView Q, flo
     }
     const float gx0 = ox, gy0 = oy;  // the guess: the check applies the predicted flow backwards
     unsigned itpack = 0u;
-    const bool ok = klt_lk_pass(P, Q, ppx0, ppy0, ox, oy, win, max_iter, eps2, min_eig, lane, dbg, itpack);
+    const bool ok = klt_lk_pass<PHOTO>(P, Q, ppx0, ppy0, ox, oy, win, max_iter, eps2, min_eig, lane, dbg, itpack);
     if (dbg && lane == 0 && pt < 896) dbg[pt] = (long long)itpack;  // (scripts/klt_iterations.py)
     bool fb_ok = true;
     if (tf.fb) {  // (kernel argument: uniform over the launch)
@@ -718,7 +757,7 @@ __global__ __launch_bounds__(64) void klt_track_kernel(PyrView P, PyrView Q, flo
             const float bx = ox - (gx0 - ppx0), by = oy - (gy0 - ppy0);
             rx = bx, ry = by;
             unsigned itback = 0u;
-            const bool sb = klt_lk_pass(Q, P, ox, oy, rx, ry, win, max_iter, eps2, min_eig, lane, nullptr, itback);
+            const bool sb = klt_lk_pass<PHOTO>(Q, P, ox, oy, rx, ry, win, max_iter, eps2, min_eig, lane, nullptr, itback);
             const float dx = rx - ppx0, dy = ry - ppy0;
             e2 = dx * dx + dy * dy;
             fb_ok = sb && (tf.fb_t2 > 0.f ? e2 <= tf.fb_t2 : true);  // (a NaN rejects)
@@ -1082,7 +1121,8 @@ static int track_points_device(ekfvio_filter* f, int n, const TrackFuse& tf = Tr
     const KltFrame& cur = f->frames[f->cur];
     const float eps = f->cfg.klt_epsilon;
     ProfScope ps(f, PC_KLT_TRACK);
-    hipLaunchKernelGGL(klt_track_kernel, dim3(n), dim3(64), 0, f->stream, make_view(prev), make_view(cur), f->klt_prev_px,
+    // ekfvio_set_klt_photometric: the kernel's other instance, with the same arguments
+    hipLaunchKernelGGL(f->klt_photo ? klt_track_kernel<true> : klt_track_kernel<false>, dim3(n), dim3(64), 0, f->stream, make_view(prev), make_view(cur), f->klt_prev_px,
                        f->klt_next_px, f->klt_status, n, f->cfg.klt_window_size, f->cfg.klt_max_iterations, eps * eps,
                        f->cfg.klt_min_eigen, f->sweep_dbg, tf);
     return EKFVIO_OK;
@@ -1235,6 +1275,28 @@ int ekfvio_klt_push_frame(ekfvio_filter* f, const uint8_t* image, int32_t width,
     const int rc = push_frame_enqueue(f, image, width, height, stride, K);
     if (rc != EKFVIO_OK) return rc;
     HIP_TRY(f, hipStreamSynchronize(f->stream));
+    return EKFVIO_OK;
+}
+
+int ekfvio_set_klt_photometric(ekfvio_filter* f, int32_t on) {
+    if (!f || (on != 0 && on != 1)) return EKFVIO_EINVAL;
+    f->klt_photo = on != 0;  // (read by the next track; the tracker is in no captured graph)
+    return EKFVIO_OK;
+}
+
+// The projection on the host: the six sums in a loop, then the lines the kernel compiles (klt_photo.h).
+int ekfvio_klt_project_gradients(const int32_t* Iv, const int32_t* Ix, const int32_t* Iy, int32_t count, int32_t* Ix_out, int32_t* Iy_out) {
+    if (!Iv || !Ix || !Iy || !Ix_out || !Iy_out || count < 1 || count > KLT_PHOTO_MAX_COUNT) return EKFVIO_EINVAL;
+    KltPhotoSums s = {0, 0, 0, 0, 0, 0};
+    for (int t = 0; t < count; t++) {
+        s.sI += Iv[t], s.sX += Ix[t], s.sY += Iy[t];
+        s.sII += (long long)Iv[t] * Iv[t], s.sIX += (long long)Iv[t] * Ix[t], s.sIY += (long long)Iv[t] * Iy[t];
+    }
+    const KltPhotoCoef c = klt_photo_coef(s, count);
+    for (int t = 0; t < count; t++) {
+        const int gx = klt_photo_project(Ix[t], Iv[t], c.mX, c.cx, c.mI), gy = klt_photo_project(Iy[t], Iv[t], c.mY, c.cy, c.mI);
+        Ix_out[t] = gx, Iy_out[t] = gy;  // (both formed first: an output may be its input)
+    }
     return EKFVIO_OK;
 }
 

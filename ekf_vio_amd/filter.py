@@ -26,7 +26,7 @@ class TightlyCoupledEKF:
     def __init__(self, max_features=100, device=0, stream=None, predict_mode=capi.PREDICT_STRUCTURED,
                  default_point_depth=0.5, default_point_depth_variance=100.0,
                  default_point_homogenous_variance=1e-5, hooks=False, gate_chi2=0.0, klt_fb_max_px=0.0, distortion=None, output_covariance=False,
-                 mask=None, mask_rectify_border=False, equalize=None, **cfg_overrides):
+                 mask=None, mask_rectify_border=False, equalize=None, klt_photometric=False, **cfg_overrides):
         # hooks=True: this handle lives in libekfvio_hip_hooks.so, the build that also has include/ekfvio_test_hooks.h (tests, profiling scripts)
         self.hooks = bool(hooks)
         self.lib = capi.load(hooks=self.hooks)
@@ -60,6 +60,8 @@ class TightlyCoupledEKF:
             self.setMask(mask, rectify_border=mask_rectify_border)
         if equalize is not None:  # likewise (ekfvio_set_equalize)
             self.setEqualize(*equalize)
+        if klt_photometric:  # likewise (ekfvio_set_klt_photometric)
+            self.setKltPhotometric(True)
 
     def _chk(self, rc, allow=()):
         if rc != capi.OK and rc not in allow:
@@ -219,6 +221,12 @@ class TightlyCoupledEKF:
         histogram equalisation of every pushed frame on the device, between the rectification and the pyramid (ekfvio_set_equalize).
         clip_limit > 0 with tiles in [1, 16]: on from the next pushed frame; clip_limit == 0: off."""
         self._chk(self.lib.ekfvio_set_equalize(self.h, float(clip_limit), int(tiles_x), int(tiles_y)))
+
+    def setKltPhotometric(self, on):
+        """Not in the reference, whose tracker assumes brightness constancy: the gain/offset term of the Lucas-Kanade passes
+        (ekfvio_set_klt_photometric): span{1, I} is projected out of the template's gradients, once per pyramid level.  On from the next
+        track, in the forward pass and in the forward-backward check's backward pass; off by default."""
+        self._chk(self.lib.ekfvio_set_klt_photometric(self.h, int(on)))
 
     def mask_blocked(self):
         """ekfvio_get_mask: the blocked map B as the device holds it, uint8 [H, W] of level 0 (1 = blocked); shape (0, 0) before the first
@@ -540,6 +548,21 @@ def equalize(image, clip_limit, tiles_x=8, tiles_y=8):
     return out
 
 
+def klt_project_gradients(Iv, Ix, Iy):
+    """ekfvio_klt_project_gradients: (Ix', Iy') of one window's pixels, int32 arrays of Iv's shape, with span{1, Iv} projected out of the two
+    gradient images as the tracker does with ekfvio_set_klt_photometric on.  A host function: no GPU involved."""
+    lib = capi.load()
+    iv, ix, iy = (np.ascontiguousarray(a, dtype=np.int32) for a in (Iv, Ix, Iy))
+    if not (iv.shape == ix.shape == iy.shape):
+        raise capi.EkfvioError(capi.EINVAL, "Iv, Ix, Iy have one shape")
+    ox, oy = np.zeros(iv.shape, np.int32), np.zeros(iv.shape, np.int32)
+    rc = lib.ekfvio_klt_project_gradients(_ip(iv) if iv.size else None, _ip(ix) if iv.size else None, _ip(iy) if iv.size else None, int(iv.size),
+                                          _ip(ox) if iv.size else None, _ip(oy) if iv.size else None)
+    if rc != capi.OK:
+        raise capi.EkfvioError(rc, "ekfvio_klt_project_gradients")
+    return ox, oy
+
+
 class EKFVIO:
     """Host mirror of the step sequence of EKFVIO::addFrame / updateStateWithNewImage
     (include/ekf_vio/EKFVIO.cpp:139-219) without ROS: frames in, odometry + landmark cloud out.
@@ -549,7 +572,8 @@ class EKFVIO:
     def __init__(self, **kw):
         # (distortion=(k1, k2, p1, p2[, k3]): raw frames are rectified on the device, setDistortion below; output_covariance=True: every frame's
         # outputs carry their covariances, setOutputCovariance below; mask=uint8 [h, w] and / or mask_rectify_border=True: the no-data mask, setMask below;
-        # equalize=(clip_limit, tiles_x, tiles_y): every frame is equalised on the device before its pyramid, setEqualize below)
+        # equalize=(clip_limit, tiles_x, tiles_y): every frame is equalised on the device before its pyramid, setEqualize below;
+        # klt_photometric=True: the tracker's gain/offset term, setKltPhotometric below)
         self.tc_ekf = TightlyCoupledEKF(**kw)
         self.tracker = KLTTracker(self.tc_ekf)
         self._imu_queue = []      # (stamp, gyro, accel), kept in stamp order; only used with use_imu = 1
@@ -582,6 +606,10 @@ class EKFVIO:
     def setEqualize(self, clip_limit, tiles_x=8, tiles_y=8):
         """TightlyCoupledEKF.setEqualize: from the next frame on the detector and the tracker see the equalised frame (clip_limit 0: off)."""
         self.tc_ekf.setEqualize(clip_limit, tiles_x, tiles_y)
+
+    def setKltPhotometric(self, on):
+        """TightlyCoupledEKF.setKltPhotometric: from the next frame on the tracker matches up to a gain and an offset."""
+        self.tc_ekf.setKltPhotometric(on)
 
     def setOutputCovariance(self, on):
         """TightlyCoupledEKF.setOutputCovariance: from the next frame on addFrame delivers the covariances with the frame's outputs."""

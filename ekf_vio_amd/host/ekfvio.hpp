@@ -62,6 +62,9 @@ struct Params {
     // equalize_tiles_x x equalize_tiles_y tiles, each in [1, 16]); 0 = off.
     float equalize_clip_limit = 0.f;
     int equalize_tiles_x = 8, equalize_tiles_y = 8;
+    // Not in the reference, whose Lucas-Kanade assumes brightness constancy: with klt_photometric = 1 the tracker matches up to a gain and an offset
+    // (ekfvio_set_klt_photometric: span{1, I} projected out of the template's gradients, once per pyramid level); 0 = off.
+    int klt_photometric = 0;
     std::map<std::string, std::string> node;  // odom_topic, camera_topic, base_frame, use_imu, publish_insight, ...
 
     Params() {
@@ -124,6 +127,10 @@ struct Params {
             if (t < 1 || t > 16) throw Error(EKFVIO_EINVAL, "parameter " + key + ": not in [1, 16]: " + value);
             (key == "equalize_tiles_x" ? equalize_tiles_x : equalize_tiles_y) = t;
         }
+        else if (key == "klt_photometric") {
+            klt_photometric = value == "true" ? 1 : (value == "false" ? 0 : integer(key, value));  // (a launch file's bool arrives as text)
+            if (klt_photometric != 0 && klt_photometric != 1) throw Error(EKFVIO_EINVAL, "parameter klt_photometric: not 0 or 1: " + value);
+        }
         else if (key == "distortion_k1") distortion[0] = number(key, value);
         else if (key == "distortion_k2") distortion[1] = number(key, value);
         else if (key == "distortion_p1") distortion[2] = number(key, value);
@@ -148,7 +155,7 @@ struct Params {
                                         "default_point_depth", "default_point_depth_variance",
                                         "default_point_homogenous_variance", "frame_buffer_size", "imu_update",
                                         "imu_gyro_variance", "imu_accel_variance", "gravity_x", "gravity_y", "gravity_z", "remove_lost", "gate_chi2",
-                                        "klt_fb_max_px", "rectify", "publish_covariance", "mask_rectify_border", "equalize_clip_limit", "equalize_tiles_x", "equalize_tiles_y", "distortion_k1", "distortion_k2", "distortion_p1", "distortion_p2", "distortion_k3"};
+                                        "klt_fb_max_px", "rectify", "publish_covariance", "mask_rectify_border", "equalize_clip_limit", "equalize_tiles_x", "equalize_tiles_y", "klt_photometric", "distortion_k1", "distortion_k2", "distortion_p1", "distortion_p2", "distortion_k3"};
         for (const auto& e : Params().node) out.push_back(e.first);
         for (const auto& e : ignored()) out.push_back(e.first);
         return out;
@@ -291,6 +298,9 @@ class TightlyCoupledEKF {
     // Not in the reference: clip-limited tile histogram equalisation of every pushed frame on the device, between the rectification and the pyramid
     // (ekfvio_set_equalize).  clip_limit > 0 with tiles in [1, 16]: on from the next frame; clip_limit == 0: off.
     void setEqualize(float clip_limit, int tiles_x = 8, int tiles_y = 8) { chk(ekfvio_set_equalize(h_, clip_limit, tiles_x, tiles_y)); }
+    // Not in the reference, whose tracker assumes brightness constancy: the gain/offset term of every Lucas-Kanade pass
+    // (ekfvio_set_klt_photometric).  On from the next track; off by default.
+    void setKltPhotometric(bool on) { chk(ekfvio_set_klt_photometric(h_, on ? 1 : 0)); }
     struct Mask {
         int width = 0, height = 0;     // level 0; 0 x 0 before the first frame pushed with the mask on
         std::vector<uint8_t> blocked;  // height x width, 1 = blocked
@@ -487,6 +497,7 @@ class EKFVIO {
         if (p.publish_covariance) tc_ekf.setOutputCovariance(true);  // (likewise)
         if (p.mask_rectify_border) tc_ekf.setMask(nullptr, 0, 0, 0, EKFVIO_MASK_RECTIFY_BORDER);  // (likewise; live once the coefficients are nonzero)
         if (p.equalize_clip_limit > 0.f) tc_ekf.setEqualize(p.equalize_clip_limit, p.equalize_tiles_x, p.equalize_tiles_y);  // (likewise)
+        if (p.klt_photometric) tc_ekf.setKltPhotometric(true);  // (likewise)
     }
     TightlyCoupledEKF tc_ekf;
     KLTTracker tracker;

@@ -104,7 +104,8 @@ class EkfvioNode {
         // told at start-up, by ekfvio::EKFVIO's constructor, to deliver the covariances with every frame's outputs; mask_rectify_border, default
         // false: with it, and rectify = 1, the black border that rectification leaves is no-data for the detector and the tracker, ekfvio_set_mask;
         // equalize_clip_limit, default 0 = off, with equalize_tiles_x / equalize_tiles_y, default 8: every frame is equalised on the device in front
-        // of its pyramid, ekfvio_set_equalize)
+        // of its pyramid, ekfvio_set_equalize; klt_photometric, default 0 = off: the tracker matches up to a gain and an offset,
+        // ekfvio_set_klt_photometric)
         for (const std::string& name : ekfvio::Params::names()) {
             XmlRpc::XmlRpcValue v;
             if (ros::param::get("~" + name, v)) params_.set(name, to_text(v));

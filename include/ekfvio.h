@@ -117,7 +117,8 @@ EKFVIO_API int ekfvio_create(const ekfvio_config* cfg, int device, void* stream,
 EKFVIO_API int ekfvio_destroy(ekfvio_filter* f);
 /* initializeBaseState(): back to mu = [0,0,0,1,0...], Sigma diag [0x7,30x9,0.5x6], no landmarks.  (The innovation gate's counts start
  * over; its threshold stays.  The same holds for the tracker's forward-backward check.  The distortion coefficients of
- * ekfvio_set_distortion stay too, and so does the setting of ekfvio_set_output_covariance.  The mask of ekfvio_set_mask stays as well, and the setting of ekfvio_set_equalize.) */
+ * ekfvio_set_distortion stay too, and so does the setting of ekfvio_set_output_covariance.  The mask of ekfvio_set_mask stays as well, and the setting of ekfvio_set_equalize.
+ * So does the tracker's gain/offset term, ekfvio_set_klt_photometric.) */
 EKFVIO_API int ekfvio_reset(ekfvio_filter* f);
 EKFVIO_API const char* ekfvio_last_error(const ekfvio_filter* f);
 
@@ -468,6 +469,41 @@ EKFVIO_API int ekfvio_get_klt_fb(ekfvio_filter* f, float* err2, uint8_t* rejecte
  * above; fb_ok = 0 where s_f == 0.  Output pointers may be NULL.  Leaves the results ekfvio_get_klt_fb reports untouched. */
 EKFVIO_API int ekfvio_klt_track_points_fb(ekfvio_filter* f, const float* prev_px, const float* init_px, int32_t count, float* out_px,
                                           uint8_t* status, float* back_px, float* err2, uint8_t* fb_ok);
+
+/* ---- gain/offset term of the tracker (not in the reference, whose Lucas-Kanade assumes brightness constancy) --------------------------
+ * Auto-exposure changes gain and offset between two consecutive frames: J(x + d) = alpha * I(x) + beta.  Then diff = J - I holds a
+ * component in span{1, I} that brightness-constancy Lucas-Kanade reads as motion.  With the setting on, span{1, I} is projected out of the
+ * template's two gradient images, once per pyramid level, which makes b = sum diff * (Ix, Iy) blind to that component (the "project-out"
+ * form of Hager-Belhumeur and Baker-Matthews); the iteration itself is unchanged.  This covers every Lucas-Kanade pass: the forward pass,
+ * the backward pass of the forward-backward check, ekfvio_klt_track, ekfvio_klt_track_points, ekfvio_klt_track_points_fb and
+ * ekfvio_step_image.  The lines below are the specification; a NumPy restatement of one pass with them (tests/_klt_photo.py) is what the
+ * device is held to, bit for bit.
+ *
+ * The pass forms the template's Iv[t], Ix[t], Iy[t] over the n = win * win window pixels exactly as without the term, as integers, at
+ * every pyramid level, before A11, A12, A22 are formed.  Then:
+ *
+ *     sI = sum Iv   sX = sum Ix   sY = sum Iy   sII = sum Iv*Iv   sIX = sum Iv*Ix   sIY = sum Iv*Iy      exact integers (64-bit where needed)
+ *     VI = n*sII - sI*sI      CX = n*sIX - sI*sX      CY = n*sIY - sI*sY                                  exact int64 (VI >= 0)
+ *     mI = (float)sI / (float)n     mX = (float)sX / (float)n     mY = (float)sY / (float)n             fp32, each conversion rounds once
+ *     cx = VI > 0 ? (float)CX / (float)VI : 0.0f          cy likewise                                     correctly rounded division
+ *     Ix'[t] = clamp((int)rint(((float)Ix[t] - mX) - cx * ((float)Iv[t] - mI)), -4080, 4080)              fp32, no fused multiply-add, rint half to even
+ *     Iy'[t] likewise with mY, cy
+ *
+ * After that, everything runs on Ix', Iy': A11, A12, A22, the min-eigenvalue test and every iteration's b1, b2.  Iv and diff are unchanged.
+ * The clamp keeps every bound the kernel's integer sums rely on (factors fit 24 bits, per-lane partials stay below 2^28); it only bites
+ * on degenerate templates.  A constant template has VI == 0: it gets the mean removed and then fails the min-eigenvalue test as before.
+ * Out of scope: the sample-based R (cfg.sample_based_uncertainty), whose SSD weights remain brightness-dependent; a per-landmark exposure
+ * state in the filter; affine window warps; the detector.
+ *
+ * on: 0 or 1, anything else EKFVIO_EINVAL.  A property of the handle: it holds from the next track and survives ekfvio_reset.  Off by
+ * default (then no launch differs and every output keeps its bits); on, the tracker's launch is the kernel's second instance with the same
+ * arguments, and nothing is allocated. */
+EKFVIO_API int ekfvio_set_klt_photometric(ekfvio_filter* f, int32_t on);
+/* The projection itself, Ix' and Iy' of `count` window pixels from their Iv, Ix, Iy (n = count): a pure host function (no handle, no
+ * device) that compiles the very inline functions the kernel compiles, as ekfvio_rectify_map does; the six sums come from a loop here and
+ * from a wavefront there.  count in [1, 441] and no NULL pointer, else EKFVIO_EINVAL.  An output may be its own input. */
+EKFVIO_API int ekfvio_klt_project_gradients(const int32_t* Iv, const int32_t* Ix, const int32_t* Iy, int32_t count, int32_t* Ix_out,
+                                            int32_t* Iy_out);
 
 /* KLTTracker::estimateUncertaintySampleBased (KLTTracker.cpp:111-175) between the two resident frames: for every
  * point a pixel-space 2x2 covariance (row-major, px^2) from 25 samples (offsets -10..10 step 5 around cur_px) of 5x5
