@@ -48,7 +48,8 @@ SYMBOLS = ["ekfvio_default_config", "ekfvio_create", "ekfvio_destroy", "ekfvio_r
            "ekfvio_set_klt_fb", "ekfvio_get_klt_fb", "ekfvio_klt_track_points_fb", "ekfvio_set_distortion", "ekfvio_rectify_map",
            "ekfvio_set_output_covariance", "ekfvio_get_odometry_covariance", "ekfvio_get_points_covariance", "ekfvio_rotation_error_jacobian",
            "ekfvio_set_mask", "ekfvio_get_mask", "ekfvio_get_mask_hits", "ekfvio_mask_blocked", "ekfvio_set_equalize", "ekfvio_equalize",
-           "ekfvio_set_klt_photometric", "ekfvio_klt_project_gradients"]
+           "ekfvio_set_klt_photometric", "ekfvio_klt_project_gradients",
+           "ekfvio_get_landmark_ids", "ekfvio_set_ended_export", "ekfvio_get_ended"]
 MASK_RECTIFY_BORDER = 1  # EKFVIO_MASK_RECTIFY_BORDER
 # every symbol include/ekfvio_test_hooks.h declares (libekfvio_hip_hooks.so only)
 HOOK_SYMBOLS = ["ekfvio_test_klt_padded_level", "ekfvio_test_blurred_level0", "ekfvio_test_gemm", "ekfvio_test_gemm_bench", "ekfvio_test_potrf_stamps",
@@ -112,6 +113,9 @@ def load(build_if_missing=True, hooks=False):
         "ekfvio_equalize": [u8p, i32, i32, i32, f32, i32, i32, u8p],  # no handle, no device
         "ekfvio_set_klt_photometric": [vp, i32],
         "ekfvio_klt_project_gradients": [ip, ip, ip, i32, ip, ip],  # no handle, no device
+        "ekfvio_get_landmark_ids": [vp, C.POINTER(C.c_int64), C.POINTER(C.c_double)],
+        "ekfvio_set_ended_export": [vp, i32],
+        "ekfvio_get_ended": [vp, C.POINTER(C.c_int64), C.POINTER(C.c_double), ip, fp, fp, i32, ip, C.POINTER(C.c_int64)],
     }
     if hooks:
         sig.update({

@@ -54,7 +54,8 @@ __global__ void init_sigma_kernel(float* P, int ld) {
 // k_dev != nullptr: the count comes from device memory (the first-fit selection's result, ekfvio_step_image: the host
 // learns it with the frame's status word, not in the middle of the frame)
 __global__ void add_features_kernel(float* P, int ld, int n_old, int k, float hv, float dv, float* mu, float* last_klt,
-                                    uint8_t* del_flag, const float* uv, int N_old, float inv_depth, const int* k_dev) {
+                                    uint8_t* del_flag, const float* uv, int N_old, float inv_depth, const int* k_dev, int64_t* id,
+                                    double* born, int64_t id_base, double stamp) {
     if (k_dev) k = *k_dev;
     const int n_new = n_old + 3 * k;
     for (size_t e = blockIdx.x * (size_t)blockDim.x + threadIdx.x; e < (size_t)3 * k * n_new;
@@ -73,6 +74,8 @@ __global__ void add_features_kernel(float* P, int ld, int n_old, int k, float hv
         last_klt[2 * (N_old + fidx)] = u;
         last_klt[2 * (N_old + fidx) + 1] = v;
         del_flag[N_old + fidx] = 0;
+        id[N_old + fidx] = id_base + fidx;  // (the host advances its counter by k where it counts the landmarks in)
+        born[N_old + fidx] = stamp;
     }
 }
 
@@ -95,19 +98,20 @@ int add_features_device(ekfvio_filter* f, int count) {
     const float inv_depth = (float)(1.0 / (double)depth);  // Feature.cpp:18  mu(2) = 1.0/depth
     hipLaunchKernelGGL(add_features_kernel, dim3(64), dim3(256), 0, f->stream, f->P, f->ldp, f->n, count,
                        f->cfg.default_point_homogenous_variance, f->cfg.default_point_depth_variance, f->mu,
-                       f->last_klt, f->del_flag, f->zmeas, f->N, inv_depth, nullptr);
+                       f->last_klt, f->del_flag, f->zmeas, f->N, inv_depth, nullptr, f->lm_id, f->lm_born, f->next_id, born_stamp(f));
     HIP_TRY(f, hipStreamSynchronize(f->stream));
     f->N += count;
     f->n += 3 * count;
+    f->next_id += count;
     return EKFVIO_OK;
 }
 // The same with the count in device memory (at most max_features - N, by construction of the selection): enqueued only.
-// The caller adds the count to f->N / f->n once it has read it (wait_status's extra word).
+// The caller adds the count to f->N / f->n and to f->next_id once it has read it (wait_status's extra word).
 void add_features_enqueue_device_count(ekfvio_filter* f, const int* count_dev) {
     const float inv_depth = (float)(1.0 / (double)f->cfg.default_point_depth);
     hipLaunchKernelGGL(add_features_kernel, dim3(64), dim3(256), 0, f->stream, f->P, f->ldp, f->n, 0,
                        f->cfg.default_point_homogenous_variance, f->cfg.default_point_depth_variance, f->mu,
-                       f->last_klt, f->del_flag, f->zmeas, f->N, inv_depth, count_dev);
+                       f->last_klt, f->del_flag, f->zmeas, f->N, inv_depth, count_dev, f->lm_id, f->lm_born, f->next_id, born_stamp(f));
 }
 
 // one workgroup; publishes the status word itself once its own writes are out (see wait_status / poll_status)
@@ -209,6 +213,8 @@ static int create_body(ekfvio_filter* f, const ekfvio_config* cfg, int device, v
     HIP_TRY(f, dev_alloc(f, &f->mu_next, f->ldp));
     HIP_TRY(f, dev_alloc(f, &f->last_klt, 2 * (size_t)maxf));
     HIP_TRY(f, dev_alloc(f, &f->del_flag, (size_t)maxf));
+    HIP_TRY(f, dev_alloc(f, &f->lm_id, (size_t)maxf));
+    HIP_TRY(f, dev_alloc(f, &f->lm_born, (size_t)maxf));
     HIP_TRY(f, dev_alloc(f, &f->P, pp));
     HIP_TRY(f, dev_alloc(f, &f->P2, pp));
     HIP_TRY(f, dev_alloc(f, &f->FA, EKF_BASE * EKF_BASE));
@@ -378,6 +384,8 @@ int ekfvio_reset(ekfvio_filter* f) {
     f->have_stamp = false;
     f->frames[0].valid = f->frames[1].valid = false;
     f->mask_hits_n = 0;  // the mask's hits of the last track go with the landmarks; the mask itself stays (ekfvio_set_mask)
+    // next_id goes on: no two landmarks of a handle's lifetime share an id.  The ended tracks' report and total start over; the setting stays
+    f->ended_count = 0, f->ended_total = 0;
     return EKFVIO_OK;
 }
 
@@ -660,11 +668,20 @@ int ekfvio_set_state(ekfvio_filter* f, int32_t N, const float* base_mu, const fl
         HIP_TRY(f, hipMemcpyAsync(f->last_klt, last_klt2N, sizeof(float) * 2 * N, hipMemcpyHostToDevice, f->stream));
         HIP_TRY(f, hipMemcpyAsync(f->del_flag, delN, N, hipMemcpyHostToDevice, f->stream));
     }
+    // the landmark set is replaced: all N get fresh ids, in order, and the handle's current time as their birth stamp
+    std::vector<int64_t> ids((size_t)N);
+    const std::vector<double> born((size_t)N, born_stamp(f));
+    for (int i = 0; i < N; i++) ids[i] = f->next_id + i;
+    if (N > 0) {
+        HIP_TRY(f, hipMemcpyAsync(f->lm_id, ids.data(), sizeof(int64_t) * N, hipMemcpyHostToDevice, f->stream));
+        HIP_TRY(f, hipMemcpyAsync(f->lm_born, born.data(), sizeof(double) * N, hipMemcpyHostToDevice, f->stream));
+    }
     HIP_TRY(f, hipMemcpy2DAsync(f->P, sizeof(float) * f->ldp, sigma, sizeof(float) * ld, sizeof(float) * n, n,
                              hipMemcpyHostToDevice, f->stream));
     HIP_TRY(f, hipStreamSynchronize(f->stream));
     f->N = N;
     f->n = n;
+    f->next_id += N;
     return EKFVIO_OK;
 }
 

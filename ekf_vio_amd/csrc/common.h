@@ -140,6 +140,14 @@ struct ekfvio_filter {
     float* mu_next = nullptr;  // [ldp]  scratch for the propagated mean
     float* last_klt = nullptr; // [2*max_features]
     uint8_t* del_flag = nullptr;  // [max_features]
+    // Identity per landmark (include/ekfvio.h, "landmark identities"): row i of both names the landmark in row i of the state.
+    // INVARIANT: exactly two kernels write them -- add_features_kernel (api.hip) appends, remove_features_kernel (remove.hip) compacts them with
+    // last_klt and del_flag, in the kept order -- and ekfvio_set_state replaces them.  Nothing else moves landmarks: process(dt), the update
+    // and ekfvio_run_uploaded leave both arrays alone.  Compaction keeps the order and new landmarks are appended with rising ids, so lm_id
+    // is STRICTLY INCREASING in landmark order at all times.
+    int64_t* lm_id = nullptr;     // [max_features] next_id + k for the k-th landmark of an append
+    double* lm_born = nullptr;    // [max_features] the stamp of the frame the landmark entered in (born_stamp below)
+    int64_t next_id = 0;          // ids handed out so far: advances where N does, never goes back, survives ekfvio_reset
     float* P = nullptr;        // [ldp*ldp] dense covariance, column-major
     float* P2 = nullptr;       // [ldp*ldp] ping-pong / scratch (X = F P, dense F)
     // --- process Jacobian blocks ---
@@ -212,6 +220,18 @@ struct ekfvio_filter {
     float* fb_pt_err2 = nullptr;  // [max_features], fb_pt_back [2*max_features], fb_pt_flag [max_features]: the same and the backward result for the
     float* fb_pt_back = nullptr;  // points of ekfvio_klt_track_points_fb
     uint8_t* fb_pt_flag = nullptr;
+    // --- the tracks that ended (ekfvio_set_ended_export; ended.hip): one record per landmark a removal is about to take out ---
+    bool ended_on = false;        // every launched removal is preceded by ended_tracks_kernel
+    // (pinned, device-mapped host memory: one allocation, made by the first ekfvio_set_ended_export(f, 1); h_ended is its base and ended_id the
+    // device's address of it.  Layout, all sized for max_features: id, born, xyz, cov, index)
+    unsigned char* h_ended = nullptr;
+    int64_t* ended_id = nullptr;
+    double* ended_born = nullptr;
+    float* ended_xyz = nullptr;   // [3 max_features]
+    float* ended_cov = nullptr;   // [9 max_features]
+    int* ended_index = nullptr;   // the landmark's row in front of the removal
+    int ended_count = 0;          // records of the most recent removal call since the setting went on (the host-known removed count)
+    int64_t ended_total = 0;      // since create / reset
     int* remove_words = nullptr;  // [4] device words of the removal kernel (remove.hip): [0] landmarks added - removed, [1] removed, [2] its ticket
     int* h_info = nullptr;     // pinned, device-mapped: the words of enum HostWord
     int* d_hinfo = nullptr;    // the device's address of h_info
@@ -219,7 +239,8 @@ struct ekfvio_filter {
     // small per-frame outputs (odometry, point cloud): kernels write them straight into pinned host memory and the host
     // waits with wait_status: no device-to-host copy into pageable memory, no interrupt-driven synchronise
     float* h_out = nullptr;    // pinned, device-mapped: base_mu[22], xyz[3 N], intensity[N] in the first EKF_BASE + 4 * max_features floats, then
-                               // at fixed offsets (out_cov_offset) pose_cov[36], twist_cov[36], cov[9 N]: EKF_BASE + 72 + 13 * max_features floats
+                               // at fixed offsets (out_cov_offset) pose_cov[36], twist_cov[36], cov[9 N]: EKF_BASE + 72 + 13 * max_features floats,
+                               // then, 8-byte aligned (out_ids_offset), id[max_features] as int64 and born[max_features] as double
     float* d_out = nullptr;    // the device's address of h_out
     bool out_fresh = false;    // h_out holds base_mu and the point cloud of the CURRENT state and frame: ekfvio_step_image's last
                                // kernel writes them with the status word, and every call that changes the state or the frame
@@ -462,7 +483,13 @@ struct Level0View {
 Level0View klt_level0(const ekfvio_filter* f);
 // Where the covariances lie in h_out / d_out (frame.hip): pose_cov[36], twist_cov[36], then 9 floats per landmark; out_words: the whole allocation
 inline size_t out_cov_offset(const ekfvio_filter* f) { return EKF_BASE + 4 * (size_t)(f->cfg.max_features > 0 ? f->cfg.max_features : 1); }
-inline size_t out_words(const ekfvio_filter* f) { return out_cov_offset(f) + 72 + 9 * (size_t)(f->cfg.max_features > 0 ? f->cfg.max_features : 1); }
+// ... and the landmark ids and birth stamps behind them, in a region of their own that starts on an 8-byte boundary (in floats, as the others)
+inline size_t out_ids_offset(const ekfvio_filter* f) {
+    return (out_cov_offset(f) + 72 + 9 * (size_t)(f->cfg.max_features > 0 ? f->cfg.max_features : 1) + 1) & ~(size_t)1;
+}
+inline size_t out_words(const ekfvio_filter* f) { return out_ids_offset(f) + 4 * (size_t)(f->cfg.max_features > 0 ? f->cfg.max_features : 1); }
+// What add_features_kernel stamps a new landmark with: the handle's current time, the stamp of the frame inside ekfvio_step_image; NaN before any stamp
+inline double born_stamp(const ekfvio_filter* f) { return f->have_stamp ? f->t_stamp : __builtin_nan(""); }
 // what the frame loop (frame.hip) enqueues of the tracker's file
 int push_frame_check(ekfvio_filter* f, const uint8_t* image, int32_t width, int32_t height, int32_t stride, const float K[9]);
 int push_frame_enqueue(ekfvio_filter* f, const uint8_t* image, int32_t width, int32_t height, int32_t stride, const float K[9]);
@@ -533,7 +560,11 @@ void launch_potrf_stamps(ekfvio_filter* f, const float* S, int ld, float* L, flo
 // K = X A^-1 (n rows, ldk) from the sweep output, as the plan says: gain_tiles_kernel, or the GEMM K = Y L^-1 (+ optional residual refinement).
 void launch_gain_from_sweep(ekfvio_filter* f, const UpdatePlan& p, const float* Laug, int ld, int n, float* K, float* scratch, int ldk, int refine);
 
-// remove.hip: Sigma, mu, last_klt, del_flag compacted in ONE launch over N + *added landmarks (added may be null); decision from
+// ended.hip: with ekfvio_set_ended_export on, launch_remove_features puts this in front of its own launch with its own arguments: one record
+// per landmark the removal is about to take out, from the mean and Sigma as they stand (f->mu, f->P)
+void launch_ended_tracks(ekfvio_filter* f, const uint8_t* remove, const int* added, bool abort_aware);
+void ended_note_removal(ekfvio_filter* f, int removed);  // the host-known count of a removal call (0 included) behind it
+// remove.hip: Sigma, mu, last_klt, del_flag, lm_id, lm_born compacted in ONE launch over N + *added landmarks (added may be null); decision from
 // `remove` (device memory), null: del_flag; abort_aware: nothing removed behind an aborted persistent sweep; host_removed: the
 // count into the pinned host word HW_REMOVED too
 void launch_remove_features(ekfvio_filter* f, const uint8_t* remove, const int* added, bool abort_aware, bool host_removed);

@@ -9,32 +9,11 @@
 #include <string.h>
 
 #include "common.h"
+#include "points.h"
 
 namespace {
 
-// EKFVIO::publishPoints (EKFVIO.cpp:479-518): camera-frame point (u/rho, v/rho, 1/rho) per landmark -- p(2) = 1.0/p(2)
-// in double, narrowed, then two float products -- and the "intensity" channel f.img.at<uchar>(e.getPixel(f)): the byte
-// at the landmark's pixel (Feature::getPixel: K(0)*mu(0) + K(2), K(4)*mu(1) + K(5); cv::Point2f -> cv::Point rounds
-// to nearest even, cvRound).  The reference reads outside the image unchecked; here such a landmark gets intensity 0.
-// img = pixel (0,0) of level 0 of the current frame, or null when no frame has been pushed (intensity 0 then).
-__device__ inline void points_one(const float* __restrict__ mu, int i, const uint8_t* __restrict__ img, int pitch, int w, int h,
-                                  float fx, float fy, float cx, float cy, float* __restrict__ xyz, float* __restrict__ intensity) {
-    const float u = mu[EKF_BASE + 3 * i], v = mu[EKF_BASE + 3 * i + 1], rho = mu[EKF_BASE + 3 * i + 2];
-    const float z = (float)(1.0 / (double)rho);
-    xyz[3 * i] = u * z;
-    xyz[3 * i + 1] = v * z;
-    xyz[3 * i + 2] = z;
-    float in = 0.f;
-    if (img) {
-        const float px = fx * u + cx, py = fy * v + cy;
-        // cvRound; compared as floats first so that NaN / huge values never reach the conversion
-        if (px >= -0.5f && px < (float)w && py >= -0.5f && py < (float)h) {
-            const int ix = __float2int_rn(px), iy = __float2int_rn(py);
-            if (ix >= 0 && ix < w && iy >= 0 && iy < h) in = (float)img[(size_t)iy * pitch + ix];
-        }
-    }
-    intensity[i] = in;
-}
+// (points_one, the point of one landmark: points.h)
 // host_word != nullptr (single-workgroup launches only): the kernel publishes the status word itself behind its writes
 __global__ void points_kernel(const float* __restrict__ mu, int N, const uint8_t* __restrict__ img, int pitch, int w, int h,
                               float fx, float fy, float cx, float cy, float* __restrict__ xyz, float* __restrict__ intensity,
@@ -90,27 +69,7 @@ __device__ inline void odom_cov_one(const float* __restrict__ mu, const float* _
     }
     out72[e] = v;
 }
-// Landmark i's 3x3 into out9N[9 i ..]: one lane per landmark; its six Sigma entries lie in three columns
-__device__ inline void points_cov_one(const float* __restrict__ mu, const float* __restrict__ P, int ld, int i, float* __restrict__ out9N) {
-    const int s = EKF_BASE + 3 * i;
-    const float u = mu[s], v = mu[s + 1], rho = mu[s + 2];
-    const float z = (float)(1.0 / (double)rho);
-    const float x = u * z, y = v * z;
-    const float jx = -(x * z), jy = -(y * z), jz = -(z * z);
-    const float* c0 = P + (size_t)s * ld + s;  // column s from its diagonal element down
-    const float* c1 = c0 + ld + 1;
-    const float L00 = c0[0], L10 = c0[1], L20 = c0[2], L11 = c1[0], L21 = c1[1], L22 = c1[ld + 1];
-    const float M00 = z * L00 + jx * L20, M02 = z * L20 + jx * L22;
-    const float M10 = z * L10 + jy * L20, M11 = z * L11 + jy * L21, M12 = z * L21 + jy * L22;
-    const float M20 = jz * L20, M21 = jz * L21, M22 = jz * L22;
-    const float C00 = M00 * z + M02 * jx;
-    const float C10 = M10 * z + M12 * jx, C11 = M11 * z + M12 * jy;
-    const float C20 = M20 * z + M22 * jx, C21 = M21 * z + M22 * jy, C22 = M22 * jz;
-    float* o = out9N + 9 * (size_t)i;
-    o[0] = C00, o[1] = C10, o[2] = C20;
-    o[3] = C10, o[4] = C11, o[5] = C21;
-    o[6] = C20, o[7] = C21, o[8] = C22;
-}
+// (points_cov_one, landmark i's 3x3: points.h)
 // The on-demand road (ekfvio_get_odometry_covariance / ekfvio_get_points_covariance), in the shape of points_kernel.
 // One workgroup; it publishes the status word itself
 __global__ __launch_bounds__(128) void odom_cov_kernel(const float* __restrict__ mu, const float* __restrict__ P, int ld, float* __restrict__ out72,
@@ -137,7 +96,7 @@ __global__ __launch_bounds__(256) void points_cov_kernel(const float* __restrict
 // the host is waiting for anyway.  ekfvio_get_odometry / ekfvio_get_points then cost a memcpy instead of a launch and a
 // wait each (the node's loop with outputs: 164 -> 140 us per frame at the node's defaults).  One workgroup; the number of
 // landmarks is N_old plus what the replenishment just added (added_dev, may be null).
-// Layout of out: base_mu[22], xyz[3 N], intensity[N].
+// Layout of out: base_mu[22], xyz[3 N], intensity[N]; the landmarks' ids and birth stamps in a region of their own (FrameIdsOut).
 // Pcol != null (round 4): launched BETWEEN the update's two Joseph GEMMs.  The mean update mu += K y, quaternion renormalised, is the
 // second GEMM's (gemm.hip, mode 2, :600-609) from K y in column n of P, which the first one has just left there: the same sums are
 // formed here (into LDS, mu itself is not touched), so the frame's outputs and status reach the host while the second GEMM still runs
@@ -151,11 +110,19 @@ struct FrameCovOut {
     int ld = 0;
     float* out = nullptr;
 };
+// The landmarks' ids and birth stamps (include/ekfvio.h, "landmark identities") go out with the cloud, rows as the cloud's: behind a removal
+// the arrays are compacted already (in place, remove.hip), and a frame that publishes early can neither add nor remove.
+struct FrameIdsOut {
+    const int64_t* id = nullptr;
+    const double* born = nullptr;
+    int64_t* out_id = nullptr;   // h_out at out_ids_offset, [max_features]
+    double* out_born = nullptr;  // ... behind it
+};
 __global__ __launch_bounds__(256) void frame_outputs_kernel(const float* __restrict__ mu, int N_old, const int* __restrict__ added_dev,
                                                             const uint8_t* __restrict__ img, int pitch, int w, int h, float fx, float fy,
                                                             float cx, float cy, float* __restrict__ out, const int* __restrict__ info,
                                                             int* host_word, int seq, const float* __restrict__ Pcol,
-                                                            const float* __restrict__ Kyp, int kyp_blocks, int kyp_ld, FrameCovOut cov) {
+                                                            const float* __restrict__ Kyp, int kyp_blocks, int kyp_ld, FrameCovOut cov, FrameIdsOut ids) {
     extern __shared__ float s_mu[];  // Pcol / Kyp: the updated mean, EKF_BASE + 3 N floats
     const int added = added_dev ? *added_dev : 0;
     const int N = N_old + added;
@@ -206,6 +173,7 @@ __global__ __launch_bounds__(256) void frame_outputs_kernel(const float* __restr
     float* xyz = out + EKF_BASE;
     float* inten = xyz + 3 * (size_t)N;
     for (int i = threadIdx.x; i < N; i += 256) points_one(mu, i, img, pitch, w, h, fx, fy, cx, cy, xyz, inten);
+    for (int i = threadIdx.x; i < N; i += 256) ids.out_id[i] = ids.id[i], ids.out_born[i] = ids.born[i];
     if (cov.S) {
         const float* S = (cov.removed_dev && cov.removed_dev[1] > 0) ? cov.S_removed : cov.S;
         if (threadIdx.x < 72) odom_cov_one(mu, S, cov.ld, threadIdx.x, cov.out);
@@ -232,8 +200,13 @@ static int launch_frame_outputs(ekfvio_filter* f, const float* mu, const int* co
         cov.S = f->P, cov.ld = f->ldp, cov.out = f->d_out + out_cov_offset(f);
         if (removed) cov.S_removed = f->P2, cov.removed_dev = f->remove_words;
     }
+    FrameIdsOut ids;
+    ids.id = f->lm_id, ids.born = f->lm_born;
+    ids.out_id = reinterpret_cast<int64_t*>(f->d_out + out_ids_offset(f));
+    ids.out_born = reinterpret_cast<double*>(ids.out_id + (f->cfg.max_features > 0 ? f->cfg.max_features : 1));
     hipLaunchKernelGGL(frame_outputs_kernel, dim3(1), dim3(256), early ? sizeof(float) * (size_t)f->n : 0, f->stream, mu, f->N, count_dev, v.img,
-                       v.pitch, v.w, v.h, v.fx, v.fy, v.cx, v.cy, f->d_out, f->info, f->d_hinfo, seq, Pcol, Kyp, kyp_blocks, early ? f->ldp : 0, cov);
+                       v.pitch, v.w, v.h, v.fx, v.fy, v.cx, v.cy, f->d_out, f->info, f->d_hinfo, seq, Pcol, Kyp, kyp_blocks, early ? f->ldp : 0, cov,
+                       ids);
     return seq;
 }
 
@@ -270,6 +243,25 @@ int ekfvio_get_points(ekfvio_filter* f, float* xyz3N, float* intensityN) {
     if (rc != EKFVIO_OK) return rc;
     if (xyz3N) memcpy(xyz3N, f->h_out + EKF_BASE, sizeof(float) * 3 * N);
     if (intensityN) memcpy(intensityN, f->h_out + EKF_BASE + 3 * (size_t)N, sizeof(float) * N);
+    return EKFVIO_OK;
+}
+
+// The landmarks' ids and birth stamps (include/ekfvio.h, "landmark identities"), rows as ekfvio_get_points' of the same moment: a memcpy
+// while the frame's outputs are fresh, else a device-to-host copy on the handle's stream and a wait, as ekfvio_get_features.
+int ekfvio_get_landmark_ids(ekfvio_filter* f, int64_t* idN, double* bornN) {
+    if (!f) return EKFVIO_EINVAL;
+    const int N = f->N;
+    if (N == 0) return EKFVIO_OK;
+    if (f->out_fresh) {
+        const int64_t* h_id = reinterpret_cast<const int64_t*>(f->h_out + out_ids_offset(f));
+        if (idN) memcpy(idN, h_id, sizeof(int64_t) * N);
+        if (bornN) memcpy(bornN, h_id + (f->cfg.max_features > 0 ? f->cfg.max_features : 1), sizeof(double) * N);
+        return EKFVIO_OK;
+    }
+    HIP_TRY(f, hipSetDevice(f->device));
+    if (idN) HIP_TRY(f, hipMemcpyAsync(idN, f->lm_id, sizeof(int64_t) * N, hipMemcpyDeviceToHost, f->stream));
+    if (bornN) HIP_TRY(f, hipMemcpyAsync(bornN, f->lm_born, sizeof(double) * N, hipMemcpyDeviceToHost, f->stream));
+    HIP_TRY(f, hipStreamSynchronize(f->stream));
     return EKFVIO_OK;
 }
 
@@ -364,6 +356,7 @@ int ekfvio_step_image(ekfvio_filter* f, double stamp, const uint8_t* image, int3
             f->t_stamp = stamp;
             f->have_stamp = true;
         }
+        if (f->cfg.remove_lost) ended_note_removal(f, 0);  // (a removing frame with no landmark: no track ended)
         if (f->cfg.replenish) return ekfvio_replenish(f, nullptr, nullptr);  // replenishFeatures(first frame) (:154)
         HIP_TRY(f, hipStreamSynchronize(f->stream));
         return EKFVIO_OK;
@@ -412,8 +405,10 @@ int ekfvio_step_image(ekfvio_filter* f, double stamp, const uint8_t* image, int3
     const bool removing = f->cfg.remove_lost && f->N > 0;
     const int* count_dev = replenishing ? f->fast_counts + 1 : nullptr;
     if (removing) {
-        launch_remove_features(f, nullptr, count_dev, true, true);
+        launch_remove_features(f, nullptr, count_dev, true, true);  // (with ekfvio_set_ended_export: the ended tracks' records in front of it)
         count_dev = f->remove_words;
+    } else if (f->cfg.remove_lost) {
+        ended_note_removal(f, 0);
     }
     // the frame's one wait: the status word, the number of new landmarks and what the node publishes after addFrame
     // (odometry, point cloud) arrive together in pinned host memory (frame_outputs_kernel)
@@ -427,7 +422,11 @@ int ekfvio_step_image(ekfvio_filter* f, double stamp, const uint8_t* image, int3
     f->out_fresh = f->tune.frame_outputs != 0;
     f->out_cov_fresh = f->out_fresh && f->output_cov;
     // (in front of a re-run, which reads f->mu and f->P as the swap leaves them; the count of landmarks: below, with `added`)
-    if (removing) remove_applied(f, 0, __atomic_load_n(&f->h_info[HW_REMOVED], __ATOMIC_ACQUIRE));
+    const int removed = removing ? __atomic_load_n(&f->h_info[HW_REMOVED], __ATOMIC_ACQUIRE) : 0;
+    if (removing) {
+        remove_applied(f, 0, removed);
+        ended_note_removal(f, removed);
+    }
     // Bit 1: the persistent sweep gave up (chol_persist.inc), the Joseph GEMMs wrote nothing, the state is the propagated one.
     // The update runs again now, with one launch per block step, over the landmarks it was enqueued for (the count is
     // bumped below): idx, the measured coordinates per row, R and the row count are where the bookkeeping left them.
@@ -448,6 +447,7 @@ int ekfvio_step_image(ekfvio_filter* f, double stamp, const uint8_t* image, int3
         f->N += added;
         f->n += 3 * added;
     }
+    f->next_id += added + removed;  // what the replenishment appended: its ids are visible from here on (not counted in above: never visible)
     return status;
 }
 

@@ -20,6 +20,8 @@ struct RemoveArgs {
     float* mu_dst;           // receives mu' (always: the host swaps the mean after every launch)
     float* last_klt;         // compacted in place
     uint8_t* del_flag;       // compacted in place
+    int* id32;               // the landmarks' ids (int64) and birth stamps (double), compacted in place: moved as pairs of 32-bit
+    int* born32;             // words, two per landmark
     const uint8_t* remove;   // the decision per landmark: nonzero = remove.  May be del_flag itself.
     int ld;
     int N_host;              // landmarks the host knows of ...
@@ -56,6 +58,22 @@ __device__ int scan_keep(const RemoveArgs& a, int N_old, bool keep_all, int* pre
     return kept;
 }
 
+// An array of two 32-bit words per landmark, compacted in place by the LAST workgroup through `stage` (2 * kept ints of LDS that nothing
+// else uses any more).  Every thread has passed a barrier behind the last use of `stage` when it gets here.
+__device__ __forceinline__ void compact_pairs(int* arr, const int* src_of, int kept, int* stage) {
+    for (int k = threadIdx.x; k < kept; k += RM_THREADS) {
+        const int s = src_of[k];
+        stage[2 * k] = arr[2 * s];
+        stage[2 * k + 1] = arr[2 * s + 1];
+    }
+    __syncthreads();
+    for (int k = threadIdx.x; k < kept; k += RM_THREADS) {
+        arr[2 * k] = stage[2 * k];
+        arr[2 * k + 1] = stage[2 * k + 1];
+    }
+    __syncthreads();
+}
+
 // state index of row r of the compacted state (r < n')
 __device__ __forceinline__ int src_row(const int* src_of, int r) {
     if (r < EKF_BASE) return r;
@@ -76,11 +94,12 @@ __device__ __forceinline__ void zero_rows(float* col, int lo, int hi, int lane) 
 }
 
 // ONE launch: Sigma' = Sigma[keep, keep] into P2 (padding up to the old n zeroed in both P and P2), mu' = mu[keep] into mu_dst
-// (mu_src zeroed in [n', n_old)), last_klt and del_flag compacted in place, the counts into `words`.
+// (mu_src zeroed in [n', n_old)), last_klt, del_flag, the ids and the birth stamps compacted in place, the counts into `words`.
 // Grid: one source column j per wavefront, sized for the most columns the state can have; surplus workgroups only take part in
 // the ticket.  Source column j is read by the wavefront that owns it and by no other, so that wavefront may clear it behind its
-// reads: no workgroup waits for another.  The mean, last_klt and del_flag are compacted by the LAST workgroup to take a ticket --
-// the decision may be del_flag itself, which every workgroup has finished reading by then.
+// reads: no workgroup waits for another.  The mean, last_klt, del_flag, the ids and the birth stamps are compacted by the LAST workgroup
+// to take a ticket -- the decision may be del_flag itself, which every workgroup has finished reading by then.  The ids and the stamps
+// take their turn in s_klt's 2 N ints, one after the other, once last_klt is back in global memory: the LDS size does not grow.
 __global__ __launch_bounds__(RM_THREADS) void remove_features_kernel(RemoveArgs a) {
     extern __shared__ int lds[];
     __shared__ int wsum[RM_THREADS];
@@ -150,6 +169,9 @@ __global__ __launch_bounds__(RM_THREADS) void remove_features_kernel(RemoveArgs 
         a.last_klt[2 * k + 1] = s_klt[2 * k + 1];
         a.del_flag[k] = s_del[k];
     }
+    __syncthreads();  // s_klt is free
+    compact_pairs(a.id32, src_of, kept, reinterpret_cast<int*>(s_klt));
+    compact_pairs(a.born32, src_of, kept, reinterpret_cast<int*>(s_klt));
     if (threadIdx.x == 0) {
         a.words[0] = (a.added ? *a.added : 0) - removed;
         a.words[1] = removed;
@@ -172,6 +194,8 @@ size_t remove_lds_bytes(const ekfvio_filter* f) {
 // from del_flag.  abort_aware: nothing is removed behind an aborted persistent sweep (ekfvio_step_image).  The caller swaps
 // mu <-> mu_next after every launch, P <-> P2 when something was removed (words[1] > 0), and applies words[0] to N.
 void launch_remove_features(ekfvio_filter* f, const uint8_t* remove, const int* added, bool abort_aware, bool host_removed) {
+    // the records of the landmarks about to leave are formed first, from the same decision and the same counts (ended.hip)
+    if (f->ended_on) launch_ended_tracks(f, remove, added, abort_aware);
     RemoveArgs a;
     a.P = f->P;
     a.P2 = f->P2;
@@ -179,6 +203,8 @@ void launch_remove_features(ekfvio_filter* f, const uint8_t* remove, const int* 
     a.mu_dst = f->mu_next;
     a.last_klt = f->last_klt;
     a.del_flag = f->del_flag;
+    a.id32 = reinterpret_cast<int*>(f->lm_id);
+    a.born32 = reinterpret_cast<int*>(f->lm_born);
     a.remove = remove ? remove : f->del_flag;
     a.ld = f->ldp;
     a.N_host = f->N;
@@ -216,7 +242,10 @@ int ekfvio_remove_features(ekfvio_filter* f, const uint8_t* remove, int32_t coun
     if (remove) {
         int k = 0;
         for (int i = 0; i < count; i++) k += remove[i] ? 1 : 0;
-        if (k == 0) return EKFVIO_OK;  // nothing launched, the state untouched
+        if (k == 0) {  // nothing launched, the state untouched
+            ended_note_removal(f, 0);
+            return EKFVIO_OK;
+        }
         f->out_fresh = false;
         // staged through the tracker's pass buffer (free between calls: ekfvio_step_image rewrites it before it reads it)
         HIP_TRY(f, hipMemcpyAsync(f->pass, remove, count, hipMemcpyHostToDevice, f->stream));
@@ -224,10 +253,14 @@ int ekfvio_remove_features(ekfvio_filter* f, const uint8_t* remove, int32_t coun
         HIP_TRY(f, hipGetLastError());
         HIP_TRY(f, hipStreamSynchronize(f->stream));  // (remove is the caller's memory)
         remove_applied(f, -k, k);
+        ended_note_removal(f, k);
         if (removed) *removed = k;
         return EKFVIO_OK;
     }
-    if (f->N == 0) return EKFVIO_OK;
+    if (f->N == 0) {
+        ended_note_removal(f, 0);
+        return EKFVIO_OK;
+    }
     f->out_fresh = false;
     // the flags are on the device: one status poll brings the count back
     launch_remove_features(f, nullptr, nullptr, false, false);
@@ -235,6 +268,7 @@ int ekfvio_remove_features(ekfvio_filter* f, const uint8_t* remove, int32_t coun
     const int rc = wait_status(f, &bad, f->remove_words + 1, &k);
     if (rc != EKFVIO_OK) return rc;
     remove_applied(f, -k, k);
+    ended_note_removal(f, k);
     if (removed) *removed = k;
     return EKFVIO_OK;
 }

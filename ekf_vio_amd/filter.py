@@ -26,7 +26,7 @@ class TightlyCoupledEKF:
     def __init__(self, max_features=100, device=0, stream=None, predict_mode=capi.PREDICT_STRUCTURED,
                  default_point_depth=0.5, default_point_depth_variance=100.0,
                  default_point_homogenous_variance=1e-5, hooks=False, gate_chi2=0.0, klt_fb_max_px=0.0, distortion=None, output_covariance=False,
-                 mask=None, mask_rectify_border=False, equalize=None, klt_photometric=False, **cfg_overrides):
+                 mask=None, mask_rectify_border=False, equalize=None, klt_photometric=False, ended_export=False, **cfg_overrides):
         # hooks=True: this handle lives in libekfvio_hip_hooks.so, the build that also has include/ekfvio_test_hooks.h (tests, profiling scripts)
         self.hooks = bool(hooks)
         self.lib = capi.load(hooks=self.hooks)
@@ -62,6 +62,8 @@ class TightlyCoupledEKF:
             self.setEqualize(*equalize)
         if klt_photometric:  # likewise (ekfvio_set_klt_photometric)
             self.setKltPhotometric(True)
+        if ended_export:  # likewise (ekfvio_set_ended_export)
+            self.setEndedExport(True)
 
     def _chk(self, rc, allow=()):
         if rc != capi.OK and rc not in allow:
@@ -164,6 +166,33 @@ class TightlyCoupledEKF:
             m = np.ascontiguousarray(np.asarray(mask).astype(bool), dtype=np.uint8).reshape(-1)
             self._chk(self.lib.ekfvio_remove_features(self.h, _u8(m), m.shape[0], C.byref(k)))
         return int(k.value)
+
+    def landmark_ids(self):
+        """Not in the reference, where a landmark's index is its identity: (ids int64[N], born float64[N]) of the landmarks, rows as points()'
+        and get_state()'s of the same moment (ekfvio_get_landmark_ids).  An id is never reused during the handle's lifetime, ids rise strictly
+        in landmark order, and born is the stamp of the frame a landmark entered in (NaN before any stamp)."""
+        N = self.num_features
+        ids, born = np.zeros(N, np.int64), np.zeros(N, np.float64)
+        self._chk(self.lib.ekfvio_get_landmark_ids(self.h, ids.ctypes.data_as(C.POINTER(C.c_int64)), born.ctypes.data_as(C.POINTER(C.c_double))))
+        return ids, born
+
+    def setEndedExport(self, on):
+        """Not in the reference: with it on, every removal (removeFeatures, addFrame with remove_lost=1) first writes one record per landmark
+        about to leave -- id, born, its row, its camera-frame point and that point's covariance (ekfvio_set_ended_export); ended() reads them."""
+        self._chk(self.lib.ekfvio_set_ended_export(self.h, int(on)))
+
+    def ended(self):
+        """ekfvio_get_ended: dict(id int64[k], born float64[k], index_before int32[k], xyz float32[k, 3], cov float32[k, 3, 3], count, total) of
+        the most recent removal call since the export went on (count 0 with it off).  Each removal overwrites the last one's records."""
+        cap = max(int(self.cfg.max_features), 1)
+        ids, born, idx = np.zeros(cap, np.int64), np.zeros(cap, np.float64), np.zeros(cap, np.int32)
+        xyz, cov = np.zeros((cap, 3), np.float32), np.zeros((cap, 3, 3), np.float32)
+        k, total = C.c_int32(0), C.c_int64(0)
+        self._chk(self.lib.ekfvio_get_ended(self.h, ids.ctypes.data_as(C.POINTER(C.c_int64)), born.ctypes.data_as(C.POINTER(C.c_double)),
+                                            idx.ctypes.data_as(C.POINTER(C.c_int32)), _fp(xyz), _fp(cov), cap, C.byref(k), C.byref(total)))
+        k = int(k.value)
+        return dict(id=ids[:k].copy(), born=born[:k].copy(), index_before=idx[:k].copy(), xyz=xyz[:k].copy(), cov=cov[:k].copy(), count=k,
+                    total=int(total.value))
 
     def setGate(self, chi2):
         """Not in the reference: the innovation gate (ekfvio_set_gate).  chi2 > 0: a landmark whose squared Mahalanobis distance on
@@ -573,7 +602,8 @@ class EKFVIO:
         # (distortion=(k1, k2, p1, p2[, k3]): raw frames are rectified on the device, setDistortion below; output_covariance=True: every frame's
         # outputs carry their covariances, setOutputCovariance below; mask=uint8 [h, w] and / or mask_rectify_border=True: the no-data mask, setMask below;
         # equalize=(clip_limit, tiles_x, tiles_y): every frame is equalised on the device before its pyramid, setEqualize below;
-        # klt_photometric=True: the tracker's gain/offset term, setKltPhotometric below)
+        # klt_photometric=True: the tracker's gain/offset term, setKltPhotometric below; ended_export=True: every removal hands out the records of
+        # the landmarks that leave, setEndedExport below)
         self.tc_ekf = TightlyCoupledEKF(**kw)
         self.tracker = KLTTracker(self.tc_ekf)
         self._imu_queue = []      # (stamp, gyro, accel), kept in stamp order; only used with use_imu = 1
@@ -610,6 +640,18 @@ class EKFVIO:
     def setKltPhotometric(self, on):
         """TightlyCoupledEKF.setKltPhotometric: from the next frame on the tracker matches up to a gain and an offset."""
         self.tc_ekf.setKltPhotometric(on)
+
+    def landmark_ids(self):
+        """TightlyCoupledEKF.landmark_ids: (ids int64[N], born float64[N]), rows as points()'; a memcpy behind a frame."""
+        return self.tc_ekf.landmark_ids()
+
+    def setEndedExport(self, on):
+        """TightlyCoupledEKF.setEndedExport: from the next frame on every removal hands out the records of the landmarks that leave."""
+        self.tc_ekf.setEndedExport(on)
+
+    def ended(self):
+        """TightlyCoupledEKF.ended: the records of the most recent removal; a consumer that wants every ended track reads it after every frame."""
+        return self.tc_ekf.ended()
 
     def setOutputCovariance(self, on):
         """TightlyCoupledEKF.setOutputCovariance: from the next frame on addFrame delivers the covariances with the frame's outputs."""

@@ -65,6 +65,10 @@ struct Params {
     // Not in the reference, whose Lucas-Kanade assumes brightness constancy: with klt_photometric = 1 the tracker matches up to a gain and an offset
     // (ekfvio_set_klt_photometric: span{1, I} projected out of the template's gradients, once per pyramid level); 0 = off.
     int klt_photometric = 0;
+    // Not in the reference, where a landmark's index is its identity: publish_ids = 1 adds a channel "id" to the node's PointCloud (the landmark's
+    // id of ekfvio_get_landmark_ids as a float: exact below 2^24, then id mod 2^24); publish_ended = 1 turns the export of the tracks that ended
+    // on (ekfvio_set_ended_export) and the node publishes their records as a second PointCloud on ended_topic.
+    int publish_ids = 0, publish_ended = 0;
     std::map<std::string, std::string> node;  // odom_topic, camera_topic, base_frame, use_imu, publish_insight, ...
 
     Params() {
@@ -74,7 +78,7 @@ struct Params {
                 {"analyze_runtime", "true"}, {"odom_topic", "invio/odom"}, {"odom_frame", "invio_odom"},
                 {"point_topic", "invio/points"}, {"camera_topic", "/camera/image_rect"}, {"base_frame", "base_link"},
                 {"world_frame", "world"}, {"camera_frame", "camera"}, {"imu_topic", "imu/measurement"},
-                {"imu_frame", "imu"}, {"use_imu", "true"}};
+                {"imu_frame", "imu"}, {"use_imu", "true"}, {"ended_topic", "invio/ended_points"}};
     }
 
     static double number(const std::string& key, const std::string& v) {
@@ -131,6 +135,8 @@ struct Params {
             klt_photometric = value == "true" ? 1 : (value == "false" ? 0 : integer(key, value));  // (a launch file's bool arrives as text)
             if (klt_photometric != 0 && klt_photometric != 1) throw Error(EKFVIO_EINVAL, "parameter klt_photometric: not 0 or 1: " + value);
         }
+        else if (key == "publish_ids") publish_ids = (value == "true" || value == "1") ? 1 : 0;
+        else if (key == "publish_ended") publish_ended = (value == "true" || value == "1") ? 1 : 0;
         else if (key == "distortion_k1") distortion[0] = number(key, value);
         else if (key == "distortion_k2") distortion[1] = number(key, value);
         else if (key == "distortion_p1") distortion[2] = number(key, value);
@@ -155,7 +161,7 @@ struct Params {
                                         "default_point_depth", "default_point_depth_variance",
                                         "default_point_homogenous_variance", "frame_buffer_size", "imu_update",
                                         "imu_gyro_variance", "imu_accel_variance", "gravity_x", "gravity_y", "gravity_z", "remove_lost", "gate_chi2",
-                                        "klt_fb_max_px", "rectify", "publish_covariance", "mask_rectify_border", "equalize_clip_limit", "equalize_tiles_x", "equalize_tiles_y", "klt_photometric", "distortion_k1", "distortion_k2", "distortion_p1", "distortion_p2", "distortion_k3"};
+                                        "klt_fb_max_px", "rectify", "publish_covariance", "mask_rectify_border", "equalize_clip_limit", "equalize_tiles_x", "equalize_tiles_y", "klt_photometric", "publish_ids", "publish_ended", "distortion_k1", "distortion_k2", "distortion_p1", "distortion_p2", "distortion_k3"};
         for (const auto& e : Params().node) out.push_back(e.first);
         for (const auto& e : ignored()) out.push_back(e.first);
         return out;
@@ -345,6 +351,39 @@ class TightlyCoupledEKF {
         chk(ekfvio_get_points_covariance(h_, out.empty() ? nullptr : out[0].data()));
         return out;
     }
+    // Not in the reference, where a landmark's index is its identity (it never removes one): the landmarks' ids and birth stamps, rows as the point
+    // cloud's of the same moment (ekfvio_get_landmark_ids).  An id is never reused during the handle's lifetime and ids rise strictly in landmark
+    // order; born is the stamp of the frame a landmark entered in (NaN before any stamp).  A memcpy behind a frame.
+    struct LandmarkIds {
+        std::vector<int64_t> id;
+        std::vector<double> born;
+    };
+    LandmarkIds getLandmarkIds() {
+        LandmarkIds r;
+        r.id.resize((size_t)numFeatures()), r.born.resize(r.id.size());
+        chk(ekfvio_get_landmark_ids(h_, r.id.empty() ? nullptr : r.id.data(), r.born.empty() ? nullptr : r.born.data()));
+        return r;
+    }
+    // Not in the reference: with the export on, every removal (removeFeatures, addFrame with cfg.remove_lost = 1) first writes one record per landmark
+    // about to leave (ekfvio_set_ended_export); getEnded reads the records of the most recent removal, so a consumer that wants every ended track
+    // reads them after every frame.  xyz and cov carry the bits getPoints / getPointsCovariance would have returned in front of the removal.
+    void setEndedExport(bool on) { chk(ekfvio_set_ended_export(h_, on ? 1 : 0)); }
+    struct Ended {
+        std::vector<int64_t> id;
+        std::vector<double> born;
+        std::vector<int32_t> index_before;        // the landmark's row in front of the removal (the rows of gate(), kltFb(), getMaskHits() of the frame)
+        std::vector<Vector3f> xyz;                // camera frame
+        std::vector<std::array<float, 9>> cov;    // row-major 3x3
+        int64_t total = 0;                        // records since create / reset
+    };
+    Ended getEnded() {
+        Ended r;
+        int32_t k = 0;
+        chk(ekfvio_get_ended(h_, nullptr, nullptr, nullptr, nullptr, nullptr, max_features_ > 0 ? max_features_ : 1, &k, &r.total));
+        r.id.resize((size_t)k), r.born.resize((size_t)k), r.index_before.resize((size_t)k), r.xyz.resize((size_t)k), r.cov.resize((size_t)k);
+        if (k > 0) chk(ekfvio_get_ended(h_, r.id.data(), r.born.data(), r.index_before.data(), r.xyz[0].data(), r.cov[0].data(), k, &k, &r.total));
+        return r;
+    }
     // Not in the reference (it flags lost landmarks, TightlyCoupledEKF.cpp:528, and keeps them): removes the landmarks whose byte
     // of `remove` is nonzero (one per landmark), or, with no mask, those flagged for deletion.  Returns the number removed.
     int removeFeatures(const std::vector<uint8_t>* remove = nullptr) {
@@ -498,6 +537,7 @@ class EKFVIO {
         if (p.mask_rectify_border) tc_ekf.setMask(nullptr, 0, 0, 0, EKFVIO_MASK_RECTIFY_BORDER);  // (likewise; live once the coefficients are nonzero)
         if (p.equalize_clip_limit > 0.f) tc_ekf.setEqualize(p.equalize_clip_limit, p.equalize_tiles_x, p.equalize_tiles_y);  // (likewise)
         if (p.klt_photometric) tc_ekf.setKltPhotometric(true);  // (likewise)
+        if (p.publish_ended) tc_ekf.setEndedExport(true);  // (likewise)
     }
     TightlyCoupledEKF tc_ekf;
     KLTTracker tracker;

@@ -7,7 +7,7 @@
 // Usage: ekfvio_replay [landmarks=256] [frames=300] [seed=0] [dt=0.0333333]
 //        ekfvio_replay --print-config [params.yaml]   (no GPU work: the node's parameter file -> ekfvio_config as JSON)
 //        ekfvio_replay --records <dir> [--out <dir>] [--params params.yaml] [--device n] [--insight] [--covariance]
-//                                [--equalize-clip-limit c] [--equalize-tiles-x n] [--equalize-tiles-y n]
+//                                [--equalize-clip-limit c] [--equalize-tiles-x n] [--equalize-tiles-y n] [--tracks FILE] [--ended FILE]
 //
 // --records replays what the node's two subscriptions deliver (EKFVIO.cpp:69-81) and writes what its two publishers
 // send (EKFVIO.cpp:444-518), with no ROS in between.  <dir>/records.txt holds one record per line, in arrival order:
@@ -23,7 +23,12 @@
 // prints, per frame, the diagonals of the pose and twist covariances the node would put into nav_msgs/Odometry:
 //     cov <stamp> <6 pose variances: x y z rotX rotY rotZ> <6 twist variances: linear, angular>
 // --equalize-clip-limit / --equalize-tiles-x / --equalize-tiles-y are the node parameters of the same names (ekfvio_set_equalize), applied
-// behind the parameter file.
+// behind the parameter file.  --tracks FILE writes one line per live landmark per frame, behind the frame,
+//     frame stamp id born x y z
+// (ekfvio_get_landmark_ids beside the cloud: one landmark's depth over time is the lines with its id).  --ended FILE turns the export of the
+// tracks that ended on (ekfvio_set_ended_export; the replay itself removes lost landmarks only with remove_lost: 1 in the parameter file) and
+// writes one line per ended record, read after every frame:
+//     frame stamp id born index_before x y z c00 c01 c02 c10 c11 c12 c20 c21 c22
 #include <cctype>
 #include <chrono>
 #include <cmath>
@@ -77,12 +82,12 @@ static int print_config(const char* path) {
                     "\"kill_pad\": %d, \"klt_min_eigen\": %.9g, \"min_new_feature_dist\": %d, \"klt_max_pyramid_level\": %d, "
                     "\"klt_window_size\": %d, \"default_point_depth\": %.9g, \"default_point_depth_variance\": %.9g, "
                     "\"default_point_homogenous_variance\": %.9g, \"sample_based_uncertainty\": %d, \"gate_chi2\": %.9g, "
-                    "\"klt_fb_max_px\": %.9g, \"rectify\": %d, \"publish_covariance\": %d, \"mask_rectify_border\": %d, \"equalize_clip_limit\": %.9g, \"equalize_tiles_x\": %d, \"equalize_tiles_y\": %d, \"klt_photometric\": %d, \"distortion\": [%.17g, %.17g, %.17g, %.17g, %.17g], \"node\": {",
+                    "\"klt_fb_max_px\": %.9g, \"rectify\": %d, \"publish_covariance\": %d, \"mask_rectify_border\": %d, \"equalize_clip_limit\": %.9g, \"equalize_tiles_x\": %d, \"equalize_tiles_y\": %d, \"klt_photometric\": %d, \"publish_ids\": %d, \"publish_ended\": %d, \"distortion\": [%.17g, %.17g, %.17g, %.17g, %.17g], \"node\": {",
                     c.max_features, c.fast_threshold, (double)c.fast_blur_sigma, c.inverse_image_scale, c.kill_pad,
                     (double)c.klt_min_eigen, c.min_new_feature_dist, c.klt_max_pyramid_level, c.klt_window_size,
                     (double)c.default_point_depth, (double)c.default_point_depth_variance,
                     (double)c.default_point_homogenous_variance, c.sample_based_uncertainty, (double)p.gate_chi2,
-                    (double)c.klt_fb_max_px, p.rectify, p.publish_covariance, p.mask_rectify_border, (double)p.equalize_clip_limit, p.equalize_tiles_x, p.equalize_tiles_y, p.klt_photometric, p.distortion[0], p.distortion[1], p.distortion[2], p.distortion[3], p.distortion[4]);
+                    (double)c.klt_fb_max_px, p.rectify, p.publish_covariance, p.mask_rectify_border, (double)p.equalize_clip_limit, p.equalize_tiles_x, p.equalize_tiles_y, p.klt_photometric, p.publish_ids, p.publish_ended, p.distortion[0], p.distortion[1], p.distortion[2], p.distortion[3], p.distortion[4]);
         bool first = true;
         for (const auto& e : p.node) {
             std::printf("%s\"%s\": \"%s\"", first ? "" : ", ", e.first.c_str(), e.second.c_str());
@@ -126,13 +131,14 @@ static bool read_pgm(const std::string& path, std::vector<uint8_t>& px, int& w, 
 }
 
 static int replay_records(const std::string& dir, const std::string& out_dir, const char* params_path, int device, bool insight, bool covariance,
-                          const std::vector<std::pair<std::string, std::string>>& overrides) {
+                          const std::vector<std::pair<std::string, std::string>>& overrides, const char* tracks_path, const char* ended_path) {
     try {
         ekfvio::Params p = params_path ? ekfvio::Params::fromFile(params_path) : ekfvio::Params();
         for (const auto& kv : overrides) p.set(kv.first, kv.second);
         if (!params_path) p.cfg.inverse_image_scale = 1;  // no parameter file: frames are used as recorded
         p.cfg.replenish = 1;                              // addFrame runs replenishFeatures itself (EKFVIO.cpp:154, :172)
         if (covariance) p.publish_covariance = 1;
+        if (ended_path) p.publish_ended = 1;
         std::ifstream rec(dir + "/records.txt");
         if (!rec) throw ekfvio::Error(EKFVIO_EINVAL, "cannot open " + dir + "/records.txt");
         // no image size anywhere: the device planes grow with the first frame that needs it (Frame::Frame takes any image)
@@ -141,6 +147,9 @@ static int replay_records(const std::string& dir, const std::string& out_dir, co
         FILE* fo = std::fopen((out_dir + "/odom.txt").c_str(), "w");
         FILE* fp = std::fopen((out_dir + "/points.txt").c_str(), "w");
         if (!fo || !fp) throw ekfvio::Error(EKFVIO_EINVAL, "cannot write into " + out_dir);
+        FILE* ft = tracks_path ? std::fopen(tracks_path, "w") : nullptr;
+        FILE* fe = ended_path ? std::fopen(ended_path, "w") : nullptr;
+        if ((tracks_path && !ft) || (ended_path && !fe)) throw ekfvio::Error(EKFVIO_EINVAL, "cannot write the tracks / ended file");
         std::string line;
         int images = 0, imus = 0, lineno = 0;
         const auto t0 = std::chrono::steady_clock::now();
@@ -180,6 +189,21 @@ static int replay_records(const std::string& dir, const std::string& out_dir, co
                 std::fprintf(fp, "cloud %.9f %zu\n", pc.stamp, pc.points.size());
                 for (size_t i = 0; i < pc.points.size(); i++)
                     std::fprintf(fp, "%.9g %.9g %.9g %.9g\n", pc.points[i][0], pc.points[i][1], pc.points[i][2], pc.intensity[i]);
+                if (ft) {  // the landmarks' identities beside the cloud: a memcpy behind the frame
+                    const ekfvio::TightlyCoupledEKF::LandmarkIds li = node.tc_ekf.getLandmarkIds();
+                    for (size_t i = 0; i < pc.points.size(); i++)
+                        std::fprintf(ft, "%d %.9f %lld %.9f %.9g %.9g %.9g\n", images, pc.stamp, (long long)li.id[i], li.born[i], pc.points[i][0],
+                                     pc.points[i][1], pc.points[i][2]);
+                }
+                if (fe) {  // the records of the landmarks this frame's removal took out
+                    const ekfvio::TightlyCoupledEKF::Ended en = node.tc_ekf.getEnded();
+                    for (size_t i = 0; i < en.id.size(); i++) {
+                        std::fprintf(fe, "%d %.9f %lld %.9f %d %.9g %.9g %.9g", images, pc.stamp, (long long)en.id[i], en.born[i], en.index_before[i],
+                                     en.xyz[i][0], en.xyz[i][1], en.xyz[i][2]);
+                        for (int c = 0; c < 9; c++) std::fprintf(fe, " %.9g", en.cov[i][c]);
+                        std::fprintf(fe, "\n");
+                    }
+                }
                 if (covariance) {  // what the node fills pose.covariance / twist.covariance from: a memcpy behind the frame
                     const ekfvio::TightlyCoupledEKF::OdometryCovariance oc = node.tc_ekf.getOdometryCovariance();
                     std::printf("cov %.9f", od.stamp);
@@ -206,6 +230,8 @@ static int replay_records(const std::string& dir, const std::string& out_dir, co
         }
         std::fclose(fo);
         std::fclose(fp);
+        if (ft) std::fclose(ft);
+        if (fe) std::fclose(fe);
         const double el = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
         std::printf("records: %d images, %d imu; %d landmarks; %.1f frames/s (file reading included)\n", images, imus,
                     node.tc_ekf.numFeatures(), images / el);
@@ -226,6 +252,7 @@ int main(int argc, char** argv) {
         const char* params = nullptr;
         int device = 0;
         bool insight = false, covariance = false;
+        const char *tracks = nullptr, *ended = nullptr;
         std::vector<std::pair<std::string, std::string>> overrides;  // options that are node parameters, by the parameter's name
         for (int i = 3; i < argc; i += 2) {
             if (std::strcmp(argv[i], "--insight") == 0 || std::strcmp(argv[i], "--covariance") == 0) {
@@ -240,6 +267,8 @@ int main(int argc, char** argv) {
             if (std::strcmp(argv[i], "--out") == 0) out = argv[i + 1];
             else if (std::strcmp(argv[i], "--params") == 0) params = argv[i + 1];
             else if (std::strcmp(argv[i], "--device") == 0) device = std::atoi(argv[i + 1]);
+            else if (std::strcmp(argv[i], "--tracks") == 0) tracks = argv[i + 1];
+            else if (std::strcmp(argv[i], "--ended") == 0) ended = argv[i + 1];
             else if (std::strcmp(argv[i], "--equalize-clip-limit") == 0) overrides.emplace_back("equalize_clip_limit", argv[i + 1]);
             else if (std::strcmp(argv[i], "--equalize-tiles-x") == 0) overrides.emplace_back("equalize_tiles_x", argv[i + 1]);
             else if (std::strcmp(argv[i], "--equalize-tiles-y") == 0) overrides.emplace_back("equalize_tiles_y", argv[i + 1]);
@@ -248,7 +277,7 @@ int main(int argc, char** argv) {
                 return 2;
             }
         }
-        return replay_records(dir, out, params, device, insight, covariance, overrides);
+        return replay_records(dir, out, params, device, insight, covariance, overrides, tracks, ended);
     }
     const int N = argc > 1 ? std::atoi(argv[1]) : 256;
     const int frames = argc > 2 ? std::atoi(argv[2]) : 300;

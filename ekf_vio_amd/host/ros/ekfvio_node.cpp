@@ -105,7 +105,11 @@ class EkfvioNode {
         // false: with it, and rectify = 1, the black border that rectification leaves is no-data for the detector and the tracker, ekfvio_set_mask;
         // equalize_clip_limit, default 0 = off, with equalize_tiles_x / equalize_tiles_y, default 8: every frame is equalised on the device in front
         // of its pyramid, ekfvio_set_equalize; klt_photometric, default 0 = off: the tracker matches up to a gain and an offset,
-        // ekfvio_set_klt_photometric)
+        // ekfvio_set_klt_photometric; publish_ids, default false: the PointCloud gets a second channel "id" with every landmark's id as a float --
+        // exact below 2^24 = 16 777 216, beyond that id mod 2^24, so that equal floats within one cloud still mean one landmark;
+        // publish_ended, default false: the handle is told to export the tracks that ended, ekfvio_set_ended_export, and their records go out
+        // behind every frame as a second PointCloud on ended_topic, default invio/ended_points, with the channels "id", "born" (seconds before
+        // the message's stamp: a float cannot hold a ROS stamp), "index_before" and the nine covariance entries "c00" .. "c22")
         for (const std::string& name : ekfvio::Params::names()) {
             XmlRpc::XmlRpcValue v;
             if (ros::param::get("~" + name, v)) params_.set(name, to_text(v));
@@ -125,6 +129,7 @@ class EkfvioNode {
             imu_sub_ = nh_.subscribe(p.at("imu_topic"), 1000, &EkfvioNode::imuCallback, this);
         odom_pub_ = nh_.advertise<nav_msgs::Odometry>(p.at("odom_topic"), 1);
         points_pub_ = nh_.advertise<sensor_msgs::PointCloud>(p.at("point_topic"), 1);
+        if (params_.publish_ended) ended_pub_ = nh_.advertise<sensor_msgs::PointCloud>(p.at("ended_topic"), 10);
     }
 
     // EKFVIO.cpp:87-107: wait up to 10 s for base -> camera, else shut down
@@ -194,6 +199,7 @@ class EkfvioNode {
         if (publish_insight_) publishInsight(img->header.stamp);
         publishOdometry(img->header.stamp);
         publishPoints(img->header.stamp);
+        if (params_.publish_ended) publishEnded(img->header.stamp, f.t);
         const double ms = (ros::WallTime::now() - start).toSec() * 1e3;
         dt_sum_ += ms;
         ROS_INFO_STREAM("average dt: " << dt_sum_ / ++dt_count_ << " this dt: " << ms);  // EKFVIO.cpp:132-136
@@ -250,7 +256,45 @@ class EkfvioNode {
         }
         ch.values = pc.intensity;
         msg.channels.push_back(ch);
+        if (params_.publish_ids) {  // rows of the ids are the rows of the cloud: both arrived with the frame's outputs
+            const ekfvio::TightlyCoupledEKF::LandmarkIds li = vio_->tc_ekf.getLandmarkIds();
+            sensor_msgs::ChannelFloat32 ids;
+            ids.name = "id";
+            ids.values.resize(li.id.size());
+            for (size_t i = 0; i < li.id.size(); i++) ids.values[i] = id_as_float(li.id[i]);
+            msg.channels.push_back(ids);
+        }
         points_pub_.publish(msg);
+    }
+
+    // a float holds every integer below 2^24 exactly
+    static float id_as_float(int64_t id) { return (float)(id % (int64_t(1) << 24)); }
+
+    // The landmarks the frame's removal took out (remove_lost = 1), each with the last estimate the filter had of it: a sparse map point.
+    // Nothing is published for a frame in which no track ended.
+    void publishEnded(const ros::Time& stamp, double t) {
+        const ekfvio::TightlyCoupledEKF::Ended en = vio_->tc_ekf.getEnded();
+        if (en.id.empty()) return;
+        static const char* const names[12] = {"id", "born", "index_before", "c00", "c01", "c02", "c10", "c11", "c12", "c20", "c21", "c22"};
+        sensor_msgs::PointCloud msg;
+        msg.header.stamp = stamp;
+        msg.header.frame_id = params_.node.at("odom_frame");
+        msg.points.resize(en.id.size());
+        msg.channels.resize(12);
+        for (int c = 0; c < 12; c++) {
+            msg.channels[c].name = names[c];
+            msg.channels[c].values.resize(en.id.size());
+        }
+        for (size_t i = 0; i < en.id.size(); i++) {
+            msg.points[i].x = en.xyz[i][0];
+            msg.points[i].y = en.xyz[i][1];
+            msg.points[i].z = en.xyz[i][2];
+            msg.channels[0].values[i] = id_as_float(en.id[i]);
+            msg.channels[1].values[i] = (float)(t - en.born[i]);  // the track's age in seconds
+            msg.channels[2].values[i] = (float)en.index_before[i];
+            for (int c = 0; c < 9; c++) msg.channels[3 + c].values[i] = en.cov[i][c];
+        }
+        ended_pub_.publish(msg);
     }
 
     // EKFVIO.cpp:379-442: the resized frame as BGR8 with a green square marker at every landmark that is not flagged for
@@ -280,7 +324,7 @@ class EkfvioNode {
     image_transport::ImageTransport it_;
     image_transport::CameraSubscriber cam_sub_;
     ros::Subscriber imu_sub_;
-    ros::Publisher insight_pub_, insight_cinfo_pub_, odom_pub_, points_pub_;
+    ros::Publisher insight_pub_, insight_cinfo_pub_, odom_pub_, points_pub_, ended_pub_;
     tf::TransformListener tf_listener_;
     tf::TransformBroadcaster br_;
     tf::Transform b2c_;

@@ -118,7 +118,10 @@ EKFVIO_API int ekfvio_destroy(ekfvio_filter* f);
 /* initializeBaseState(): back to mu = [0,0,0,1,0...], Sigma diag [0x7,30x9,0.5x6], no landmarks.  (The innovation gate's counts start
  * over; its threshold stays.  The same holds for the tracker's forward-backward check.  The distortion coefficients of
  * ekfvio_set_distortion stay too, and so does the setting of ekfvio_set_output_covariance.  The mask of ekfvio_set_mask stays as well, and the setting of ekfvio_set_equalize.
- * So does the tracker's gain/offset term, ekfvio_set_klt_photometric.) */
+ * So does the tracker's gain/offset term, ekfvio_set_klt_photometric.)
+ * (The landmark id counter does NOT start over: the first landmark behind a reset gets an id above every id the handle has handed out,
+ * so a consumer never sees two points under one id.  The setting of ekfvio_set_ended_export stays; its report is empty and its total
+ * starts over, as the gate's.) */
 EKFVIO_API int ekfvio_reset(ekfvio_filter* f);
 EKFVIO_API const char* ekfvio_last_error(const ekfvio_filter* f);
 
@@ -182,6 +185,58 @@ EKFVIO_API int ekfvio_set_state(ekfvio_filter* f, int32_t n_features, const floa
  * remove == NULL: the landmarks flagged for deletion (the tracker lost them, TightlyCoupledEKF.cpp:528) are removed.
  * *removed (may be NULL) receives the number removed.  Not in the reference, which flags but never removes. */
 EKFVIO_API int ekfvio_remove_features(ekfvio_filter* f, const uint8_t* remove, int32_t count, int32_t* removed);
+
+/* ---- landmark identities and the tracks that ended (not in the reference, which never removes a landmark, so that a landmark's index
+ * is its identity there) ---------------------------------------------------------------------------------------------------------------
+ * A removal compacts the state: row i of ekfvio_get_points, ekfvio_get_points_covariance, ekfvio_get_features, ekfvio_get_gate,
+ * ekfvio_get_klt_fb and ekfvio_get_mask_hits names another physical point from one frame to the next.  Two arrays travel with the state on
+ * the device, through the kernels that move it, and say which (always on, no setting):
+ *
+ *     id    int64.  The handle keeps a counter next_id, 0 at ekfvio_create.  The k-th landmark a call appends (k = 0, 1, ...) gets
+ *           next_id + k, and next_id advances by the number appended where the landmark count does: at the end of ekfvio_add_features,
+ *           ekfvio_replenish and ekfvio_set_state, and in ekfvio_step_image with the frame's status word (a frame that returns an error
+ *           without counting its new landmarks in does not advance it either: those ids were never visible).  ekfvio_set_state replaces
+ *           the landmark set: all n_features landmarks get fresh ids, in order.  An id is never reused during the handle's lifetime;
+ *           the counter does not start over at ekfvio_reset.
+ *     born  double.  The stamp of the ekfvio_step_image call in which the landmark entered; for ekfvio_add_features, ekfvio_replenish and
+ *           ekfvio_set_state outside a frame the handle's current time (the stamp of the last frame or IMU record), NaN before any stamp.
+ *
+ * A removal keeps the order of the rest and new landmarks are appended, so id is STRICTLY INCREASING in landmark order at all times: a
+ * consumer associates two frames' clouds with one merge pass.  Nothing but an append, a removal and ekfvio_set_state touches either array:
+ * process(dt), the updates and ekfvio_run_uploaded leave them alone (the measurement streams of ekfvio_run_uploaded carry no ids).
+ *
+ * ekfvio_get_landmark_ids: room for ekfvio_num_features entries each; either pointer may be NULL.  Rows are the rows of ekfvio_get_points
+ * of the same moment.  Behind ekfvio_step_image both arrays arrive with the frame's other outputs and the call is a memcpy until the state
+ * changes; otherwise it is a device-to-host copy on the handle's stream and a wait, as ekfvio_get_features. */
+EKFVIO_API int ekfvio_get_landmark_ids(ekfvio_filter* f, int64_t* idN, double* bornN);
+/* The tracks that ended.  A landmark that leaves the state takes a 3-D estimate and a covariance with it that the filter has paid for; the
+ * removal is the only moment a sparse map point can be handed out.  With the setting on, every removal that is launched --
+ * ekfvio_remove_features with a mask or with NULL, ekfvio_step_image with cfg.remove_lost = 1 -- is preceded on the stream by one launch
+ * that reads the removal's own decision and writes one record per landmark about to leave, in landmark order:
+ *
+ *     id (int64)   born (double)   index_before (int32: the landmark's row in front of this removal -- the row numbering that ekfvio_get_gate,
+ *                                  ekfvio_get_klt_fb and ekfvio_get_mask_hits of the same frame use; the caller joins them for a reason)
+ *     xyz[3]       the camera-frame point, by the lines of ekfvio_get_points
+ *     cov[9]       its covariance, row-major 3x3, by the lines of ekfvio_get_points_covariance
+ *
+ * from the mean and Sigma as they stand in front of the removal (in a frame: behind the update's last GEMM and behind the replenishment).
+ * xyz and cov are, bit for bit, what the two getters would have returned for that row had they been called in front of the removal: the
+ * device compiles one statement of that arithmetic for all of them.  Behind an aborted persistent sweep a frame's removal removes nothing,
+ * and nothing ends.  Out of scope: a reason code per record, world-frame points (the frame's odometry is in the same output block), removal
+ * or lookup by id, observation counts.
+ *
+ * on: 0 or 1, anything else EKFVIO_EINVAL.  A property of the handle: it holds from the next removal, survives ekfvio_reset and drops no
+ * captured graph.  Off by default (then no launch differs, nothing is allocated and every output keeps its bits); on, it costs one launch of
+ * one workgroup per removal and 68 bytes of pinned host memory per landmark of max_features, taken when it is first turned on (the kernel writes
+ * the records there, and ekfvio_get_ended is a memcpy). */
+EKFVIO_API int ekfvio_set_ended_export(ekfvio_filter* f, int32_t on);
+/* The records of the MOST RECENT removal call since the setting was turned on (any pointer may be NULL; the arrays need room for *count
+ * records).  *count = the host-known removed count of that call; a removal call that removes nothing -- an explicit mask of zeros, NULL with
+ * nothing flagged, a frame with no landmark, an aborted sweep -- reports 0, and so does a handle with the setting off.  cap < *count:
+ * EKFVIO_EINVAL, with *count and *total still set.  *total = records since create or the last ekfvio_reset.  Each removal overwrites the
+ * last one's records: a consumer that wants every ended track reads them after every frame (and after every ekfvio_remove_features). */
+EKFVIO_API int ekfvio_get_ended(ekfvio_filter* f, int64_t* id, double* born, int32_t* index_before, float* xyz3, float* cov9, int32_t cap,
+                                int32_t* count, int64_t* total);
 
 /* ---- innovation gate (not in the reference: its Params.h has an "OUTLIER DETECTION" section whose thresholds nothing reads) ---------
  * A chi-square test per landmark, evaluated on the device on the propagated state in front of the update's measurement bookkeeping
