@@ -54,7 +54,8 @@ MASK_RECTIFY_BORDER = 1  # EKFVIO_MASK_RECTIFY_BORDER
 # every symbol include/ekfvio_test_hooks.h declares (libekfvio_hip_hooks.so only)
 HOOK_SYMBOLS = ["ekfvio_test_klt_padded_level", "ekfvio_test_blurred_level0", "ekfvio_test_gemm", "ekfvio_test_gemm_bench", "ekfvio_test_potrf_stamps",
                 "ekfvio_test_sweep_stamps", "ekfvio_test_sweep_fault", "ekfvio_test_sweep_delay", "ekfvio_test_cholesky_solve", "ekfvio_test_plan", "ekfvio_test_persist_grid", "ekfvio_test_t2_pair",
-                "ekfvio_test_gemm_plan", "ekfvio_test_predict_plan", "ekfvio_test_run_plan", "ekfvio_test_mem", "ekfvio_test_mem_fail"]
+                "ekfvio_test_gemm_plan", "ekfvio_test_predict_plan", "ekfvio_test_run_plan", "ekfvio_test_mem", "ekfvio_test_mem_fail",
+                "ekfvio_test_fill_update_scratch"]
 
 _libs = {}
 
@@ -136,6 +137,7 @@ def load(build_if_missing=True, hooks=False):
             "ekfvio_test_run_plan": [i32] * 4 + [ip, i32, ip],  # ... and plan_run
             "ekfvio_test_mem": [vp, C.POINTER(C.c_int64)],  # csrc/mem.h: what a handle's ledger holds (None: the whole library copy)
             "ekfvio_test_mem_fail": [vp, i32],
+            "ekfvio_test_fill_update_scratch": [vp, C.c_uint32],  # a word into the update's float work buffers: a handle with a history
         })
     for name, args in sig.items():
         fn = getattr(lib, name)

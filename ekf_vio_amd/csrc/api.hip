@@ -1329,6 +1329,26 @@ int ekfvio_test_t2_pair(int32_t p, int32_t pair[2]) {
     pair[0] = ta, pair[1] = tb;
     return EKFVIO_OK;
 }
+
+// `word` into every 32-bit element of the float buffers process(dt) and the update use as scratch, on the handle's stream: what a long-lived
+// handle finds there is then no longer the zero fill of dev_alloc.  The state (P, P2, mu and the landmark bookkeeping), the measurement inputs,
+// the sweep's flags and every integer buffer (idx, inv_idx, Lsign, info) are left alone: a garbage index would send a load out of its
+// allocation.  None of the regions filled is written once at create and only read later ("Who owns the update's work buffers"), so
+// nothing is put back here.
+int ekfvio_test_fill_update_scratch(ekfvio_filter* f, uint32_t word) {
+    if (!f) return EKFVIO_EINVAL;
+    HIP_TRY(f, hipSetDevice(f->device));
+    const size_t maxf = (size_t)(f->cfg.max_features > 0 ? f->cfg.max_features : 0);
+    const size_t aug = (size_t)f->ld_aug * f->m_cap, pm = (size_t)f->ldp * f->m_cap;
+    const struct { float* p; size_t count; } regions[] = {
+        {f->Saug, aug}, {f->Laug, aug}, {f->Linv, 64 * (size_t)f->m_cap}, {f->Km, pm}, {f->Wt, pm}, {f->Gm, pm},
+        {f->yres, (size_t)f->m_cap}, {f->Rm, 2 * (size_t)f->m_cap}, {f->Fdense, (size_t)f->ldp * f->ldp},
+        {f->FA, (size_t)EKF_BASE * EKF_BASE}, {f->FB, 27 * maxf}, {f->FD, 9 * maxf}, {f->mu_next, (size_t)f->ldp},
+    };
+    for (const auto& r : regions)
+        if (r.p && r.count) HIP_TRY(f, hipMemsetD32Async((hipDeviceptr_t)r.p, (int)word, r.count, f->stream));
+    return EKFVIO_OK;
+}
 #endif  // EKFVIO_TEST_HOOKS
 
 }  // extern "C"

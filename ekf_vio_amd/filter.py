@@ -420,6 +420,12 @@ class TightlyCoupledEKF:
         self._need_hooks()
         self._chk(self.lib.ekfvio_test_sweep_delay(self.h, int(workgroup), int(point), int(ticks)))
 
+    def fill_update_scratch(self, word):
+        """The 32-bit pattern `word` into every element of the float work buffers of process(dt) and the update
+        (ekfvio_test_fill_update_scratch; hooks build).  The state, the inputs, the sweep's flags and the integer buffers stay."""
+        self._need_hooks()
+        self._chk(self.lib.ekfvio_test_fill_update_scratch(self.h, int(word) & 0xFFFFFFFF))
+
     def test_cholesky_solve(self, S, Crhs):
         """Returns (L, X = Crhs @ inv(S), info).  (hooks build)"""
         self._need_hooks()

@@ -80,6 +80,14 @@ EKFVIO_API int ekfvio_test_mem(ekfvio_filter* f, int64_t out[8]);
 /* Failure injection for the ledger: the handle's nth acquisition from now reports out-of-memory WITHOUT calling the runtime, once; 0 disarms.
  * f == NULL arms the ledger of the next ekfvio_create of this copy of the library. */
 EKFVIO_API int ekfvio_test_mem_fail(ekfvio_filter* f, int32_t nth);
+/* History of a handle (NOT fault injection): writes `word` into every 32-bit element of the floating-point buffers that process(dt) and the
+ * update use as scratch -- Saug, Laug, Linv, Km, Wt, Gm, yres, Rm, the dense-F / T2 buffer, FA, FB, FD and mu_next -- on the handle's stream,
+ * so that an update no longer finds the zero fill of a fresh handle there.  An update's result must not depend on `word`.  Left alone: the
+ * state and its padding (P, P2, mu, the landmark bookkeeping), the measurement inputs, the persistent sweep's flag words and every integer
+ * buffer (idx, inv_idx, Lsign, info).  No filled region is written at create and only read afterwards, so none is restored ("Who
+ * owns the update's work buffers").  mu_next and mu swap roles with every process(dt): the entries of a filled mu_next from 22 + 3N on become
+ * mu's padding, which nothing reads.  Call it between entry points, not inside a device-resident run. */
+EKFVIO_API int ekfvio_test_fill_update_scratch(ekfvio_filter* f, uint32_t word);
 
 #ifdef __cplusplus
 }

@@ -20,8 +20,6 @@ neighbour's R, a pass mask off by one landmark) move the fp64 answer by at least
 
 Each handle is closed before the next is created (a second live handle moves every update to the per-step sweep).
 """
-import functools
-
 import numpy as np
 import pytest
 
@@ -30,10 +28,10 @@ from ekf_vio_amd.sim import Scenario
 from oracle import OracleFilter, set_threads
 
 import _update_cases as U
+from _update_run import check_against_oracles, hip_update, run_case  # (shared with tests/test_gpu_update_history.py)
 
 pytestmark = pytest.mark.gpu
 
-KEYS = ("base_mu", "feat_mu", "last_klt", "del_flag", "Sigma")
 RAN = {}  # case -> the flow signature observed, for the closing test
 
 
@@ -43,54 +41,6 @@ def oracle_threads():
     U.use_threads()
     yield
     set_threads(1)
-
-
-def hip_update(cap, st0, sp, dt, z, R, p, device_sized):
-    """process(dt) (bit-equal to the fp32 oracle's `sp`) and the update on a handle of its own.  Returns (rc, state, gate, signature)."""
-    g = TightlyCoupledEKF(max_features=cap)
-    try:
-        g.set_state(st0)
-        if device_sized:
-            g.setGate(U.FLT_MAX)
-        g.process(dt)
-        got = g.get_state()
-        for key in KEYS:
-            assert np.array_equal(got[key], sp[key]), ("process(dt) against the fp32 oracle", key)
-        g.profile(1)
-        c0 = g.counters()
-        rc = g.updateWithFeaturePositions(z, R, p)
-        c1, rep = g.counters(), g.profile_report()
-        g.profile(0)
-        sig = (c1["persistent"] - c0["persistent"], rep["solve"]["launches"], rep["gemm_update"]["launches"],
-               c1["t2_updates"] - c0["t2_updates"])
-        return rc, g.get_state(), (g.gate() if device_sized else None), sig
-    finally:
-        g.close()
-
-
-@functools.lru_cache(maxsize=None)
-def run_case(case):
-    N, cap, k, layout, sizing, kind = case
-    dt, st0, sp, z, R, p = U.inputs(N, k, layout, kind)
-    return hip_update(cap, st0, sp, dt, z, R, p, sizing == "device")
-
-
-def check_against_oracles(what, sp, z, p, rc, got, ref):
-    """Section 2 of the module docstring for one result; prints each figure before it asserts."""
-    s64 = ref["s64"]
-    assert np.array_equal(got["del_flag"], ref["del_flag32"]) and np.array_equal(got["last_klt"], ref["last_klt32"]), what
-    assert (rc == capi.OK) == (ref["info32"] == 0) and rc in (capi.OK, capi.ENUMERIC), (what, rc, ref["info32"])
-    assert abs(np.linalg.norm(got["base_mu"][3:7].astype(np.float64)) - 1) < 1e-6, what
-    assert np.isfinite(got["Sigma"]).all() and np.isfinite(got["feat_mu"]).all() and np.isfinite(got["base_mu"]).all(), what
-    err, tol = U.errors(got, s64), U.tolerances(s64, ref["scatter"])
-    print("%s: %s" % (what, "  ".join("%s %.3g of %.3g" % (key, err[key], tol[key]) for key in tol)))
-    for key in tol:
-        assert err[key] <= tol[key], (what, key, err[key], tol[key], ref["scatter"])
-    # every measured landmark moves towards its measurement, where the fp64 evaluation says it does
-    in64 = U.moves_towards_z(sp, s64, z, p)
-    assert (~in64).sum() <= 0.05 * p.sum(), (what, "the inputs do not support this check", np.nonzero(~in64)[0])
-    bad = np.nonzero(in64 & ~U.moves_towards_z(sp, got, z, p))[0]
-    assert bad.size == 0, (what, "landmarks that moved away from their measurement", bad[:16], "state rows", U.BASE + 3 * bad[:16])
 
 
 @pytest.mark.parametrize("case", U.CASES, ids=U.case_id)
