@@ -49,13 +49,14 @@ SYMBOLS = ["ekfvio_default_config", "ekfvio_create", "ekfvio_destroy", "ekfvio_r
            "ekfvio_set_output_covariance", "ekfvio_get_odometry_covariance", "ekfvio_get_points_covariance", "ekfvio_rotation_error_jacobian",
            "ekfvio_set_mask", "ekfvio_get_mask", "ekfvio_get_mask_hits", "ekfvio_mask_blocked", "ekfvio_set_equalize", "ekfvio_equalize",
            "ekfvio_set_klt_photometric", "ekfvio_klt_project_gradients",
-           "ekfvio_get_landmark_ids", "ekfvio_set_ended_export", "ekfvio_get_ended"]
+           "ekfvio_get_landmark_ids", "ekfvio_set_ended_export", "ekfvio_get_ended",
+           "ekfvio_set_zupt", "ekfvio_zupt_update", "ekfvio_get_zupt", "ekfvio_zupt_decide"]
 MASK_RECTIFY_BORDER = 1  # EKFVIO_MASK_RECTIFY_BORDER
 # every symbol include/ekfvio_test_hooks.h declares (libekfvio_hip_hooks.so only)
 HOOK_SYMBOLS = ["ekfvio_test_klt_padded_level", "ekfvio_test_blurred_level0", "ekfvio_test_gemm", "ekfvio_test_gemm_bench", "ekfvio_test_potrf_stamps",
                 "ekfvio_test_sweep_stamps", "ekfvio_test_sweep_fault", "ekfvio_test_sweep_delay", "ekfvio_test_cholesky_solve", "ekfvio_test_plan", "ekfvio_test_persist_grid", "ekfvio_test_t2_pair",
                 "ekfvio_test_gemm_plan", "ekfvio_test_predict_plan", "ekfvio_test_run_plan", "ekfvio_test_mem", "ekfvio_test_mem_fail",
-                "ekfvio_test_fill_update_scratch"]
+                "ekfvio_test_fill_update_scratch", "ekfvio_test_zupt_decide"]
 
 _libs = {}
 
@@ -117,6 +118,9 @@ def load(build_if_missing=True, hooks=False):
         "ekfvio_get_landmark_ids": [vp, C.POINTER(C.c_int64), C.POINTER(C.c_double)],
         "ekfvio_set_ended_export": [vp, i32],
         "ekfvio_get_ended": [vp, C.POINTER(C.c_int64), C.POINTER(C.c_double), ip, fp, fp, i32, ip, C.POINTER(C.c_int64)],
+        "ekfvio_set_zupt": [vp, f32, i32, f32, f32, f32], "ekfvio_zupt_update": [vp, f32, f32],
+        "ekfvio_get_zupt": [vp, fp, ip, ip, ip, ip, C.POINTER(C.c_int64)],
+        "ekfvio_zupt_decide": [fp, fp, u8p, i32, f32, i32, f32, fp, ip, ip, ip],  # no handle, no device
     }
     if hooks:
         sig.update({
@@ -138,6 +142,7 @@ def load(build_if_missing=True, hooks=False):
             "ekfvio_test_mem": [vp, C.POINTER(C.c_int64)],  # csrc/mem.h: what a handle's ledger holds (None: the whole library copy)
             "ekfvio_test_mem_fail": [vp, i32],
             "ekfvio_test_fill_update_scratch": [vp, C.c_uint32],  # a word into the update's float work buffers: a handle with a history
+            "ekfvio_test_zupt_decide": [vp, fp, fp, u8p, i32, f32, i32, f32, fp, ip, ip, ip],  # the device's zero-velocity decision on arbitrary points
         })
     for name, args in sig.items():
         fn = getattr(lib, name)

@@ -386,6 +386,8 @@ int ekfvio_reset(ekfvio_filter* f) {
     f->mask_hits_n = 0;  // the mask's hits of the last track go with the landmarks; the mask itself stays (ekfvio_set_mask)
     // next_id goes on: no two landmarks of a handle's lifetime share an id.  The ended tracks' report and total start over; the setting stays
     f->ended_count = 0, f->ended_total = 0;
+    // ... and so do the zero-velocity update's report and total (ekfvio_set_zupt)
+    f->zupt_n = f->zupt_pass = f->zupt_still = f->zupt_applied_last = 0, f->zupt_applied_total = 0;
     return EKFVIO_OK;
 }
 

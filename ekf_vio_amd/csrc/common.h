@@ -232,6 +232,16 @@ struct ekfvio_filter {
     int* ended_index = nullptr;   // the landmark's row in front of the removal
     int ended_count = 0;          // records of the most recent removal call since the setting went on (the host-known removed count)
     int64_t ended_total = 0;      // since create / reset
+    // --- zero-velocity update (ekfvio_set_zupt; zupt.hip): the decision from the tracker's results and the update on state rows 7..12 ---
+    float zupt_max_flow_px = 0.f;  // > 0: ekfvio_step_image decides behind the tracker and updates in front of the camera update; 0: off
+    int zupt_min_tracks = 0;
+    float zupt_min_ratio = 0.f, zupt_vel_var = 0.f, zupt_omega_var = 0.f;
+    // (memory: made by the first ekfvio_set_zupt that turns the setting on)
+    int* zupt_words = nullptr;     // [4] device words: stationary, n_pass, n_still, landmarks seen (the Joseph kernel reads the first)
+    int* h_zupt = nullptr;         // pinned, device-mapped: the same four words, then flow2[max_features] as floats
+    int* d_hzupt = nullptr;        // the device's address of h_zupt
+    int zupt_n = 0, zupt_pass = 0, zupt_still = 0, zupt_applied_last = 0;  // the most recent frame's decision as the host read it with the status word
+    int64_t zupt_applied_total = 0;  // since create / reset
     int* remove_words = nullptr;  // [4] device words of the removal kernel (remove.hip): [0] landmarks added - removed, [1] removed, [2] its ticket
     int* h_info = nullptr;     // pinned, device-mapped: the words of enum HostWord
     int* d_hinfo = nullptr;    // the device's address of h_info
@@ -496,6 +506,10 @@ int push_frame_enqueue(ekfvio_filter* f, const uint8_t* image, int32_t width, in
 int klt_track_device(ekfvio_filter* f);  // the tracker over the current landmarks; results in f->zmeas / Rmeas / pass (device)
 // imu.hip
 void launch_imu_update(ekfvio_filter* f, const float gyro[3], const float accel[3]);
+// zupt.hip: the frame's zero-velocity decision and update, enqueued behind the tracker (setting on, N > 0), and the host's end of it behind
+// the frame's status word (decided: launch_zupt_frame ran in this frame)
+void launch_zupt_frame(ekfvio_filter* f);
+void zupt_note_frame(ekfvio_filter* f, bool decided);
 // fast.hip
 int fast_alloc(ekfvio_filter* f);
 int fast_ensure(ekfvio_filter* f, int w, int h);  // grows the detector's per-pixel buffers to a w x h level 0 (synchronises if it must)

@@ -26,7 +26,8 @@ class TightlyCoupledEKF:
     def __init__(self, max_features=100, device=0, stream=None, predict_mode=capi.PREDICT_STRUCTURED,
                  default_point_depth=0.5, default_point_depth_variance=100.0,
                  default_point_homogenous_variance=1e-5, hooks=False, gate_chi2=0.0, klt_fb_max_px=0.0, distortion=None, output_covariance=False,
-                 mask=None, mask_rectify_border=False, equalize=None, klt_photometric=False, ended_export=False, **cfg_overrides):
+                 mask=None, mask_rectify_border=False, equalize=None, klt_photometric=False, ended_export=False, zupt=None,
+                 **cfg_overrides):
         # hooks=True: this handle lives in libekfvio_hip_hooks.so, the build that also has include/ekfvio_test_hooks.h (tests, profiling scripts)
         self.hooks = bool(hooks)
         self.lib = capi.load(hooks=self.hooks)
@@ -64,6 +65,8 @@ class TightlyCoupledEKF:
             self.setKltPhotometric(True)
         if ended_export:  # likewise (ekfvio_set_ended_export)
             self.setEndedExport(True)
+        if zupt is not None:  # likewise (ekfvio_set_zupt)
+            self.setZupt(*zupt)
 
     def _chk(self, rc, allow=()):
         if rc != capi.OK and rc not in allow:
@@ -154,6 +157,25 @@ class TightlyCoupledEKF:
         g = np.ascontiguousarray(gyro, dtype=np.float32)
         a = np.ascontiguousarray(accel, dtype=np.float32)
         self._chk(self.lib.ekfvio_imu_update(self.h, _fp(g), _fp(a)))
+
+    def setZupt(self, max_flow_px, min_tracks=8, min_ratio=0.75, vel_variance=1e-4, omega_variance=1e-4):
+        """Not in the reference: the zero-velocity update (ekfvio_set_zupt).  max_flow_px > 0: a frame of addFrame in which at least min_tracks
+        landmarks passed the tracker and at least min_ratio of those moved no more than max_flow_px pixels is taken as standing still, and
+        z = 0 on the velocity and the body rate (with these variances) updates the propagated state in front of the camera update; 0: off."""
+        self._chk(self.lib.ekfvio_set_zupt(self.h, float(max_flow_px), int(min_tracks), float(min_ratio), float(vel_variance), float(omega_variance)))
+
+    def zuptUpdate(self, vel_variance=1e-4, omega_variance=1e-4):
+        """ekfvio_zupt_update: that update alone, unconditional (a caller with its own stop detector); asynchronous."""
+        self._chk(self.lib.ekfvio_zupt_update(self.h, float(vel_variance), float(omega_variance)))
+
+    def zupt(self):
+        """ekfvio_get_zupt: dict(flow2[n], n_landmarks, n_pass, n_still, applied_last, applied_total) of the most recent frame's decision."""
+        cap = max(int(self.cfg.max_features), 1)
+        flow2 = np.zeros(cap, np.float32)
+        n, npass, nstill, last, total = C.c_int32(0), C.c_int32(0), C.c_int32(0), C.c_int32(0), C.c_int64(0)
+        self._chk(self.lib.ekfvio_get_zupt(self.h, _fp(flow2), C.byref(n), C.byref(npass), C.byref(nstill), C.byref(last), C.byref(total)))
+        return dict(flow2=flow2[:n.value].copy(), n_landmarks=int(n.value), n_pass=int(npass.value), n_still=int(nstill.value),
+                    applied_last=int(last.value), applied_total=int(total.value))
 
     def removeFeatures(self, mask=None):
         """Not in the reference, which flags a lost landmark (TightlyCoupledEKF.cpp:528) and keeps it: removes landmarks from the
@@ -609,7 +631,8 @@ class EKFVIO:
         # outputs carry their covariances, setOutputCovariance below; mask=uint8 [h, w] and / or mask_rectify_border=True: the no-data mask, setMask below;
         # equalize=(clip_limit, tiles_x, tiles_y): every frame is equalised on the device before its pyramid, setEqualize below;
         # klt_photometric=True: the tracker's gain/offset term, setKltPhotometric below; ended_export=True: every removal hands out the records of
-        # the landmarks that leave, setEndedExport below)
+        # the landmarks that leave, setEndedExport below; zupt=(max_flow_px, min_tracks, min_ratio, vel_var, omega_var): the zero-velocity update,
+        # setZupt below)
         self.tc_ekf = TightlyCoupledEKF(**kw)
         self.tracker = KLTTracker(self.tc_ekf)
         self._imu_queue = []      # (stamp, gyro, accel), kept in stamp order; only used with use_imu = 1
@@ -658,6 +681,18 @@ class EKFVIO:
     def ended(self):
         """TightlyCoupledEKF.ended: the records of the most recent removal; a consumer that wants every ended track reads it after every frame."""
         return self.tc_ekf.ended()
+
+    def setZupt(self, max_flow_px, min_tracks=8, min_ratio=0.75, vel_variance=1e-4, omega_variance=1e-4):
+        """TightlyCoupledEKF.setZupt: from the next frame on a frame whose tracks stand still updates velocity and body rate with z = 0."""
+        self.tc_ekf.setZupt(max_flow_px, min_tracks, min_ratio, vel_variance, omega_variance)
+
+    def zuptUpdate(self, vel_variance=1e-4, omega_variance=1e-4):
+        """TightlyCoupledEKF.zuptUpdate: the update alone, for a caller with its own stop detector."""
+        self.tc_ekf.zuptUpdate(vel_variance, omega_variance)
+
+    def zupt(self):
+        """TightlyCoupledEKF.zupt: the most recent frame's decision; a memcpy behind a frame."""
+        return self.tc_ekf.zupt()
 
     def setOutputCovariance(self, on):
         """TightlyCoupledEKF.setOutputCovariance: from the next frame on addFrame delivers the covariances with the frame's outputs."""

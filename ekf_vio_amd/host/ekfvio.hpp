@@ -69,6 +69,12 @@ struct Params {
     // id of ekfvio_get_landmark_ids as a float: exact below 2^24, then id mod 2^24); publish_ended = 1 turns the export of the tracks that ended
     // on (ekfvio_set_ended_export) and the node publishes their records as a second PointCloud on ended_topic.
     int publish_ids = 0, publish_ended = 0;
+    // Not in the reference, whose filter learns that the camera stands still only through the landmarks' pixels: with zupt_max_flow_px > 0 a frame in
+    // which at least zupt_min_tracks landmarks passed the tracker and at least zupt_min_ratio of them moved no more than that many pixels of the
+    // RESIZED frame updates the velocity and the body rate with z = 0 (ekfvio_set_zupt; variances zupt_vel_variance, zupt_omega_variance); 0 = off.
+    float zupt_max_flow_px = 0.f;
+    int zupt_min_tracks = 8;
+    float zupt_min_ratio = 0.75f, zupt_vel_variance = 1e-4f, zupt_omega_variance = 1e-4f;
     std::map<std::string, std::string> node;  // odom_topic, camera_topic, base_frame, use_imu, publish_insight, ...
 
     Params() {
@@ -137,6 +143,24 @@ struct Params {
         }
         else if (key == "publish_ids") publish_ids = (value == "true" || value == "1") ? 1 : 0;
         else if (key == "publish_ended") publish_ended = (value == "true" || value == "1") ? 1 : 0;
+        else if (key == "zupt_max_flow_px") {
+            zupt_max_flow_px = (float)number(key, value);
+            // (number() refuses NaN and infinities as text; the narrowing to float can still overflow: what ekfvio_set_zupt would refuse is refused here)
+            if (!(zupt_max_flow_px >= 0.f) || !std::isfinite(zupt_max_flow_px)) throw Error(EKFVIO_EINVAL, "parameter zupt_max_flow_px: not a finite value >= 0: " + value);
+        }
+        else if (key == "zupt_min_tracks") {
+            zupt_min_tracks = integer(key, value);
+            if (zupt_min_tracks < 1) throw Error(EKFVIO_EINVAL, "parameter zupt_min_tracks: below 1: " + value);
+        }
+        else if (key == "zupt_min_ratio") {
+            zupt_min_ratio = (float)number(key, value);
+            if (!(zupt_min_ratio > 0.f && zupt_min_ratio <= 1.f)) throw Error(EKFVIO_EINVAL, "parameter zupt_min_ratio: not in (0, 1]: " + value);
+        }
+        else if (key == "zupt_vel_variance" || key == "zupt_omega_variance") {
+            const float v = (float)number(key, value);
+            if (!(v > 0.f) || !std::isfinite(v)) throw Error(EKFVIO_EINVAL, "parameter " + key + ": not a finite value > 0: " + value);
+            (key == "zupt_vel_variance" ? zupt_vel_variance : zupt_omega_variance) = v;
+        }
         else if (key == "distortion_k1") distortion[0] = number(key, value);
         else if (key == "distortion_k2") distortion[1] = number(key, value);
         else if (key == "distortion_p1") distortion[2] = number(key, value);
@@ -161,7 +185,7 @@ struct Params {
                                         "default_point_depth", "default_point_depth_variance",
                                         "default_point_homogenous_variance", "frame_buffer_size", "imu_update",
                                         "imu_gyro_variance", "imu_accel_variance", "gravity_x", "gravity_y", "gravity_z", "remove_lost", "gate_chi2",
-                                        "klt_fb_max_px", "rectify", "publish_covariance", "mask_rectify_border", "equalize_clip_limit", "equalize_tiles_x", "equalize_tiles_y", "klt_photometric", "publish_ids", "publish_ended", "distortion_k1", "distortion_k2", "distortion_p1", "distortion_p2", "distortion_k3"};
+                                        "klt_fb_max_px", "rectify", "publish_covariance", "mask_rectify_border", "equalize_clip_limit", "equalize_tiles_x", "equalize_tiles_y", "klt_photometric", "publish_ids", "publish_ended", "zupt_max_flow_px", "zupt_min_tracks", "zupt_min_ratio", "zupt_vel_variance", "zupt_omega_variance", "distortion_k1", "distortion_k2", "distortion_p1", "distortion_p2", "distortion_k3"};
         for (const auto& e : Params().node) out.push_back(e.first);
         for (const auto& e : ignored()) out.push_back(e.first);
         return out;
@@ -307,6 +331,26 @@ class TightlyCoupledEKF {
     // Not in the reference, whose tracker assumes brightness constancy: the gain/offset term of every Lucas-Kanade pass
     // (ekfvio_set_klt_photometric).  On from the next track; off by default.
     void setKltPhotometric(bool on) { chk(ekfvio_set_klt_photometric(h_, on ? 1 : 0)); }
+    // Not in the reference: the zero-velocity update (ekfvio_set_zupt).  max_flow_px > 0: a frame in which at least min_tracks landmarks passed the
+    // tracker and at least min_ratio of those moved no more than max_flow_px pixels updates the velocity and the body rate with z = 0 in front of
+    // the camera update; 0: off.  zuptUpdate: that update alone, unconditional, for a caller with a stop detector of its own.
+    void setZupt(float max_flow_px, int min_tracks = 8, float min_ratio = 0.75f, float vel_variance = 1e-4f, float omega_variance = 1e-4f) {
+        chk(ekfvio_set_zupt(h_, max_flow_px, min_tracks, min_ratio, vel_variance, omega_variance));
+    }
+    void zuptUpdate(float vel_variance = 1e-4f, float omega_variance = 1e-4f) { chk(ekfvio_zupt_update(h_, vel_variance, omega_variance)); }
+    struct Zupt {
+        std::vector<float> flow2;  // per landmark of the most recent frame's decision: squared pixel flow (-1: the tracker did not pass it)
+        int32_t n_pass = 0, n_still = 0, applied_last = 0;
+        int64_t applied_total = 0;
+    };
+    Zupt getZupt() {
+        Zupt r;
+        r.flow2.assign((size_t)(max_features_ > 0 ? max_features_ : 1), -1.f);
+        int32_t n = 0;
+        chk(ekfvio_get_zupt(h_, r.flow2.data(), &n, &r.n_pass, &r.n_still, &r.applied_last, &r.applied_total));
+        r.flow2.resize((size_t)n);
+        return r;
+    }
     struct Mask {
         int width = 0, height = 0;     // level 0; 0 x 0 before the first frame pushed with the mask on
         std::vector<uint8_t> blocked;  // height x width, 1 = blocked
@@ -538,6 +582,7 @@ class EKFVIO {
         if (p.equalize_clip_limit > 0.f) tc_ekf.setEqualize(p.equalize_clip_limit, p.equalize_tiles_x, p.equalize_tiles_y);  // (likewise)
         if (p.klt_photometric) tc_ekf.setKltPhotometric(true);  // (likewise)
         if (p.publish_ended) tc_ekf.setEndedExport(true);  // (likewise)
+        if (p.zupt_max_flow_px > 0.f) tc_ekf.setZupt(p.zupt_max_flow_px, p.zupt_min_tracks, p.zupt_min_ratio, p.zupt_vel_variance, p.zupt_omega_variance);  // (likewise)
     }
     TightlyCoupledEKF tc_ekf;
     KLTTracker tracker;

@@ -109,7 +109,9 @@ class EkfvioNode {
         // exact below 2^24 = 16 777 216, beyond that id mod 2^24, so that equal floats within one cloud still mean one landmark;
         // publish_ended, default false: the handle is told to export the tracks that ended, ekfvio_set_ended_export, and their records go out
         // behind every frame as a second PointCloud on ended_topic, default invio/ended_points, with the channels "id", "born" (seconds before
-        // the message's stamp: a float cannot hold a ROS stamp), "index_before" and the nine covariance entries "c00" .. "c22")
+        // the message's stamp: a float cannot hold a ROS stamp), "index_before" and the nine covariance entries "c00" .. "c22";
+        // zupt_max_flow_px, default 0 = off, with zupt_min_tracks 8, zupt_min_ratio 0.75, zupt_vel_variance and zupt_omega_variance 1e-4: a frame
+        // whose tracks stand still updates the velocity and the body rate with z = 0 on the device, ekfvio_set_zupt, told at start-up likewise)
         for (const std::string& name : ekfvio::Params::names()) {
             XmlRpc::XmlRpcValue v;
             if (ros::param::get("~" + name, v)) params_.set(name, to_text(v));

@@ -121,7 +121,7 @@ EKFVIO_API int ekfvio_destroy(ekfvio_filter* f);
  * So does the tracker's gain/offset term, ekfvio_set_klt_photometric.)
  * (The landmark id counter does NOT start over: the first landmark behind a reset gets an id above every id the handle has handed out,
  * so a consumer never sees two points under one id.  The setting of ekfvio_set_ended_export stays; its report is empty and its total
- * starts over, as the gate's.) */
+ * starts over, as the gate's.  The same holds for ekfvio_set_zupt: the setting stays, its report and its count start over.) */
 EKFVIO_API int ekfvio_reset(ekfvio_filter* f);
 EKFVIO_API const char* ekfvio_last_error(const ekfvio_filter* f);
 
@@ -603,6 +603,82 @@ EKFVIO_API int ekfvio_fast_detect(ekfvio_filter* f, int32_t threshold, int32_t n
 EKFVIO_API int ekfvio_imu(ekfvio_filter* f, double stamp, const float gyro[3], const float accel[3]);
 /* The update alone (no propagation), whatever cfg.use_imu says: for tests and callers that propagate themselves. */
 EKFVIO_API int ekfvio_imu_update(ekfvio_filter* f, const float gyro[3], const float accel[3]);
+
+/* ---- zero-velocity update (not in the reference, whose filter learns that the camera stands still only through noisy pixel measurements of
+ * landmarks at uncertain depth, against a motion model whose Q keeps re-inflating velocity, body rate and acceleration) --------------------
+ * A decision per frame, on the device, from the tracker's results, and -- when it says the camera stands still -- a pseudo-measurement
+ * z = 0 of the velocity and the body rate.  The lines below are the specification: everything in fp32, the association order fixed, without
+ * fused multiply-add, division and square root correctly rounded; a NumPy restatement of them (tests/_zupt.py) is what the device is held
+ * to, bit for bit.
+ *
+ * Decision, per frame of ekfvio_step_image, behind the tracker, in front of the update's measurement bookkeeping and the innovation gate.
+ * pass[i]: the tracker's final verdict as the update would receive it (behind the forward status, the forward-backward check, the kill box
+ * and the mask).  (qx, qy): the tracked pixel.  (px, py): the reference pixel as the tracker forms it, last_klt[2i] * fx + cx and
+ * last_klt[2i+1] * fy + cy with the PREVIOUS frame's intrinsics (multiply, then add).
+ *
+ *     for pass[i] != 0:   dx = qx - px    dy = qy - py    e2 = dx*dx + dy*dy    still_i  <=>  e2 <= t2
+ *                         (t2 = max_flow_px*max_flow_px, formed once on the host in fp32; a NaN is not still)
+ *     n_pass = #pass      n_still = #still
+ *     stationary  <=>  n_pass >= min_tracks  and  (float)n_still >= min_ratio * (float)n_pass
+ *     flow2[i] = e2, or -1 where pass[i] == 0
+ *
+ * Update, when stationary, on the propagated state, in front of the camera update (the gate and the camera update then read the state it
+ * leaves): z = 0 on h(x) = [vel (mu[7..9]); omega (mu[10..12])], H the selection of state rows 7..12, R = diag(R_0 .. R_5) with
+ * R_0..2 = vel_variance and R_3..5 = omega_variance, Joseph form.  It is the IMU update's arithmetic (ekfvio_imu_update) with H a selection.
+ * P(i,j) is Sigma's element in row i, column j AS STORED (both triangles agree only up to rounding); r, s, c run over 0..5 and every sum
+ * runs over an ascending index and associates to the left, starting from its first written term:
+ *
+ *     S(r,s) = P(7+r, 7+s) + (r == s ? R_r : nothing added)               r >= s: the lower triangle alone is read
+ *     L: left-looking Cholesky, for j = 0..5:   d = S(j,j) - L(j,0)*L(j,0) - ... - L(j,j-1)*L(j,j-1)      L(j,j) = sqrt(d)
+ *                                  for r > j:   v = S(r,j) - L(r,0)*L(j,0) - ... - L(r,j-1)*L(j,j-1)      L(r,j) = v / L(j,j)
+ *     y_r = -mu[7+r]
+ *     per state row i = 0 .. n-1:
+ *         x_r = P(i, 7+r)          w_r = P(7+r, i)
+ *         forward,  r = 0..5:      k_r = (x_r - k_0*L(r,0) - ... - k_{r-1}*L(r,r-1)) / L(r,r)
+ *         backward, r = 5..0:      k_r = (k_r - k_{r+1}*L(r+1,r) - ... - k_5*L(5,r)) / L(r,r)
+ *         t_c = x_c - k_0*P(7,7+c) - ... - k_5*P(12,7+c)
+ *         g_r = k_r*R_r - t_r
+ *         dm  = 0 + k_0*y_0 + ... + k_5*y_5
+ *         mu'_i = mu_i + dm
+ *     quaternion: qn = sqrt(mu'_3*mu'_3 + mu'_4*mu'_4 + mu'_5*mu'_5 + mu'_6*mu'_6), mu'_3..6 divided by qn
+ *     Sigma'(i,j) = flush((P(i,j) - k_0(i)*w_0(j) - ... - k_5(i)*w_5(j)) + g_0(i)*k_0(j) + ... + g_5(i)*k_5(j))
+ *     flush(v) = v where |v| > 1e-8f * 1e-5f, else 0 (the reference's prune)
+ *
+ * When not stationary, Sigma is untouched and the mean keeps every bit (the mean is updated in place: nothing is copied or swapped).  The
+ * landmarks' last KLT results, delete flags, ids and birth stamps are never touched.  Behind an aborted persistent sweep the camera update
+ * runs again from the state this update left; the zero-velocity update is not repeated.  ekfvio_run_uploaded and its captured graphs carry no
+ * tracker results and run none; ekfvio_klt_track + ekfvio_update get none automatically: their caller decides and calls
+ * ekfvio_zupt_update.
+ *
+ * What it does not do.  It is for standing still, not for braking: slammed onto the first frame of an abrupt stop it moves the position
+ * through the cross-covariances by more than the filter's own convergence would (README, "zero-velocity update").  A distant scene under slow
+ * translation looks still in pixels: no threshold is recommended beyond "off".  Acceleration and the biases are not measured.  The camera update
+ * is not skipped.
+ *
+ * ekfvio_set_zupt.  max_flow_px == 0: off (default; then no launch differs, nothing is allocated and every output keeps its bits; the other
+ * arguments are not looked at).  On: max_flow_px finite and > 0, min_tracks >= 1, 0 < min_ratio <= 1, both variances finite and > 0; anything
+ * else EKFVIO_EINVAL, and the setting stays what it was.  A property of the handle: it holds from the next frame, survives ekfvio_reset (the
+ * counts start over, as the gate's) and drops no captured graph.  On, it costs two launches per frame with landmarks -- every workgroup of the
+ * gain kernel evaluates the decision for itself, and both kernels return at once on a "no" -- and 16 bytes of device and 16 + 4 max_features
+ * bytes of pinned host memory, taken when it is first turned on. */
+EKFVIO_API int ekfvio_set_zupt(ekfvio_filter* f, float max_flow_px, int32_t min_tracks, float min_ratio, float vel_variance,
+                               float omega_variance);
+/* The update alone, unconditional, whatever the setting says: for tests and for callers with a stop detector of their own (wheel odometry).
+ * Both variances finite and > 0, else EKFVIO_EINVAL.  Asynchronous, as ekfvio_imu_update. */
+EKFVIO_API int ekfvio_zupt_update(ekfvio_filter* f, float vel_variance, float omega_variance);
+/* The decision of the most recent frame of ekfvio_step_image (any pointer may be NULL): flow2 per landmark as defined above, with room for
+ * max_features entries; *n_landmarks = the landmark count that decision saw (indices are its indices, before any removal or replenishment of
+ * the same frame); n_pass, n_still; *applied_last = 1 where that frame's update ran; the number of frames it ran in since create / reset.
+ * A frame without a decision (the first frame, no landmark) reports zeros, and so does a handle with the setting off.  A memcpy: the
+ * decision's words and flow2 arrive in pinned host memory in front of the frame's status word. */
+EKFVIO_API int ekfvio_get_zupt(ekfvio_filter* f, float* flow2N, int32_t* n_landmarks, int32_t* n_pass, int32_t* n_still,
+                               int32_t* applied_last, int64_t* applied_total);
+/* The decision itself for `count` points: a pure host function (no handle, no device) that compiles the very inline functions the kernels
+ * compile, as ekfvio_rectify_map does; the two counts come from a loop here and from wavefront ballots there.  prev_px, cur_px: the reference
+ * and the tracked pixels, x,y interleaved; pass: one byte each.  flow2 (room for count entries), n_pass, n_still, stationary may be NULL.
+ * A negative count, NULL inputs with count > 0, or max_flow_px, min_tracks, min_ratio that ekfvio_set_zupt would refuse as "on": EKFVIO_EINVAL. */
+EKFVIO_API int ekfvio_zupt_decide(const float* prev_px, const float* cur_px, const uint8_t* pass, int32_t count, float max_flow_px,
+                                  int32_t min_tracks, float min_ratio, float* flow2, int32_t* n_pass, int32_t* n_still, int32_t* stationary);
 
 /* ---- device-resident measurement sequences (benchmark / replay) ---------------------- */
 /* Copies `frames` consecutive (z, R, pass) triples for the current landmark count to HBM. */

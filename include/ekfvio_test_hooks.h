@@ -88,6 +88,13 @@ EKFVIO_API int ekfvio_test_mem_fail(ekfvio_filter* f, int32_t nth);
  * owns the update's work buffers").  mu_next and mu swap roles with every process(dt): the entries of a filled mu_next from 22 + 3N on become
  * mu's padding, which nothing reads.  Call it between entry points, not inside a device-resident run. */
 EKFVIO_API int ekfvio_test_fill_update_scratch(ekfvio_filter* f, uint32_t word);
+/* The zero-velocity decision (include/ekfvio.h) on the device for `count` arbitrary points, arguments and results as ekfvio_zupt_decide's: the
+ * points are uploaded into the tracker's own buffers (count above max_features: EKFVIO_ECAPACITY) and one workgroup runs the device function
+ * every workgroup of the frame's gain kernel runs -- the same inline functions, ballots and publication into pinned host memory; the
+ * reference pixel is formed as prev_px * 1 + 0, which is exact.  Overwrites the flow2 that ekfvio_get_zupt reports; waits for the stream. */
+EKFVIO_API int ekfvio_test_zupt_decide(ekfvio_filter* f, const float* prev_px, const float* cur_px, const uint8_t* pass, int32_t count,
+                                       float max_flow_px, int32_t min_tracks, float min_ratio, float* flow2, int32_t* n_pass, int32_t* n_still,
+                                       int32_t* stationary);
 
 #ifdef __cplusplus
 }
