@@ -50,7 +50,9 @@ SYMBOLS = ["ekfvio_default_config", "ekfvio_create", "ekfvio_destroy", "ekfvio_r
            "ekfvio_set_mask", "ekfvio_get_mask", "ekfvio_get_mask_hits", "ekfvio_mask_blocked", "ekfvio_set_equalize", "ekfvio_equalize",
            "ekfvio_set_klt_photometric", "ekfvio_klt_project_gradients",
            "ekfvio_get_landmark_ids", "ekfvio_set_ended_export", "ekfvio_get_ended",
-           "ekfvio_set_zupt", "ekfvio_zupt_update", "ekfvio_get_zupt", "ekfvio_zupt_decide"]
+           "ekfvio_set_zupt", "ekfvio_zupt_update", "ekfvio_get_zupt", "ekfvio_zupt_decide",
+           "ekfvio_set_imu_extrinsics", "ekfvio_get_imu_extrinsics", "ekfvio_set_gravity", "ekfvio_get_gravity",
+           "ekfvio_gravity_from_accel", "ekfvio_imu_model"]
 MASK_RECTIFY_BORDER = 1  # EKFVIO_MASK_RECTIFY_BORDER
 # every symbol include/ekfvio_test_hooks.h declares (libekfvio_hip_hooks.so only)
 HOOK_SYMBOLS = ["ekfvio_test_klt_padded_level", "ekfvio_test_blurred_level0", "ekfvio_test_gemm", "ekfvio_test_gemm_bench", "ekfvio_test_potrf_stamps",
@@ -121,6 +123,10 @@ def load(build_if_missing=True, hooks=False):
         "ekfvio_set_zupt": [vp, f32, i32, f32, f32, f32], "ekfvio_zupt_update": [vp, f32, f32],
         "ekfvio_get_zupt": [vp, fp, ip, ip, ip, ip, C.POINTER(C.c_int64)],
         "ekfvio_zupt_decide": [fp, fp, u8p, i32, f32, i32, f32, fp, ip, ip, ip],  # no handle, no device
+        "ekfvio_set_imu_extrinsics": [vp, fp, fp], "ekfvio_get_imu_extrinsics": [vp, fp, fp, ip],
+        "ekfvio_set_gravity": [vp, fp], "ekfvio_get_gravity": [vp, fp],
+        "ekfvio_gravity_from_accel": [fp, C.POINTER(C.c_double), f32, fp],  # no handle, no device
+        "ekfvio_imu_model": [fp, fp, fp, fp, fp, fp, fp, fp],  # no handle, no device
     }
     if hooks:
         sig.update({

@@ -334,6 +334,7 @@ int ekfvio_create(const ekfvio_config* cfg, int device, void* stream, ekfvio_fil
     f->mem.fail_nth(g_next_create_fail.exchange(0));
 #endif
     f->cfg = *cfg;
+    for (int k = 0; k < 3; k++) f->imu_gravity[k] = cfg->gravity[k];  // until ekfvio_set_gravity says otherwise
     f->device = device;
     if (device < 64) live_registry()[device].fetch_add(1, std::memory_order_relaxed);
     const int rc = create_body(f, cfg, device, stream);

@@ -242,6 +242,12 @@ struct ekfvio_filter {
     int* d_hzupt = nullptr;        // the device's address of h_zupt
     int zupt_n = 0, zupt_pass = 0, zupt_still = 0, zupt_applied_last = 0;  // the most recent frame's decision as the host read it with the status word
     int64_t zupt_applied_total = 0;  // since create / reset
+    // --- the IMU in its own frame and gravity at run time (ekfvio_set_imu_extrinsics, ekfvio_set_gravity; imu.hip): host values alone, handed to
+    // the IMU update's launch as kernel arguments; both survive ekfvio_reset ---
+    bool imu_ext_on = false;      // launch_imu_update takes imu_gain_kernel<true>
+    float imu_R_ci[9] = {1.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f, 1.f};  // as given: row-major, IMU -> camera axes
+    float imu_p_ci[3] = {0.f, 0.f, 0.f};                                  // the IMU's origin in the camera frame (m)
+    float imu_gravity[3] = {0.f, 0.f, 0.f};  // cfg.gravity at ekfvio_create, then whatever ekfvio_set_gravity said last
     int* remove_words = nullptr;  // [4] device words of the removal kernel (remove.hip): [0] landmarks added - removed, [1] removed, [2] its ticket
     int* h_info = nullptr;     // pinned, device-mapped: the words of enum HostWord
     int* d_hinfo = nullptr;    // the device's address of h_info

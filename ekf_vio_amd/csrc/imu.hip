@@ -10,7 +10,16 @@
 // touch sixteen state columns, so the update is two small launches: gains per state row (S is 6 x 6: factored by every
 // workgroup for itself), then one elementwise pass Sigma <- Sigma - K (H Sigma) + G K^T.  With cfg.use_imu = 0 (default)
 // ekfvio_imu stays the reference's no-op.
+//
+// ekfvio_set_imu_extrinsics puts the IMU into its own frame: h(x) = [M omega + b_gyr ; M (a + omega x (omega x p) - R(q)^T g) + b_acc] with
+// M = R_ci^T and p = p_ci (include/ekfvio.h has the lines, imu_model.h the functions, shared with the host's ekfvio_imu_model).  The gain
+// kernel is a template on it: the instance without is the kernel as it was, the instance with forms the denser H and residual in front of the
+// first barrier; the Joseph pass is the same launch.  g is the handle's gravity (cfg.gravity until ekfvio_set_gravity replaces it).
 #include "common.h"
+#include "imu_model.h"
+
+#include <cstring>
+#include <type_traits>
 
 namespace {
 
@@ -19,42 +28,19 @@ struct ImuArgs {
     float gyro_var, accel_var;
     float g[3];
 };
+// ... with the IMU in its own frame (ekfvio_set_imu_extrinsics): M = R_ci^T row-major and p = p_ci
+struct ImuArgsExt : ImuArgs {
+    float M[9], p[3];
+};
 
 __constant__ const int kImuCols[16] = {3, 4, 5, 6, 10, 11, 12, 13, 14, 15, 16, 17, 18, 19, 20, 21};
 
-__device__ inline void cross3f(const float* a, const float* b, float* o) {
-    o[0] = a[1] * b[2] - a[2] * b[1];
-    o[1] = a[2] * b[0] - a[0] * b[2];
-    o[2] = a[0] * b[1] - a[1] * b[0];
-}
-
-// R(q)^T g with the filter's rotation formula on the conjugate (q not normalised), and d/d(w,x,y,z) (row-major 3 x 4)
-__device__ inline void rt_gravity(const float* q, const float* g, float* out, float* jac) {
-    const float w = q[0];
-    const float c[3] = {-q[1], -q[2], -q[3]};
-    float uv[3], cu[3];
-    cross3f(c, g, uv);
-    for (int k = 0; k < 3; k++) uv[k] = uv[k] + uv[k];
-    cross3f(c, uv, cu);
-    for (int k = 0; k < 3; k++) {
-        out[k] = g[k] + w * uv[k] + cu[k];
-        jac[4 * k] = uv[k];
-    }
-    for (int k = 0; k < 3; k++) {
-        const float e[3] = {k == 0 ? 1.f : 0.f, k == 1 ? 1.f : 0.f, k == 2 ? 1.f : 0.f};
-        float ev[3], a[3], b[3];
-        cross3f(e, g, ev);
-        for (int r = 0; r < 3; r++) ev[r] = ev[r] + ev[r];
-        cross3f(e, uv, a);
-        cross3f(c, ev, b);
-        for (int r = 0; r < 3; r++) jac[4 * r + 1 + k] = -(w * ev[r] + a[r] + b[r]);
-    }
-}
-
-// gains, G = K R - T H^T, W = H Sigma and the updated mean, one state row per thread
+// gains, G = K R - T H^T, W = H Sigma and the updated mean, one state row per thread.  EXT: the model of imu_model.h with the extrinsics
+// (a denser H and residual in front of the first barrier; from there on the instances are the same lines)
+template <bool EXT>
 __global__ __launch_bounds__(256) void imu_gain_kernel(const float* __restrict__ P, int ld, int n, const float* __restrict__ mu,
-                                                       float* __restrict__ mu_out, ImuArgs a, float* __restrict__ K6,
-                                                       float* __restrict__ G6, float* __restrict__ W6) {
+                                                       float* __restrict__ mu_out, std::conditional_t<EXT, ImuArgsExt, ImuArgs> a,
+                                                       float* __restrict__ K6, float* __restrict__ G6, float* __restrict__ W6) {
     __shared__ float sH[6][16];      // H on its sixteen columns
     __shared__ float sPb[16][16];    // Sigma(cols[r], cols[c])
     __shared__ float sWb[6][16];     // (H Sigma)(s, cols[c])
@@ -63,19 +49,23 @@ __global__ __launch_bounds__(256) void imu_gain_kernel(const float* __restrict__
     const int tid = threadIdx.x;
     const int i = blockIdx.x * 256 + tid;
     if (tid == 0) {
-        float q[4] = {mu[3], mu[4], mu[5], mu[6]};
-        float rg[3], jac[12];
-        rt_gravity(q, a.g, rg, jac);
-        for (int r = 0; r < 6; r++)
-            for (int c = 0; c < 16; c++) sH[r][c] = 0.f;
-        for (int r = 0; r < 3; r++) {
-            sH[r][4 + r] = 1.f;
-            sH[r][13 + r] = 1.f;
-            sH[3 + r][7 + r] = 1.f;
-            sH[3 + r][10 + r] = 1.f;
-            for (int k = 0; k < 4; k++) sH[3 + r][k] = -jac[4 * r + k];
-            sy[r] = a.gyro[r] - (mu[10 + r] + mu[19 + r]);
-            sy[3 + r] = a.accel[r] - ((mu[13 + r] + mu[16 + r]) - rg[r]);
+        if constexpr (EXT) {
+            imu_model_ext(mu, a.g, a.M, a.p, a.gyro, a.accel, sy, &sH[0][0]);
+        } else {  // (imu_model_plain's lines, kept in place: see imu_model.h)
+            float q[4] = {mu[3], mu[4], mu[5], mu[6]};
+            float rg[3], jac[12];
+            rt_gravity(q, a.g, rg, jac);
+            for (int r = 0; r < 6; r++)
+                for (int c = 0; c < 16; c++) sH[r][c] = 0.f;
+            for (int r = 0; r < 3; r++) {
+                sH[r][4 + r] = 1.f;
+                sH[r][13 + r] = 1.f;
+                sH[3 + r][7 + r] = 1.f;
+                sH[3 + r][10 + r] = 1.f;
+                for (int k = 0; k < 4; k++) sH[3 + r][k] = -jac[4 * r + k];
+                sy[r] = a.gyro[r] - (mu[10 + r] + mu[19 + r]);
+                sy[3 + r] = a.accel[r] - ((mu[13 + r] + mu[16 + r]) - rg[r]);
+            }
         }
     }
     {
@@ -196,19 +186,97 @@ __global__ __launch_bounds__(256) void imu_joseph_kernel(float* __restrict__ P, 
 }  // namespace
 
 void launch_imu_update(ekfvio_filter* f, const float gyro[3], const float accel[3]) {
-    ImuArgs a;
+    ImuArgsExt a;
     for (int k = 0; k < 3; k++) {
         a.gyro[k] = gyro[k];
         a.accel[k] = accel[k];
-        a.g[k] = f->cfg.gravity[k];
+        a.g[k] = f->imu_gravity[k];
     }
     a.gyro_var = f->cfg.imu_gyro_variance;
     a.accel_var = f->cfg.imu_accel_variance;
     const int n = f->n, ld = f->ldp;
     ProfScope ps(f, PC_UPDATE_MISC, 0, 2);
     // the three n x 6 work matrices live in the first six columns of the camera update's buffers (free between updates)
-    hipLaunchKernelGGL(imu_gain_kernel, dim3((n + 255) / 256), dim3(256), 0, f->stream, f->P, ld, n, f->mu, f->mu_next, a, f->Km, f->Gm,
-                       f->Wt);
+    if (f->imu_ext_on) {
+        for (int r = 0; r < 3; r++) {
+            for (int k = 0; k < 3; k++) a.M[3 * r + k] = f->imu_R_ci[3 * k + r];
+            a.p[r] = f->imu_p_ci[r];
+        }
+        hipLaunchKernelGGL(imu_gain_kernel<true>, dim3((n + 255) / 256), dim3(256), 0, f->stream, f->P, ld, n, f->mu, f->mu_next, a, f->Km,
+                           f->Gm, f->Wt);
+    } else {
+        hipLaunchKernelGGL(imu_gain_kernel<false>, dim3((n + 255) / 256), dim3(256), 0, f->stream, f->P, ld, n, f->mu, f->mu_next,
+                           static_cast<const ImuArgs&>(a), f->Km, f->Gm, f->Wt);
+    }
     hipLaunchKernelGGL(imu_joseph_kernel, dim3((n + 255) / 256, n), dim3(256), 0, f->stream, f->P, ld, n, f->Km, f->Gm, f->Wt);
     std::swap(f->mu, f->mu_next);
 }
+
+extern "C" {
+
+int ekfvio_set_imu_extrinsics(ekfvio_filter* f, const float* R_ci, const float* p_ci) {
+    if (!f || (R_ci == nullptr) != (p_ci == nullptr)) return EKFVIO_EINVAL;
+    if (!R_ci) {  // off: the next IMU update launches the instance without them
+        f->imu_ext_on = false;
+        return EKFVIO_OK;
+    }
+    if (!imu_extrinsics_valid(R_ci, p_ci)) return EKFVIO_EINVAL;  // (the setting stays what it was)
+    // (read by the next launch_imu_update; the IMU update is in no captured graph).  Stored as given, not re-orthonormalised.
+    memcpy(f->imu_R_ci, R_ci, sizeof(float) * 9);
+    memcpy(f->imu_p_ci, p_ci, sizeof(float) * 3);
+    f->imu_ext_on = true;
+    return EKFVIO_OK;
+}
+
+int ekfvio_get_imu_extrinsics(ekfvio_filter* f, float* R_ci, float* p_ci, int32_t* on) {
+    if (!f) return EKFVIO_EINVAL;
+    static const float eye[9] = {1.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f, 1.f}, zero[3] = {0.f, 0.f, 0.f};
+    if (R_ci) memcpy(R_ci, f->imu_ext_on ? f->imu_R_ci : eye, sizeof(float) * 9);
+    if (p_ci) memcpy(p_ci, f->imu_ext_on ? f->imu_p_ci : zero, sizeof(float) * 3);
+    if (on) *on = f->imu_ext_on ? 1 : 0;
+    return EKFVIO_OK;
+}
+
+int ekfvio_set_gravity(ekfvio_filter* f, const float* g) {
+    if (!f || !g || !isfinite(g[0]) || !isfinite(g[1]) || !isfinite(g[2])) return EKFVIO_EINVAL;
+    memcpy(f->imu_gravity, g, sizeof(float) * 3);
+    return EKFVIO_OK;
+}
+
+int ekfvio_get_gravity(ekfvio_filter* f, float* g) {
+    if (!f || !g) return EKFVIO_EINVAL;
+    memcpy(g, f->imu_gravity, sizeof(float) * 3);
+    return EKFVIO_OK;
+}
+
+int ekfvio_gravity_from_accel(const float* R_ci, const double* mean_accel, float magnitude, float* g_out) {
+    if (!mean_accel || !g_out || !isfinite(magnitude)) return EKFVIO_EINVAL;
+    double r[9] = {1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0};
+    for (int k = 0; k < 9 && R_ci; k++) {
+        if (!isfinite(R_ci[k])) return EKFVIO_EINVAL;
+        r[k] = (double)R_ci[k];
+    }
+    const double m[3] = {mean_accel[0], mean_accel[1], mean_accel[2]};
+    const double norm = sqrt(m[0] * m[0] + m[1] * m[1] + m[2] * m[2]);
+    if (!isfinite(norm) || norm == 0.0) return EKFVIO_EINVAL;
+    const double scale = magnitude > 0.f ? (double)magnitude / norm : 1.0;
+    for (int i = 0; i < 3; i++) g_out[i] = (float)(-(r[3 * i] * m[0] + r[3 * i + 1] * m[1] + r[3 * i + 2] * m[2]) * scale);
+    return EKFVIO_OK;
+}
+
+int ekfvio_imu_model(const float* base_mu, const float* g, const float* R_ci, const float* p_ci, const float* gyro, const float* accel,
+                     float* y, float* H) {
+    if (!base_mu || !g || !gyro || !accel || !y || !H || (R_ci == nullptr) != (p_ci == nullptr)) return EKFVIO_EINVAL;
+    if (!R_ci) {
+        imu_model_plain(base_mu, g, gyro, accel, y, H);
+        return EKFVIO_OK;
+    }
+    if (!imu_extrinsics_valid(R_ci, p_ci)) return EKFVIO_EINVAL;
+    float M[9];
+    for (int r = 0; r < 3; r++)
+        for (int k = 0; k < 3; k++) M[3 * r + k] = R_ci[3 * k + r];
+    imu_model_ext(base_mu, g, M, p_ci, gyro, accel, y, H);
+    return EKFVIO_OK;
+}
+
+}  // extern "C"

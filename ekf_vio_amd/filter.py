@@ -27,7 +27,7 @@ class TightlyCoupledEKF:
                  default_point_depth=0.5, default_point_depth_variance=100.0,
                  default_point_homogenous_variance=1e-5, hooks=False, gate_chi2=0.0, klt_fb_max_px=0.0, distortion=None, output_covariance=False,
                  mask=None, mask_rectify_border=False, equalize=None, klt_photometric=False, ended_export=False, zupt=None,
-                 **cfg_overrides):
+                 imu_extrinsics=None, **cfg_overrides):
         # hooks=True: this handle lives in libekfvio_hip_hooks.so, the build that also has include/ekfvio_test_hooks.h (tests, profiling scripts)
         self.hooks = bool(hooks)
         self.lib = capi.load(hooks=self.hooks)
@@ -67,6 +67,8 @@ class TightlyCoupledEKF:
             self.setEndedExport(True)
         if zupt is not None:  # likewise (ekfvio_set_zupt)
             self.setZupt(*zupt)
+        if imu_extrinsics is not None:  # likewise (ekfvio_set_imu_extrinsics)
+            self.setImuExtrinsics(*imu_extrinsics)
 
     def _chk(self, rc, allow=()):
         if rc != capi.OK and rc not in allow:
@@ -157,6 +159,34 @@ class TightlyCoupledEKF:
         g = np.ascontiguousarray(gyro, dtype=np.float32)
         a = np.ascontiguousarray(accel, dtype=np.float32)
         self._chk(self.lib.ekfvio_imu_update(self.h, _fp(g), _fp(a)))
+
+    def setImuExtrinsics(self, R_ci=None, p_ci=None):
+        """Not in the reference: the IMU in its own frame (ekfvio_set_imu_extrinsics).  R_ci [3, 3] maps IMU coordinates to camera coordinates
+        (the rotation of Kalibr's T_cam_imu), p_ci is the IMU's origin in the camera frame in metres (its translation); both None: off.
+        Holds from the next IMU update and survives initializeBaseState."""
+        if R_ci is None and p_ci is None:
+            self._chk(self.lib.ekfvio_set_imu_extrinsics(self.h, None, None))
+            return
+        R = None if R_ci is None else np.ascontiguousarray(R_ci, dtype=np.float32).reshape(9)
+        p = None if p_ci is None else np.ascontiguousarray(p_ci, dtype=np.float32).reshape(3)
+        self._chk(self.lib.ekfvio_set_imu_extrinsics(self.h, None if R is None else _fp(R), None if p is None else _fp(p)))
+
+    def imuExtrinsics(self):
+        """ekfvio_get_imu_extrinsics: (R_ci [3, 3], p_ci [3], on)."""
+        R, p, on = np.zeros(9, np.float32), np.zeros(3, np.float32), C.c_int32(0)
+        self._chk(self.lib.ekfvio_get_imu_extrinsics(self.h, _fp(R), _fp(p), C.byref(on)))
+        return R.reshape(3, 3), p, bool(on.value)
+
+    def setGravity(self, g):
+        """ekfvio_set_gravity: replaces the configuration's gravity vector (world frame, m/s^2) from the next IMU update on."""
+        g = np.ascontiguousarray(g, dtype=np.float32).reshape(3)
+        self._chk(self.lib.ekfvio_set_gravity(self.h, _fp(g)))
+
+    def gravity(self):
+        """ekfvio_get_gravity."""
+        g = np.zeros(3, np.float32)
+        self._chk(self.lib.ekfvio_get_gravity(self.h, _fp(g)))
+        return g
 
     def setZupt(self, max_flow_px, min_tracks=8, min_ratio=0.75, vel_variance=1e-4, omega_variance=1e-4):
         """Not in the reference: the zero-velocity update (ekfvio_set_zupt).  max_flow_px > 0: a frame of addFrame in which at least min_tracks
@@ -632,13 +662,58 @@ class EKFVIO:
         # equalize=(clip_limit, tiles_x, tiles_y): every frame is equalised on the device before its pyramid, setEqualize below;
         # klt_photometric=True: the tracker's gain/offset term, setKltPhotometric below; ended_export=True: every removal hands out the records of
         # the landmarks that leave, setEndedExport below; zupt=(max_flow_px, min_tracks, min_ratio, vel_var, omega_var): the zero-velocity update,
-        # setZupt below)
+        # setZupt below; imu_extrinsics=(R_ci, p_ci): the IMU in its own frame, setImuExtrinsics below; gravity_align_samples=K: the first K IMU
+        # records that come up for application are not applied but averaged, and their mean accelerometer reading sets the gravity vector:
+        # the rig is taken to be AT REST through them, with an accelerometer bias negligible against 9.81; frames meanwhile are processed as
+        # without an IMU)
+        self.gravity_align_samples = int(kw.pop("gravity_align_samples", 0))
+        if self.gravity_align_samples < 0:
+            raise capi.EkfvioError(capi.EINVAL, "gravity_align_samples < 0")
         self.tc_ekf = TightlyCoupledEKF(**kw)
         self.tracker = KLTTracker(self.tc_ekf)
         self._imu_queue = []      # (stamp, gyro, accel), kept in stamp order; only used with use_imu = 1
         self._t_filter = None     # the stamp the device state stands at
         self._last_K = None
         self.dropped_imu = 0
+        self._align_left = self.gravity_align_samples  # records still to be averaged
+        self._align_sum = np.zeros(3, np.float64)
+
+    def reset(self):
+        """initializeBaseState, an empty IMU queue, and the gravity alignment starts over (the extrinsics and the gravity set so far stay)."""
+        self.tc_ekf.initializeBaseState()
+        self._imu_queue = []
+        self._t_filter = None  # (ekfvio_reset forgets the filter's clock)
+        self._align_left = self.gravity_align_samples
+        self._align_sum = np.zeros(3, np.float64)
+
+    def setImuExtrinsics(self, R_ci=None, p_ci=None):
+        """TightlyCoupledEKF.setImuExtrinsics: from the next IMU record on the update models the IMU in its own frame."""
+        self.tc_ekf.setImuExtrinsics(R_ci, p_ci)
+
+    def setGravity(self, g):
+        """TightlyCoupledEKF.setGravity: the gravity vector in the world frame from the next IMU record on."""
+        self.tc_ekf.setGravity(g)
+
+    def _apply_imu(self, stamp, g, a):
+        """One record, in stamp order: averaged while the gravity alignment runs, else ekfvio_imu."""
+        e = self.tc_ekf
+        if self._align_left > 0 and e.cfg.use_imu:
+            self._align_sum += a.astype(np.float64)
+            self._align_left -= 1
+            if self._t_filter is None:  # the first message of all only sets the filter's clock (ekfvio_imu), as without the alignment
+                e._chk(e.lib.ekfvio_imu(e.h, stamp, _fp(g), _fp(a)))
+                self._t_filter = stamp
+            if self._align_left == 0:
+                mean = np.ascontiguousarray(self._align_sum / self.gravity_align_samples)
+                R, _, on = e.imuExtrinsics()
+                gvec = np.zeros(3, np.float32)
+                mag = float(np.linalg.norm(np.array(list(e.cfg.gravity), np.float32).astype(np.float64)))
+                e._chk(e.lib.ekfvio_gravity_from_accel(_fp(np.ascontiguousarray(R.reshape(9))) if on else None,
+                                                       mean.ctypes.data_as(C.POINTER(C.c_double)), mag, _fp(gvec)))
+                e.setGravity(gvec)
+            return
+        e._chk(e.lib.ekfvio_imu(e.h, stamp, _fp(g), _fp(a)))
+        self._t_filter = stamp
 
     def addFrame(self, stamp, img, K):
         img = np.ascontiguousarray(img, dtype=np.uint8)
@@ -752,8 +827,7 @@ class EKFVIO:
         """ekfvio_imu directly, for a caller that delivers records in stamp order itself (EKFVIO_EINVAL for an older one)."""
         g = np.ascontiguousarray(gyro, dtype=np.float32)
         a = np.ascontiguousarray(accel, dtype=np.float32)
-        self.tc_ekf._chk(self.tc_ekf.lib.ekfvio_imu(self.tc_ekf.h, float(stamp), _fp(g), _fp(a)))
-        self._t_filter = float(stamp)
+        self._apply_imu(float(stamp), g, a)
 
     def _drain_imu(self, until):
         while self._imu_queue and self._imu_queue[0][0] <= until:
@@ -761,8 +835,7 @@ class EKFVIO:
             if self._t_filter is not None and stamp < self._t_filter:
                 self.dropped_imu += 1
                 continue
-            self.tc_ekf._chk(self.tc_ekf.lib.ekfvio_imu(self.tc_ekf.h, stamp, _fp(g), _fp(a)))
-            self._t_filter = stamp
+            self._apply_imu(stamp, g, a)
 
     def insight(self):
         """publishInsight's image (EKFVIO.cpp:379-442): the resized frame as BGR8 [h, w, 3] with a green 22-pixel square

@@ -21,6 +21,7 @@
 #include <deque>
 #include <fstream>
 #include <map>
+#include <sstream>
 #include <stdexcept>
 #include <string>
 #include <vector>
@@ -75,6 +76,14 @@ struct Params {
     float zupt_max_flow_px = 0.f;
     int zupt_min_tracks = 8;
     float zupt_min_ratio = 0.75f, zupt_vel_variance = 1e-4f, zupt_omega_variance = 1e-4f;
+    // Not in the reference, which has no IMU update: the IMU in its own frame (ekfvio_set_imu_extrinsics).  imu_rotation: nine numbers, row-major,
+    // IMU -> camera axes (the rotation of Kalibr's T_cam_imu); imu_position: three numbers, the IMU's origin in the camera frame in metres (its
+    // translation).  Either one given turns the setting on (the other then defaults to the identity / zero).  gravity_align_samples = K > 0: the
+    // first K IMU records that come up for application are averaged instead of applied and set the gravity vector (ekfvio_gravity_from_accel,
+    // ekfvio_set_gravity): the rig is taken to stand still through them, with an accelerometer bias negligible against 9.81.
+    std::array<float, 9> imu_rotation{{1.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f, 1.f}};
+    std::array<float, 3> imu_position{{0.f, 0.f, 0.f}};
+    int imu_extrinsics = 0, gravity_align_samples = 0;
     std::map<std::string, std::string> node;  // odom_topic, camera_topic, base_frame, use_imu, publish_insight, ...
 
     Params() {
@@ -97,6 +106,19 @@ struct Params {
         const double x = number(key, v);
         if (x != std::floor(x) || std::fabs(x) > 1e9) throw Error(EKFVIO_EINVAL, "parameter " + key + ": not an integer: " + v);
         return (int)x;
+    }
+    // `count` numbers separated by commas and / or blanks, with or without brackets around them: "[0, -1, 0, ...]" or "0 -1 0 ..."
+    static void numbers(const std::string& key, std::string v, float* out, int count) {
+        for (char& c : v)
+            if (c == '[' || c == ']' || c == ',') c = ' ';
+        std::istringstream in(v);
+        std::string tok;
+        int k = 0;
+        while (in >> tok) {
+            if (k == count) throw Error(EKFVIO_EINVAL, "parameter " + key + ": more than " + std::to_string(count) + " numbers: " + v);
+            out[k++] = (float)number(key, tok);
+        }
+        if (k != count) throw Error(EKFVIO_EINVAL, "parameter " + key + ": needs " + std::to_string(count) + " numbers: " + v);
     }
 
     void set(std::string key, const std::string& value) {
@@ -161,6 +183,18 @@ struct Params {
             if (!(v > 0.f) || !std::isfinite(v)) throw Error(EKFVIO_EINVAL, "parameter " + key + ": not a finite value > 0: " + value);
             (key == "zupt_vel_variance" ? zupt_vel_variance : zupt_omega_variance) = v;
         }
+        else if (key == "imu_rotation") {  // (what ekfvio_set_imu_extrinsics would refuse is refused when the handle is made)
+            numbers(key, value, imu_rotation.data(), 9);
+            imu_extrinsics = 1;
+        }
+        else if (key == "imu_position") {
+            numbers(key, value, imu_position.data(), 3);
+            imu_extrinsics = 1;
+        }
+        else if (key == "gravity_align_samples") {
+            gravity_align_samples = integer(key, value);
+            if (gravity_align_samples < 0) throw Error(EKFVIO_EINVAL, "parameter gravity_align_samples: negative: " + value);
+        }
         else if (key == "distortion_k1") distortion[0] = number(key, value);
         else if (key == "distortion_k2") distortion[1] = number(key, value);
         else if (key == "distortion_p1") distortion[2] = number(key, value);
@@ -185,7 +219,7 @@ struct Params {
                                         "default_point_depth", "default_point_depth_variance",
                                         "default_point_homogenous_variance", "frame_buffer_size", "imu_update",
                                         "imu_gyro_variance", "imu_accel_variance", "gravity_x", "gravity_y", "gravity_z", "remove_lost", "gate_chi2",
-                                        "klt_fb_max_px", "rectify", "publish_covariance", "mask_rectify_border", "equalize_clip_limit", "equalize_tiles_x", "equalize_tiles_y", "klt_photometric", "publish_ids", "publish_ended", "zupt_max_flow_px", "zupt_min_tracks", "zupt_min_ratio", "zupt_vel_variance", "zupt_omega_variance", "distortion_k1", "distortion_k2", "distortion_p1", "distortion_p2", "distortion_k3"};
+                                        "klt_fb_max_px", "rectify", "publish_covariance", "mask_rectify_border", "equalize_clip_limit", "equalize_tiles_x", "equalize_tiles_y", "klt_photometric", "publish_ids", "publish_ended", "zupt_max_flow_px", "zupt_min_tracks", "zupt_min_ratio", "zupt_vel_variance", "zupt_omega_variance", "imu_rotation", "imu_position", "gravity_align_samples", "distortion_k1", "distortion_k2", "distortion_p1", "distortion_p2", "distortion_k3"};
         for (const auto& e : Params().node) out.push_back(e.first);
         for (const auto& e : ignored()) out.push_back(e.first);
         return out;
@@ -338,6 +372,21 @@ class TightlyCoupledEKF {
         chk(ekfvio_set_zupt(h_, max_flow_px, min_tracks, min_ratio, vel_variance, omega_variance));
     }
     void zuptUpdate(float vel_variance = 1e-4f, float omega_variance = 1e-4f) { chk(ekfvio_zupt_update(h_, vel_variance, omega_variance)); }
+    // Not in the reference: the IMU in its own frame (ekfvio_set_imu_extrinsics).  R_ci: nine floats, row-major, IMU -> camera axes (the rotation of
+    // Kalibr's T_cam_imu); p_ci: the IMU's origin in the camera frame, metres (its translation); both nullptr: off.  From the next IMU update on.
+    void setImuExtrinsics(const float* R_ci, const float* p_ci) { chk(ekfvio_set_imu_extrinsics(h_, R_ci, p_ci)); }
+    bool getImuExtrinsics(std::array<float, 9>& R_ci, std::array<float, 3>& p_ci) {
+        int32_t on = 0;
+        chk(ekfvio_get_imu_extrinsics(h_, R_ci.data(), p_ci.data(), &on));
+        return on != 0;
+    }
+    // ekfvio_set_gravity: the gravity vector in the filter's world frame replaces the configuration's from the next IMU update on.
+    void setGravity(const Vector3f& g) { chk(ekfvio_set_gravity(h_, g.data())); }
+    Vector3f getGravity() {
+        Vector3f g{};
+        chk(ekfvio_get_gravity(h_, g.data()));
+        return g;
+    }
     struct Zupt {
         std::vector<float> flow2;  // per landmark of the most recent frame's decision: squared pixel flow (-1: the tracker did not pass it)
         int32_t n_pass = 0, n_still = 0, applied_last = 0;
@@ -570,7 +619,10 @@ class EKFVIO {
    public:
     explicit EKFVIO(int max_features = 100, int device = 0, const ekfvio_config* cfg = nullptr)
         : tc_ekf(max_features, device, cfg), tracker(tc_ekf), use_imu_(cfg ? cfg->use_imu != 0 : false),
-          scale_(cfg && cfg->inverse_image_scale > 1 ? cfg->inverse_image_scale : 1) {}
+          scale_(cfg && cfg->inverse_image_scale > 1 ? cfg->inverse_image_scale : 1) {
+        if (cfg) gravity_magnitude_ = std::sqrt((double)cfg->gravity[0] * cfg->gravity[0] + (double)cfg->gravity[1] * cfg->gravity[1] +
+                                                (double)cfg->gravity[2] * cfg->gravity[2]);
+    }
     // the node's constructor (EKFVIO.cpp:19-67): parameters by the reference's names (see Params)
     explicit EKFVIO(const Params& p, int device = 0)
         : tc_ekf(p.cfg.max_features, device, &p.cfg), tracker(tc_ekf), params(p.node), use_imu_(p.cfg.use_imu != 0),
@@ -583,6 +635,25 @@ class EKFVIO {
         if (p.klt_photometric) tc_ekf.setKltPhotometric(true);  // (likewise)
         if (p.publish_ended) tc_ekf.setEndedExport(true);  // (likewise)
         if (p.zupt_max_flow_px > 0.f) tc_ekf.setZupt(p.zupt_max_flow_px, p.zupt_min_tracks, p.zupt_min_ratio, p.zupt_vel_variance, p.zupt_omega_variance);  // (likewise)
+        if (p.imu_extrinsics) tc_ekf.setImuExtrinsics(p.imu_rotation.data(), p.imu_position.data());  // (likewise)
+        gravity_magnitude_ = std::sqrt((double)p.cfg.gravity[0] * p.cfg.gravity[0] + (double)p.cfg.gravity[1] * p.cfg.gravity[1] +
+                                       (double)p.cfg.gravity[2] * p.cfg.gravity[2]);
+        setGravityAlignSamples(p.gravity_align_samples);
+    }
+    // K > 0: the next K IMU records that come up for application (drainImu) are not applied: their accelerometer readings are averaged in
+    // double precision, and behind the K-th the gravity vector is set from the mean (ekfvio_gravity_from_accel with the handle's R_ci and the
+    // configured gravity's magnitude; ekfvio_set_gravity).  The assumption: the rig stands still through them and the accelerometer's bias is
+    // negligible against 9.81.  Frames meanwhile are processed as without an IMU.  0: off.  Starts the averaging over.
+    void setGravityAlignSamples(int k) {
+        align_samples_ = align_left_ = k > 0 ? k : 0;
+        align_sum_[0] = align_sum_[1] = align_sum_[2] = 0.0;
+    }
+    // initializeBaseState, an empty IMU queue, and the gravity alignment starts over (the extrinsics and the gravity set so far stay)
+    void reset() {
+        tc_ekf.initializeBaseState();
+        imu_queue_.clear();
+        have_time_ = false;  // (ekfvio_reset forgets the filter's clock)
+        setGravityAlignSamples(align_samples_);
     }
     TightlyCoupledEKF tc_ekf;
     KLTTracker tracker;
@@ -701,6 +772,25 @@ class EKFVIO {
                 dropped_imu_++;
                 continue;
             }
+            if (align_left_ > 0) {  // the gravity alignment: averaged, not applied
+                for (int k = 0; k < 3; k++) align_sum_[k] += (double)r.accel[k];
+                align_left_--;
+                if (!have_time_) {  // the first message of all only sets the filter's clock (ekfvio_imu), as without the alignment
+                    tc_ekf.chk(ekfvio_imu(tc_ekf.handle(), r.stamp, r.gyro.data(), r.accel.data()));
+                    t_filter_ = r.stamp;
+                    have_time_ = true;
+                }
+                if (align_left_ == 0) {
+                    const double mean[3] = {align_sum_[0] / align_samples_, align_sum_[1] / align_samples_, align_sum_[2] / align_samples_};
+                    std::array<float, 9> R{};
+                    std::array<float, 3> p{};
+                    const bool on = tc_ekf.getImuExtrinsics(R, p);
+                    Vector3f g{};
+                    tc_ekf.chk(ekfvio_gravity_from_accel(on ? R.data() : nullptr, mean, (float)gravity_magnitude_, g.data()));
+                    tc_ekf.setGravity(g);
+                }
+                continue;
+            }
             tc_ekf.chk(ekfvio_imu(tc_ekf.handle(), r.stamp, r.gyro.data(), r.accel.data()));
             t_filter_ = r.stamp;
             have_time_ = true;
@@ -722,6 +812,9 @@ class EKFVIO {
     std::array<float, 9> last_K_{};
     std::deque<ImuRecord> imu_queue_;
     int dropped_imu_ = 0;
+    int align_samples_ = 0, align_left_ = 0;  // the gravity alignment: records to average in all, and still to come
+    double align_sum_[3] = {0.0, 0.0, 0.0};
+    double gravity_magnitude_ = 9.81;  // |cfg.gravity|
 };
 
 }  // namespace ekfvio

@@ -9,6 +9,7 @@
 //        ekfvio_replay --records <dir> [--out <dir>] [--params params.yaml] [--device n] [--insight] [--covariance]
 //                                [--equalize-clip-limit c] [--equalize-tiles-x n] [--equalize-tiles-y n] [--tracks FILE] [--ended FILE]
 //                                [--zupt-max-flow-px p] [--zupt-min-tracks n] [--zupt-min-ratio r] [--zupt-vel-variance v] [--zupt-omega-variance v]
+//                                [--imu-rotation "r00 r01 ... r22"] [--imu-position "x y z"] [--gravity-align-samples k]
 //
 // --records replays what the node's two subscriptions deliver (EKFVIO.cpp:69-81) and writes what its two publishers
 // send (EKFVIO.cpp:444-518), with no ROS in between.  <dir>/records.txt holds one record per line, in arrival order:
@@ -24,7 +25,9 @@
 // prints, per frame, the diagonals of the pose and twist covariances the node would put into nav_msgs/Odometry:
 //     cov <stamp> <6 pose variances: x y z rotX rotY rotZ> <6 twist variances: linear, angular>
 // --equalize-clip-limit / --equalize-tiles-x / --equalize-tiles-y are the node parameters of the same names (ekfvio_set_equalize), applied
-// behind the parameter file, and so are the five --zupt-* options (ekfvio_set_zupt; --print-config echoes the parameters).  --tracks FILE writes one line per live landmark per frame, behind the frame,
+// behind the parameter file, and so are the five --zupt-* options (ekfvio_set_zupt; --print-config echoes the parameters) and --imu-rotation (nine numbers, row-major,
+// IMU -> camera axes) / --imu-position (three numbers, metres) / --gravity-align-samples (ekfvio_set_imu_extrinsics, ekfvio_set_gravity: the node
+// parameters imu_rotation, imu_position, gravity_align_samples).  --tracks FILE writes one line per live landmark per frame, behind the frame,
 //     frame stamp id born x y z
 // (ekfvio_get_landmark_ids beside the cloud: one landmark's depth over time is the lines with its id).  --ended FILE turns the export of the
 // tracks that ended on (ekfvio_set_ended_export; the replay itself removes lost landmarks only with remove_lost: 1 in the parameter file) and
@@ -83,12 +86,15 @@ static int print_config(const char* path) {
                     "\"kill_pad\": %d, \"klt_min_eigen\": %.9g, \"min_new_feature_dist\": %d, \"klt_max_pyramid_level\": %d, "
                     "\"klt_window_size\": %d, \"default_point_depth\": %.9g, \"default_point_depth_variance\": %.9g, "
                     "\"default_point_homogenous_variance\": %.9g, \"sample_based_uncertainty\": %d, \"gate_chi2\": %.9g, "
-                    "\"klt_fb_max_px\": %.9g, \"rectify\": %d, \"publish_covariance\": %d, \"mask_rectify_border\": %d, \"equalize_clip_limit\": %.9g, \"equalize_tiles_x\": %d, \"equalize_tiles_y\": %d, \"klt_photometric\": %d, \"publish_ids\": %d, \"publish_ended\": %d, \"zupt_max_flow_px\": %.9g, \"zupt_min_tracks\": %d, \"zupt_min_ratio\": %.9g, \"zupt_vel_variance\": %.9g, \"zupt_omega_variance\": %.9g, \"distortion\": [%.17g, %.17g, %.17g, %.17g, %.17g], \"node\": {",
+                    "\"klt_fb_max_px\": %.9g, \"rectify\": %d, \"publish_covariance\": %d, \"mask_rectify_border\": %d, \"equalize_clip_limit\": %.9g, \"equalize_tiles_x\": %d, \"equalize_tiles_y\": %d, \"klt_photometric\": %d, \"publish_ids\": %d, \"publish_ended\": %d, \"zupt_max_flow_px\": %.9g, \"zupt_min_tracks\": %d, \"zupt_min_ratio\": %.9g, \"zupt_vel_variance\": %.9g, \"zupt_omega_variance\": %.9g, \"imu_extrinsics\": %d, \"imu_rotation\": [%.9g, %.9g, %.9g, %.9g, %.9g, %.9g, %.9g, %.9g, %.9g], \"imu_position\": [%.9g, %.9g, %.9g], \"gravity_align_samples\": %d, \"distortion\": [%.17g, %.17g, %.17g, %.17g, %.17g], \"node\": {",
                     c.max_features, c.fast_threshold, (double)c.fast_blur_sigma, c.inverse_image_scale, c.kill_pad,
                     (double)c.klt_min_eigen, c.min_new_feature_dist, c.klt_max_pyramid_level, c.klt_window_size,
                     (double)c.default_point_depth, (double)c.default_point_depth_variance,
                     (double)c.default_point_homogenous_variance, c.sample_based_uncertainty, (double)p.gate_chi2,
-                    (double)c.klt_fb_max_px, p.rectify, p.publish_covariance, p.mask_rectify_border, (double)p.equalize_clip_limit, p.equalize_tiles_x, p.equalize_tiles_y, p.klt_photometric, p.publish_ids, p.publish_ended, (double)p.zupt_max_flow_px, p.zupt_min_tracks, (double)p.zupt_min_ratio, (double)p.zupt_vel_variance, (double)p.zupt_omega_variance, p.distortion[0], p.distortion[1], p.distortion[2], p.distortion[3], p.distortion[4]);
+                    (double)c.klt_fb_max_px, p.rectify, p.publish_covariance, p.mask_rectify_border, (double)p.equalize_clip_limit, p.equalize_tiles_x, p.equalize_tiles_y, p.klt_photometric, p.publish_ids, p.publish_ended, (double)p.zupt_max_flow_px, p.zupt_min_tracks, (double)p.zupt_min_ratio, (double)p.zupt_vel_variance, (double)p.zupt_omega_variance, p.imu_extrinsics,
+                    (double)p.imu_rotation[0], (double)p.imu_rotation[1], (double)p.imu_rotation[2], (double)p.imu_rotation[3], (double)p.imu_rotation[4],
+                    (double)p.imu_rotation[5], (double)p.imu_rotation[6], (double)p.imu_rotation[7], (double)p.imu_rotation[8],
+                    (double)p.imu_position[0], (double)p.imu_position[1], (double)p.imu_position[2], p.gravity_align_samples, p.distortion[0], p.distortion[1], p.distortion[2], p.distortion[3], p.distortion[4]);
         bool first = true;
         for (const auto& e : p.node) {
             std::printf("%s\"%s\": \"%s\"", first ? "" : ", ", e.first.c_str(), e.second.c_str());
@@ -278,6 +284,9 @@ int main(int argc, char** argv) {
             else if (std::strcmp(argv[i], "--zupt-min-ratio") == 0) overrides.emplace_back("zupt_min_ratio", argv[i + 1]);
             else if (std::strcmp(argv[i], "--zupt-vel-variance") == 0) overrides.emplace_back("zupt_vel_variance", argv[i + 1]);
             else if (std::strcmp(argv[i], "--zupt-omega-variance") == 0) overrides.emplace_back("zupt_omega_variance", argv[i + 1]);
+            else if (std::strcmp(argv[i], "--imu-rotation") == 0) overrides.emplace_back("imu_rotation", argv[i + 1]);
+            else if (std::strcmp(argv[i], "--imu-position") == 0) overrides.emplace_back("imu_position", argv[i + 1]);
+            else if (std::strcmp(argv[i], "--gravity-align-samples") == 0) overrides.emplace_back("gravity_align_samples", argv[i + 1]);
             else {
                 std::fprintf(stderr, "unknown option %s\n", argv[i]);
                 return 2;

@@ -111,7 +111,11 @@ class EkfvioNode {
         // behind every frame as a second PointCloud on ended_topic, default invio/ended_points, with the channels "id", "born" (seconds before
         // the message's stamp: a float cannot hold a ROS stamp), "index_before" and the nine covariance entries "c00" .. "c22";
         // zupt_max_flow_px, default 0 = off, with zupt_min_tracks 8, zupt_min_ratio 0.75, zupt_vel_variance and zupt_omega_variance 1e-4: a frame
-        // whose tracks stand still updates the velocity and the body rate with z = 0 on the device, ekfvio_set_zupt, told at start-up likewise)
+        // whose tracks stand still updates the velocity and the body rate with z = 0 on the device, ekfvio_set_zupt, told at start-up likewise;
+        // imu_rotation, nine numbers row-major, and imu_position, three numbers in metres, each given as ONE STRING of numbers separated by
+        // blanks or commas (a YAML list is a parameter of unsupported type here): the rotation and translation of Kalibr's T_cam_imu,
+        // ekfvio_set_imu_extrinsics, so that imu_update models the IMU in its own frame; gravity_align_samples, default 0 = off: that many IMU
+        // records at the start are averaged, not applied, and set the gravity vector, ekfvio_set_gravity -- the rig has to stand still)
         for (const std::string& name : ekfvio::Params::names()) {
             XmlRpc::XmlRpcValue v;
             if (ros::param::get("~" + name, v)) params_.set(name, to_text(v));

@@ -604,6 +604,67 @@ EKFVIO_API int ekfvio_imu(ekfvio_filter* f, double stamp, const float gyro[3], c
 /* The update alone (no propagation), whatever cfg.use_imu says: for tests and callers that propagate themselves. */
 EKFVIO_API int ekfvio_imu_update(ekfvio_filter* f, const float gyro[3], const float accel[3]);
 
+/* ---- the IMU in its own frame; gravity at run time (not in the reference, which has no IMU update) -------------------------------------------
+ * The filter's body frame is the camera's optical frame (z forward, y down), and the model above takes the IMU's axes to be the camera's and
+ * the sensor to sit in the optical centre.  ekfvio_set_imu_extrinsics gives the update the calibration every visual-inertial rig has:
+ *
+ *     R_ci  row-major 3 x 3, maps IMU coordinates to camera coordinates, v_cam = R_ci v_imu: the rotation block of Kalibr's T_cam_imu
+ *     p_ci  the IMU's origin in the camera frame, metres: T_cam_imu's translation
+ *           (EuRoC's T_BS with B = IMU is the inverse transform: R_ci = R_BS^T, p_ci = -R_BS^T p_BS)
+ *
+ * With them h(x) = [M omega + b_gyr ; M (a + omega x (omega x p) - R(q)^T g) + b_acc], M = R_ci^T.  The biases live in the sensor's own axes
+ * (the IMU frame), where they physically are.  The accelerometer at p reads the centripetal term omega x (omega x p) more than the optical
+ * centre does; the angular-acceleration term alpha x p is NEGLECTED: the state has no alpha, the motion model holds omega constant between
+ * updates.  R = diag(gyro_var x3, accel_var x3) is isotropic per sensor and means the same in either frame.
+ *
+ * The lines below are the specification of the part in front of H and y; from H and y on the update is ekfvio_imu_update's, line for line
+ * (W = H Sigma, S = W H^T + R, Cholesky, the gains per state row over all sixteen columns, T, G, the mean, the quaternion's renormalisation,
+ * the Joseph pass).  Everything in fp32 without fused multiply-add, every sum associated as the brackets say; a NumPy restatement
+ * (tests/_imu_extrinsics.py: kernel_order_fp32_ext) is what the device and ekfvio_imu_model are held to, bit for bit.
+ * M[r][k] = R_ci[3 k + r]; w = mu[10..12], a = mu[13..15], p = p_ci; rg = R(q)^T g and jac = d rg / d(qw, qx, qy, qz) (3 x 4) as in the
+ * model without extrinsics; cross(u, v) = (u_1*v_2 - u_2*v_1, u_2*v_0 - u_0*v_2, u_0*v_1 - u_1*v_0).
+ *
+ *     t = cross(w, p)        c = cross(w, t)
+ *     s_k  = (a_k + c_k) - rg_k
+ *     hg_r = ((M[r][0]*w_0 + M[r][1]*w_1) + M[r][2]*w_2) + mu[19+r]
+ *     ha_r = ((M[r][0]*s_0 + M[r][1]*s_1) + M[r][2]*s_2) + mu[16+r]
+ *     y_r  = gyro_r - hg_r        y_{3+r} = accel_r - ha_r
+ *     d = (w_0*p_0 + w_1*p_1) + w_2*p_2
+ *     C[i][j] = (w_i*p_j - (2*p_i)*w_j) + (i == j ? d : nothing added)                                   = d c / d w
+ *     H on the sixteen state columns {3..6, 10..21}, position in that list in brackets, zero elsewhere:
+ *       gyro row r :  omega [4+k] = M[r][k]         b_gyr [13+r] = 1
+ *       accel row r:  q     [k]   = -((M[r][0]*jac[0][k] + M[r][1]*jac[1][k]) + M[r][2]*jac[2][k])      k = 0..3
+ *                     omega [4+k] =   (M[r][0]*C[0][k]   + M[r][1]*C[1][k])   + M[r][2]*C[2][k]         k = 0..2
+ *                     a     [7+k] = M[r][k]         b_acc [10+r] = 1
+ *
+ * ekfvio_set_imu_extrinsics.  Both pointers NULL: off (default; then no launch differs, nothing is allocated and every output keeps its
+ * bits).  One NULL and the other not, a non-finite entry, det(R_ci) <= 0, or max |R_ci R_ci^T - I| > 1e-3 (evaluated in fp64 from the fp32
+ * entries): EKFVIO_EINVAL, and the setting stays what it was.  The bound is a condition, not a measurement: a calibration printed to four
+ * decimals passes it; a row-major / column-major mix-up cannot be told from a rotation and passes too, but a reflection, a scaled matrix or
+ * the first nine numbers of a 4 x 4 with a translation in them do not; what it lets through scales gravity by at most about 1e-2 m/s^2,
+ * against an accelerometer sigma of 0.1.  The values are stored as given, not re-orthonormalised.  A property of the handle, not of
+ * ekfvio_config: it holds from the next IMU update (ekfvio_imu, ekfvio_imu_update), survives ekfvio_reset and drops no captured graph (the IMU
+ * update is in none).  On, the update stays two launches on sixteen state columns; only H and the residual get denser. */
+EKFVIO_API int ekfvio_set_imu_extrinsics(ekfvio_filter* f, const float R_ci[9], const float p_ci[3]);
+/* Reads the setting back (any pointer may be NULL): the values as given and *on = 1; with the setting off the identity, zeros and *on = 0. */
+EKFVIO_API int ekfvio_get_imu_extrinsics(ekfvio_filter* f, float R_ci[9], float p_ci[3], int32_t* on);
+/* Replaces cfg.gravity (the gravity vector in the filter's world frame, m/s^2) from the next IMU update on; survives ekfvio_reset.  cfg.gravity's
+ * default (0, 9.81, 0) assumes a camera that is level at the first frame; a rig that starts tilted has another g for its whole life (see
+ * ekfvio_gravity_from_accel).  A non-finite value: EKFVIO_EINVAL, and the setting stays.  ekfvio_get_gravity reads it back. */
+EKFVIO_API int ekfvio_set_gravity(ekfvio_filter* f, const float g[3]);
+EKFVIO_API int ekfvio_get_gravity(ekfvio_filter* f, float g[3]);
+/* The gravity vector in the camera frame of a rig AT REST whose accelerometer reads mean_accel on average (IMU axes; its bias negligible against
+ * 9.81): g = -(R_ci mean_accel) * (magnitude > 0 ? magnitude / |mean_accel| : 1), evaluated in fp64 and rounded to fp32.  That frame is the
+ * filter's world frame while q = (1, 0, 0, 0).  R_ci may be NULL: the identity.  A pure host function: no handle, no device.
+ * |mean_accel| == 0 or a non-finite input: EKFVIO_EINVAL. */
+EKFVIO_API int ekfvio_gravity_from_accel(const float R_ci[9], const double mean_accel[3], float magnitude, float g_out[3]);
+/* The model alone: the residual y[6] and the 6 x 16 Jacobian H (row-major, on the sixteen state columns {3..6, 10..21}) of one IMU record at
+ * the base state base_mu[22] with gravity g.  A pure host function (no handle, no device) that compiles the very inline functions the
+ * kernel compiles (csrc/imu_model.h), as ekfvio_zupt_decide and ekfvio_rectify_map do.  R_ci = p_ci = NULL: the model without extrinsics.
+ * A NULL among the other arguments, one of R_ci / p_ci NULL alone, or extrinsics that ekfvio_set_imu_extrinsics would refuse: EKFVIO_EINVAL. */
+EKFVIO_API int ekfvio_imu_model(const float base_mu[22], const float g[3], const float R_ci[9], const float p_ci[3], const float gyro[3],
+                                const float accel[3], float y[6], float H[96]);
+
 /* ---- zero-velocity update (not in the reference, whose filter learns that the camera stands still only through noisy pixel measurements of
  * landmarks at uncertain depth, against a motion model whose Q keeps re-inflating velocity, body rate and acceleration) --------------------
  * A decision per frame, on the device, from the tracker's results, and -- when it says the camera stands still -- a pseudo-measurement
