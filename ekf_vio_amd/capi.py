@@ -52,13 +52,17 @@ SYMBOLS = ["ekfvio_default_config", "ekfvio_create", "ekfvio_destroy", "ekfvio_r
            "ekfvio_get_landmark_ids", "ekfvio_set_ended_export", "ekfvio_get_ended",
            "ekfvio_set_zupt", "ekfvio_zupt_update", "ekfvio_get_zupt", "ekfvio_zupt_decide",
            "ekfvio_set_imu_extrinsics", "ekfvio_get_imu_extrinsics", "ekfvio_set_gravity", "ekfvio_get_gravity",
-           "ekfvio_gravity_from_accel", "ekfvio_imu_model"]
+           "ekfvio_gravity_from_accel", "ekfvio_imu_model",
+           "ekfvio_set_camera_model", "ekfvio_get_camera_model", "ekfvio_rectify_map_model", "ekfvio_mask_blocked_model"]
 MASK_RECTIFY_BORDER = 1  # EKFVIO_MASK_RECTIFY_BORDER
+CAMERA_PLUMB_BOB, CAMERA_RATIONAL, CAMERA_EQUIDISTANT = 0, 1, 2  # EKFVIO_CAMERA_*
+CAMERA_MODELS = {"plumb_bob": CAMERA_PLUMB_BOB, "rational_polynomial": CAMERA_RATIONAL, "rational": CAMERA_RATIONAL,
+                 "equidistant": CAMERA_EQUIDISTANT, "fisheye": CAMERA_EQUIDISTANT}  # CameraInfo.distortion_model's names
 # every symbol include/ekfvio_test_hooks.h declares (libekfvio_hip_hooks.so only)
 HOOK_SYMBOLS = ["ekfvio_test_klt_padded_level", "ekfvio_test_blurred_level0", "ekfvio_test_gemm", "ekfvio_test_gemm_bench", "ekfvio_test_potrf_stamps",
                 "ekfvio_test_sweep_stamps", "ekfvio_test_sweep_fault", "ekfvio_test_sweep_delay", "ekfvio_test_cholesky_solve", "ekfvio_test_plan", "ekfvio_test_persist_grid", "ekfvio_test_t2_pair",
                 "ekfvio_test_gemm_plan", "ekfvio_test_predict_plan", "ekfvio_test_run_plan", "ekfvio_test_mem", "ekfvio_test_mem_fail",
-                "ekfvio_test_fill_update_scratch", "ekfvio_test_zupt_decide"]
+                "ekfvio_test_fill_update_scratch", "ekfvio_test_zupt_decide", "ekfvio_test_rectify_map"]
 
 _libs = {}
 
@@ -127,6 +131,10 @@ def load(build_if_missing=True, hooks=False):
         "ekfvio_set_gravity": [vp, fp], "ekfvio_get_gravity": [vp, fp],
         "ekfvio_gravity_from_accel": [fp, C.POINTER(C.c_double), f32, fp],  # no handle, no device
         "ekfvio_imu_model": [fp, fp, fp, fp, fp, fp, fp, fp],  # no handle, no device
+        "ekfvio_set_camera_model": [vp, i32, C.POINTER(C.c_double), i32, fp],
+        "ekfvio_get_camera_model": [vp, ip, C.POINTER(C.c_double), ip, fp, ip, ip],
+        "ekfvio_rectify_map_model": [fp, i32, C.POINTER(C.c_double), i32, fp, i32, i32, ip, ip],  # no handle, no device
+        "ekfvio_mask_blocked_model": [fp, i32, C.POINTER(C.c_double), i32, fp, u8p, i32, i32, i32, i32, i32, i32, u8p],  # no handle, no device
     }
     if hooks:
         sig.update({
@@ -149,6 +157,7 @@ def load(build_if_missing=True, hooks=False):
             "ekfvio_test_mem_fail": [vp, i32],
             "ekfvio_test_fill_update_scratch": [vp, C.c_uint32],  # a word into the update's float work buffers: a handle with a history
             "ekfvio_test_zupt_decide": [vp, fp, fp, u8p, i32, f32, i32, f32, fp, ip, ip, ip],  # the device's zero-velocity decision on arbitrary points
+            "ekfvio_test_rectify_map": [vp, ip, ip, i32, ip, ip],  # the rectification map as the device holds it
         })
     for name, args in sig.items():
         fn = getattr(lib, name)

@@ -83,7 +83,9 @@ struct KltFrame {
 // What the rectification map of a handle was formed for (rectify.hip): compared as bits
 struct RectifyKey {
     float K[4];   // fx, cx, fy, cy of the K passed with the frame
-    double D[5];
+    double D[8];  // the model's coefficients in the caller's order
+    float P[4];   // fx', cx', fy', cy' where has_P, else zeros
+    int model, has_P;
     int w, h;
 };
 
@@ -287,8 +289,12 @@ struct ekfvio_filter {
     uint8_t* h_image = nullptr;    // pinned host staging: the caller's frame is copied here, so its buffer is free on return without a stream sync
     size_t src_cap = 0;            // bytes of staging / h_image (the uploaded, un-resized frame)
     // --- rectification of distorted frames (ekfvio_set_distortion; rectify.hip) ---
-    double dist[5] = {0, 0, 0, 0, 0};  // k1, k2, p1, p2, k3
-    bool rect_on = false;          // some coefficient is nonzero: frames pass rectify_kernel between the upload and the pyramid
+    double dist[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // the model's coefficients in the caller's order (ekfvio_set_camera_model), zeros behind dist_count
+    int dist_count = 0;            // the count the last setter was given
+    int cam_model = 0;             // EKFVIO_CAMERA_*: which instance of rectify_map_kernel forms the map
+    float cam_P[4] = {0, 0, 0, 0}; // fx', cx', fy', cy' of the rectified camera, where cam_has_P
+    bool cam_has_P = false;        // frames are rectified onto P, and everything behind the rectification takes P for the frame's K
+    bool rect_on = false;          // the setting is on (a coefficient, the equidistant model or P): frames pass rectify_kernel between the upload and the pyramid
     // (device memory: allocated with the first frame pushed while rect_on, ensure_frame_capacity in klt.hip)
     int* rect_sx = nullptr;        // [rect_cap + 16] the map, fixed point with 5 fractional bits; INT32_MIN: no source pixel
     int* rect_sy = nullptr;

@@ -1250,11 +1250,14 @@ int push_frame_enqueue(ekfvio_filter* f, const uint8_t* image, int32_t width, in
     f->cur ^= 1;  // the former current frame becomes the previous one (frame_buffer depth 2)
     KltFrame& fr = f->frames[f->cur];
     for (int i = 0; i < 9; i++) fr.K[i] = K[i];
+    // ekfvio_set_camera_model with P: the frame behind the rectification is the rectified camera's (rectify_enqueue alone keeps the K as passed)
+    if (f->cam_has_P) fr.K[0] = f->cam_P[0], fr.K[2] = f->cam_P[1], fr.K[4] = f->cam_P[2], fr.K[5] = f->cam_P[3];
     if (s > 1) {
-        fr.K[0] = (float)((double)K[0] / s);
-        fr.K[2] = (float)((double)K[2] / s);
-        fr.K[4] = (float)((double)K[4] / s);
-        fr.K[5] = (float)((double)K[5] / s);
+        const float k0 = fr.K[0], k2 = fr.K[2], k4 = fr.K[4], k5 = fr.K[5];
+        fr.K[0] = (float)((double)k0 / s);
+        fr.K[2] = (float)((double)k2 / s);
+        fr.K[4] = (float)((double)k4 / s);
+        fr.K[5] = (float)((double)k5 / s);
     }
     // ekfvio_set_distortion: the full-size frame is rectified first (with the K as passed), and the pyramid reads that plane instead
     const uint8_t* full = f->rect_on ? rectify_enqueue(f, f->staging, width, height, K, st) : f->staging;

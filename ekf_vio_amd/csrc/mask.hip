@@ -232,22 +232,20 @@ int ekfvio_get_mask_hits(ekfvio_filter* f, uint8_t* masked, int32_t* n_landmarks
 
 // B on the host, by the three steps as they are written: n per full-size pixel (the map entry from rectify_map_entry, the taps from
 // mask_tap_nodata), N per s x s block, then the window OR along rows and along columns (an OR over a rectangle is separable).
-int ekfvio_mask_blocked(const float K[9], const double* D, int32_t count, const uint8_t* mask, int32_t width, int32_t height, int32_t stride,
-                        int32_t inverse_image_scale, int32_t kill_pad, int32_t flags, uint8_t* blocked) {
-    double d[5];
+int ekfvio_mask_blocked_model(const float K[9], int32_t model, const double* D, int32_t count, const float P[4], const uint8_t* mask, int32_t width,
+                              int32_t height, int32_t stride, int32_t inverse_image_scale, int32_t kill_pad, int32_t flags, uint8_t* blocked) {
+    double d[8];
     if (!blocked || !mask_flags_ok(flags) || width < 1 || height < 1 || width > 16384 || height > 16384 || (mask && stride < width) ||
-        !rectify_coefficients(D, count, d))
+        !rectify_model_arguments(model, D, count, P, d))
         return EKFVIO_EINVAL;
     const int s = inverse_image_scale > 1 ? inverse_image_scale : 1, pad = mask_pad(kill_pad);
     const int W = width / s, H = height / s;
     if (W < 1 || H < 1) return EKFVIO_EINVAL;
-    bool border = false;
-    for (int i = 0; i < 5; i++) border = border || d[i] != 0.0;
-    border = border && (flags & EKFVIO_MASK_RECTIFY_BORDER);
+    const bool border = rectify_model_on(model, d, P) && (flags & EKFVIO_MASK_RECTIFY_BORDER);  // live as on the handle: flag set and the setting on
     if (border && !K) return EKFVIO_EINVAL;
     RectifyCam cam;
     memset(&cam, 0, sizeof(cam));
-    if (border) cam = rectify_cam(K, d);
+    if (border) cam = rectify_cam(K, model, d, P);
     std::vector<uint8_t> N((size_t)W * H, 0), Bh((size_t)W * H);
     for (int Y = 0; Y < H; Y++)
         for (int X = 0; X < W; X++) {
@@ -258,7 +256,7 @@ int ekfvio_mask_blocked(const float K[9], const double* D, int32_t count, const 
                     if (mask) nd = nd || mask[(size_t)y * stride + x] == 0;
                     if (border && !nd) {
                         int vx, vy;
-                        rectify_map_entry(cam, x, y, &vx, &vy);
+                        rectify_map_entry_of(model, cam, x, y, &vx, &vy);
                         nd = mask_tap_nodata(vx, vy, width, height);
                     }
                 }
@@ -268,6 +266,13 @@ int ekfvio_mask_blocked(const float K[9], const double* D, int32_t count, const 
     for (int Y = 0; Y < H; Y++) mask_window_or_line(N.data() + (size_t)Y * W, Bh.data() + (size_t)Y * W, W, 1, pad, pre);
     for (int X = 0; X < W; X++) mask_window_or_line(Bh.data() + X, blocked + X, H, (size_t)W, pad, pre);
     return EKFVIO_OK;
+}
+
+// the plumb_bob, no-P case
+int ekfvio_mask_blocked(const float K[9], const double* D, int32_t count, const uint8_t* mask, int32_t width, int32_t height, int32_t stride,
+                        int32_t inverse_image_scale, int32_t kill_pad, int32_t flags, uint8_t* blocked) {
+    return ekfvio_mask_blocked_model(K, EKFVIO_CAMERA_PLUMB_BOB, D, count, nullptr, mask, width, height, stride, inverse_image_scale, kill_pad, flags,
+                                     blocked);
 }
 
 }  // extern "C"

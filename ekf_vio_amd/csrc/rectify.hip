@@ -3,10 +3,12 @@
 // What a deployment of the reference runs in front of the node (image_proc/rectify: cv::initUndistortRectifyMap with R = I and the new
 // camera matrix = K, then cv::remap(INTER_LINEAR, BORDER_CONSTANT 0)); the reference itself assumes a pinhole image (Frame.h:31, its D at
 // :32 is never read; EKFVIO.cpp:429 "TODO add distortion coeffs").  The arithmetic is specified line by line in include/ekfvio.h
-// (ekfvio_set_distortion): rectify_map_entry (rectify_map.h) is that block, compiled for the host (ekfvio_rectify_map) and for the device
+// (ekfvio_set_distortion; ekfvio_set_camera_model for the rational and the equidistant lens and for a rectified camera P of its own):
+// rectify_map_entry (rectify_map.h) is that block, compiled for the host (ekfvio_rectify_map, ekfvio_rectify_map_model) and for the device
 // (rectify_map_kernel) out of the same lines, in fp64 without contraction, so that both give the bits of a NumPy restatement.
 //
-// Kernels: rectify_map_kernel writes the two fixed-point planes (once per camera: the host keeps the key it was formed for);
+// Kernels: rectify_map_kernel, one instance per camera model, writes the two fixed-point planes (once per camera: the host keeps the key
+// it was formed for; the lens model lives in the map alone, so what reads the planes is the same code for every lens);
 // rectify_kernel reads the uploaded frame through them and writes a second staging plane, which the pyramid kernel is then given in
 // place of the first.  With distortion off neither is launched and nothing is allocated.
 #include <math.h>
@@ -19,11 +21,12 @@ namespace {
 
 // The frame as ONE run of w * h pixels, the planes likewise (no pitch: every row of four entries is 16-byte aligned whatever the
 // width).  n4 = ceil(w h / 4) lanes' worth of entries are written; those behind the frame's last pixel hold the sentinel.
+template <int MODEL>
 __global__ __launch_bounds__(256) void rectify_map_kernel(RectifyCam c, int w, int npix, int n4, int* __restrict__ sx, int* __restrict__ sy) {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= 4 * n4) return;
     int vx = INT32_MIN, vy = INT32_MIN;
-    if (i < npix) rectify_map_entry(c, i % w, i / w, &vx, &vy);
+    if (i < npix) rectify_map_entry<MODEL>(c, i % w, i / w, &vx, &vy);
     sx[i] = vx;
     sy[i] = vy;
 }
@@ -84,13 +87,23 @@ const uint8_t* rectify_enqueue(ekfvio_filter* f, const uint8_t* src, int w, int 
     RectifyKey key;
     memset(&key, 0, sizeof(key));
     key.K[0] = K[0], key.K[1] = K[2], key.K[2] = K[4], key.K[3] = K[5];
-    for (int i = 0; i < 5; i++) key.D[i] = f->dist[i];
+    for (int i = 0; i < 8; i++) key.D[i] = f->dist[i];
+    key.model = f->cam_model, key.has_P = f->cam_has_P ? 1 : 0;
+    if (f->cam_has_P)
+        for (int i = 0; i < 4; i++) key.P[i] = f->cam_P[i];
     key.w = w, key.h = h;
     const int npix = w * h, n4 = (npix + 3) / 4;
     ProfScope ps(f, PC_KLT_PYRAMID);
     if (!f->rect_key_valid || memcmp(&key, &f->rect_key, sizeof(key)) != 0) {
-        hipLaunchKernelGGL(rectify_map_kernel, dim3((4 * n4 + 255) / 256), dim3(256), 0, st, rectify_cam(K, f->dist), w, npix, n4, f->rect_sx,
-                           f->rect_sy);
+        // one instance per model; the plumb_bob one with or without P (without: K twice)
+        const RectifyCam cam = rectify_cam(K, f->cam_model, f->dist, f->cam_has_P ? f->cam_P : nullptr);
+        const dim3 grid((4 * n4 + 255) / 256), block(256);
+        if (f->cam_model == EKFVIO_CAMERA_EQUIDISTANT)
+            hipLaunchKernelGGL(rectify_map_kernel<EKFVIO_CAMERA_EQUIDISTANT>, grid, block, 0, st, cam, w, npix, n4, f->rect_sx, f->rect_sy);
+        else if (f->cam_model == EKFVIO_CAMERA_RATIONAL)
+            hipLaunchKernelGGL(rectify_map_kernel<EKFVIO_CAMERA_RATIONAL>, grid, block, 0, st, cam, w, npix, n4, f->rect_sx, f->rect_sy);
+        else
+            hipLaunchKernelGGL(rectify_map_kernel<EKFVIO_CAMERA_PLUMB_BOB>, grid, block, 0, st, cam, w, npix, n4, f->rect_sx, f->rect_sy);
         f->rect_key = key;
         f->rect_key_valid = true;
         ps.launches = 2;
@@ -100,32 +113,87 @@ const uint8_t* rectify_enqueue(ekfvio_filter* f, const uint8_t* src, int w, int 
     return f->rect_img;
 }
 
-extern "C" {
+namespace {
 
-int ekfvio_set_distortion(ekfvio_filter* f, const double* D, int32_t count) {
-    double d[5];
-    if (!f || !rectify_coefficients(D, count, d)) return EKFVIO_EINVAL;
-    bool on = false;
-    for (int i = 0; i < 5; i++) {
-        f->dist[i] = d[i];
-        on = on || d[i] != 0.0;
-    }
-    f->rect_on = on;  // (read by the next pushed frame; frame ingest is in no captured graph)
+// the one setter behind ekfvio_set_distortion and ekfvio_set_camera_model (the last call wins)
+int set_camera_model(ekfvio_filter* f, int32_t model, const double* D, int32_t count, const float* P) {
+    double d[8];
+    if (!f || !rectify_model_arguments(model, D, count, P, d)) return EKFVIO_EINVAL;
+    for (int i = 0; i < 8; i++) f->dist[i] = d[i];
+    f->dist_count = count, f->cam_model = model;
+    f->cam_has_P = P != nullptr;
+    for (int i = 0; i < 4; i++) f->cam_P[i] = P ? P[i] : 0.f;
+    f->rect_on = rectify_model_on(model, d, P);  // (read by the next pushed frame; frame ingest is in no captured graph)
     return EKFVIO_OK;
 }
 
-int ekfvio_rectify_map(const float K[9], const double* D, int32_t count, int32_t width, int32_t height, int32_t* sx, int32_t* sy) {
-    double d[5];
-    if (!K || !sx || !sy || width < 1 || height < 1 || width > 16384 || height > 16384 || !rectify_coefficients(D, count, d)) return EKFVIO_EINVAL;
-    const RectifyCam c = rectify_cam(K, d);
+int rectify_map_host(const float K[9], int32_t model, const double D[8], const float* P, int32_t width, int32_t height, int32_t* sx, int32_t* sy) {
+    const RectifyCam c = rectify_cam(K, model, D, P);
     for (int y = 0; y < height; y++)
         for (int x = 0; x < width; x++) {
             int vx, vy;
-            rectify_map_entry(c, x, y, &vx, &vy);
+            rectify_map_entry_of(model, c, x, y, &vx, &vy);
             sx[(size_t)y * width + x] = vx;
             sy[(size_t)y * width + x] = vy;
         }
     return EKFVIO_OK;
 }
+
+}  // namespace
+
+extern "C" {
+
+int ekfvio_set_distortion(ekfvio_filter* f, const double* D, int32_t count) {
+    return set_camera_model(f, EKFVIO_CAMERA_PLUMB_BOB, D, count, nullptr);  // the plumb_bob, no-P case
+}
+
+int ekfvio_set_camera_model(ekfvio_filter* f, int32_t model, const double* D, int32_t count, const float P[4]) {
+    return set_camera_model(f, model, D, count, P);
+}
+
+int ekfvio_get_camera_model(ekfvio_filter* f, int32_t* model, double D[8], int32_t* count, float P[4], int32_t* has_P, int32_t* on) {
+    if (!f) return EKFVIO_EINVAL;
+    if (model) *model = f->cam_model;
+    if (D)
+        for (int i = 0; i < 8; i++) D[i] = f->dist[i];
+    if (count) *count = f->dist_count;
+    if (P)
+        for (int i = 0; i < 4; i++) P[i] = f->cam_P[i];
+    if (has_P) *has_P = f->cam_has_P ? 1 : 0;
+    if (on) *on = f->rect_on ? 1 : 0;
+    return EKFVIO_OK;
+}
+
+int ekfvio_rectify_map(const float K[9], const double* D, int32_t count, int32_t width, int32_t height, int32_t* sx, int32_t* sy) {
+    double d[8];
+    if (!K || !sx || !sy || width < 1 || height < 1 || width > 16384 || height > 16384 || !rectify_coefficients(D, count, d)) return EKFVIO_EINVAL;
+    return rectify_map_host(K, EKFVIO_CAMERA_PLUMB_BOB, d, nullptr, width, height, sx, sy);
+}
+
+int ekfvio_rectify_map_model(const float K[9], int32_t model, const double* D, int32_t count, const float P[4], int32_t width, int32_t height,
+                             int32_t* sx, int32_t* sy) {
+    double d[8];
+    if (!K || !sx || !sy || width < 1 || height < 1 || width > 16384 || height > 16384 || !rectify_model_arguments(model, D, count, P, d))
+        return EKFVIO_EINVAL;
+    return rectify_map_host(K, model, d, P, width, height, sx, sy);
+}
+
+#ifdef EKFVIO_TEST_HOOKS  // include/ekfvio_test_hooks.h: only in libekfvio_hip_hooks.so
+int ekfvio_test_rectify_map(ekfvio_filter* f, int32_t* sx, int32_t* sy, int32_t cap, int32_t* w, int32_t* h) {
+    if (!f || cap < 0) return EKFVIO_EINVAL;
+    if (!f->rect_key_valid) return EKFVIO_ESTATE;
+    const int W = f->rect_key.w, H = f->rect_key.h;
+    if (w) *w = W;
+    if (h) *h = H;
+    if (!sx || !sy) return EKFVIO_OK;
+    const size_t n = (size_t)W * H;
+    if ((size_t)cap < n || n > f->rect_cap) return EKFVIO_EINVAL;
+    HIP_TRY(f, hipSetDevice(f->device));
+    HIP_TRY(f, hipMemcpyAsync(sx, f->rect_sx, n * sizeof(int), hipMemcpyDeviceToHost, f->stream));
+    HIP_TRY(f, hipMemcpyAsync(sy, f->rect_sy, n * sizeof(int), hipMemcpyDeviceToHost, f->stream));
+    HIP_TRY(f, hipStreamSynchronize(f->stream));
+    return EKFVIO_OK;
+}
+#endif
 
 }  // extern "C"

@@ -27,7 +27,7 @@ class TightlyCoupledEKF:
                  default_point_depth=0.5, default_point_depth_variance=100.0,
                  default_point_homogenous_variance=1e-5, hooks=False, gate_chi2=0.0, klt_fb_max_px=0.0, distortion=None, output_covariance=False,
                  mask=None, mask_rectify_border=False, equalize=None, klt_photometric=False, ended_export=False, zupt=None,
-                 imu_extrinsics=None, **cfg_overrides):
+                 imu_extrinsics=None, camera_model=None, **cfg_overrides):
         # hooks=True: this handle lives in libekfvio_hip_hooks.so, the build that also has include/ekfvio_test_hooks.h (tests, profiling scripts)
         self.hooks = bool(hooks)
         self.lib = capi.load(hooks=self.hooks)
@@ -55,6 +55,8 @@ class TightlyCoupledEKF:
             self.setGate(gate_chi2)
         if distortion is not None:  # likewise a property of the handle (ekfvio_set_distortion)
             self.setDistortion(distortion)
+        if camera_model is not None:  # likewise (ekfvio_set_camera_model): (model, D[, P]); behind distortion=, so it wins
+            self.setCameraModel(*camera_model)
         if output_covariance:  # likewise (ekfvio_set_output_covariance)
             self.setOutputCovariance(True)
         if mask is not None or mask_rectify_border:  # likewise (ekfvio_set_mask)
@@ -281,6 +283,24 @@ class TightlyCoupledEKF:
         None, () or all zeros: off."""
         d = np.ascontiguousarray([] if D is None else D, dtype=np.float64).reshape(-1)
         self._chk(self.lib.ekfvio_set_distortion(self.h, d.ctypes.data_as(C.POINTER(C.c_double)) if d.size else None, int(d.size)))
+
+    def setCameraModel(self, model, D=None, P=None):
+        """Not in the reference: the camera's lens model and, optionally, the rectified camera (ekfvio_set_camera_model).  model:
+        capi.CAMERA_PLUMB_BOB / CAMERA_RATIONAL / CAMERA_EQUIDISTANT or CameraInfo.distortion_model's name ("plumb_bob",
+        "rational_polynomial", "equidistant", "fisheye"); D: 0, 4 or 5 / 8 / 4 coefficients; P: (fx', cx', fy', cy') of the rectified image
+        or None for the raw camera's own K.  From the next pushed frame on frames are rectified through that model onto P, and everything
+        behind the rectification takes P for the frame's intrinsics.  The last of setDistortion and setCameraModel wins."""
+        m, d, p = _camera_model_args(model, D, P)
+        self._chk(self.lib.ekfvio_set_camera_model(self.h, m, d.ctypes.data_as(C.POINTER(C.c_double)) if d.size else None, int(d.size),
+                                                   None if p is None else _fp(p)))
+
+    def cameraModel(self):
+        """ekfvio_get_camera_model: dict(model, D[count], P (4 floats or None), on) as the handle holds the setting."""
+        m, n, has, on = C.c_int32(0), C.c_int32(0), C.c_int32(0), C.c_int32(0)
+        d, p = np.zeros(8, np.float64), np.zeros(4, np.float32)
+        self._chk(self.lib.ekfvio_get_camera_model(self.h, C.byref(m), d.ctypes.data_as(C.POINTER(C.c_double)), C.byref(n), _fp(p), C.byref(has),
+                                                   C.byref(on)))
+        return dict(model=int(m.value), D=d[:n.value].copy(), P=p if has.value else None, on=bool(on.value))
 
     def setMask(self, mask, rectify_border=False):
         """Not in the reference, which passes no mask to cv::FAST: the no-data mask (ekfvio_set_mask).  mask: uint8 [height, width] at the FULL
@@ -596,6 +616,55 @@ def rectify_map(K, D, width, height):
     return sx, sy
 
 
+def _camera_model_args(model, D, P):
+    """(model as int32, D as float64 [count], P as float32 [4] or None) of the camera-model entry points; a model's name is looked up."""
+    if isinstance(model, str):
+        if model not in capi.CAMERA_MODELS:
+            raise capi.EkfvioError(capi.EINVAL, "unknown camera model %r" % model)
+        model = capi.CAMERA_MODELS[model]
+    d = np.ascontiguousarray([] if D is None else D, dtype=np.float64).reshape(-1)
+    p = None if P is None else np.ascontiguousarray(P, dtype=np.float32).reshape(-1)
+    if p is not None and p.size != 4:
+        raise capi.EkfvioError(capi.EINVAL, "P is (fx', cx', fy', cy')")
+    return int(model), d, p
+
+
+def rectify_map_model(K, model, D, P, width, height):
+    """ekfvio_rectify_map_model: rectify_map for any camera model (TightlyCoupledEKF.setCameraModel's model, D, P).  A host function: no GPU
+    involved."""
+    lib = capi.load()
+    K = np.ascontiguousarray(K, dtype=np.float32).reshape(9)
+    m, d, p = _camera_model_args(model, D, P)
+    sx, sy = np.zeros((int(height), int(width)), np.int32), np.zeros((int(height), int(width)), np.int32)
+    rc = lib.ekfvio_rectify_map_model(_fp(K), m, d.ctypes.data_as(C.POINTER(C.c_double)) if d.size else None, int(d.size),
+                                      None if p is None else _fp(p), int(width), int(height), _ip(sx), _ip(sy))
+    if rc != capi.OK:
+        raise capi.EkfvioError(rc, "ekfvio_rectify_map_model")
+    return sx, sy
+
+
+def mask_blocked_model(K, model, D, P, mask, width, height, inverse_image_scale, kill_pad, flags):
+    """ekfvio_mask_blocked_model: mask_blocked for any camera model (model, D, P as rectify_map_model takes them).  A host function: no GPU
+    involved."""
+    lib = capi.load()
+    Kp = None if K is None else _fp(np.ascontiguousarray(K, dtype=np.float32).reshape(9))
+    m, d, p = _camera_model_args(model, D, P)
+    mp, stride = None, 0
+    if mask is not None:
+        mk = np.asarray(mask)
+        if mk.dtype != np.uint8 or mk.ndim != 2 or mk.strides[1] != 1 or mk.shape != (int(height), int(width)):
+            mk = np.ascontiguousarray(mk, dtype=np.uint8).reshape(int(height), int(width))
+        mp, stride = C.cast(mk.ctypes.data, C.POINTER(C.c_uint8)), int(mk.strides[0])
+    s = max(int(inverse_image_scale), 1)
+    out = np.zeros((max(int(height) // s, 0), max(int(width) // s, 0)), np.uint8)
+    rc = lib.ekfvio_mask_blocked_model(Kp, m, d.ctypes.data_as(C.POINTER(C.c_double)) if d.size else None, int(d.size),
+                                       None if p is None else _fp(p), mp, int(width), int(height), stride, int(inverse_image_scale), int(kill_pad),
+                                       int(flags), _u8(out) if out.size else None)
+    if rc != capi.OK:
+        raise capi.EkfvioError(rc, "ekfvio_mask_blocked_model")
+    return out
+
+
 def mask_blocked(K, D, mask, width, height, inverse_image_scale, kill_pad, flags):
     """ekfvio_mask_blocked: the blocked map B (include/ekfvio.h, ekfvio_set_mask), uint8 [height // s, width // s], that a handle with these
     settings holds for width x height frames: K, D as rectify_map takes them, mask uint8 [height, width] or None (any row stride of the array is
@@ -657,7 +726,8 @@ class EKFVIO:
     on the device; otherwise call replenishFeatures() (or addNewFeatures) yourself."""
 
     def __init__(self, **kw):
-        # (distortion=(k1, k2, p1, p2[, k3]): raw frames are rectified on the device, setDistortion below; output_covariance=True: every frame's
+        # (distortion=(k1, k2, p1, p2[, k3]): raw frames are rectified on the device, setDistortion below; camera_model=(model, D[, P]): the
+        # same for a rational or an equidistant lens and onto a rectified camera P, setCameraModel below; output_covariance=True: every frame's
         # outputs carry their covariances, setOutputCovariance below; mask=uint8 [h, w] and / or mask_rectify_border=True: the no-data mask, setMask below;
         # equalize=(clip_limit, tiles_x, tiles_y): every frame is equalised on the device before its pyramid, setEqualize below;
         # klt_photometric=True: the tracker's gain/offset term, setKltPhotometric below; ended_export=True: every removal hands out the records of
@@ -732,6 +802,11 @@ class EKFVIO:
     def setDistortion(self, D):
         """The camera's plumb_bob coefficients (TightlyCoupledEKF.setDistortion): from the next frame on addFrame takes raw frames."""
         self.tc_ekf.setDistortion(D)
+
+    def setCameraModel(self, model, D=None, P=None):
+        """The camera's lens model and the rectified camera (TightlyCoupledEKF.setCameraModel): from the next frame on addFrame takes raw
+        frames of that lens; K stays the raw camera's, and with P the outputs are the rectified camera's."""
+        self.tc_ekf.setCameraModel(model, D, P)
 
     def setMask(self, mask, rectify_border=False):
         """TightlyCoupledEKF.setMask: from the next frame on no landmark is taken or passed within the kill-pad window of a no-data pixel."""
@@ -846,8 +921,9 @@ class EKFVIO:
         h, w = grey.shape
         out = np.repeat(grey[:, :, None], 3, axis=2).copy()
         s = max(int(self.tc_ekf.cfg.inverse_image_scale), 1)
-        fx = np.float32(np.float64(self._last_K[0]) / s)
-        fy = np.float32(np.float64(self._last_K[4]) / s)
+        P = self.tc_ekf.cameraModel()["P"]  # (fx', cx', fy', cy') where set: level 0 is then the rectified camera's image
+        fx = np.float32(np.float64(self._last_K[0] if P is None else P[0]) / s)
+        fy = np.float32(np.float64(self._last_K[4] if P is None else P[2]) / s)
         st = self.tc_ekf.get_state()
         for (u, v, _), flag in zip(st["feat_mu"], st["del_flag"]):
             if flag:

@@ -52,6 +52,29 @@ struct Params {
     // CameraInfo.D (the ROS node) or from the distortion_* parameters (a caller without CameraInfo, the replay driver); all zero = off.
     int rectify = 0;
     std::array<double, 5> distortion{};
+    // Other lenses, another rectified camera (ekfvio_set_camera_model).  distortion_model: CameraInfo.distortion_model's names, "plumb_bob"
+    // (default), "rational_polynomial" (k1 k2 p1 p2 k3 k4 k5 k6) or "equidistant" / "fisheye" (k1 k2 k3 k4); distortion_k4..k6 are the
+    // coefficients the plumb_bob parameters lack.  rectified_fx/fy/cx/cy: the intrinsics P of the RECTIFIED image (CameraInfo.P); taken once
+    // rectified_fx and rectified_fy are positive, otherwise frames are rectified onto the raw camera's own K.
+    std::string distortion_model = "plumb_bob";
+    std::array<double, 3> distortion_k456{};
+    std::array<float, 4> rectified{};  // fx', cx', fy', cy'
+    bool rectifiedSet() const { return rectified[0] > 0.f && rectified[2] > 0.f; }
+    // CameraInfo.distortion_model's name -> EKFVIO_CAMERA_*; -1: a model the device does not know
+    static int cameraModelOf(const std::string& name) {
+        if (name == "plumb_bob") return EKFVIO_CAMERA_PLUMB_BOB;
+        if (name == "rational_polynomial") return EKFVIO_CAMERA_RATIONAL;
+        if (name == "equidistant" || name == "fisheye") return EKFVIO_CAMERA_EQUIDISTANT;
+        return -1;
+    }
+    // the coefficients of the distortion_* parameters in the order ekfvio_set_camera_model takes them for distortion_model
+    std::vector<double> cameraCoefficients() const {
+        const int m = cameraModelOf(distortion_model);
+        if (m == EKFVIO_CAMERA_EQUIDISTANT) return {distortion[0], distortion[1], distortion[4], distortion_k456[0]};
+        std::vector<double> D(distortion.begin(), distortion.end());
+        if (m == EKFVIO_CAMERA_RATIONAL) D.insert(D.end(), distortion_k456.begin(), distortion_k456.end());
+        return D;
+    }
     // Not in the reference, which publishes all-zero covariances (EKFVIO.cpp:473): with publish_covariance = 1 every frame carries the covariances of
     // its odometry and point cloud (ekfvio_set_output_covariance) and the node fills nav_msgs/Odometry's two 6x6 blocks from them.
     int publish_covariance = 0;
@@ -200,6 +223,19 @@ struct Params {
         else if (key == "distortion_p1") distortion[2] = number(key, value);
         else if (key == "distortion_p2") distortion[3] = number(key, value);
         else if (key == "distortion_k3") distortion[4] = number(key, value);
+        else if (key == "distortion_k4") distortion_k456[0] = number(key, value);
+        else if (key == "distortion_k5") distortion_k456[1] = number(key, value);
+        else if (key == "distortion_k6") distortion_k456[2] = number(key, value);
+        else if (key == "distortion_model") {
+            if (cameraModelOf(value) < 0) throw Error(EKFVIO_EINVAL, "parameter distortion_model: not plumb_bob, rational_polynomial, equidistant or fisheye: " + value);
+            distortion_model = value;
+        }
+        else if (key == "rectified_fx" || key == "rectified_cx" || key == "rectified_fy" || key == "rectified_cy") {
+            const float v = (float)number(key, value);
+            if (!std::isfinite(v) || ((key == "rectified_fx" || key == "rectified_fy") && v < 0.f))
+                throw Error(EKFVIO_EINVAL, "parameter " + key + ": not a finite value (a focal length: >= 0, 0 = unset): " + value);
+            rectified[key == "rectified_fx" ? 0 : key == "rectified_cx" ? 1 : key == "rectified_fy" ? 2 : 3] = v;
+        }
         else if (key == "imu_gyro_variance") cfg.imu_gyro_variance = (float)number(key, value);
         else if (key == "imu_accel_variance") cfg.imu_accel_variance = (float)number(key, value);
         else if (key == "gravity_x") cfg.gravity[0] = (float)number(key, value);
@@ -219,7 +255,8 @@ struct Params {
                                         "default_point_depth", "default_point_depth_variance",
                                         "default_point_homogenous_variance", "frame_buffer_size", "imu_update",
                                         "imu_gyro_variance", "imu_accel_variance", "gravity_x", "gravity_y", "gravity_z", "remove_lost", "gate_chi2",
-                                        "klt_fb_max_px", "rectify", "publish_covariance", "mask_rectify_border", "equalize_clip_limit", "equalize_tiles_x", "equalize_tiles_y", "klt_photometric", "publish_ids", "publish_ended", "zupt_max_flow_px", "zupt_min_tracks", "zupt_min_ratio", "zupt_vel_variance", "zupt_omega_variance", "imu_rotation", "imu_position", "gravity_align_samples", "distortion_k1", "distortion_k2", "distortion_p1", "distortion_p2", "distortion_k3"};
+                                        "klt_fb_max_px", "rectify", "publish_covariance", "mask_rectify_border", "equalize_clip_limit", "equalize_tiles_x", "equalize_tiles_y", "klt_photometric", "publish_ids", "publish_ended", "zupt_max_flow_px", "zupt_min_tracks", "zupt_min_ratio", "zupt_vel_variance", "zupt_omega_variance", "imu_rotation", "imu_position", "gravity_align_samples", "distortion_k1", "distortion_k2", "distortion_p1", "distortion_p2", "distortion_k3",
+                                        "distortion_model", "distortion_k4", "distortion_k5", "distortion_k6", "rectified_fx", "rectified_fy", "rectified_cx", "rectified_cy"};
         for (const auto& e : Params().node) out.push_back(e.first);
         for (const auto& e : ignored()) out.push_back(e.first);
         return out;
@@ -355,6 +392,18 @@ class TightlyCoupledEKF {
     // Not in the reference, which assumes a pinhole image (Frame.h:31): the camera's plumb_bob coefficients k1 k2 p1 p2 [k3] (ekfvio_set_distortion).
     // From the next frame on, frames are rectified on the device between the upload and the pyramid; empty or all zero: off.
     void setDistortion(const std::vector<double>& D) { chk(ekfvio_set_distortion(h_, D.empty() ? nullptr : D.data(), (int32_t)D.size())); }
+    // Not in the reference: the camera's lens model (EKFVIO_CAMERA_PLUMB_BOB with 0, 4 or 5 coefficients, EKFVIO_CAMERA_RATIONAL with 8,
+    // EKFVIO_CAMERA_EQUIDISTANT with 4) and, optionally, the rectified camera P = fx', cx', fy', cy' (nullptr: the raw camera's own K)
+    // (ekfvio_set_camera_model).  With P, everything behind the rectification takes P for the frame's intrinsics.  The last of the two setters wins.
+    void setCameraModel(int model, const std::vector<double>& D, const float* P = nullptr) {
+        chk(ekfvio_set_camera_model(h_, model, D.empty() ? nullptr : D.data(), (int32_t)D.size(), P));
+    }
+    // the rectified camera where one is set (ekfvio_get_camera_model): what level 0 of a pushed frame is then the image of
+    bool rectifiedCamera(float P[4]) {
+        int32_t has = 0;
+        chk(ekfvio_get_camera_model(h_, nullptr, nullptr, nullptr, P, &has, nullptr));
+        return has != 0;
+    }
     // Not in the reference, which passes no mask to cv::FAST: the no-data mask (ekfvio_set_mask).  mask: w x h bytes at the FULL frame size with a row
     // stride, nonzero = scene, or nullptr (w = h = stride = 0); flags: EKFVIO_MASK_RECTIFY_BORDER or 0.  From the next frame on no landmark is
     // detected or passed within the kill-pad window of a no-data pixel; nullptr and 0: off.  While a mask is set, frames of another size are refused.
@@ -628,7 +677,11 @@ class EKFVIO {
         : tc_ekf(p.cfg.max_features, device, &p.cfg), tracker(tc_ekf), params(p.node), use_imu_(p.cfg.use_imu != 0),
           scale_(p.cfg.inverse_image_scale > 1 ? p.cfg.inverse_image_scale : 1) {
         if (p.gate_chi2 > 0.f) tc_ekf.setGate(p.gate_chi2);  // (behind ekfvio_create: the gate is a property of the handle)
-        if (p.rectify) tc_ekf.setDistortion(std::vector<double>(p.distortion.begin(), p.distortion.end()));  // (likewise; a node replaces them with CameraInfo.D)
+        // (likewise; a node replaces them with CameraInfo.D.  The plumb_bob model without a rectified camera stays ekfvio_set_distortion's call)
+        if (p.rectify && Params::cameraModelOf(p.distortion_model) == EKFVIO_CAMERA_PLUMB_BOB && !p.rectifiedSet())
+            tc_ekf.setDistortion(std::vector<double>(p.distortion.begin(), p.distortion.end()));
+        else if (p.rectify)
+            tc_ekf.setCameraModel(Params::cameraModelOf(p.distortion_model), p.cameraCoefficients(), p.rectifiedSet() ? p.rectified.data() : nullptr);
         if (p.publish_covariance) tc_ekf.setOutputCovariance(true);  // (likewise)
         if (p.mask_rectify_border) tc_ekf.setMask(nullptr, 0, 0, 0, EKFVIO_MASK_RECTIFY_BORDER);  // (likewise; live once the coefficients are nonzero)
         if (p.equalize_clip_limit > 0.f) tc_ekf.setEqualize(p.equalize_clip_limit, p.equalize_tiles_x, p.equalize_tiles_y);  // (likewise)
@@ -716,8 +769,11 @@ class EKFVIO {
         o.bgr.resize((size_t)w * h * 3);
         for (size_t i = 0; i < grey.size(); i++) o.bgr[3 * i] = o.bgr[3 * i + 1] = o.bgr[3 * i + 2] = grey[i];  // CV_GRAY2BGR
         // Frame::Frame's K (Frame.cpp:26-33), then Feature::getPixel with the K(2) / K(5) indexing quirk (Feature.h:60-66)
-        const float fx = (float)((double)last_K_[0] / scale_), fy = (float)((double)last_K_[4] / scale_);
-        const float cx = (float)((double)last_K_[2] / scale_), cy = (float)((double)last_K_[5] / scale_);
+        // (with a rectified camera set, ekfvio_set_camera_model, the frame is that camera's: P in K's places)
+        float P[4];
+        const bool hasP = tc_ekf.rectifiedCamera(P);
+        const float fx = (float)((double)(hasP ? P[0] : last_K_[0]) / scale_), fy = (float)((double)(hasP ? P[2] : last_K_[4]) / scale_);
+        const float cx = (float)((double)(hasP ? P[1] : last_K_[2]) / scale_), cy = (float)((double)(hasP ? P[3] : last_K_[5]) / scale_);
         const std::vector<Vector3f> mus = tc_ekf.featureMus();
         const std::vector<uint8_t> flags = tc_ekf.deleteFlags();
         auto put = [&](int x, int y) {

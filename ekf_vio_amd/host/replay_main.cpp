@@ -10,7 +10,11 @@
 //                                [--equalize-clip-limit c] [--equalize-tiles-x n] [--equalize-tiles-y n] [--tracks FILE] [--ended FILE]
 //                                [--zupt-max-flow-px p] [--zupt-min-tracks n] [--zupt-min-ratio r] [--zupt-vel-variance v] [--zupt-omega-variance v]
 //                                [--imu-rotation "r00 r01 ... r22"] [--imu-position "x y z"] [--gravity-align-samples k]
+//                                [--distortion-model plumb_bob|rational_polynomial|equidistant|fisheye] [--rectified-camera "fx fy cx cy"]
 //
+// --distortion-model and --rectified-camera are the node parameters distortion_model and rectified_fx/fy/cx/cy (ekfvio_set_camera_model; live
+// with rectify: 1 and the distortion_* coefficients in the parameter file): the records' K stays the raw camera's, the outputs are the
+// rectified camera's.
 // --records replays what the node's two subscriptions deliver (EKFVIO.cpp:69-81) and writes what its two publishers
 // send (EKFVIO.cpp:444-518), with no ROS in between.  <dir>/records.txt holds one record per line, in arrival order:
 //     image <stamp> <file> <K0> ... <K8>      8-bit binary PGM (P5), intrinsics row-major as in sensor_msgs/CameraInfo.K
@@ -86,7 +90,7 @@ static int print_config(const char* path) {
                     "\"kill_pad\": %d, \"klt_min_eigen\": %.9g, \"min_new_feature_dist\": %d, \"klt_max_pyramid_level\": %d, "
                     "\"klt_window_size\": %d, \"default_point_depth\": %.9g, \"default_point_depth_variance\": %.9g, "
                     "\"default_point_homogenous_variance\": %.9g, \"sample_based_uncertainty\": %d, \"gate_chi2\": %.9g, "
-                    "\"klt_fb_max_px\": %.9g, \"rectify\": %d, \"publish_covariance\": %d, \"mask_rectify_border\": %d, \"equalize_clip_limit\": %.9g, \"equalize_tiles_x\": %d, \"equalize_tiles_y\": %d, \"klt_photometric\": %d, \"publish_ids\": %d, \"publish_ended\": %d, \"zupt_max_flow_px\": %.9g, \"zupt_min_tracks\": %d, \"zupt_min_ratio\": %.9g, \"zupt_vel_variance\": %.9g, \"zupt_omega_variance\": %.9g, \"imu_extrinsics\": %d, \"imu_rotation\": [%.9g, %.9g, %.9g, %.9g, %.9g, %.9g, %.9g, %.9g, %.9g], \"imu_position\": [%.9g, %.9g, %.9g], \"gravity_align_samples\": %d, \"distortion\": [%.17g, %.17g, %.17g, %.17g, %.17g], \"node\": {",
+                    "\"klt_fb_max_px\": %.9g, \"rectify\": %d, \"publish_covariance\": %d, \"mask_rectify_border\": %d, \"equalize_clip_limit\": %.9g, \"equalize_tiles_x\": %d, \"equalize_tiles_y\": %d, \"klt_photometric\": %d, \"publish_ids\": %d, \"publish_ended\": %d, \"zupt_max_flow_px\": %.9g, \"zupt_min_tracks\": %d, \"zupt_min_ratio\": %.9g, \"zupt_vel_variance\": %.9g, \"zupt_omega_variance\": %.9g, \"imu_extrinsics\": %d, \"imu_rotation\": [%.9g, %.9g, %.9g, %.9g, %.9g, %.9g, %.9g, %.9g, %.9g], \"imu_position\": [%.9g, %.9g, %.9g], \"gravity_align_samples\": %d, \"distortion\": [%.17g, %.17g, %.17g, %.17g, %.17g], \"distortion_model\": \"%s\", \"distortion_k456\": [%.17g, %.17g, %.17g], \"rectified\": [%.9g, %.9g, %.9g, %.9g], \"node\": {",
                     c.max_features, c.fast_threshold, (double)c.fast_blur_sigma, c.inverse_image_scale, c.kill_pad,
                     (double)c.klt_min_eigen, c.min_new_feature_dist, c.klt_max_pyramid_level, c.klt_window_size,
                     (double)c.default_point_depth, (double)c.default_point_depth_variance,
@@ -94,7 +98,9 @@ static int print_config(const char* path) {
                     (double)c.klt_fb_max_px, p.rectify, p.publish_covariance, p.mask_rectify_border, (double)p.equalize_clip_limit, p.equalize_tiles_x, p.equalize_tiles_y, p.klt_photometric, p.publish_ids, p.publish_ended, (double)p.zupt_max_flow_px, p.zupt_min_tracks, (double)p.zupt_min_ratio, (double)p.zupt_vel_variance, (double)p.zupt_omega_variance, p.imu_extrinsics,
                     (double)p.imu_rotation[0], (double)p.imu_rotation[1], (double)p.imu_rotation[2], (double)p.imu_rotation[3], (double)p.imu_rotation[4],
                     (double)p.imu_rotation[5], (double)p.imu_rotation[6], (double)p.imu_rotation[7], (double)p.imu_rotation[8],
-                    (double)p.imu_position[0], (double)p.imu_position[1], (double)p.imu_position[2], p.gravity_align_samples, p.distortion[0], p.distortion[1], p.distortion[2], p.distortion[3], p.distortion[4]);
+                    (double)p.imu_position[0], (double)p.imu_position[1], (double)p.imu_position[2], p.gravity_align_samples, p.distortion[0], p.distortion[1], p.distortion[2], p.distortion[3], p.distortion[4],
+                    p.distortion_model.c_str(), p.distortion_k456[0], p.distortion_k456[1], p.distortion_k456[2],
+                    (double)p.rectified[0], (double)p.rectified[1], (double)p.rectified[2], (double)p.rectified[3]);
         bool first = true;
         for (const auto& e : p.node) {
             std::printf("%s\"%s\": \"%s\"", first ? "" : ", ", e.first.c_str(), e.second.c_str());
@@ -287,6 +293,17 @@ int main(int argc, char** argv) {
             else if (std::strcmp(argv[i], "--imu-rotation") == 0) overrides.emplace_back("imu_rotation", argv[i + 1]);
             else if (std::strcmp(argv[i], "--imu-position") == 0) overrides.emplace_back("imu_position", argv[i + 1]);
             else if (std::strcmp(argv[i], "--gravity-align-samples") == 0) overrides.emplace_back("gravity_align_samples", argv[i + 1]);
+            else if (std::strcmp(argv[i], "--distortion-model") == 0) overrides.emplace_back("distortion_model", argv[i + 1]);
+            else if (std::strcmp(argv[i], "--rectified-camera") == 0) {  // "fx fy cx cy": the four rectified_* parameters
+                std::istringstream in(argv[i + 1]);
+                std::string tok[4], extra;
+                if (!(in >> tok[0] >> tok[1] >> tok[2] >> tok[3]) || (in >> extra)) {
+                    std::fprintf(stderr, "option --rectified-camera needs \"fx fy cx cy\"\n");
+                    return 2;
+                }
+                const char* names[4] = {"rectified_fx", "rectified_fy", "rectified_cx", "rectified_cy"};
+                for (int k = 0; k < 4; k++) overrides.emplace_back(names[k], tok[k]);
+            }
             else {
                 std::fprintf(stderr, "unknown option %s\n", argv[i]);
                 return 2;

@@ -123,6 +123,9 @@ class EkfvioNode {
         params_.cfg.replenish = 1;  // addFrame runs replenishFeatures itself (EKFVIO.cpp:154, :172)
         int device = 0;
         ros::param::param<int>("~hip_device", device, 0);
+        // rectify_use_p, default false: with rectify = 1 the frames are rectified onto CameraInfo.P (the calibration's rectified camera) instead
+        // of the raw camera's K, and odometry, cloud and insight are that camera's (ekfvio_set_camera_model)
+        ros::param::param<bool>("~rectify_use_p", rectify_use_p_, false);
         vio_.reset(new ekfvio::EKFVIO(params_, device));
         const auto& p = params_.node;
         cam_sub_ = it_.subscribeCamera(p.at("camera_topic"), 10, &EkfvioNode::cameraCallback, this);
@@ -157,15 +160,28 @@ class EkfvioNode {
     }
 
    private:
-    // The coefficients travel with every CameraInfo (plumb_bob: k1 k2 p1 p2 k3); the handle is told when they change.  Another model is
-    // refused loudly and the frames go through as they are: the equidistant and rational models are not implemented on the device.
+    // The model and its coefficients travel with every CameraInfo: "plumb_bob" (k1 k2 p1 p2 [k3]: 0, 4 or 5 coefficients), "rational_polynomial"
+    // (8) and "equidistant" / "fisheye" (4) map onto ekfvio_set_camera_model's models; with rectify_use_p the rectified camera is CameraInfo.P's
+    // fx', cx', fy', cy' (P[0], P[2], P[5], P[6]), else frames are rectified onto K.  The handle is told when any of it changes.  A model that is
+    // still unknown (or a count that does not fit its model) is refused loudly and the frames go through as they are.
     void setDistortionFrom(const sensor_msgs::CameraInfo& cam) {
-        const bool plumb_bob = distortion_model_of(cam, 0) == "plumb_bob" && (cam.D.empty() || cam.D.size() == 4 || cam.D.size() == 5);
-        if (!plumb_bob) ROS_ERROR_THROTTLE(5.0, "rectify: only the plumb_bob model with 4 or 5 coefficients is supported; frames are not rectified");
-        const std::vector<double> D = plumb_bob ? cam.D : std::vector<double>();
-        if (have_D_ && D == last_D_) return;
-        vio_->tc_ekf.setDistortion(D);
-        last_D_ = D;
+        int model = ekfvio::Params::cameraModelOf(distortion_model_of(cam, 0));
+        const size_t n = cam.D.size();
+        const bool known = (model == EKFVIO_CAMERA_PLUMB_BOB && (n == 0 || n == 4 || n == 5)) || (model == EKFVIO_CAMERA_RATIONAL && n == 8) ||
+                           (model == EKFVIO_CAMERA_EQUIDISTANT && n == 4);
+        if (!known)
+            ROS_ERROR_THROTTLE(5.0, "rectify: only the plumb_bob model with 4 or 5 coefficients, rational_polynomial with 8 and equidistant with 4 are supported; frames are not rectified");
+        if (!known) model = EKFVIO_CAMERA_PLUMB_BOB;
+        const std::vector<double> D = known ? cam.D : std::vector<double>();
+        std::vector<float> P;
+        if (known && rectify_use_p_) {
+            if (cam.P[0] > 0.0 && cam.P[5] > 0.0) P = {(float)cam.P[0], (float)cam.P[2], (float)cam.P[5], (float)cam.P[6]};
+            else ROS_ERROR_THROTTLE(5.0, "rectify_use_p: CameraInfo.P has no positive focal lengths; frames are rectified onto K");
+        }
+        if (have_D_ && D == last_D_ && model == last_model_ && P == last_P_) return;
+        if (model == EKFVIO_CAMERA_PLUMB_BOB && P.empty()) vio_->tc_ekf.setDistortion(D);
+        else vio_->tc_ekf.setCameraModel(model, D, P.empty() ? nullptr : P.data());
+        last_D_ = D, last_model_ = model, last_P_ = P;
         have_D_ = true;
     }
 
@@ -340,6 +356,9 @@ class EkfvioNode {
     bool publish_insight_ = false;
     std::vector<double> last_D_;  // the coefficients the handle was told last (rectify = 1)
     bool have_D_ = false;
+    int last_model_ = 0;         // ... and the model and the rectified camera that went with them
+    std::vector<float> last_P_;
+    bool rectify_use_p_ = false;  // ~rectify_use_p: rectify onto CameraInfo.P instead of K
     double dt_sum_ = 0;
     int dt_count_ = 0;
 };

@@ -117,7 +117,7 @@ EKFVIO_API int ekfvio_create(const ekfvio_config* cfg, int device, void* stream,
 EKFVIO_API int ekfvio_destroy(ekfvio_filter* f);
 /* initializeBaseState(): back to mu = [0,0,0,1,0...], Sigma diag [0x7,30x9,0.5x6], no landmarks.  (The innovation gate's counts start
  * over; its threshold stays.  The same holds for the tracker's forward-backward check.  The distortion coefficients of
- * ekfvio_set_distortion stay too, and so does the setting of ekfvio_set_output_covariance.  The mask of ekfvio_set_mask stays as well, and the setting of ekfvio_set_equalize.
+ * ekfvio_set_distortion and the setting of ekfvio_set_camera_model stay too, and so does the setting of ekfvio_set_output_covariance.  The mask of ekfvio_set_mask stays as well, and the setting of ekfvio_set_equalize.
  * So does the tracker's gain/offset term, ekfvio_set_klt_photometric.)
  * (The landmark id counter does NOT start over: the first landmark behind a reset gets an id above every id the handle has handed out,
  * so a consumer never sees two points under one id.  The setting of ekfvio_set_ended_export stays; its report is empty and its total
@@ -293,8 +293,8 @@ EKFVIO_API int ekfvio_get_gate(ekfvio_filter* f, float* d2, uint8_t* gated, int3
  * contributes 0 (so the sentinel gives 0 by itself); out = (sum + 512) >> 10.  With D = 0 the map is exactly (32x, 32y) and the frame
  * keeps every byte.  The rectified full-size frame then takes the road of an uploaded one: the resize and the pyramid read it, K is
  * unchanged, and the intensity channel of ekfvio_get_points reads it.  The map is formed on the device once per (fx, cx, fy, cy, D, w, h)
- * and kept.  Out of scope: the equidistant and rational models, and a new camera matrix or alpha crop.  (The black border these lines
- * leave, as image_proc/rectify does, is kept away from the detector and the tracker by ekfvio_set_mask, below.)
+ * and kept.  The rational and the equidistant model and a new camera matrix: ekfvio_set_camera_model, below; out of scope: an alpha crop.
+ * (The black border these lines leave, as image_proc/rectify does, is kept away from the detector and the tracker by ekfvio_set_mask, below.)
  *
  * count = 5: D as above; count = 4: k3 = 0; count = 0 (D may be NULL) or all coefficients zero: off (default; then no launch differs and
  * every output keeps its bits).  A non-finite coefficient, any other count, NULL with count > 0: EKFVIO_EINVAL, and the setting stays
@@ -305,6 +305,80 @@ EKFVIO_API int ekfvio_set_distortion(ekfvio_filter* f, const double* D, int32_t 
  * (a tap outside the frame means no data there).  D, count as above (count = 0: the identity map). */
 EKFVIO_API int ekfvio_rectify_map(const float K[9], const double* D, int32_t count, int32_t width, int32_t height, int32_t* sx,
                                   int32_t* sy);
+
+/* ---- camera models: the rational and the equidistant lens, and a rectified camera of its own (not in the reference) -------------------
+ * ekfvio_set_distortion knows the plumb_bob lens and rectifies onto the raw camera's own K.  This section adds the two models a wide-angle
+ * camera is usually calibrated with -- rational_polynomial (8 coefficients, what ROS camera_calibration emits for a wide lens) and
+ * equidistant (Kannala-Brandt, cv::fisheye, Kalibr's "equidistant": 4 coefficients) -- and P, the intrinsics of the RECTIFIED image
+ * (CameraInfo.P), so that a fisheye frame can be zoomed out to keep its field of view or zoomed in to keep its resolution.  The lines below
+ * are the specification; csrc/rectify_map.h implements them, one inline function for the host and the device, and a NumPy restatement
+ * (tests/_camera_models.py) is what the device is held to, bit for bit.  Everything in fp64, in this order, without fused multiply-add;
+ * division and square root are IEEE correctly rounded.
+ *
+ * Destination pixel (x, y) of the full-size w x h frame; (fx, cx, fy, cy) = K[0], K[2], K[4], K[5] of the K passed with the frame;
+ * (fx', cx', fy', cy') = P where set, otherwise the same four values of K:
+ *
+ *     xn = (x - cx') / fx'      yn = (y - cy') / fy'
+ *     xx = xn*xn   yy = yn*yn   xy = xn*yn   r2 = xx + yy
+ *
+ *     PLUMB_BOB   (k1,k2,p1,p2[,k3])          rad, xd, yd: the lines of ekfvio_set_distortion (with P absent: its bits)
+ *     RATIONAL    (k1,k2,p1,p2,k3,k4,k5,k6)   num = 1 + ((k3*r2 + k2)*r2 + k1)*r2
+ *                                             den = 1 + ((k6*r2 + k5)*r2 + k4)*r2
+ *                                             rad = num / den
+ *                                             xd, yd by the plumb_bob lines with this rad
+ *     EQUIDISTANT (k1,k2,k3,k4)               r = sqrt(r2)     th = atan_spec(r)     t2 = th*th
+ *                                             thd = th * (1 + (((k4*t2 + k3)*t2 + k2)*t2 + k1)*t2)
+ *                                             sc = (r == 0) ? 1 : thd / r
+ *                                             xd = xn*sc       yd = yn*sc
+ *
+ *     u = fx*xd + cx    v = fy*yd + cy    then valid / sx / sy / sentinel, and the integer remap, exactly as for ekfvio_set_distortion
+ *
+ * Two properties follow from the lines: RATIONAL with k4 = k5 = k6 = 0 has den == 1 and rad == num, so it gives the plumb_bob map; and a P
+ * whose four floats equal K's gives the map without P.
+ *
+ * atan_spec(r), r >= 0, is a fixed fp64 recipe, so that the device, the host function and NumPy cannot disagree in the last place the way
+ * three libm implementations can (within 3 ulp of a correctly rounded arctan over [0, 50] and over 1e-300 .. 1e300; atan_spec(0) = 0,
+ * atan_spec(inf) = PI_2):
+ *
+ *     T8 = 0.41421356237309503    PI_4 = 0.7853981633974483    PI_2 = 1.5707963267948966      (the doubles these literals read as)
+ *     inv = r > 1          t = inv ? 1/r : r
+ *     sh  = t > T8         t = sh ? (t - 1)/(t + 1) : t
+ *     q = t*t
+ *     p = c19;  for k = 18 .. 0:  p = p*q + c_k        c_k = (k even ? +1 : -1) * (1.0 / (2k+1)), k = 0..19
+ *     a = t*p
+ *     if sh:  a = PI_4 + a
+ *     if inv: a = PI_2 - a
+ *
+ * Where P goes.  The rectification reads the K as passed (the raw camera).  With P set, everything BEHIND the rectification sees the
+ * rectified camera: the pushed frame's K takes P's four values in K's places before the division by inverse_image_scale, so the pixel <->
+ * metric conversion, the tracker's guesses, R's scaling, replenishment and the point cloud's pixel all use P.  The K argument of
+ * ekfvio_klt_push_frame and ekfvio_step_image stays "the raw camera's intrinsics".
+ *
+ * The device side: one instance of the map kernel per model, launched once per (K, model, coefficients, P, w, h) and kept; the per-frame
+ * remap, the pyramid, the tracker and the update are the same code for every lens.  The mask's border term (ekfvio_set_mask) reads the
+ * same map, whatever the model, and is live whenever this setting is on.
+ *
+ * ekfvio_set_camera_model.  count: PLUMB_BOB 0, 4 or 5; RATIONAL 8; EQUIDISTANT 4 (zeros allowed: the ideal fisheye lens).  P: fx', cx',
+ * fy', cy', or NULL for K.  Off: PLUMB_BOB or RATIONAL with every coefficient zero and P == NULL (then no launch differs, nothing is
+ * allocated and every output keeps its bits).  On otherwise -- that includes P alone (a pure re-projection) and EQUIDISTANT with zero
+ * coefficients (atan is not the identity).  An unknown model, a wrong count, NULL with count > 0, a non-finite value, fx' <= 0 or fy' <= 0:
+ * EKFVIO_EINVAL, and the setting stays what it was.  ekfvio_set_distortion is the PLUMB_BOB, P == NULL case of this call, and the last of the
+ * two setters wins.  A property of the handle: it holds from the next pushed frame and survives ekfvio_reset.
+ *
+ * Out of scope: thin-prism and tilt coefficients (OpenCV's 12 and 14); choosing P automatically (alpha, balance); tracking on the raw
+ * fisheye image without rectification; and the fold-over of a polynomial beyond its calibrated field, which these lines reproduce as they
+ * stand (a rational den that crosses zero gives invalid entries and, behind it, a mirrored ring: mask it). */
+enum { EKFVIO_CAMERA_PLUMB_BOB = 0, EKFVIO_CAMERA_RATIONAL = 1, EKFVIO_CAMERA_EQUIDISTANT = 2 };
+EKFVIO_API int ekfvio_set_camera_model(ekfvio_filter* f, int32_t model, const double* D, int32_t count,
+                                       const float P[4] /* fx', cx', fy', cy'; NULL: K */);
+/* The setting as the handle holds it: the model, its coefficients in the setter's order (zeros behind *count), P (zeros unless *has_P),
+ * and whether frames are rectified.  Any pointer may be NULL. */
+EKFVIO_API int ekfvio_get_camera_model(ekfvio_filter* f, int32_t* model, double D[8], int32_t* count, float P[4], int32_t* has_P,
+                                       int32_t* on);
+/* ekfvio_rectify_map for any model and P: a pure host function (no handle, no device) over the very inline function the map kernels
+ * compile.  Arguments as ekfvio_set_camera_model and ekfvio_rectify_map take them. */
+EKFVIO_API int ekfvio_rectify_map_model(const float K[9], int32_t model, const double* D, int32_t count, const float P[4], int32_t width,
+                                        int32_t height, int32_t* sx, int32_t* sy);
 
 /* ---- no-data mask (not in the reference, which passes no mask to cv::FAST, EKFVIO.cpp:224-311) ----------------------------------------
  * Keeps the detector and the tracker off pixels that hold no scene.  Two sources: the black border that rectification leaves (FAST fires on
@@ -360,6 +434,11 @@ EKFVIO_API int ekfvio_get_mask_hits(ekfvio_filter* f, uint8_t* masked, int32_t* 
  * kernels compile, as ekfvio_rectify_map does.  K, D, count as there (K may be NULL where the border term is not live); mask may be NULL. */
 EKFVIO_API int ekfvio_mask_blocked(const float K[9], const double* D, int32_t count, const uint8_t* mask, int32_t width, int32_t height,
                                    int32_t stride, int32_t inverse_image_scale, int32_t kill_pad, int32_t flags, uint8_t* blocked);
+/* The same for any camera model and P (ekfvio_set_camera_model): the border term is live where the flag is set and that setting is on, and
+ * reads the map of ekfvio_rectify_map_model.  A pure host function. */
+EKFVIO_API int ekfvio_mask_blocked_model(const float K[9], int32_t model, const double* D, int32_t count, const float P[4],
+                                         const uint8_t* mask, int32_t width, int32_t height, int32_t stride, int32_t inverse_image_scale,
+                                         int32_t kill_pad, int32_t flags, uint8_t* blocked);
 
 /* ---- equalisation of pushed frames (not in the reference, whose detector runs at a fixed contrast threshold, EKFVIO.cpp:224-311, and whose
  * tracker assumes brightness constancy; VINS-style front ends run a cv::CLAHE pass on the host in front of the tracker) ----------------------

@@ -95,6 +95,10 @@ EKFVIO_API int ekfvio_test_fill_update_scratch(ekfvio_filter* f, uint32_t word);
 EKFVIO_API int ekfvio_test_zupt_decide(ekfvio_filter* f, const float* prev_px, const float* cur_px, const uint8_t* pass, int32_t count,
                                        float max_flow_px, int32_t min_tracks, float min_ratio, float* flow2, int32_t* n_pass, int32_t* n_still,
                                        int32_t* stationary);
+/* The rectification map as the device holds it (include/ekfvio.h, ekfvio_set_distortion and ekfvio_set_camera_model): the two fixed-point
+ * planes the map kernel wrote for the frame pushed last, row-major *w x *h int32 each.  sx, sy may be NULL (the size alone); cap < *w * *h:
+ * EKFVIO_EINVAL; no map formed yet: EKFVIO_ESTATE.  Waits for the stream. */
+EKFVIO_API int ekfvio_test_rectify_map(ekfvio_filter* f, int32_t* sx, int32_t* sy, int32_t cap, int32_t* w, int32_t* h);
 
 #ifdef __cplusplus
 }
