@@ -452,7 +452,7 @@ __device__ __forceinline__ void gain_tile2(const PersistArgs& a, const GatherArg
             a.dbg[100 + 8 * ((ib ? 3 : 0) + (cb == 0 ? 0 : cb == 3 ? 1 : 2)) + kb] = (long long)__builtin_amdgcn_s_memrealtime();
     };
     if constexpr (WAIT) {
-        for (int kb = 0; kb < mb - 2; kb++) {
+        for (int kb = 0; kb < mb - 1; kb++) {  // (block column mb-2: an ordinary column, but its wait is not lazy -- the launch's tail begins with it)
             __syncthreads();  // (the previous block column's readers of Ti / Tj / Th)
             const unsigned long long neg = fetch(kb);
             __syncthreads();
@@ -471,39 +471,24 @@ __device__ __forceinline__ void gain_tile2(const PersistArgs& a, const GatherArg
         }
     }
     if constexpr (WAIT) {
-        // The last two block columns, together.  An owner of block column mb-1 publishes its finished tile and THEN its panel block of column
-        // mb-2 (each behind its own completed stores), so the panel blocks' flags imply the tiles'; the chain ends a moment later.  ONE look
-        // therefore covers both columns -- the panel blocks of column mb-2 and ready[mb-1] -- and ONE round trip brings all their operands
-        // (column mb-2's into LDS, column mb-1's -- three finished tiles, L_last, its inverses, its signs -- into registers, where they wait
-        // under column mb-2's products).  One column after the other, the launch's tail was two looks and two round trips longer.
-        const int kl = mb - 1, k6 = mb - 2;
-        const bool gk6 = k6 >= cb;
+        // The last block column.  An owner of an X or identity row block announces its panel block (`pan`, behind its last step's product) BEFORE its
+        // finished tile (`fin`): nothing follows from column mb-2's `pan` flags about column mb-1's finished tiles, although the same owners raise
+        // both.  So the wait names ready[mb-1] and EVERY finished tile read below, in ONE look; ONE round trip then brings the three tiles' data,
+        // L_last, its inverses and its signs, through registers.  (Measured, profiles/early_panel.txt: that round trip requested in front of column
+        // mb-2's products, or between its two products, costs more than it hides -- the wait in front of it then delays products that could run.)
+        const int kl = mb - 1;
         const __amdgpu_buffer_rsrc_t bI = persist_rsrc(a.Linv, (unsigned)(mb * PB * PB));
         const bool zi = a.grid.compact() && cb == kl;  // (compact launch: tile (idb0 + mb-1, mb-1) is the identity and nobody's)
-        __syncthreads();
-        // column mb-2's panel blocks as soon as THEY are out (their flags also cover column mb-1's finished tiles, see above): its operands travel
-        // while ready[mb-1] is still on its way.  (A tile with no Z panel block in column mb-2 looks at the finished tile (iz, mb-1) instead, which it
-        // reads behind ready[mb-1]; the row blocks' flags also cover the rows gathered from column mb-1's finished tiles.)
-        persist_wait(a, column_flags(k6, gk6 ? a.pan + iz * mb + k6 : (zi ? nullptr : a.fin + iz * mb + kl)), tid, false);
+        // What the wait for the last block column looks at, lane by lane: lane 0 ready[mb-1] (the chain's four wavefronts), lane 1 the finished tile
+        // (iy, mb-1), lane 2 the finished tile (iz, mb-1) (zi: none), lanes 3 .. the finished tile of EVERY X row block alo .. ahi, the range the row
+        // gather hq is addressed by -- at most nX + 3 lanes, which a shape that takes this flow has (plan.h, t2_skip_owners).
+        const int axl = alo + tid - 3;
+        const PollLane last_flags = {tid == 0 ? a.ready + kl : tid == 1 ? a.fin + iy * mb + kl : tid == 2 ? (zi ? nullptr : a.fin + iz * mb + kl)
+                                     : (axl <= ahi) ? a.fin + (mb + axl) * mb + kl : nullptr, tid == 0 ? 4 : 1};
+        __syncthreads();  // (column mb-2's readers of Ti / Tj / Th)
         RegTile ql, qi, qj;
         float hq[16];
-        unsigned long long neg6;
-        {
-            RegTile pi6, pj6;
-            float h6[16];
-            pi6.request(bL, (unsigned)(k6 * PB) * (unsigned)ldl + (unsigned)(iy * PB), ldl, tid);
-            if (gk6) pj6.request(bL, (unsigned)(k6 * PB) * (unsigned)ldl + (unsigned)(iz * PB), ldl, tid);
-#pragma unroll
-            for (int ps = 0; ps < 16; ps++)
-                h6[ps] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(bL, ((unsigned)(k6 * PB + wave + 4 * ps) * (unsigned)ldl + (unsigned)(mb * PB) + sqc) * 4u, 0, 16));
-            neg6 = ld_sign_sc1(a.Lsign + k6);
-            pi6.put(Ti, tid);
-            if (gk6) pj6.put(Tj, tid);
-#pragma unroll
-            for (int ps = 0; ps < 16; ps++) Th[(wave + 4 * ps) * PLD + lane] = (sq >= 0) ? h6[ps] : 0.f;
-        }
-        // ... then the last column's (its look also is the barrier behind column mb-2's LDS writes): requested into registers, under column mb-2's products
-        persist_wait(a, a.ready + kl, nullptr, nullptr, tid, 4, false);
+        persist_wait(a, last_flags, tid, false);
         ql.request(bL, (unsigned)(kl * PB) * (unsigned)ldl + (unsigned)(kl * PB), ldl, tid);
         qi.request(bS, (unsigned)(kl * PB) * (unsigned)a.lds + (unsigned)(iy * PB), a.lds, tid);
         if (!zi) qj.request(bS, (unsigned)(kl * PB) * (unsigned)a.lds + (unsigned)(iz * PB), a.lds, tid);
@@ -512,8 +497,6 @@ __device__ __forceinline__ void gain_tile2(const PersistArgs& a, const GatherArg
 #pragma unroll
         for (int ps = 0; ps < 16; ps++)
             hq[ps] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(bS, ((unsigned)(kl * PB + wave + 4 * ps) * (unsigned)a.lds + (unsigned)(mb * PB) + sqc) * 4u, 0, 16));
-        products(mb - 2, neg6, false);
-        __syncthreads();
         ql.put(Tl, tid);
         qi.put(Ti, tid);
         if (zi) identity_tile(Tj, tid);
@@ -608,9 +591,9 @@ __device__ __forceinline__ void t2_tile(const PersistArgs& a, float* Ti, float* 
         if (dbg && tid == 0) dbg[kb] = (long long)__builtin_amdgcn_s_memrealtime();
     };
     if constexpr (WAIT) {
-        for (int kb = 0; kb < mb - 2; kb++) {
+        for (int kb = 0; kb < mb - 1; kb++) {
             __syncthreads();  // (the previous product's readers of Ti / Tj, the previous turn's of Tl)
-            persist_wait(a, nullptr, a.pan + ia * mb + kb, diag ? nullptr : a.pan + ib * mb + kb, tid, 1, true);
+            persist_wait(a, nullptr, a.pan + ia * mb + kb, diag ? nullptr : a.pan + ib * mb + kb, tid, 1, kb < mb - 2);
             load_tile_sc1(Ti, bL, (unsigned)(kb * PB) * (unsigned)ldl + (unsigned)(ia * PB), ldl, tid);
             if (!diag) load_tile_sc1(Tj, bL, (unsigned)(kb * PB) * (unsigned)ldl + (unsigned)(ib * PB), ldl, tid);
             const unsigned long long neg = ld_sign_sc1(a.Lsign + kb);
@@ -628,27 +611,20 @@ __device__ __forceinline__ void t2_tile(const PersistArgs& a, float* Ti, float* 
         }
     }
     if constexpr (WAIT) {
-        // the last two block columns together, as in gain_tile2: the panel blocks' flags of column mb-2 imply the finished tiles of column
-        // mb-1 (same owners, published in that order); ONE look with ready[mb-1], ONE round trip for both columns' operands
-        const int kl = mb - 1, k6 = mb - 2;
+        // The last block column (column mb-2 was an ordinary column of the loop, its wait not lazy).  Nothing follows from column mb-2's `pan` flags
+        // about the finished tiles of column mb-1 -- their owners announce the panel block first and the tile later -- so the ONE look names
+        // ready[mb-1] and both finished tiles read here; ONE round trip then brings the tiles, L_last, its inverses and its signs.
+        const int kl = mb - 1;
         const __amdgpu_buffer_rsrc_t bS = persist_rsrc(a.S, (unsigned)a.lds * (unsigned)(mb * PB));
         const __amdgpu_buffer_rsrc_t bI = persist_rsrc(a.Linv, (unsigned)(mb * PB * PB));
         __syncthreads();
-        persist_wait(a, a.ready + kl, a.pan + ia * mb + k6, diag ? nullptr : a.pan + ib * mb + k6, tid, 4, false);
-        RegTile pi6, pj6, ql, qi, qj;
-        pi6.request(bL, (unsigned)(k6 * PB) * (unsigned)ldl + (unsigned)(ia * PB), ldl, tid);
-        if (!diag) pj6.request(bL, (unsigned)(k6 * PB) * (unsigned)ldl + (unsigned)(ib * PB), ldl, tid);
-        const unsigned long long neg6 = ld_sign_sc1(a.Lsign + k6);
+        RegTile ql, qi, qj;
+        persist_wait(a, a.ready + kl, a.fin + ia * mb + kl, diag ? nullptr : a.fin + ib * mb + kl, tid, 4, false);
         ql.request(bL, (unsigned)(kl * PB) * (unsigned)ldl + (unsigned)(kl * PB), ldl, tid);
         qi.request(bS, (unsigned)(kl * PB) * (unsigned)a.lds + (unsigned)(ia * PB), a.lds, tid);
         if (!diag) qj.request(bS, (unsigned)(kl * PB) * (unsigned)a.lds + (unsigned)(ib * PB), a.lds, tid);
         const float4 qv = ld_sc1(bI, (unsigned)(kl * PB * PB) + tid * 4);
         const unsigned long long neg7 = ld_sign_sc1(a.Lsign + kl);
-        pi6.put(Ti, tid);
-        if (!diag) pj6.put(Tj, tid);
-        __syncthreads();
-        apply(k6, neg6);
-        __syncthreads();
         ql.put(Tl, tid);
         qi.put(Ti, tid);
         if (!diag) qj.put(Tj, tid);
@@ -1156,6 +1132,15 @@ __global__ __launch_bounds__(256) void chol_persist_kernel(PersistArgs a, Gather
     do {                                                                                                                \
         if (a.dbg && i == j + 1 && i < mb && k == klast && tid == 0) a.dbg[600 + 8 * j + (n)] = (long long)__builtin_amdgcn_s_memtime(); \
     } while (0)
+    // ... and of the last step of block column mb-1's owners of X / identity row blocks (scripts/t2_stamps.py): 0 the panel block (i, mb-2) is final
+    // in LDS, 1 `fin` is up, 2 `pan` is up -- what the gain and T2 tiles' last two block columns wait for, on the 100 MHz clock
+#define OSTAMP(n)                                                                                                       \
+    do {                                                                                                                \
+        if (a.dbg && tid == 0 && j == mb - 1 && i >= mb && i - mb < 40) a.dbg[904 + 3 * (i - mb) + (n)] = (long long)__builtin_amdgcn_s_memrealtime(); \
+    } while (0)
+    // an X or identity row block off the diagonal, with the gain formed inside this launch: its panel block (i, j-1) is an operand of the gain and T2
+    // tiles and leaves write-through right behind the last step's substitution, with a flag (`pan`) of its own
+    const bool early_pan = a.gain && i >= mb && i != j;
     unsigned long long neg = 0ull;
     int k = k0;
     for (; k <= klast; k++) {
@@ -1203,6 +1188,16 @@ __global__ __launch_bounds__(256) void chol_persist_kernel(PersistArgs a, Gather
             tri_solve_fwd(Ti, Tl, Tinv, wave, lane);
         __syncthreads();
         HSTAMP(3);
+        if (k == klast) OSTAMP(0);
+        if (early_pan && k == klast) {
+            // The panel block (i, j-1) is final in Ti: it leaves NOW, write-through, and travels under the product below, which only reads Ti.  Its flag
+            // goes up behind the product (every wavefront's wait for its stores, the barrier, one lane).  Nothing follows from `pan` about this
+            // owner's finished tile any more: that one is stored and announced (`fin`) later, and whoever reads it waits for `fin`.
+            const unsigned od = (unsigned)(klast * PB) * (unsigned)ldl + (unsigned)(i * PB);
+            PERSIST_TEST_DELAY(a, 1);
+            if (neg != 0ull && i >= idb0) store_tile_signed_sc1(Ti, bL, od, ldl, tid, neg);
+            else store_tile_sc1<false>(Ti, bL, od, ldl, tid);
+        }
         const float* Bj = (i != j) ? Tj : Ti;
         const f32x16 up = (neg == 0ull) ? mma64(Ti, 1, PLD, Bj, 1, PLD, wr, wc, lane) : mma64_signed(Ti, 1, PLD, Bj, 1, PLD, wr, wc, lane, neg);
 #pragma unroll
@@ -1210,6 +1205,10 @@ __global__ __launch_bounds__(256) void chol_persist_kernel(PersistArgs a, Gather
         HSTAMP(4);
     }
     k = klast;
+    if (early_pan && klast >= k0) {  // the panel block left in front of the last product: announced, in the publishing form, before anything else
+        persist_publish(a.pan + i * mb + klast, tid);
+        OSTAMP(2);
+    }
     // the finished tile goes out once (write-through, whole 128-byte lines through L_kk's LDS tile, free since the
     // substitutions) and is announced
     if (klast >= k0 || fused) {  // (fused launch: a tile without steps -- an identity block -- exists nowhere yet either)
@@ -1223,19 +1222,13 @@ __global__ __launch_bounds__(256) void chol_persist_kernel(PersistArgs a, Gather
     if ((int)blockIdx.x != a.stall_wg) persist_publish(a.fin + i * mb + j, tid);
     else __syncthreads();
     HSTAMP(5);
+    OSTAMP(1);
     if (a.dbg && tid == 0 && i < mb && (i == j + 1 || i == j)) a.dbg[(i == j ? 740 : 720) + j] = (long long)__builtin_amdgcn_s_memrealtime();
-    if (klast >= k0 && i != j) {  // the panel block of row block i in block column j-1
-        if (a.gain && i >= mb) {  // an X or identity row block: an operand of the gain tiles formed inside this launch
-            const unsigned od = (unsigned)(klast * PB) * (unsigned)ldl + (unsigned)(i * PB);
-            PERSIST_TEST_DELAY(a, 1);
-            if (neg != 0ull && i >= idb0) store_tile_signed_sc1(Ti, bL, od, ldl, tid, neg);
-            else store_tile_sc1<false>(Ti, bL, od, ldl, tid);
-            persist_publish(a.pan + i * mb + klast, tid);
-        } else {  // (read by later launches only)
-            float* dst = L + (size_t)klast * PB * ldl + (size_t)i * PB;
-            if (neg != 0ull && i >= idb0) store_tile_signed(Ti, dst, ldl, tid, neg);
-            else store_tile(Ti, dst, ldl, tid);
-        }
+    if (klast >= k0 && i != j && !early_pan) {  // the panel block of row block i in block column j-1: read by later launches only
+        // (an X or identity row block's, with the gain formed inside this launch, is an operand of the gain and T2 tiles: out already, see the last step)
+        float* dst = L + (size_t)klast * PB * ldl + (size_t)i * PB;
+        if (neg != 0ull && i >= idb0) store_tile_signed(Ti, dst, ldl, tid, neg);
+        else store_tile(Ti, dst, ldl, tid);
     }
     if (a.t2) {
         // round 6: this workgroup's tile is done and nothing else is left for an owner of a launch that forms the gain itself -- it adopts
@@ -1288,6 +1281,7 @@ __global__ __launch_bounds__(256) void chol_persist_kernel(PersistArgs a, Gather
     PEXIT();
 #undef PEXIT
 #undef HSTAMP
+#undef OSTAMP
 #undef PSTAMP
 }
 

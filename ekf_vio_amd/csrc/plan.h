@@ -120,7 +120,8 @@ struct PersistFlags {
 inline size_t persist_flag_words(int m_pad, int n_pad) { return PersistFlags(m_pad, n_pad).words(); }
 inline int persist_zero_words(int m_pad, int n_pad) { return PersistFlags(m_pad, n_pad).zero_words(); }
 // Flags ONE look of a waiting wavefront can carry: a lane each, lane 63 the abort word (chol_persist.inc, persist_poll).  A gain tile of the T2
-// flow looks at its two panel blocks and at one flag per X row block its measurement rows span -- at most nX + 2 (gain_tile2, column_flags).
+// flow looks at its two panel blocks and at one flag per X row block its measurement rows span -- at most nX + 2 (gain_tile2, column_flags); for
+// the last block column at ready[mb-1], its two finished tiles and one finished tile per such row block -- at most nX + 3 (last_flags).
 #define PERSIST_POLL_FLAGS 63
 
 // ---- the sizes a capacity implies ----------------------------------------------------------------------------------------------
@@ -394,7 +395,7 @@ inline int t2_skip_owners(const Tuning& t, const PlanShape& s, int m_pad, int n_
     if (!t.t2_flow || !t.persist_gain || t.schur || !gain_in_sweep_shape(t, s, m_pad, n_pad)) return -1;
     const PersistGrid g{GRID_COMPACT, m_pad / EKF_TILE, n_pad / EKF_TILE, s.ldp / 64};
     if (g.total() > s.num_cus) return -1;  // the compact launch: every workgroup has its compute unit from the start
-    if (g.nX + 2 > PERSIST_POLL_FLAGS) return -1;  // the gain tiles' waits: one flag per X row block in ONE look
+    if (g.nX + 3 > PERSIST_POLL_FLAGS) return -1;  // the gain tiles' waits: one flag per X row block in ONE look (the last block column's: and three more)
                                                    // (out of reach today: t2_pairs(nX) <= owners() holds nX to 38 below EKF_SWEEP_SPLIT_MB block columns, to 22 on 256 compute units)
     return (t2_pairs(g.nX) <= g.owners()) ? 0 : -1;
 }

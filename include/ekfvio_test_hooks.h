@@ -33,7 +33,9 @@ EKFVIO_API int ekfvio_test_sweep_fault(ekfvio_filter* f, int32_t spin_limit, int
 /* Arrival order of the persistent sweep's hand-offs (NOT fault injection: nothing is withheld and no wait runs out).  Owner workgroup `workgroup`
    of the launch -- numbered like stall_workgroup, mapped through PersistGrid::owner_block; -1: none -- idles `ticks` of the 100 MHz clock and then
    goes on as always.  point 0: in front of the store of its finished tile (the store behind which fin[i][j] goes up); point 1: in front of the
-   store of its panel block (the store behind which pan[i][j-1] goes up).  The idling comes BEFORE the data, not between data and flag: a consumer
+   store of its panel block (the store behind which pan[i][j-1] goes up).  The panel block leaves first, right behind the owner's last
+   substitution, and the tile after the last product: late at point 1 an owner is late with both, late at point 0 its `pan` is up while its
+   tile is not (tests/test_gpu_early_panel.py).  The idling comes BEFORE the data, not between data and flag: a consumer
    that reads without waiting for the flag finds what the previous update left there.  EKFVIO_EINVAL for another point or more than
    EKFVIO_TEST_SWEEP_DELAY_MAX_TICKS (1 ms, a third of the default 3 ms wait bound; EKFVIO_SWEEP_WAIT_MS can set a shorter one).  An owner
    has a panel block to store only where it is an operand of the gain formed inside the launch (an X or identity row block off the diagonal);

@@ -44,6 +44,21 @@ for w, name in enumerate(("first", "middle", "last")):
     b = 840 + 16 * w
     if v[b + 14]:
         print("T2 pair %-6s adopted at %.1f, block columns done at %s, stored at %.1f" % (name, us(v[b + 14]), ["%.1f" % us(v[b + k]) for k in range(mb)], us(v[b + 15])))
+# block column mb-1's owners of X / identity row blocks, last step: the panel block (i, mb-2) final in LDS, `fin` up, `pan` up -- next to when the
+# sampled gain tiles are done with block columns mb-2 and mb-1, which wait for exactly these flags
+rows = [ro for ro in range(40) if v[904 + 3 * ro]]
+if rows:
+    print("owners of block column %d, row block (X: 0..%d, identity: %d..): substitution done / fin up / pan up, and substitution -> pan" % (mb - 1, nX - 1, nX))
+    gaps = []
+    for ro in rows:
+        s_, f_, p_ = (v[904 + 3 * ro + q] for q in range(3))
+        gaps.append((p_ - s_) / 100.0 if p_ else float("nan"))
+        print("    %2d  %5.1f %5.1f %5.1f   %4.1f" % (ro, us(s_), us(f_), us(p_), gaps[-1]))
+    print("substitution -> pan: min %.1f, median %.1f, max %.1f us; the last pan is up at %.1f, the last fin at %.1f us" % (
+        min(gaps), sorted(gaps)[len(gaps) // 2], max(gaps), max(us(v[904 + 3 * ro + 2]) for ro in rows), max(us(v[904 + 3 * ro + 1]) for ro in rows)))
+    for w, name in enumerate(("(0,0)", "(0,3)", "(0,7)", "(6,0)", "(6,3)", "(6,7)")):
+        if mb <= 8 and v[100 + 8 * w + mb - 1]:
+            print("gain tile %s: block column %d done at %.1f, block column %d at %.1f" % (name, mb - 2, us(v[100 + 8 * w + mb - 2]), mb - 1, us(v[100 + 8 * w + mb - 1])))
 print("blocks 252..267 start at", ["%.1f/xcc%d" % (us(v[160 + i]), v[176 + i]) for i in range(16) if v[160 + i]])
 print("owners 0..7 are done with their tile at", ["%.1f" % us(v[192 + i]) for i in range(8) if v[192 + i]])
 print("the launch's last workgroup (block %d) leaves at %.1f us" % (v[899], us(v[898])))
