@@ -5,4 +5,4 @@ filter.py (host mirror of the reference's TightlyCoupledEKF interface), sim.py (
 synthetic scenario generator).  There is no CPU compute path in this package.
 """
 from .capi import EkfvioError, load  # noqa: F401
-from .filter import EKFVIO, KLTTracker, TightlyCoupledEKF, equalize, klt_project_gradients, mask_blocked, mask_blocked_model, rectify_map, rectify_map_model, rotation_error_jacobian  # noqa: F401
+from .filter import EKFVIO, KLTTracker, TightlyCoupledEKF, equalize, klt_project_gradients, mask_blocked, mask_blocked_model, rectify_map, rectify_map_model, replenish_select, rotation_error_jacobian  # noqa: F401

@@ -335,6 +335,7 @@ struct ekfvio_filter {
     int* new_xy = nullptr;         // pixels of the landmarks added by the last replenishment
     int* fast_counts = nullptr;    // [0] keypoints found, [1] landmarks added
     int fast_cap_w = 0, fast_cap_h = 0;  // level-0 size the detector's buffers were allocated for
+    int replenish_cells_x = 0, replenish_cells_y = 0;  // ekfvio_set_replenish_grid: (0, 0) = off, the raster first fit; else replenish_select_kernel's grid instance
     double t_stamp = 0;
     bool have_stamp = false;
 
@@ -547,7 +548,7 @@ int poll_status(ekfvio_filter* f, int seq, int* status, int* extra_out);
 // api.hip: addNewFeatures with the k new (u,v) already in f->zmeas on the device
 int add_features_device(ekfvio_filter* f, int k);
 void add_features_enqueue_device_count(ekfvio_filter* f, const int* count_dev);  // enqueue only; the caller updates N / n
-int replenish_enqueue(ekfvio_filter* f, int* enqueued);  // fast.hip: FAST + first-fit selection, count left in f->fast_counts[1]
+int replenish_enqueue(ekfvio_filter* f, int* enqueued);  // fast.hip: FAST + selection (first fit, or the grid's rounds), count left in f->fast_counts[1]
 
 int live_handles_on(int device);  // api.hip: handles alive on that device in this process
 void drop_graph(ekfvio_filter* f);  // api.hip: the ONE invalidation of ekfvio_filter::graphs (the next run captures again)

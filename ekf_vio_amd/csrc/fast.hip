@@ -14,7 +14,10 @@
 // in keypoint order: one wavefront takes 64 keypoints at a time, tests them against the occupancy mask in parallel,
 // accepts the first free one, stamps its circle (one lane per circle row, bit mask in LDS) and re-tests the rest; four
 // wavefronts prepare the mask (existing landmarks' circles) before that.
+// Not in the reference: with ekfvio_set_replenish_grid the selection runs rounds of "the strongest free corner of every cell of a grid,
+// emptier cells first" instead (include/ekfvio.h has the specification; replenish_select_kernel's GRID instances below).
 #include "common.h"
+#include "select.h"  // circle_half_width, the kill-box test, the grid's cell and keys: shared with ekfvio_replenish_select below
 
 namespace {
 
@@ -187,28 +190,6 @@ __global__ __launch_bounds__(1024) void fast_gather_kernel(const unsigned* __res
     fast_gather_body<1024>(row_kp, row_cnt, w, h, cap, kp_xy, kp_score, total, s_w, &s_carry);
 }
 
-// drawing.cpp Circle(), filled: half-width of the span in row cy + dyrow (-1: the row is outside the circle)
-__device__ inline int circle_half_width(int radius, int dyrow) {
-    // The midpoint walk emits, for each step (dx, dy): rows +-dy get half-width dx, rows +-dx get half-width dy.
-    // A row |r| is reached as a "dy row" while dx >= dy, and as a "dx row" each time dx takes the value |r|
-    // (then with the LAST dy written before dx decrements being the widest).  Re-walk it: the circle is small.
-    const int ar = dyrow < 0 ? -dyrow : dyrow;
-    int best = -1;
-    int err = 0, dx = radius, dy = 0, plus = 1, minus = (radius << 1) - 1;
-    while (dx >= dy) {
-        if (dy == ar) best = max(best, dx);
-        if (dx == ar) best = max(best, dy);
-        dy++;
-        err += plus;
-        plus += 2;
-        const int m = (err <= 0) - 1;
-        err -= minus & m;
-        dx += m;
-        minus -= m & 2;
-    }
-    return best;
-}
-
 // The occupancy image (checkImg) as a bit mask: in LDS when it fits (w*h bits <= 64 KB: every 640x480-class
 // frame), otherwise in global memory behind agent-scope atomics (one wavefront reads what it just wrote).
 #define OCC_LDS_WORDS 16384
@@ -247,20 +228,72 @@ __device__ inline void stamp_circle(const OccMask<LDSMASK>& mask, int w, int h, 
     }
 }
 
+// The first fit of one wavefront over up to 64 keypoints in lane order (cand: this lane holds one, at (x, y)): test them against the
+// current mask in parallel, accept the first free one, stamp its circle, re-test the rest, until none is free or `wanted` are added.
+// GRID: lane 0 also counts the accepted landmark into its cell (s_cnt, LDS).
+template <bool LDSMASK, bool GRID>
+__device__ inline int first_fit_wave(const OccMask<LDSMASK>& mask, bool cand, int x, int y, int lane, int added, int wanted, int* new_xy,
+                                     float* new_uv, float fx, float fy, float cx, float cy, int w, int h, int radius,
+                                     const int (&hw)[OCC_PASSES], int* s_cnt, int cw, int ch, int cells_x) {
+    unsigned long long todo = __ballot(cand);
+    while (todo && added < wanted) {
+        // test the remaining candidates against the current mask
+        const bool is_free = cand && ((todo >> lane) & 1ull) && !mask.test(x, y);
+        const unsigned long long fb = __ballot(is_free);
+        if (!fb) break;
+        const int L = __ffsll((long long)fb) - 1;
+        const int ax = __shfl(x, L, 64), ay = __shfl(y, L, 64);
+        if (lane == 0) {
+            new_xy[2 * added] = ax;
+            new_xy[2 * added + 1] = ay;
+            // Feature::pixel2Metric (Feature.h:60-62)
+            new_uv[2 * added] = ((float)ax - cx) / fx;
+            new_uv[2 * added + 1] = ((float)ay - cy) / fy;
+            if (GRID) s_cnt[select_cell(ax, ay, cw, ch, cells_x)]++;  // (read again only behind the round's last barrier)
+        }
+        added++;
+        stamp_circle(mask, w, h, ax, ay, radius, lane, hw);
+        // this wavefront's own ORs must have landed before it tests the mask again; without the grid wavefronts 1-3 have exited, so
+        // a workgroup barrier here would be a barrier after a partial exit (and with it they wait at the round's last barrier, which
+        // this wavefront reaches only behind its walk): wait for the wave's own memory operations
+        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+        __builtin_amdgcn_wave_barrier();
+        todo &= ~((2ull << L) - 1ull);  // everything up to and including L is consumed
+    }
+    return added;
+}
+
 // replenishFeatures' selection.  Four wavefronts clear the mask and stamp the existing landmarks' circles (order-free:
 // bit ORs; every wavefront fetches 64 landmark pixels at once and takes every fourth); the first fit itself is sequential
 // by definition and stays with wavefront 0.  The global mask (LDSMASK = false) is zeroed, or filled with the no-data mask's B, by the caller.
-template <bool LDSMASK>
+//
+// GRID (ekfvio_set_replenish_grid; the specification is in include/ekfvio.h): rounds of "the strongest free corner of every cell, emptier
+// cells first".  GridDims is (int cells_x, int cells_y) in that instance and EMPTY without the grid, whose two instances thus keep the
+// arguments, and the code, they had before the grid existed.  Per round all four wavefronts stride over the keypoints, each lane tests the
+// kill box and one bit of the mask and sends an LDS atomic max of select_key(s, k) to its cell; one cell per lane then ranks its winner
+// by counting the winners in front of it (select_before: no two compare equal, so the ranks are a permutation) and puts it into rank
+// order in LDS; wavefront 0 walks that list with the first fit above.  Unlike the instances without the grid, ALL FOUR wavefronts stay to
+// the last barrier: the round loop has two exits (no cell has a candidate; `wanted` are added), both decided from LDS words read behind a
+// barrier by every lane alike, so the workgroup leaves together and no barrier stands behind a partial exit.
+template <bool LDSMASK, bool GRID, typename... GridDims>
 __global__ __launch_bounds__(256) void replenish_select_kernel(const int* kp_xy, const int* kp_count, int cap_kp,
                                                               const float* __restrict__ mu, int N_old, float fx, float fy, float cx,
                                                               float cy, int num_features, int w, int h, int radius, int kill_pad,
                                                               unsigned* gmask, int* new_xy, float* new_uv, int* new_count,
                                                               const unsigned* __restrict__ row_kp, const int* __restrict__ row_cnt,
                                                               int* kp_xy_out, short* kp_score_out, int* kp_total_out,
-                                                              const unsigned* __restrict__ blocked) {
+                                                              const unsigned* __restrict__ blocked, GridDims... grid_dims) {
+    static_assert(sizeof...(GridDims) == (GRID ? 2 : 0), "the grid's instance takes cells_x, cells_y; the others nothing");
     __shared__ unsigned lmask[LDSMASK ? OCC_LDS_WORDS : 1];
     __shared__ int s_gw[4];
     __shared__ int s_gcarry;
+    __shared__ unsigned long long s_best[GRID ? SELECT_MAX_CELLS : 1];  // per cell: the round's largest key (0: no candidate)
+    __shared__ unsigned long long s_list[GRID ? SELECT_MAX_CELLS : 1];  // the winners' keys in rank order
+    __shared__ int s_cnt[GRID ? SELECT_MAX_CELLS : 1];                  // per cell: landmarks in it
+    __shared__ int s_round[2];                                          // [0] winners of this round, [1] landmarks added so far
+    const int gd[3] = {grid_dims..., 0};
+    const int cells_x = GRID ? gd[0] : 1, cells_y = GRID ? gd[sizeof...(GridDims) / 2] : 1;
+    const int cw = select_cell_size(w, cells_x), ch = select_cell_size(h, cells_y);
     // row_kp != nullptr: the detector's row lists are flattened here, by the same four wavefronts that prepare the mask
     // (fast_gather_kernel's launch saved); kp_xy / kp_count then alias the arrays written here
     if (row_kp) {
@@ -274,6 +307,11 @@ __global__ __launch_bounds__(256) void replenish_select_kernel(const int* kp_xy,
     OccMask<LDSMASK> mask;
     mask.wpr = (w + 31) / 32;
     mask.words = LDSMASK ? lmask : gmask;
+    if (GRID) {
+        s_cnt[threadIdx.x] = 0;  // (256 lanes, SELECT_MAX_CELLS entries)
+        if (threadIdx.x < 2) s_round[threadIdx.x] = 0;
+        __syncthreads();  // (a barrier of its own: wavefront 0 counts into s_cnt below, whatever the mask's fill does)
+    }
     if (LDSMASK) {
         // (blocked: the no-data mask's B, mask.hip, in this layout -- a blocked keypoint is then skipped exactly as an occupied one is; null: off)
         for (int i = threadIdx.x; i < mask.wpr * h; i += 256) lmask[i] = blocked ? blocked[i] : 0u;
@@ -292,11 +330,71 @@ __global__ __launch_bounds__(256) void replenish_select_kernel(const int* kp_xy,
         const int mypx = __float2int_rn(u * fx + cx), mypy = __float2int_rn(v * fy + cy);
         const int cnt = min(64, N_old - i0);
         for (int j = wave; j < cnt; j += 4) stamp_circle(mask, w, h, __shfl(mypx, j, 64), __shfl(mypy, j, 64), radius, lane, hw);
+        // cnt[c]: the landmarks whose rounded pixel lies inside the frame, by wavefront 0 (every wavefront holds all 64 pixels)
+        if (GRID && wave == 0 && lane < cnt && mypx >= 0 && mypx < w && mypy >= 0 && mypy < h)
+            atomicAdd(&s_cnt[select_cell(mypx, mypy, cw, ch, cells_x)], 1);
     }
     if (!LDSMASK) __threadfence();  // the other wavefronts' ORs went to the global mask
     __syncthreads();
+    const int wanted = num_features - N_old;
+    if (GRID) {
+        const int nk = min(*kp_count, cap_kp);  // (one word, written in front of the gather's barrier: the same in every lane)
+        const int ncells = cells_x * cells_y, tid = threadIdx.x;
+        int added = 0;
+        while (added < wanted) {  // (uniform: `added` is s_round[1], read behind the round's last barrier)
+            // (the previous round's readers of s_best and of s_round[0] are done: both are read in front of that round's last barrier)
+            s_best[tid] = 0ull;
+            if (tid == 0) s_round[0] = 0;
+            __syncthreads();
+            for (int k = tid; k < nk; k += 256) {
+                const int x = kp_xy[2 * k], y = kp_xy[2 * k + 1];
+                if (select_in_box(x, y, w, h, kill_pad) && !mask.test(x, y))
+                    atomicMax(&s_best[select_cell(x, y, cw, ch, cells_x)], select_key((int)kp_score_out[k], k));
+            }
+            __syncthreads();
+            // one cell per lane: its rank among the winners = how many of them stand in front of it
+            const unsigned long long key = tid < ncells ? s_best[tid] : 0ull;
+            if (key) {
+                const int mycnt = s_cnt[tid];
+                int rank = 0;
+                for (int j = 0; j < ncells; j++) {
+                    const unsigned long long kj = s_best[j];
+                    rank += (kj != 0ull && j != tid && select_before(s_cnt[j], kj, mycnt, key)) ? 1 : 0;
+                }
+                s_list[rank] = key;
+                atomicAdd(&s_round[0], 1);
+            }
+            __syncthreads();
+            const int nlist = s_round[0];
+            if (nlist == 0) break;  // no cell has a candidate (uniform: one LDS word, read by every lane behind the barrier)
+            if (wave == 0) {
+                int mine = added;  // (wavefront 0's own count while it walks: `added` itself stays what every lane read from LDS)
+                for (int c0 = 0; c0 < nlist && mine < wanted; c0 += 64) {
+                    const bool cand = c0 + lane < nlist;
+                    int x = 0, y = 0;
+                    if (cand) {
+                        const int k = select_key_index(s_list[c0 + lane]);
+                        x = kp_xy[2 * k];
+                        y = kp_xy[2 * k + 1];
+                    }
+                    mine = first_fit_wave<LDSMASK, true>(mask, cand, x, y, lane, mine, wanted, new_xy, new_uv, fx, fy, cx, cy, w, h, radius, hw,
+                                                         s_cnt, cw, ch, cells_x);
+                }
+                if (lane == 0) s_round[1] = mine;
+            }
+            if (!LDSMASK) __threadfence();  // wavefront 0's ORs went to the global mask
+            __syncthreads();
+            // the first entry of the list is always taken (it was free when it was tested, and nothing has been stamped since), so every
+            // round adds: at most `wanted` rounds.  Should one ever add nothing, leave rather than spin (uniform: the same LDS word)
+            const int now = s_round[1];
+            if (now == added) break;
+            added = now;
+        }
+        if (tid == 0) *new_count = added;
+        return;
+    }
     if (wave != 0) return;  // (no workgroup barrier below this line)
-    int wanted = num_features - N_old, added = 0;
+    int added = 0;
     const int nk = min(*kp_count, cap_kp);
     for (int c0 = 0; c0 < nk && added < wanted; c0 += 64) {
         const int k = c0 + lane;
@@ -305,31 +403,9 @@ __global__ __launch_bounds__(256) void replenish_select_kernel(const int* kp_xy,
         if (k < nk) {
             x = kp_xy[2 * k];
             y = kp_xy[2 * k + 1];
-            cand = !(x < kill_pad || y < kill_pad || w - x < kill_pad || h - y < kill_pad);  // Frame::isPixelInBox
+            cand = select_in_box(x, y, w, h, kill_pad);  // Frame::isPixelInBox
         }
-        unsigned long long todo = __ballot(cand);
-        while (todo && added < wanted) {
-            // test the remaining candidates against the current mask
-            const bool is_free = cand && ((todo >> lane) & 1ull) && !mask.test(x, y);
-            const unsigned long long fb = __ballot(is_free);
-            if (!fb) break;
-            const int L = __ffsll((long long)fb) - 1;
-            const int ax = __shfl(x, L, 64), ay = __shfl(y, L, 64);
-            if (lane == 0) {
-                new_xy[2 * added] = ax;
-                new_xy[2 * added + 1] = ay;
-                // Feature::pixel2Metric (Feature.h:60-62)
-                new_uv[2 * added] = ((float)ax - cx) / fx;
-                new_uv[2 * added + 1] = ((float)ay - cy) / fy;
-            }
-            added++;
-            stamp_circle(mask, w, h, ax, ay, radius, lane, hw);
-            // this wavefront's own ORs must have landed before it tests the mask again; wavefronts 1-3 have exited, so
-            // a workgroup barrier here would be a barrier after a partial exit: wait for the wave's own memory operations
-            asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-            __builtin_amdgcn_wave_barrier();
-            todo &= ~((2ull << L) - 1ull);  // everything up to and including L is consumed
-        }
+        added = first_fit_wave<LDSMASK, false>(mask, cand, x, y, lane, added, wanted, new_xy, new_uv, fx, fy, cx, cy, w, h, radius, hw, nullptr, 1, 1, 1);
     }
     if (lane == 0) *new_count = added;
 }
@@ -463,15 +539,27 @@ int replenish_enqueue(ekfvio_filter* f, int* enqueued) {
     const float fx = v.fx, fy = v.fy, cx = v.cx, cy = v.cy;
     const size_t mask_words = (size_t)((w + 31) / 32) * h;
     const unsigned* blocked = mask_blocked_for(f, w, h);  // ekfvio_set_mask: the occupancy image starts as B instead of empty (null: off)
-    if (mask_words <= OCC_LDS_WORDS) {
-        hipLaunchKernelGGL(replenish_select_kernel<true>, dim3(1), dim3(256), 0, f->stream, f->fast_kp_xy, f->fast_counts, f->fast_kp_cap,
+    const int gx = f->replenish_cells_x, gy = f->replenish_cells_y;  // ekfvio_set_replenish_grid: the kernels' grid instances, two more arguments
+    if (!select_grid_off(gx, gy)) {
+        const bool lds = mask_words <= OCC_LDS_WORDS;
+        if (!lds) {
+            if (blocked) HIP_TRY(f, hipMemcpyAsync(f->occ_mask, blocked, mask_words * sizeof(unsigned), hipMemcpyDeviceToDevice, f->stream));
+            else HIP_TRY(f, hipMemsetAsync(f->occ_mask, 0, mask_words * sizeof(unsigned), f->stream));
+        }
+        auto kern = lds ? replenish_select_kernel<true, true, int, int> : replenish_select_kernel<false, true, int, int>;
+        hipLaunchKernelGGL(kern, dim3(1), dim3(256), 0, f->stream, f->fast_kp_xy, f->fast_counts, f->fast_kp_cap, f->mu, f->N, fx, fy, cx, cy,
+                           f->cfg.max_features, w, h, f->cfg.min_new_feature_dist, f->cfg.kill_pad, (unsigned*)f->occ_mask, f->new_xy, f->zmeas,
+                           f->fast_counts + 1, f->fast_row_kp, f->fast_row_cnt, f->fast_kp_xy, f->fast_kp_score, f->fast_counts,
+                           lds ? blocked : (const unsigned*)nullptr, gx, gy);
+    } else if (mask_words <= OCC_LDS_WORDS) {
+        hipLaunchKernelGGL((replenish_select_kernel<true, false>), dim3(1), dim3(256), 0, f->stream, f->fast_kp_xy, f->fast_counts, f->fast_kp_cap,
                            f->mu, f->N, fx, fy, cx, cy, f->cfg.max_features, w, h, f->cfg.min_new_feature_dist, f->cfg.kill_pad,
                            (unsigned*)f->occ_mask, f->new_xy, f->zmeas, f->fast_counts + 1, f->fast_row_kp, f->fast_row_cnt, f->fast_kp_xy,
                            f->fast_kp_score, f->fast_counts, blocked);
     } else {
         if (blocked) HIP_TRY(f, hipMemcpyAsync(f->occ_mask, blocked, mask_words * sizeof(unsigned), hipMemcpyDeviceToDevice, f->stream));
         else HIP_TRY(f, hipMemsetAsync(f->occ_mask, 0, mask_words * sizeof(unsigned), f->stream));
-        hipLaunchKernelGGL(replenish_select_kernel<false>, dim3(1), dim3(256), 0, f->stream, f->fast_kp_xy, f->fast_counts, f->fast_kp_cap,
+        hipLaunchKernelGGL((replenish_select_kernel<false, false>), dim3(1), dim3(256), 0, f->stream, f->fast_kp_xy, f->fast_counts, f->fast_kp_cap,
                            f->mu, f->N, fx, fy, cx, cy, f->cfg.max_features, w, h, f->cfg.min_new_feature_dist, f->cfg.kill_pad,
                            (unsigned*)f->occ_mask, f->new_xy, f->zmeas, f->fast_counts + 1, f->fast_row_kp, f->fast_row_cnt, f->fast_kp_xy,
                            f->fast_kp_score, f->fast_counts, (const unsigned*)nullptr);
@@ -534,6 +622,97 @@ int ekfvio_replenish(ekfvio_filter* f, int32_t* added, int32_t* new_px_xy) {
     }
     HIP_TRY(f, hipStreamSynchronize(f->stream));
     if (added) *added = k;
+    return EKFVIO_OK;
+}
+
+int ekfvio_set_replenish_grid(ekfvio_filter* f, int32_t cells_x, int32_t cells_y) {
+    if (!f || !select_grid_valid(cells_x, cells_y)) return EKFVIO_EINVAL;
+    f->replenish_cells_x = cells_x, f->replenish_cells_y = cells_y;  // (read by the next replenishment, which is in no captured graph)
+    return EKFVIO_OK;
+}
+
+int ekfvio_get_replenish_grid(ekfvio_filter* f, int32_t* cells_x, int32_t* cells_y) {
+    if (!f) return EKFVIO_EINVAL;
+    if (cells_x) *cells_x = f->replenish_cells_x;
+    if (cells_y) *cells_y = f->replenish_cells_y;
+    return EKFVIO_OK;
+}
+
+// The selection on the host: the occupancy image as bytes, the circles from the rows' half-widths, the cells' maxima and ranks from loops,
+// all through the inline functions the kernel compiles (select.h).
+int ekfvio_replenish_select(const int32_t* kp_xy, const int32_t* score, int32_t count, const int32_t* existing_px_xy, int32_t n_existing,
+                            const uint8_t* blocked, int32_t W, int32_t H, int32_t radius, int32_t kill_pad, int32_t cells_x, int32_t cells_y,
+                            int32_t wanted, int32_t* new_xy, int32_t* added_out) {
+    if (!added_out || count < 0 || n_existing < 0 || wanted < 0 || W < 1 || H < 1 || radius < 0 || radius > SELECT_MAX_RADIUS ||
+        !select_grid_valid(cells_x, cells_y) || (count > 0 && (!kp_xy || !score)) || (n_existing > 0 && !existing_px_xy) || (wanted > 0 && !new_xy))
+        return EKFVIO_EINVAL;
+    for (int k = 0; k < count; k++)
+        if (kp_xy[2 * k] < 0 || kp_xy[2 * k] >= W || kp_xy[2 * k + 1] < 0 || kp_xy[2 * k + 1] >= H || score[k] < 0) return EKFVIO_EINVAL;
+    std::vector<uint8_t> O((size_t)W * H, 0);
+    if (blocked)
+        for (size_t i = 0; i < O.size(); i++) O[i] = blocked[i] != 0;
+    std::vector<int> hw(2 * radius + 1);
+    for (int r = -radius; r <= radius; r++) hw[r + radius] = circle_half_width(radius, r);
+    auto stamp = [&](int px, int py) {
+        for (int r = -radius; r <= radius; r++) {
+            const int y = py + r;
+            if (hw[r + radius] < 0 || y < 0 || y >= H) continue;
+            const long long xa = std::max<long long>((long long)px - hw[r + radius], 0), xb = std::min<long long>((long long)px + hw[r + radius], W - 1);
+            for (long long x = xa; x <= xb; x++) O[(size_t)y * W + x] = 1;
+        }
+    };
+    auto take = [&](int k, int added) {
+        new_xy[2 * added] = kp_xy[2 * k], new_xy[2 * added + 1] = kp_xy[2 * k + 1];
+        stamp(kp_xy[2 * k], kp_xy[2 * k + 1]);
+    };
+    // (a landmark far outside the frame stamps nothing: keep the row arithmetic inside int)
+    auto far_out = [&](int px, int py) { return px < -64 || py < -64 || px > W + 64 || py > H + 64; };
+    for (int i = 0; i < n_existing; i++)
+        if (!far_out(existing_px_xy[2 * i], existing_px_xy[2 * i + 1])) stamp(existing_px_xy[2 * i], existing_px_xy[2 * i + 1]);
+    int added = 0;
+    if (select_grid_off(cells_x, cells_y)) {  // the raster first fit
+        for (int k = 0; k < count && added < wanted; k++) {
+            const int x = kp_xy[2 * k], y = kp_xy[2 * k + 1];
+            if (!select_in_box(x, y, W, H, kill_pad) || O[(size_t)y * W + x]) continue;
+            take(k, added++);
+        }
+        *added_out = added;
+        return EKFVIO_OK;
+    }
+    const int cw = select_cell_size(W, cells_x), ch = select_cell_size(H, cells_y), ncells = cells_x * cells_y;
+    std::vector<int> cnt(ncells, 0);
+    for (int i = 0; i < n_existing; i++) {
+        const int px = existing_px_xy[2 * i], py = existing_px_xy[2 * i + 1];
+        if (px >= 0 && px < W && py >= 0 && py < H) cnt[select_cell(px, py, cw, ch, cells_x)]++;
+    }
+    std::vector<unsigned long long> best(ncells), list(ncells);
+    while (added < wanted) {
+        std::fill(best.begin(), best.end(), 0ull);
+        for (int k = 0; k < count; k++) {
+            const int x = kp_xy[2 * k], y = kp_xy[2 * k + 1];
+            if (!select_in_box(x, y, W, H, kill_pad) || O[(size_t)y * W + x]) continue;
+            unsigned long long& b = best[select_cell(x, y, cw, ch, cells_x)];
+            b = std::max(b, select_key(score[k], k));
+        }
+        int nlist = 0;
+        for (int c = 0; c < ncells; c++) {
+            if (!best[c]) continue;
+            int rank = 0;
+            for (int j = 0; j < ncells; j++) rank += (best[j] != 0ull && j != c && select_before(cnt[j], best[j], cnt[c], best[c])) ? 1 : 0;
+            list[rank] = best[c];
+            nlist++;
+        }
+        if (nlist == 0) break;
+        // (the ranks above were formed from cnt as it stood at the start of the round; the walk changes it)
+        for (int i = 0; i < nlist && added < wanted; i++) {
+            const int k = select_key_index(list[i]);
+            const int x = kp_xy[2 * k], y = kp_xy[2 * k + 1];
+            if (O[(size_t)y * W + x]) continue;  // a neighbouring cell's winner has covered it
+            take(k, added++);
+            cnt[select_cell(x, y, cw, ch, cells_x)]++;
+        }
+    }
+    *added_out = added;
     return EKFVIO_OK;
 }
 

@@ -27,7 +27,7 @@ class TightlyCoupledEKF:
                  default_point_depth=0.5, default_point_depth_variance=100.0,
                  default_point_homogenous_variance=1e-5, hooks=False, gate_chi2=0.0, klt_fb_max_px=0.0, distortion=None, output_covariance=False,
                  mask=None, mask_rectify_border=False, equalize=None, klt_photometric=False, ended_export=False, zupt=None,
-                 imu_extrinsics=None, camera_model=None, **cfg_overrides):
+                 imu_extrinsics=None, camera_model=None, replenish_grid=None, **cfg_overrides):
         # hooks=True: this handle lives in libekfvio_hip_hooks.so, the build that also has include/ekfvio_test_hooks.h (tests, profiling scripts)
         self.hooks = bool(hooks)
         self.lib = capi.load(hooks=self.hooks)
@@ -71,6 +71,8 @@ class TightlyCoupledEKF:
             self.setZupt(*zupt)
         if imu_extrinsics is not None:  # likewise (ekfvio_set_imu_extrinsics)
             self.setImuExtrinsics(*imu_extrinsics)
+        if replenish_grid is not None:  # likewise (ekfvio_set_replenish_grid): (cells_x, cells_y)
+            self.setReplenishGrid(*replenish_grid)
 
     def _chk(self, rc, allow=()):
         if rc != capi.OK and rc not in allow:
@@ -328,6 +330,17 @@ class TightlyCoupledEKF:
         (ekfvio_set_klt_photometric): span{1, I} is projected out of the template's gradients, once per pyramid level.  On from the next
         track, in the forward pass and in the forward-backward check's backward pass; off by default."""
         self._chk(self.lib.ekfvio_set_klt_photometric(self.h, int(on)))
+
+    def setReplenishGrid(self, cells_x, cells_y):
+        """New landmarks spread over the image (ekfvio_set_replenish_grid): from the next replenishment on the strongest free corner of every
+        cell of a cells_x x cells_y grid, emptier cells first, instead of the raster first fit.  (0, 0): off; (1, 1): strongest corner first."""
+        self._chk(self.lib.ekfvio_set_replenish_grid(self.h, int(cells_x), int(cells_y)))
+
+    def replenishGrid(self):
+        """ekfvio_get_replenish_grid: (cells_x, cells_y); (0, 0) = off."""
+        cx, cy = C.c_int32(0), C.c_int32(0)
+        self._chk(self.lib.ekfvio_get_replenish_grid(self.h, C.byref(cx), C.byref(cy)))
+        return cx.value, cy.value
 
     def mask_blocked(self):
         """ekfvio_get_mask: the blocked map B as the device holds it, uint8 [H, W] of level 0 (1 = blocked); shape (0, 0) before the first
@@ -719,6 +732,30 @@ def klt_project_gradients(Iv, Ix, Iy):
     return ox, oy
 
 
+def replenish_select(kp_xy, score, existing_px_xy, blocked, width, height, radius, kill_pad, cells_x, cells_y, wanted):
+    """ekfvio_replenish_select: the pixels (int32 [k, 2], in the order taken) the replenishment's selection takes among the keypoints kp_xy
+    (int [n, 2], raster order) with scores `score`, given the rounded pixels of the landmarks in the state and the blocked map (uint8 [h, w]
+    or None).  cells_x = cells_y = 0: the raster first fit.  A host function: no GPU involved."""
+    lib = capi.load()
+    xy = np.ascontiguousarray(kp_xy, dtype=np.int32).reshape(-1, 2)
+    sc = np.ascontiguousarray(score, dtype=np.int32).reshape(-1)
+    ex = np.ascontiguousarray(existing_px_xy, dtype=np.int32).reshape(-1, 2)
+    if xy.shape[0] != sc.shape[0]:
+        raise capi.EkfvioError(capi.EINVAL, "one score per keypoint")
+    b = None
+    if blocked is not None:
+        b = np.ascontiguousarray(blocked, dtype=np.uint8)
+        if b.shape != (int(height), int(width)):
+            raise capi.EkfvioError(capi.EINVAL, "blocked is [height, width]")
+    out, k = np.zeros((max(int(wanted), 1), 2), np.int32), C.c_int32(0)
+    rc = lib.ekfvio_replenish_select(_ip(xy) if xy.size else None, _ip(sc) if sc.size else None, int(xy.shape[0]), _ip(ex) if ex.size else None,
+                                     int(ex.shape[0]), _u8(b) if b is not None else None, int(width), int(height), int(radius), int(kill_pad),
+                                     int(cells_x), int(cells_y), int(wanted), _ip(out), C.byref(k))
+    if rc != capi.OK:
+        raise capi.EkfvioError(rc, "ekfvio_replenish_select")
+    return out[:k.value].copy()
+
+
 class EKFVIO:
     """Host mirror of the step sequence of EKFVIO::addFrame / updateStateWithNewImage
     (include/ekf_vio/EKFVIO.cpp:139-219) without ROS: frames in, odometry + landmark cloud out.
@@ -732,7 +769,8 @@ class EKFVIO:
         # equalize=(clip_limit, tiles_x, tiles_y): every frame is equalised on the device before its pyramid, setEqualize below;
         # klt_photometric=True: the tracker's gain/offset term, setKltPhotometric below; ended_export=True: every removal hands out the records of
         # the landmarks that leave, setEndedExport below; zupt=(max_flow_px, min_tracks, min_ratio, vel_var, omega_var): the zero-velocity update,
-        # setZupt below; imu_extrinsics=(R_ci, p_ci): the IMU in its own frame, setImuExtrinsics below; gravity_align_samples=K: the first K IMU
+        # setZupt below; imu_extrinsics=(R_ci, p_ci): the IMU in its own frame, setImuExtrinsics below; replenish_grid=(cells_x, cells_y): new
+        # landmarks spread over a grid of cells, setReplenishGrid below; gravity_align_samples=K: the first K IMU
         # records that come up for application are not applied but averaged, and their mean accelerometer reading sets the gravity vector:
         # the rig is taken to be AT REST through them, with an accelerometer bias negligible against 9.81; frames meanwhile are processed as
         # without an IMU)
@@ -820,6 +858,10 @@ class EKFVIO:
         """TightlyCoupledEKF.setKltPhotometric: from the next frame on the tracker matches up to a gain and an offset."""
         self.tc_ekf.setKltPhotometric(on)
 
+    def setReplenishGrid(self, cells_x, cells_y):
+        """TightlyCoupledEKF.setReplenishGrid: from the next replenishment on new landmarks are spread over a grid of cells ((0, 0): off)."""
+        self.tc_ekf.setReplenishGrid(cells_x, cells_y)
+
     def landmark_ids(self):
         """TightlyCoupledEKF.landmark_ids: (ids int64[N], born float64[N]), rows as points()'; a memcpy behind a frame."""
         return self.tc_ekf.landmark_ids()
@@ -859,7 +901,8 @@ class EKFVIO:
 
     def replenishFeatures(self):
         """EKFVIO::replenishFeatures (EKFVIO.cpp:224-311) on the current frame, on the device: FAST-9/16 with
-        non-maximum suppression, occupancy circles, first fit, addNewFeatures.  Returns the new landmarks' pixels."""
+        non-maximum suppression, occupancy circles, first fit (or, with setReplenishGrid, the grid's rounds), addNewFeatures.  Returns the new
+        landmarks' pixels."""
         k = C.c_int32(0)
         px = np.zeros((max(self.tc_ekf.cfg.max_features, 1), 2), np.int32)
         self.tc_ekf._chk(self.tc_ekf.lib.ekfvio_replenish(self.tc_ekf.h, C.byref(k), _ip(px)))

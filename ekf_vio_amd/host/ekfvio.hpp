@@ -107,6 +107,10 @@ struct Params {
     std::array<float, 9> imu_rotation{{1.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f, 1.f}};
     std::array<float, 3> imu_position{{0.f, 0.f, 0.f}};
     int imu_extrinsics = 0, gravity_align_samples = 0;
+    // Not in the reference, whose replenishFeatures takes the detector's corners in raster order, first fit: with replenish_grid_x, replenish_grid_y >= 1
+    // (at most 256 cells together) new landmarks are the strongest free corner of every cell of that grid over the resized frame, emptier cells first
+    // (ekfvio_set_replenish_grid); both 0 = off.  One of them alone is an error when the handle is made.
+    int replenish_grid_x = 0, replenish_grid_y = 0;
     std::map<std::string, std::string> node;  // odom_topic, camera_topic, base_frame, use_imu, publish_insight, ...
 
     Params() {
@@ -206,6 +210,11 @@ struct Params {
             if (!(v > 0.f) || !std::isfinite(v)) throw Error(EKFVIO_EINVAL, "parameter " + key + ": not a finite value > 0: " + value);
             (key == "zupt_vel_variance" ? zupt_vel_variance : zupt_omega_variance) = v;
         }
+        else if (key == "replenish_grid_x" || key == "replenish_grid_y") {
+            const int c = integer(key, value);
+            if (c < 0 || c > 256) throw Error(EKFVIO_EINVAL, "parameter " + key + ": not in [0, 256]: " + value);
+            (key == "replenish_grid_x" ? replenish_grid_x : replenish_grid_y) = c;
+        }
         else if (key == "imu_rotation") {  // (what ekfvio_set_imu_extrinsics would refuse is refused when the handle is made)
             numbers(key, value, imu_rotation.data(), 9);
             imu_extrinsics = 1;
@@ -255,7 +264,7 @@ struct Params {
                                         "default_point_depth", "default_point_depth_variance",
                                         "default_point_homogenous_variance", "frame_buffer_size", "imu_update",
                                         "imu_gyro_variance", "imu_accel_variance", "gravity_x", "gravity_y", "gravity_z", "remove_lost", "gate_chi2",
-                                        "klt_fb_max_px", "rectify", "publish_covariance", "mask_rectify_border", "equalize_clip_limit", "equalize_tiles_x", "equalize_tiles_y", "klt_photometric", "publish_ids", "publish_ended", "zupt_max_flow_px", "zupt_min_tracks", "zupt_min_ratio", "zupt_vel_variance", "zupt_omega_variance", "imu_rotation", "imu_position", "gravity_align_samples", "distortion_k1", "distortion_k2", "distortion_p1", "distortion_p2", "distortion_k3",
+                                        "klt_fb_max_px", "rectify", "publish_covariance", "mask_rectify_border", "equalize_clip_limit", "equalize_tiles_x", "equalize_tiles_y", "klt_photometric", "publish_ids", "publish_ended", "zupt_max_flow_px", "zupt_min_tracks", "zupt_min_ratio", "zupt_vel_variance", "zupt_omega_variance", "imu_rotation", "imu_position", "gravity_align_samples", "replenish_grid_x", "replenish_grid_y", "distortion_k1", "distortion_k2", "distortion_p1", "distortion_p2", "distortion_k3",
                                         "distortion_model", "distortion_k4", "distortion_k5", "distortion_k6", "rectified_fx", "rectified_fy", "rectified_cx", "rectified_cy"};
         for (const auto& e : Params().node) out.push_back(e.first);
         for (const auto& e : ignored()) out.push_back(e.first);
@@ -414,6 +423,9 @@ class TightlyCoupledEKF {
     // Not in the reference, whose tracker assumes brightness constancy: the gain/offset term of every Lucas-Kanade pass
     // (ekfvio_set_klt_photometric).  On from the next track; off by default.
     void setKltPhotometric(bool on) { chk(ekfvio_set_klt_photometric(h_, on ? 1 : 0)); }
+    // New landmarks spread over the image (ekfvio_set_replenish_grid): from the next replenishment on the strongest free corner of every cell of a
+    // cells_x x cells_y grid, emptier cells first, instead of the raster first fit.  (0, 0): off, the default; (1, 1): strongest corner first.
+    void setReplenishGrid(int cells_x, int cells_y) { chk(ekfvio_set_replenish_grid(h_, cells_x, cells_y)); }
     // Not in the reference: the zero-velocity update (ekfvio_set_zupt).  max_flow_px > 0: a frame in which at least min_tracks landmarks passed the
     // tracker and at least min_ratio of those moved no more than max_flow_px pixels updates the velocity and the body rate with z = 0 in front of
     // the camera update; 0: off.  zuptUpdate: that update alone, unconditional, for a caller with a stop detector of its own.
@@ -686,6 +698,7 @@ class EKFVIO {
         if (p.mask_rectify_border) tc_ekf.setMask(nullptr, 0, 0, 0, EKFVIO_MASK_RECTIFY_BORDER);  // (likewise; live once the coefficients are nonzero)
         if (p.equalize_clip_limit > 0.f) tc_ekf.setEqualize(p.equalize_clip_limit, p.equalize_tiles_x, p.equalize_tiles_y);  // (likewise)
         if (p.klt_photometric) tc_ekf.setKltPhotometric(true);  // (likewise)
+        if (p.replenish_grid_x || p.replenish_grid_y) tc_ekf.setReplenishGrid(p.replenish_grid_x, p.replenish_grid_y);  // (likewise; one of the two alone is refused here)
         if (p.publish_ended) tc_ekf.setEndedExport(true);  // (likewise)
         if (p.zupt_max_flow_px > 0.f) tc_ekf.setZupt(p.zupt_max_flow_px, p.zupt_min_tracks, p.zupt_min_ratio, p.zupt_vel_variance, p.zupt_omega_variance);  // (likewise)
         if (p.imu_extrinsics) tc_ekf.setImuExtrinsics(p.imu_rotation.data(), p.imu_position.data());  // (likewise)

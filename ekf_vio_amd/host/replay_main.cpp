@@ -10,6 +10,7 @@
 //                                [--equalize-clip-limit c] [--equalize-tiles-x n] [--equalize-tiles-y n] [--tracks FILE] [--ended FILE]
 //                                [--zupt-max-flow-px p] [--zupt-min-tracks n] [--zupt-min-ratio r] [--zupt-vel-variance v] [--zupt-omega-variance v]
 //                                [--imu-rotation "r00 r01 ... r22"] [--imu-position "x y z"] [--gravity-align-samples k]
+//                                [--replenish-grid-x n] [--replenish-grid-y n]
 //                                [--distortion-model plumb_bob|rational_polynomial|equidistant|fisheye] [--rectified-camera "fx fy cx cy"]
 //
 // --distortion-model and --rectified-camera are the node parameters distortion_model and rectified_fx/fy/cx/cy (ekfvio_set_camera_model; live
@@ -31,7 +32,8 @@
 // --equalize-clip-limit / --equalize-tiles-x / --equalize-tiles-y are the node parameters of the same names (ekfvio_set_equalize), applied
 // behind the parameter file, and so are the five --zupt-* options (ekfvio_set_zupt; --print-config echoes the parameters) and --imu-rotation (nine numbers, row-major,
 // IMU -> camera axes) / --imu-position (three numbers, metres) / --gravity-align-samples (ekfvio_set_imu_extrinsics, ekfvio_set_gravity: the node
-// parameters imu_rotation, imu_position, gravity_align_samples).  --tracks FILE writes one line per live landmark per frame, behind the frame,
+// parameters imu_rotation, imu_position, gravity_align_samples).  --replenish-grid-x / --replenish-grid-y set the grid the new landmarks are
+// spread over (ekfvio_set_replenish_grid: the node parameters replenish_grid_x, replenish_grid_y; 0 0 = off).  --tracks FILE writes one line per live landmark per frame, behind the frame,
 //     frame stamp id born x y z
 // (ekfvio_get_landmark_ids beside the cloud: one landmark's depth over time is the lines with its id).  --ended FILE turns the export of the
 // tracks that ended on (ekfvio_set_ended_export; the replay itself removes lost landmarks only with remove_lost: 1 in the parameter file) and
@@ -90,7 +92,7 @@ static int print_config(const char* path) {
                     "\"kill_pad\": %d, \"klt_min_eigen\": %.9g, \"min_new_feature_dist\": %d, \"klt_max_pyramid_level\": %d, "
                     "\"klt_window_size\": %d, \"default_point_depth\": %.9g, \"default_point_depth_variance\": %.9g, "
                     "\"default_point_homogenous_variance\": %.9g, \"sample_based_uncertainty\": %d, \"gate_chi2\": %.9g, "
-                    "\"klt_fb_max_px\": %.9g, \"rectify\": %d, \"publish_covariance\": %d, \"mask_rectify_border\": %d, \"equalize_clip_limit\": %.9g, \"equalize_tiles_x\": %d, \"equalize_tiles_y\": %d, \"klt_photometric\": %d, \"publish_ids\": %d, \"publish_ended\": %d, \"zupt_max_flow_px\": %.9g, \"zupt_min_tracks\": %d, \"zupt_min_ratio\": %.9g, \"zupt_vel_variance\": %.9g, \"zupt_omega_variance\": %.9g, \"imu_extrinsics\": %d, \"imu_rotation\": [%.9g, %.9g, %.9g, %.9g, %.9g, %.9g, %.9g, %.9g, %.9g], \"imu_position\": [%.9g, %.9g, %.9g], \"gravity_align_samples\": %d, \"distortion\": [%.17g, %.17g, %.17g, %.17g, %.17g], \"distortion_model\": \"%s\", \"distortion_k456\": [%.17g, %.17g, %.17g], \"rectified\": [%.9g, %.9g, %.9g, %.9g], \"node\": {",
+                    "\"klt_fb_max_px\": %.9g, \"rectify\": %d, \"publish_covariance\": %d, \"mask_rectify_border\": %d, \"equalize_clip_limit\": %.9g, \"equalize_tiles_x\": %d, \"equalize_tiles_y\": %d, \"klt_photometric\": %d, \"publish_ids\": %d, \"publish_ended\": %d, \"zupt_max_flow_px\": %.9g, \"zupt_min_tracks\": %d, \"zupt_min_ratio\": %.9g, \"zupt_vel_variance\": %.9g, \"zupt_omega_variance\": %.9g, \"imu_extrinsics\": %d, \"imu_rotation\": [%.9g, %.9g, %.9g, %.9g, %.9g, %.9g, %.9g, %.9g, %.9g], \"imu_position\": [%.9g, %.9g, %.9g], \"gravity_align_samples\": %d, \"replenish_grid_x\": %d, \"replenish_grid_y\": %d, \"distortion\": [%.17g, %.17g, %.17g, %.17g, %.17g], \"distortion_model\": \"%s\", \"distortion_k456\": [%.17g, %.17g, %.17g], \"rectified\": [%.9g, %.9g, %.9g, %.9g], \"node\": {",
                     c.max_features, c.fast_threshold, (double)c.fast_blur_sigma, c.inverse_image_scale, c.kill_pad,
                     (double)c.klt_min_eigen, c.min_new_feature_dist, c.klt_max_pyramid_level, c.klt_window_size,
                     (double)c.default_point_depth, (double)c.default_point_depth_variance,
@@ -98,7 +100,7 @@ static int print_config(const char* path) {
                     (double)c.klt_fb_max_px, p.rectify, p.publish_covariance, p.mask_rectify_border, (double)p.equalize_clip_limit, p.equalize_tiles_x, p.equalize_tiles_y, p.klt_photometric, p.publish_ids, p.publish_ended, (double)p.zupt_max_flow_px, p.zupt_min_tracks, (double)p.zupt_min_ratio, (double)p.zupt_vel_variance, (double)p.zupt_omega_variance, p.imu_extrinsics,
                     (double)p.imu_rotation[0], (double)p.imu_rotation[1], (double)p.imu_rotation[2], (double)p.imu_rotation[3], (double)p.imu_rotation[4],
                     (double)p.imu_rotation[5], (double)p.imu_rotation[6], (double)p.imu_rotation[7], (double)p.imu_rotation[8],
-                    (double)p.imu_position[0], (double)p.imu_position[1], (double)p.imu_position[2], p.gravity_align_samples, p.distortion[0], p.distortion[1], p.distortion[2], p.distortion[3], p.distortion[4],
+                    (double)p.imu_position[0], (double)p.imu_position[1], (double)p.imu_position[2], p.gravity_align_samples, p.replenish_grid_x, p.replenish_grid_y, p.distortion[0], p.distortion[1], p.distortion[2], p.distortion[3], p.distortion[4],
                     p.distortion_model.c_str(), p.distortion_k456[0], p.distortion_k456[1], p.distortion_k456[2],
                     (double)p.rectified[0], (double)p.rectified[1], (double)p.rectified[2], (double)p.rectified[3]);
         bool first = true;
@@ -293,6 +295,8 @@ int main(int argc, char** argv) {
             else if (std::strcmp(argv[i], "--imu-rotation") == 0) overrides.emplace_back("imu_rotation", argv[i + 1]);
             else if (std::strcmp(argv[i], "--imu-position") == 0) overrides.emplace_back("imu_position", argv[i + 1]);
             else if (std::strcmp(argv[i], "--gravity-align-samples") == 0) overrides.emplace_back("gravity_align_samples", argv[i + 1]);
+            else if (std::strcmp(argv[i], "--replenish-grid-x") == 0) overrides.emplace_back("replenish_grid_x", argv[i + 1]);
+            else if (std::strcmp(argv[i], "--replenish-grid-y") == 0) overrides.emplace_back("replenish_grid_y", argv[i + 1]);
             else if (std::strcmp(argv[i], "--distortion-model") == 0) overrides.emplace_back("distortion_model", argv[i + 1]);
             else if (std::strcmp(argv[i], "--rectified-camera") == 0) {  // "fx fy cx cy": the four rectified_* parameters
                 std::istringstream in(argv[i + 1]);

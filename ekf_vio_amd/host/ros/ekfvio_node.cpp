@@ -115,7 +115,9 @@ class EkfvioNode {
         // imu_rotation, nine numbers row-major, and imu_position, three numbers in metres, each given as ONE STRING of numbers separated by
         // blanks or commas (a YAML list is a parameter of unsupported type here): the rotation and translation of Kalibr's T_cam_imu,
         // ekfvio_set_imu_extrinsics, so that imu_update models the IMU in its own frame; gravity_align_samples, default 0 = off: that many IMU
-        // records at the start are averaged, not applied, and set the gravity vector, ekfvio_set_gravity -- the rig has to stand still)
+        // records at the start are averaged, not applied, and set the gravity vector, ekfvio_set_gravity -- the rig has to stand still;
+        // replenish_grid_x and replenish_grid_y, default 0 0 = off: new landmarks are the strongest free corner of every cell of that grid over
+        // the resized frame, emptier cells first, instead of the detector's raster order, ekfvio_set_replenish_grid -- at most 256 cells)
         for (const std::string& name : ekfvio::Params::names()) {
             XmlRpc::XmlRpcValue v;
             if (ros::param::get("~" + name, v)) params_.set(name, to_text(v));

@@ -670,6 +670,59 @@ EKFVIO_API int ekfvio_step_image(ekfvio_filter* f, double stamp, const uint8_t* 
  * exist.  `added` (may be NULL) receives the number of new landmarks, new_px_xy (may be NULL, room for
  * 2*max_features ints) their pixels. */
 EKFVIO_API int ekfvio_replenish(ekfvio_filter* f, int32_t* added, int32_t* new_px_xy);
+
+/* ---- new landmarks spread over the image (not in the reference, whose replenishFeatures takes FAST keypoints in raster order, first fit: a
+ * filter that needs a few landmarks gets them all from the top rows, one that needs many fills from the top left) -------------------------
+ * For a monocular EKF the spread of bearings conditions rotation against translation.  With the setting on, the replenishment lays a grid of
+ * cells over level 0 and takes, round by round, the strongest free corner of every cell, emptier cells first.  The corner score is the
+ * detector's own (cornerScore, what ekfvio_fast_detect reports).  A 1 x 1 grid is "globally strongest corner first".  The lines below are
+ * the specification; all of it is integer work, so there is no floating-point order to fix, and a pure-Python restatement of them
+ * (tests/_replenish_grid.py) is what the device and ekfvio_replenish_select are held to, pixel for pixel and in order.
+ *
+ * Frame and keypoints:
+ *     level 0 of the current frame is W x H
+ *     FAST (threshold, nonmax, optional blur) gives keypoints k = 0..nk-1 in raster order with pixel (x_k, y_k) and score s_k, exactly as
+ *     without the setting
+ *     wanted = max_features - N_old      radius = min_new_feature_dist      pad = kill_pad
+ * Cells:
+ *     cw = ceil(W / cells_x)      ch = ceil(H / cells_y)
+ *     cell(x, y) = (y / ch) * cells_x + x / cw                    integer division
+ * Start:
+ *     O = the occupancy image as without the setting: B of ekfvio_set_mask where that is on, else empty
+ *     stamp the circle of every landmark in the state at cvRound(u fx + cx, v fy + cy); flagged landmarks are included, as without the setting
+ *     cnt[c] = the number of those landmarks whose rounded pixel lies inside [0,W) x [0,H) and in cell c
+ *     added = 0
+ * Repeat while added < wanted:
+ *     1. a keypoint is a candidate when it passes the kill-box test (Frame::isPixelInBox, as without the setting) and O(x_k, y_k) == 0
+ *     2. best[c] = the candidate of cell c with the largest s_k, ties to the smallest k; if no cell has one, stop
+ *     3. L = the cells that have a best, ordered by cnt[c] ascending, then s descending, then k ascending (integer comparisons; no two keys
+ *        are equal); cnt is read as it stood at the start of the round
+ *     4. walk through L in order and stop at added == wanted: if O(x, y) is still 0, take the keypoint -- new_xy[added] and new_uv[added]
+ *        by Feature::pixel2Metric as without the setting, added++, stamp its circle into O, cnt[c]++; otherwise skip it (a neighbouring
+ *        cell's winner has covered it)
+ * The first entry of L is always taken, so the loop ends after at most `wanted` rounds.
+ *
+ * What it does not do: another detector or score, sub-pixel refinement of the new corners, a cap on the landmarks per cell, removing landmarks
+ * to rebalance the cells; ekfvio_add_features is untouched (a caller's own detector is the caller's business).
+ *
+ * ekfvio_set_replenish_grid.  (0, 0): off (default; then no launch differs, nothing is allocated and every output keeps its bits).  On: both
+ * values >= 1 and cells_x * cells_y <= 256; anything else EKFVIO_EINVAL, and the setting stays what it was.  A property of the handle, not of
+ * ekfvio_config: it holds from the next replenishment (ekfvio_replenish, and ekfvio_step_image with cfg.replenish = 1), survives ekfvio_reset and
+ * drops no captured graph (the replenishment is in none).  On, the selection stays one launch of one workgroup, the kernel's grid instance; it
+ * then passes over the keypoints once per round instead of once (README, "new landmarks spread over the image", has the measured cost). */
+EKFVIO_API int ekfvio_set_replenish_grid(ekfvio_filter* f, int32_t cells_x, int32_t cells_y);
+/* Reads the setting back (either pointer may be NULL). */
+EKFVIO_API int ekfvio_get_replenish_grid(ekfvio_filter* f, int32_t* cells_x, int32_t* cells_y);
+/* The selection itself: a pure host function (no handle, no device) that compiles the very inline functions the kernel compiles
+ * (csrc/select.h: cell(), the keys and their order, the kill-box test, the circle's rows), as ekfvio_rectify_map and ekfvio_zupt_decide do; the
+ * cells' maxima come from a loop here and from LDS atomics there.  kp_xy, score: `count` keypoints in raster order, x,y interleaved, inside the
+ * frame, scores >= 0.  existing_px_xy: the rounded pixels of the n_existing landmarks in the state (any value; outside the frame they count for no
+ * cell).  blocked: one byte per level-0 pixel, non-zero = blocked (ekfvio_mask_blocked's output), or NULL.  new_xy: room for 2 * wanted ints.
+ * cells_x = cells_y = 0: the raster first fit of ekfvio_replenish without the setting.  A NULL among the needed pointers, a negative count, a
+ * keypoint outside the frame, a radius outside [0, 63], or a grid that ekfvio_set_replenish_grid would refuse: EKFVIO_EINVAL. */
+EKFVIO_API int ekfvio_replenish_select(const int32_t* kp_xy, const int32_t* score, int32_t count, const int32_t* existing_px_xy,
+                                       int32_t n_existing, const uint8_t* blocked, int32_t W, int32_t H, int32_t radius, int32_t kill_pad,
+                                       int32_t cells_x, int32_t cells_y, int32_t wanted, int32_t* new_xy, int32_t* added);
 /* Test hook: cv::FAST(level 0 of the current frame, blurred first if cfg.fast_blur_sigma != 0, threshold, nonmax),
  * TYPE_9_16, keypoints in raster order. */
 EKFVIO_API int ekfvio_fast_detect(ekfvio_filter* f, int32_t threshold, int32_t nonmax, int32_t cap, int32_t* xy, int32_t* score,
