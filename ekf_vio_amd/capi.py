@@ -63,7 +63,7 @@ CAMERA_MODELS = {"plumb_bob": CAMERA_PLUMB_BOB, "rational_polynomial": CAMERA_RA
 HOOK_SYMBOLS = ["ekfvio_test_klt_padded_level", "ekfvio_test_blurred_level0", "ekfvio_test_gemm", "ekfvio_test_gemm_bench", "ekfvio_test_potrf_stamps",
                 "ekfvio_test_sweep_stamps", "ekfvio_test_sweep_fault", "ekfvio_test_sweep_delay", "ekfvio_test_cholesky_solve", "ekfvio_test_plan", "ekfvio_test_persist_grid", "ekfvio_test_t2_pair",
                 "ekfvio_test_gemm_plan", "ekfvio_test_predict_plan", "ekfvio_test_run_plan", "ekfvio_test_mem", "ekfvio_test_mem_fail",
-                "ekfvio_test_fill_update_scratch", "ekfvio_test_zupt_decide", "ekfvio_test_rectify_map"]
+                "ekfvio_test_fill_update_scratch", "ekfvio_test_zupt_decide", "ekfvio_test_rectify_map", "ekfvio_test_klt_pixels"]
 
 _libs = {}
 
@@ -161,6 +161,7 @@ def load(build_if_missing=True, hooks=False):
             "ekfvio_test_fill_update_scratch": [vp, C.c_uint32],  # a word into the update's float work buffers: a handle with a history
             "ekfvio_test_zupt_decide": [vp, fp, fp, u8p, i32, f32, i32, f32, fp, ip, ip, ip],  # the device's zero-velocity decision on arbitrary points
             "ekfvio_test_rectify_map": [vp, ip, ip, i32, ip, ip],  # the rectification map as the device holds it
+            "ekfvio_test_klt_pixels": [vp, fp, fp, i32],  # the tracker's pixel buffers behind the landmarks' last track
         })
     for name, args in sig.items():
         fn = getattr(lib, name)

@@ -1423,6 +1423,19 @@ int ekfvio_test_klt_padded_level(ekfvio_filter* f, int32_t level, int32_t* borde
     HIP_TRY(f, hipStreamSynchronize(f->stream));
     return EKFVIO_OK;
 }
+
+// The tracker's pixel buffers for the handle's landmarks as the last track left them; copies, nothing else
+int ekfvio_test_klt_pixels(ekfvio_filter* f, float* prev_px, float* next_px, int32_t cap) {
+    if (!f || cap < 0) return EKFVIO_EINVAL;
+    const int N = f->N;
+    if (cap < N) return EKFVIO_EINVAL;
+    if (N == 0) return EKFVIO_OK;
+    HIP_TRY(f, hipSetDevice(f->device));
+    if (prev_px) HIP_TRY(f, hipMemcpyAsync(prev_px, f->klt_prev_px, sizeof(float) * 2 * N, hipMemcpyDeviceToHost, f->stream));
+    if (next_px) HIP_TRY(f, hipMemcpyAsync(next_px, f->klt_next_px, sizeof(float) * 2 * N, hipMemcpyDeviceToHost, f->stream));
+    HIP_TRY(f, hipStreamSynchronize(f->stream));
+    return EKFVIO_OK;
+}
 #endif
 
 }  // extern "C"

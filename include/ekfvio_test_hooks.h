@@ -101,6 +101,11 @@ EKFVIO_API int ekfvio_test_zupt_decide(ekfvio_filter* f, const float* prev_px, c
  * planes the map kernel wrote for the frame pushed last, row-major *w x *h int32 each.  sx, sy may be NULL (the size alone); cap < *w * *h:
  * EKFVIO_EINVAL; no map formed yet: EKFVIO_ESTATE.  Waits for the stream. */
 EKFVIO_API int ekfvio_test_rectify_map(ekfvio_filter* f, int32_t* sx, int32_t* sy, int32_t cap, int32_t* w, int32_t* h);
+/* The tracker's pixel buffers as the most recent track of the handle's landmarks (ekfvio_klt_track, ekfvio_step_image) left them: the
+ * reference pixels it tracked from and the pixels it tracked to, x,y interleaved, one pair per landmark; read-only.  These are the pixels the
+ * frame's zero-velocity decision reads (include/ekfvio.h).  Either pointer may be NULL; cap (in points) below the landmark count:
+ * EKFVIO_EINVAL.  An entry point that uploads points of its own (ekfvio_klt_track_points, ...) overwrites them.  Waits for the stream. */
+EKFVIO_API int ekfvio_test_klt_pixels(ekfvio_filter* f, float* prev_px, float* next_px, int32_t cap);
 
 #ifdef __cplusplus
 }

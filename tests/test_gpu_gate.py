@@ -19,8 +19,10 @@ import pytest
 from PIL import Image
 
 from ekf_vio_amd import EKFVIO, TightlyCoupledEKF, capi
-from ekf_vio_amd.sim import Scenario, translated_sequence
+from ekf_vio_amd.sim import Scenario
 from oracle import OracleFilter
+
+from _frame_twin import moving_object_sequence  # (the builder lives with the frame twin's sequence, which uses it too)
 
 pytestmark = pytest.mark.gpu
 
@@ -359,21 +361,6 @@ def test_clustered_rejections_give_the_same_bits_under_both_sweeps(monkeypatch):
 # ------------------------------------------------------------------ 6. image loop
 def grey(name="640_480_test"):
     return np.asarray(Image.open(os.path.join(IMG, name + "_gray.png")))
-
-
-def moving_object_sequence(frames=24, first=12, last=17):
-    """The loop tests' translated plane (the camera moves sideways: the image moves by (-3.1, -1.3) pixels a frame) with a moving object
-    in front of it for frames first .. last: a 160 x 160 patch of frame first - 1 that moves by (+3, +1) pixels a frame, against the
-    camera motion.  Returns (images, (y0, y1, x0, x1) of the patch in frame first - 1, first, last)."""
-    seq = translated_sequence(grey(), frames, dx=-3.1, dy=-1.3)
-    y0, y1, x0, x1 = 160, 320, 240, 400
-    patch = seq[first - 1][y0:y1, x0:x1].copy()
-    for j, i in enumerate(range(first, last + 1)):
-        ox, oy = 3 * (j + 1), j + 1
-        img = seq[i].copy()
-        img[y0 + oy:y1 + oy, x0 + ox:x1 + ox] = patch
-        seq[i] = img
-    return seq, (y0, y1, x0, x1), first, last
 
 
 def test_image_loop_gates_a_moving_object_and_removes_it_in_the_same_frame():
