@@ -54,7 +54,8 @@ SYMBOLS = ["ekfvio_default_config", "ekfvio_create", "ekfvio_destroy", "ekfvio_r
            "ekfvio_set_imu_extrinsics", "ekfvio_get_imu_extrinsics", "ekfvio_set_gravity", "ekfvio_get_gravity",
            "ekfvio_gravity_from_accel", "ekfvio_imu_model",
            "ekfvio_set_camera_model", "ekfvio_get_camera_model", "ekfvio_rectify_map_model", "ekfvio_mask_blocked_model",
-           "ekfvio_set_replenish_grid", "ekfvio_get_replenish_grid", "ekfvio_replenish_select"]
+           "ekfvio_set_replenish_grid", "ekfvio_get_replenish_grid", "ekfvio_replenish_select",
+           "ekfvio_aid_update", "ekfvio_aid", "ekfvio_set_frame_aid", "ekfvio_get_aid", "ekfvio_aid_innovation", "ekfvio_aid_rows_body_velocity"]
 MASK_RECTIFY_BORDER = 1  # EKFVIO_MASK_RECTIFY_BORDER
 CAMERA_PLUMB_BOB, CAMERA_RATIONAL, CAMERA_EQUIDISTANT = 0, 1, 2  # EKFVIO_CAMERA_*
 CAMERA_MODELS = {"plumb_bob": CAMERA_PLUMB_BOB, "rational_polynomial": CAMERA_RATIONAL, "rational": CAMERA_RATIONAL,
@@ -138,6 +139,10 @@ def load(build_if_missing=True, hooks=False):
         "ekfvio_mask_blocked_model": [fp, i32, C.POINTER(C.c_double), i32, fp, u8p, i32, i32, i32, i32, i32, i32, u8p],  # no handle, no device
         "ekfvio_set_replenish_grid": [vp, i32, i32], "ekfvio_get_replenish_grid": [vp, ip, ip],
         "ekfvio_replenish_select": [ip, ip, i32, ip, i32, u8p, i32, i32, i32, i32, i32, i32, i32, ip, ip],  # no handle, no device
+        "ekfvio_aid_update": [vp, i32, fp, fp, fp, f32], "ekfvio_aid": [vp, C.c_double, i32, fp, fp, fp, f32],
+        "ekfvio_set_frame_aid": [vp, i32, fp, fp, fp, f32], "ekfvio_get_aid": [vp, fp, ip, C.POINTER(C.c_int64), C.POINTER(C.c_int64)],
+        "ekfvio_aid_innovation": [fp, fp, i32, fp, fp, fp, fp, fp, fp, ip],  # no handle, no device
+        "ekfvio_aid_rows_body_velocity": [fp, fp, fp, fp, fp, fp, fp],  # no handle, no device
     }
     if hooks:
         sig.update({

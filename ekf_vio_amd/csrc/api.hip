@@ -381,7 +381,9 @@ int ekfvio_reset(ekfvio_filter* f) {
     HIP_TRY(f, hipMemsetAsync(f->info, 0, 4 * sizeof(int), f->stream));
     if (f->gate_words) HIP_TRY(f, hipMemsetAsync(f->gate_words, 0, 4 * sizeof(int), f->stream));  // the gate's counts start over; its threshold stays
     if (f->fb_words) HIP_TRY(f, hipMemsetAsync(f->fb_words, 0, 8 * sizeof(int), f->stream));  // ... and the forward-backward check's, likewise
+    HIP_TRY(f, aid_reset_enqueue(f));  // ... and the aiding measurement's verdict and counts; the standing measurement stays (ekfvio_set_frame_aid)
     HIP_TRY(f, hipStreamSynchronize(f->stream));
+    aid_reset_done(f);
     f->have_stamp = false;
     f->frames[0].valid = f->frames[1].valid = false;
     f->mask_hits_n = 0;  // the mask's hits of the last track go with the landmarks; the mask itself stays (ekfvio_set_mask)

@@ -244,6 +244,14 @@ struct ekfvio_filter {
     int* d_hzupt = nullptr;        // the device's address of h_zupt
     int zupt_n = 0, zupt_pass = 0, zupt_still = 0, zupt_applied_last = 0;  // the most recent frame's decision as the host read it with the status word
     int64_t zupt_applied_total = 0;  // since create / reset
+    // --- linear aiding measurement of the base state (ekfvio_aid_update, ekfvio_set_frame_aid; aid.hip) ---
+    int frame_aid_k = 0;           // > 0: ekfvio_step_image applies the standing measurement behind the tracker, in front of the zero-velocity update; 0: off
+    float frame_aid_H[6 * 22] = {}, frame_aid_z[6] = {}, frame_aid_R[36] = {}, frame_aid_chi2 = 0.f;  // as given; survive ekfvio_reset
+    // (memory: made by the first aiding call or the first ekfvio_set_frame_aid that turns the setting on)
+    long long* aid_words = nullptr;  // [4] device words: accepted, applied and rejected since create / reset, d2's bits (the Joseph kernel reads the first)
+    long long* h_aid = nullptr;      // pinned, device-mapped: the same four words
+    long long* d_haid = nullptr;     // the device's address of h_aid
+    bool aid_pending = false;        // an aiding launch is enqueued that no wait of the host lies behind yet: ekfvio_get_aid waits for the stream
     // --- the IMU in its own frame and gravity at run time (ekfvio_set_imu_extrinsics, ekfvio_set_gravity; imu.hip): host values alone, handed to
     // the IMU update's launch as kernel arguments; both survive ekfvio_reset ---
     bool imu_ext_on = false;      // launch_imu_update takes imu_gain_kernel<true>
@@ -523,6 +531,12 @@ void launch_imu_update(ekfvio_filter* f, const float gyro[3], const float accel[
 // the frame's status word (decided: launch_zupt_frame ran in this frame)
 void launch_zupt_frame(ekfvio_filter* f);
 void zupt_note_frame(ekfvio_filter* f, bool decided);
+// aid.hip: the frame's standing aiding measurement (ekfvio_set_frame_aid), enqueued behind the tracker and in front of the zero-velocity update
+// (setting on), the host's end of it behind the frame's status word, and ekfvio_reset's two parts (in front of its wait and behind it): the counts start over
+void launch_aid_frame(ekfvio_filter* f);
+void aid_note_frame(ekfvio_filter* f);
+hipError_t aid_reset_enqueue(ekfvio_filter* f);
+void aid_reset_done(ekfvio_filter* f);
 // fast.hip
 int fast_alloc(ekfvio_filter* f);
 int fast_ensure(ekfvio_filter* f, int w, int h);  // grows the detector's per-pixel buffers to a w x h level 0 (synchronises if it must)

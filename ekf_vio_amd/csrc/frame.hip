@@ -365,11 +365,15 @@ int ekfvio_step_image(ekfvio_filter* f, double stamp, const uint8_t* image, int3
     UpdateInputs in;  // the frame's update (and its re-run behind an aborted persistent sweep)
     in.z = f->zmeas, in.R = f->Rmeas, in.pass = f->pass, in.m_on_device = true;
     const bool zupt = f->zupt_max_flow_px > 0.f && f->N > 0;  // (off, or no landmark: nothing is launched)
+    const bool aid = f->frame_aid_k > 0;  // ekfvio_set_frame_aid: the standing measurement, landmarks or not
+    if (aid && f->N <= 0) launch_aid_frame(f);
     if (f->N > 0) {  // "run update if we have enough features" (EKFVIO.cpp:166)
         rc = klt_track_device(f);
         if (rc != EKFVIO_OK) return fail(rc);
         // ekfvio_set_zupt: the zero-velocity decision over the tracker's results and, on a "yes", its update of the propagated state: the
         // gate and the update below read the state it leaves.  Outside `in`: the re-run behind an aborted sweep does not repeat it
+        // ekfvio_set_frame_aid sits in front of it, likewise outside `in`: the zero-velocity update reads the state the aiding update leaves
+        if (aid) launch_aid_frame(f);
         if (zupt) launch_zupt_frame(f);
         // the pass flags stay on the device: the update is launched for m = 2N measurement rows and its kernels take
         // the true count from the bookkeeping (rows beyond it are identity padding, exact zeros in every product)
@@ -425,6 +429,7 @@ int ekfvio_step_image(ekfvio_filter* f, double stamp, const uint8_t* image, int3
     if (rc != EKFVIO_OK) return rc;
     f->out_fresh = f->tune.frame_outputs != 0;
     f->out_cov_fresh = f->out_fresh && f->output_cov;
+    if (aid) aid_note_frame(f);  // (its words likewise)
     if (f->zupt_max_flow_px > 0.f) zupt_note_frame(f, zupt);  // the decision's words arrived in pinned host memory in front of the status word
     // (in front of a re-run, which reads f->mu and f->P as the swap leaves them; the count of landmarks: below, with `added`)
     const int removed = removing ? __atomic_load_n(&f->h_info[HW_REMOVED], __ATOMIC_ACQUIRE) : 0;

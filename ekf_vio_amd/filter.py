@@ -27,7 +27,7 @@ class TightlyCoupledEKF:
                  default_point_depth=0.5, default_point_depth_variance=100.0,
                  default_point_homogenous_variance=1e-5, hooks=False, gate_chi2=0.0, klt_fb_max_px=0.0, distortion=None, output_covariance=False,
                  mask=None, mask_rectify_border=False, equalize=None, klt_photometric=False, ended_export=False, zupt=None,
-                 imu_extrinsics=None, camera_model=None, replenish_grid=None, **cfg_overrides):
+                 imu_extrinsics=None, camera_model=None, replenish_grid=None, frame_aid=None, **cfg_overrides):
         # hooks=True: this handle lives in libekfvio_hip_hooks.so, the build that also has include/ekfvio_test_hooks.h (tests, profiling scripts)
         self.hooks = bool(hooks)
         self.lib = capi.load(hooks=self.hooks)
@@ -73,6 +73,8 @@ class TightlyCoupledEKF:
             self.setImuExtrinsics(*imu_extrinsics)
         if replenish_grid is not None:  # likewise (ekfvio_set_replenish_grid): (cells_x, cells_y)
             self.setReplenishGrid(*replenish_grid)
+        if frame_aid is not None:  # likewise (ekfvio_set_frame_aid): (H, z, R[, chi2])
+            self.setFrameAid(*frame_aid)
 
     def _chk(self, rc, allow=()):
         if rc != capi.OK and rc not in allow:
@@ -210,6 +212,46 @@ class TightlyCoupledEKF:
         self._chk(self.lib.ekfvio_get_zupt(self.h, _fp(flow2), C.byref(n), C.byref(npass), C.byref(nstill), C.byref(last), C.byref(total)))
         return dict(flow2=flow2[:n.value].copy(), n_landmarks=int(n.value), n_pass=int(npass.value), n_still=int(nstill.value),
                     applied_last=int(last.value), applied_total=int(total.value))
+
+    @staticmethod
+    def _aid_rows(H, z, R):
+        """(k, H [k * 22], z [k], R [k * k]) as fp32 for the aiding entry points; R may be given as its diagonal."""
+        z = np.ascontiguousarray(z, dtype=np.float32).reshape(-1)
+        k = int(z.shape[0])
+        H = np.ascontiguousarray(H, dtype=np.float32).reshape(-1)
+        R = np.asarray(R, dtype=np.float32)
+        R = np.ascontiguousarray(np.diag(R) if R.ndim == 1 and k > 1 and R.size == k else R, dtype=np.float32).reshape(-1)
+        if k == 0 or H.size != k * 22 or R.size != k * k:
+            raise capi.EkfvioError(capi.EINVAL, "aiding rows: H must be [k, 22], z [k], R [k, k] or its diagonal")
+        return k, H, z, R
+
+    def aidUpdate(self, H, z, R, chi2=0.0):
+        """Not in the reference: a linear aiding measurement of the base state, z = H x[0:22] + v, v ~ N(0, R), k = 1..6 rows, Joseph form on
+        the device (ekfvio_aid_update): wheel speed, a position or altitude fix, a constraint.  chi2 > 0: rejected where the normalised innovation
+        squared exceeds it.  The update alone; asynchronous."""
+        k, H, z, R = self._aid_rows(H, z, R)
+        self._chk(self.lib.ekfvio_aid_update(self.h, k, _fp(H), _fp(z), _fp(R), float(chi2)))
+
+    def aid(self, stamp, H, z, R, chi2=0.0):
+        """ekfvio_aid: propagates to `stamp` (process(dt), whatever use_imu says; the first stamp only sets the time), then aidUpdate."""
+        k, H, z, R = self._aid_rows(H, z, R)
+        self._chk(self.lib.ekfvio_aid(self.h, float(stamp), k, _fp(H), _fp(z), _fp(R), float(chi2)))
+
+    def setFrameAid(self, H=None, z=None, R=None, chi2=0.0):
+        """ekfvio_set_frame_aid: a standing measurement applied in every frame of addFrame behind the tracker, in front of the zero-velocity
+        update and the camera update (a nonholonomic constraint, a planar robot).  H None: off."""
+        if H is None:
+            self._chk(self.lib.ekfvio_set_frame_aid(self.h, 0, None, None, None, 0.0))
+            return
+        k, H, z, R = self._aid_rows(H, z, R)
+        self._chk(self.lib.ekfvio_set_frame_aid(self.h, k, _fp(H), _fp(z), _fp(R), float(chi2)))
+
+    def aid_status(self):
+        """ekfvio_get_aid: dict(d2_last, accepted_last, applied_total, rejected_total) of the handle's most recent aiding update; a memcpy
+        behind a frame, a wait for the stream behind a bare aid / aidUpdate."""
+        d2, acc, ap, rej = C.c_float(0), C.c_int32(0), C.c_int64(0), C.c_int64(0)
+        self._chk(self.lib.ekfvio_get_aid(self.h, C.byref(d2), C.byref(acc), C.byref(ap), C.byref(rej)))
+        return dict(d2_last=float(d2.value), accepted_last=int(acc.value), applied_total=int(ap.value), rejected_total=int(rej.value))
 
     def removeFeatures(self, mask=None):
         """Not in the reference, which flags a lost landmark (TightlyCoupledEKF.cpp:528) and keeps it: removes landmarks from the
@@ -770,7 +812,8 @@ class EKFVIO:
         # klt_photometric=True: the tracker's gain/offset term, setKltPhotometric below; ended_export=True: every removal hands out the records of
         # the landmarks that leave, setEndedExport below; zupt=(max_flow_px, min_tracks, min_ratio, vel_var, omega_var): the zero-velocity update,
         # setZupt below; imu_extrinsics=(R_ci, p_ci): the IMU in its own frame, setImuExtrinsics below; replenish_grid=(cells_x, cells_y): new
-        # landmarks spread over a grid of cells, setReplenishGrid below; gravity_align_samples=K: the first K IMU
+        # landmarks spread over a grid of cells, setReplenishGrid below; frame_aid=(H, z, R[, chi2]): a standing aiding measurement of the base
+        # state in every frame, setFrameAid below; gravity_align_samples=K: the first K IMU
         # records that come up for application are not applied but averaged, and their mean accelerometer reading sets the gravity vector:
         # the rig is taken to be AT REST through them, with an accelerometer bias negligible against 9.81; frames meanwhile are processed as
         # without an IMU)
@@ -885,6 +928,29 @@ class EKFVIO:
     def zupt(self):
         """TightlyCoupledEKF.zupt: the most recent frame's decision; a memcpy behind a frame."""
         return self.tc_ekf.zupt()
+
+    def aidUpdate(self, H, z, R, chi2=0.0):
+        """TightlyCoupledEKF.aidUpdate: a linear aiding measurement of the base state on the state as it stands."""
+        self.tc_ekf.aidUpdate(H, z, R, chi2)
+
+    def aid(self, stamp, H, z, R, chi2=0.0):
+        """TightlyCoupledEKF.aid in arrival order: the queued IMU records up to `stamp` first, then process(dt) to the stamp and the update.
+        A stamp older than the filter's time is not applied (out-of-order records are not supported) and False is returned."""
+        stamp = float(stamp)
+        self._drain_imu(stamp)
+        if self._t_filter is not None and stamp < self._t_filter:
+            return False
+        self.tc_ekf.aid(stamp, H, z, R, chi2)
+        self._t_filter = stamp
+        return True
+
+    def setFrameAid(self, H=None, z=None, R=None, chi2=0.0):
+        """TightlyCoupledEKF.setFrameAid: from the next frame on every frame applies the standing measurement; H None: off."""
+        self.tc_ekf.setFrameAid(H, z, R, chi2)
+
+    def aid_status(self):
+        """TightlyCoupledEKF.aid_status: the most recent aiding update's d2, verdict and counts."""
+        return self.tc_ekf.aid_status()
 
     def setOutputCovariance(self, on):
         """TightlyCoupledEKF.setOutputCovariance: from the next frame on addFrame delivers the covariances with the frame's outputs."""

@@ -111,6 +111,13 @@ struct Params {
     // (at most 256 cells together) new landmarks are the strongest free corner of every cell of that grid over the resized frame, emptier cells first
     // (ekfvio_set_replenish_grid); both 0 = off.  One of them alone is an error when the handle is made.
     int replenish_grid_x = 0, replenish_grid_y = 0;
+    // Not in the reference, whose monocular filter has no metric input: the nonholonomic constraint of a wheeled vehicle as a standing aiding
+    // measurement (ekfvio_set_frame_aid).  nhc_variance > 0: every frame measures the velocity along the vehicle's y and z axes (x is forward) as
+    // zero with that variance, (m/s)^2; 0 = off.  nhc_R_cv: nine numbers, row-major, vehicle -> camera axes (v_cam = R_cv v_vehicle); the default
+    // is a forward-looking camera in its optical frame (z forward, x right, y down) on a vehicle with x forward, y left, z up, for which the
+    // constraint reads v_x = v_y = 0 in the camera frame.
+    float nhc_variance = 0.f;
+    std::array<float, 9> nhc_R_cv{{0.f, -1.f, 0.f, 0.f, 0.f, -1.f, 1.f, 0.f, 0.f}};
     std::map<std::string, std::string> node;  // odom_topic, camera_topic, base_frame, use_imu, publish_insight, ...
 
     Params() {
@@ -215,6 +222,17 @@ struct Params {
             if (c < 0 || c > 256) throw Error(EKFVIO_EINVAL, "parameter " + key + ": not in [0, 256]: " + value);
             (key == "replenish_grid_x" ? replenish_grid_x : replenish_grid_y) = c;
         }
+        else if (key == "nhc_variance") {
+            nhc_variance = (float)number(key, value);
+            if (!(nhc_variance >= 0.f) || !std::isfinite(nhc_variance)) throw Error(EKFVIO_EINVAL, "parameter nhc_variance: not a finite value >= 0: " + value);
+        }
+        else if (key == "nhc_R_cv") {  // (what ekfvio_aid_rows_body_velocity refuses is refused here: a pure host function)
+            std::array<float, 9> r{};
+            numbers(key, value, r.data(), 9);
+            float H[44], z[2], R[4];
+            if (!nhcRows(r.data(), 1.f, H, z, R)) throw Error(EKFVIO_EINVAL, "parameter nhc_R_cv: not a rotation: " + value);
+            nhc_R_cv = r;
+        }
         else if (key == "imu_rotation") {  // (what ekfvio_set_imu_extrinsics would refuse is refused when the handle is made)
             numbers(key, value, imu_rotation.data(), 9);
             imu_extrinsics = 1;
@@ -257,6 +275,18 @@ struct Params {
         else throw Error(EKFVIO_EINVAL, "unknown parameter: " + key);
     }
 
+    // The two rows of the nonholonomic constraint: rows 1 and 2 (the vehicle's y and z axes) of ekfvio_aid_rows_body_velocity at zero velocity
+    // and without a lever arm, z = 0, R = variance I.  H: 2 x 22 row-major.  false: R_cv or the variance is refused.
+    static bool nhcRows(const float* R_cv, float variance, float* H, float* z, float* R) {
+        const float v[3] = {0.f, 0.f, 0.f}, cov[9] = {variance, 0.f, 0.f, 0.f, variance, 0.f, 0.f, 0.f, variance};
+        float H3[66], z3[3], R3[9];
+        if (ekfvio_aid_rows_body_velocity(R_cv, nullptr, v, cov, H3, z3, R3) != EKFVIO_OK) return false;
+        for (int e = 0; e < 44; e++) H[e] = H3[22 + e];
+        z[0] = z[1] = 0.f;
+        R[0] = R[3] = variance, R[1] = R[2] = 0.f;
+        return true;
+    }
+
     // every private parameter name the node accepts (EKFVIO.cpp:20-67): what a ROS front end asks the parameter server for
     static std::vector<std::string> names() {
         std::vector<std::string> out = {"num_features", "fast_threshold", "fast_blur_sigma", "inverse_image_scale", "kill_pad",
@@ -264,7 +294,7 @@ struct Params {
                                         "default_point_depth", "default_point_depth_variance",
                                         "default_point_homogenous_variance", "frame_buffer_size", "imu_update",
                                         "imu_gyro_variance", "imu_accel_variance", "gravity_x", "gravity_y", "gravity_z", "remove_lost", "gate_chi2",
-                                        "klt_fb_max_px", "rectify", "publish_covariance", "mask_rectify_border", "equalize_clip_limit", "equalize_tiles_x", "equalize_tiles_y", "klt_photometric", "publish_ids", "publish_ended", "zupt_max_flow_px", "zupt_min_tracks", "zupt_min_ratio", "zupt_vel_variance", "zupt_omega_variance", "imu_rotation", "imu_position", "gravity_align_samples", "replenish_grid_x", "replenish_grid_y", "distortion_k1", "distortion_k2", "distortion_p1", "distortion_p2", "distortion_k3",
+                                        "klt_fb_max_px", "rectify", "publish_covariance", "mask_rectify_border", "equalize_clip_limit", "equalize_tiles_x", "equalize_tiles_y", "klt_photometric", "publish_ids", "publish_ended", "zupt_max_flow_px", "zupt_min_tracks", "zupt_min_ratio", "zupt_vel_variance", "zupt_omega_variance", "imu_rotation", "imu_position", "gravity_align_samples", "replenish_grid_x", "replenish_grid_y", "nhc_variance", "nhc_R_cv", "distortion_k1", "distortion_k2", "distortion_p1", "distortion_p2", "distortion_k3",
                                         "distortion_model", "distortion_k4", "distortion_k5", "distortion_k6", "rectified_fx", "rectified_fy", "rectified_cx", "rectified_cy"};
         for (const auto& e : Params().node) out.push_back(e.first);
         for (const auto& e : ignored()) out.push_back(e.first);
@@ -433,6 +463,26 @@ class TightlyCoupledEKF {
         chk(ekfvio_set_zupt(h_, max_flow_px, min_tracks, min_ratio, vel_variance, omega_variance));
     }
     void zuptUpdate(float vel_variance = 1e-4f, float omega_variance = 1e-4f) { chk(ekfvio_zupt_update(h_, vel_variance, omega_variance)); }
+    // Not in the reference: a linear aiding measurement of the base state, z = H x[0:22] + v, v ~ N(0, R) (ekfvio_aid_update): k = 1..6 rows, H k x 22
+    // row-major, R k x k row-major (lower triangle read), Joseph form on the device; chi2 > 0 gates it on the normalised innovation squared.
+    // aidUpdate: on the state as it stands; aid: behind process(dt) to `stamp`, whatever use_imu says (the first stamp only sets the time);
+    // setFrameAid: a standing measurement applied in every frame behind the tracker, in front of the zero-velocity and the camera update
+    // (k = 0: off).  All asynchronous.  aidStatus: the most recent one's d2, verdict and counts.
+    void aidUpdate(int k, const float* H, const float* z, const float* R, float chi2 = 0.f) { chk(ekfvio_aid_update(h_, k, H, z, R, chi2)); }
+    void aid(double stamp, int k, const float* H, const float* z, const float* R, float chi2 = 0.f) { chk(ekfvio_aid(h_, stamp, k, H, z, R, chi2)); }
+    void setFrameAid(int k, const float* H = nullptr, const float* z = nullptr, const float* R = nullptr, float chi2 = 0.f) {
+        chk(ekfvio_set_frame_aid(h_, k, H, z, R, chi2));
+    }
+    struct AidStatus {
+        float d2_last = 0.f;
+        int32_t accepted_last = 0;
+        int64_t applied_total = 0, rejected_total = 0;
+    };
+    AidStatus aidStatus() {
+        AidStatus r;
+        chk(ekfvio_get_aid(h_, &r.d2_last, &r.accepted_last, &r.applied_total, &r.rejected_total));
+        return r;
+    }
     // Not in the reference: the IMU in its own frame (ekfvio_set_imu_extrinsics).  R_ci: nine floats, row-major, IMU -> camera axes (the rotation of
     // Kalibr's T_cam_imu); p_ci: the IMU's origin in the camera frame, metres (its translation); both nullptr: off.  From the next IMU update on.
     void setImuExtrinsics(const float* R_ci, const float* p_ci) { chk(ekfvio_set_imu_extrinsics(h_, R_ci, p_ci)); }
@@ -702,6 +752,11 @@ class EKFVIO {
         if (p.publish_ended) tc_ekf.setEndedExport(true);  // (likewise)
         if (p.zupt_max_flow_px > 0.f) tc_ekf.setZupt(p.zupt_max_flow_px, p.zupt_min_tracks, p.zupt_min_ratio, p.zupt_vel_variance, p.zupt_omega_variance);  // (likewise)
         if (p.imu_extrinsics) tc_ekf.setImuExtrinsics(p.imu_rotation.data(), p.imu_position.data());  // (likewise)
+        if (p.nhc_variance > 0.f) {  // (likewise: the nonholonomic constraint as the handle's standing aiding measurement)
+            float H[44], z[2], R[4];
+            if (!Params::nhcRows(p.nhc_R_cv.data(), p.nhc_variance, H, z, R)) throw Error(EKFVIO_EINVAL, "nhc_variance / nhc_R_cv refused");
+            tc_ekf.setFrameAid(2, H, z, R);
+        }
         gravity_magnitude_ = std::sqrt((double)p.cfg.gravity[0] * p.cfg.gravity[0] + (double)p.cfg.gravity[1] * p.cfg.gravity[1] +
                                        (double)p.cfg.gravity[2] * p.cfg.gravity[2]);
         setGravityAlignSamples(p.gravity_align_samples);
@@ -864,6 +919,17 @@ class EKFVIO {
             t_filter_ = r.stamp;
             have_time_ = true;
         }
+    }
+    // An aiding record in arrival order (ekfvio_aid): the IMU records up to its stamp first, then process(dt) to the stamp and the update.  A stamp
+    // older than the filter's time is not applied (out-of-order records are not supported) and false is returned; the first stamp of all only
+    // sets the filter's clock.
+    bool aid(double stamp, int k, const float* H, const float* z, const float* R, float chi2 = 0.f) {
+        drainImu(stamp);
+        if (have_time_ && stamp < t_filter_) return false;
+        tc_ekf.aid(stamp, k, H, z, R, chi2);
+        t_filter_ = stamp;
+        have_time_ = true;
+        return true;
     }
     int droppedImuRecords() const { return dropped_imu_; }
     size_t queuedImuRecords() const { return imu_queue_.size(); }

@@ -5,12 +5,13 @@
 // R = 1e-5 I, every landmark measured) through ekfvio::TightlyCoupledEKF and prints the
 // final odometry next to the ground truth, the checkSigma numbers and the step rate.
 // Usage: ekfvio_replay [landmarks=256] [frames=300] [seed=0] [dt=0.0333333]
-//        ekfvio_replay --print-config [params.yaml]   (no GPU work: the node's parameter file -> ekfvio_config as JSON)
+//        ekfvio_replay --print-config [params.yaml] [--nhc-variance v] [--nhc-R-cv "r00 ... r22"]
+//                                                      (no GPU work: the node's parameter file -> ekfvio_config as JSON)
 //        ekfvio_replay --records <dir> [--out <dir>] [--params params.yaml] [--device n] [--insight] [--covariance]
 //                                [--equalize-clip-limit c] [--equalize-tiles-x n] [--equalize-tiles-y n] [--tracks FILE] [--ended FILE]
 //                                [--zupt-max-flow-px p] [--zupt-min-tracks n] [--zupt-min-ratio r] [--zupt-vel-variance v] [--zupt-omega-variance v]
 //                                [--imu-rotation "r00 r01 ... r22"] [--imu-position "x y z"] [--gravity-align-samples k]
-//                                [--replenish-grid-x n] [--replenish-grid-y n]
+//                                [--replenish-grid-x n] [--replenish-grid-y n] [--nhc-variance v] [--nhc-R-cv "r00 r01 ... r22"]
 //                                [--distortion-model plumb_bob|rational_polynomial|equidistant|fisheye] [--rectified-camera "fx fy cx cy"]
 //
 // --distortion-model and --rectified-camera are the node parameters distortion_model and rectified_fx/fy/cx/cy (ekfvio_set_camera_model; live
@@ -20,6 +21,10 @@
 // send (EKFVIO.cpp:444-518), with no ROS in between.  <dir>/records.txt holds one record per line, in arrival order:
 //     image <stamp> <file> <K0> ... <K8>      8-bit binary PGM (P5), intrinsics row-major as in sensor_msgs/CameraInfo.K
 //     imu   <stamp> <gx> <gy> <gz> <ax> <ay> <az>
+//     aid   <stamp> <k> <H: 22 k numbers, row-major> <z: k> <R: k k, row-major, lower triangle read> [chi2]
+// An aid record is a linear aiding measurement of the base state (ekfvio_aid: wheel speed, a position fix): the filter is propagated to its
+// stamp and updated; a record older than the filter's time is counted and skipped.  --nhc-variance v (and --nhc-R-cv, vehicle -> camera axes)
+// are the node parameters nhc_variance / nhc_R_cv: the nonholonomic constraint as a standing measurement in every frame (ekfvio_set_frame_aid).
 // Every image record goes through EKFVIO::addFrame (frame ingest, process(dt), KLT, update, FAST replenishment:
 // cfg.replenish = 1); after it one odometry record and one point-cloud record are appended to
 //     <out>/odom.txt     stamp px py pz qw qx qy qz vx vy vz wx wy wz numeric_ok
@@ -84,15 +89,16 @@ Q mul(Q a, Q b) {
 }
 }  // namespace
 
-static int print_config(const char* path) {
+static int print_config(const char* path, const std::vector<std::pair<std::string, std::string>>& overrides) {
     try {
-        const ekfvio::Params p = path ? ekfvio::Params::fromFile(path) : ekfvio::Params();
+        ekfvio::Params p = path ? ekfvio::Params::fromFile(path) : ekfvio::Params();
+        for (const auto& kv : overrides) p.set(kv.first, kv.second);
         const ekfvio_config& c = p.cfg;
         std::printf("{\"max_features\": %d, \"fast_threshold\": %d, \"fast_blur_sigma\": %.9g, \"inverse_image_scale\": %d, "
                     "\"kill_pad\": %d, \"klt_min_eigen\": %.9g, \"min_new_feature_dist\": %d, \"klt_max_pyramid_level\": %d, "
                     "\"klt_window_size\": %d, \"default_point_depth\": %.9g, \"default_point_depth_variance\": %.9g, "
                     "\"default_point_homogenous_variance\": %.9g, \"sample_based_uncertainty\": %d, \"gate_chi2\": %.9g, "
-                    "\"klt_fb_max_px\": %.9g, \"rectify\": %d, \"publish_covariance\": %d, \"mask_rectify_border\": %d, \"equalize_clip_limit\": %.9g, \"equalize_tiles_x\": %d, \"equalize_tiles_y\": %d, \"klt_photometric\": %d, \"publish_ids\": %d, \"publish_ended\": %d, \"zupt_max_flow_px\": %.9g, \"zupt_min_tracks\": %d, \"zupt_min_ratio\": %.9g, \"zupt_vel_variance\": %.9g, \"zupt_omega_variance\": %.9g, \"imu_extrinsics\": %d, \"imu_rotation\": [%.9g, %.9g, %.9g, %.9g, %.9g, %.9g, %.9g, %.9g, %.9g], \"imu_position\": [%.9g, %.9g, %.9g], \"gravity_align_samples\": %d, \"replenish_grid_x\": %d, \"replenish_grid_y\": %d, \"distortion\": [%.17g, %.17g, %.17g, %.17g, %.17g], \"distortion_model\": \"%s\", \"distortion_k456\": [%.17g, %.17g, %.17g], \"rectified\": [%.9g, %.9g, %.9g, %.9g], \"node\": {",
+                    "\"klt_fb_max_px\": %.9g, \"rectify\": %d, \"publish_covariance\": %d, \"mask_rectify_border\": %d, \"equalize_clip_limit\": %.9g, \"equalize_tiles_x\": %d, \"equalize_tiles_y\": %d, \"klt_photometric\": %d, \"publish_ids\": %d, \"publish_ended\": %d, \"zupt_max_flow_px\": %.9g, \"zupt_min_tracks\": %d, \"zupt_min_ratio\": %.9g, \"zupt_vel_variance\": %.9g, \"zupt_omega_variance\": %.9g, \"imu_extrinsics\": %d, \"imu_rotation\": [%.9g, %.9g, %.9g, %.9g, %.9g, %.9g, %.9g, %.9g, %.9g], \"imu_position\": [%.9g, %.9g, %.9g], \"gravity_align_samples\": %d, \"replenish_grid_x\": %d, \"replenish_grid_y\": %d, \"nhc_variance\": %.9g, \"nhc_R_cv\": [%.9g, %.9g, %.9g, %.9g, %.9g, %.9g, %.9g, %.9g, %.9g], \"distortion\": [%.17g, %.17g, %.17g, %.17g, %.17g], \"distortion_model\": \"%s\", \"distortion_k456\": [%.17g, %.17g, %.17g], \"rectified\": [%.9g, %.9g, %.9g, %.9g], \"node\": {",
                     c.max_features, c.fast_threshold, (double)c.fast_blur_sigma, c.inverse_image_scale, c.kill_pad,
                     (double)c.klt_min_eigen, c.min_new_feature_dist, c.klt_max_pyramid_level, c.klt_window_size,
                     (double)c.default_point_depth, (double)c.default_point_depth_variance,
@@ -100,7 +106,9 @@ static int print_config(const char* path) {
                     (double)c.klt_fb_max_px, p.rectify, p.publish_covariance, p.mask_rectify_border, (double)p.equalize_clip_limit, p.equalize_tiles_x, p.equalize_tiles_y, p.klt_photometric, p.publish_ids, p.publish_ended, (double)p.zupt_max_flow_px, p.zupt_min_tracks, (double)p.zupt_min_ratio, (double)p.zupt_vel_variance, (double)p.zupt_omega_variance, p.imu_extrinsics,
                     (double)p.imu_rotation[0], (double)p.imu_rotation[1], (double)p.imu_rotation[2], (double)p.imu_rotation[3], (double)p.imu_rotation[4],
                     (double)p.imu_rotation[5], (double)p.imu_rotation[6], (double)p.imu_rotation[7], (double)p.imu_rotation[8],
-                    (double)p.imu_position[0], (double)p.imu_position[1], (double)p.imu_position[2], p.gravity_align_samples, p.replenish_grid_x, p.replenish_grid_y, p.distortion[0], p.distortion[1], p.distortion[2], p.distortion[3], p.distortion[4],
+                    (double)p.imu_position[0], (double)p.imu_position[1], (double)p.imu_position[2], p.gravity_align_samples, p.replenish_grid_x, p.replenish_grid_y, (double)p.nhc_variance,
+                    (double)p.nhc_R_cv[0], (double)p.nhc_R_cv[1], (double)p.nhc_R_cv[2], (double)p.nhc_R_cv[3], (double)p.nhc_R_cv[4], (double)p.nhc_R_cv[5],
+                    (double)p.nhc_R_cv[6], (double)p.nhc_R_cv[7], (double)p.nhc_R_cv[8], p.distortion[0], p.distortion[1], p.distortion[2], p.distortion[3], p.distortion[4],
                     p.distortion_model.c_str(), p.distortion_k456[0], p.distortion_k456[1], p.distortion_k456[2],
                     (double)p.rectified[0], (double)p.rectified[1], (double)p.rectified[2], (double)p.rectified[3]);
         bool first = true;
@@ -166,7 +174,7 @@ static int replay_records(const std::string& dir, const std::string& out_dir, co
         FILE* fe = ended_path ? std::fopen(ended_path, "w") : nullptr;
         if ((tracks_path && !ft) || (ended_path && !fe)) throw ekfvio::Error(EKFVIO_EINVAL, "cannot write the tracks / ended file");
         std::string line;
-        int images = 0, imus = 0, lineno = 0;
+        int images = 0, imus = 0, aids = 0, aids_late = 0, lineno = 0;
         const auto t0 = std::chrono::steady_clock::now();
         while (std::getline(rec, line)) {
             lineno++;
@@ -181,6 +189,16 @@ static int replay_records(const std::string& dir, const std::string& out_dir, co
                     throw ekfvio::Error(EKFVIO_EINVAL, "records.txt line " + std::to_string(lineno) + ": imu needs 6 numbers");
                 node.imu_callback(stamp, g, a);
                 imus++;
+            } else if (kind == "aid") {
+                int k = 0;
+                if (!(ls >> k) || k < 1 || k > 6) throw ekfvio::Error(EKFVIO_EINVAL, "records.txt line " + std::to_string(lineno) + ": aid needs a row count 1..6");
+                std::vector<float> v((size_t)(22 * k + k + k * k));
+                for (float& x : v)
+                    if (!(ls >> x)) throw ekfvio::Error(EKFVIO_EINVAL, "records.txt line " + std::to_string(lineno) + ": aid needs 22 k + k + k k numbers");
+                float chi2 = 0.f;
+                ls >> chi2;  // (optional)
+                if (node.aid(stamp, k, v.data(), v.data() + 22 * k, v.data() + 23 * k, chi2)) aids++;
+                else aids_late++;
             } else if (kind == "image") {
                 std::string file;
                 ekfvio::Frame f;
@@ -250,6 +268,11 @@ static int replay_records(const std::string& dir, const std::string& out_dir, co
         const double el = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
         std::printf("records: %d images, %d imu; %d landmarks; %.1f frames/s (file reading included)\n", images, imus,
                     node.tc_ekf.numFeatures(), images / el);
+        if (aids || aids_late || p.nhc_variance > 0.f) {
+            const ekfvio::TightlyCoupledEKF::AidStatus as = node.tc_ekf.aidStatus();
+            std::printf("aid: %d records applied to the filter, %d skipped (older than the filter's time); updates accepted %lld, rejected %lld, last d2 %.6g\n",
+                        aids, aids_late, (long long)as.applied_total, (long long)as.rejected_total, (double)as.d2_last);
+        }
         if (p.cfg.use_imu)
             std::printf("imu: %d records dropped (older than the filter's time), %zu still queued behind the last frame\n",
                         node.droppedImuRecords(), node.queuedImuRecords());
@@ -261,7 +284,19 @@ static int replay_records(const std::string& dir, const std::string& out_dir, co
 }
 
 int main(int argc, char** argv) {
-    if (argc > 1 && std::strcmp(argv[1], "--print-config") == 0) return print_config(argc > 2 ? argv[2] : nullptr);
+    if (argc > 1 && std::strcmp(argv[1], "--print-config") == 0) {
+        const char* path = argc > 2 && std::strncmp(argv[2], "--", 2) != 0 ? argv[2] : nullptr;
+        std::vector<std::pair<std::string, std::string>> overrides;
+        for (int i = path ? 3 : 2; i < argc; i += 2) {
+            if (i + 1 < argc && std::strcmp(argv[i], "--nhc-variance") == 0) overrides.emplace_back("nhc_variance", argv[i + 1]);
+            else if (i + 1 < argc && std::strcmp(argv[i], "--nhc-R-cv") == 0) overrides.emplace_back("nhc_R_cv", argv[i + 1]);
+            else {
+                std::fprintf(stderr, "error: --print-config takes a parameter file, --nhc-variance v and --nhc-R-cv \"...\"\n");
+                return 2;
+            }
+        }
+        return print_config(path, overrides);
+    }
     if (argc > 2 && std::strcmp(argv[1], "--records") == 0) {
         std::string dir = argv[2], out = argv[2];
         const char* params = nullptr;
@@ -297,6 +332,8 @@ int main(int argc, char** argv) {
             else if (std::strcmp(argv[i], "--gravity-align-samples") == 0) overrides.emplace_back("gravity_align_samples", argv[i + 1]);
             else if (std::strcmp(argv[i], "--replenish-grid-x") == 0) overrides.emplace_back("replenish_grid_x", argv[i + 1]);
             else if (std::strcmp(argv[i], "--replenish-grid-y") == 0) overrides.emplace_back("replenish_grid_y", argv[i + 1]);
+            else if (std::strcmp(argv[i], "--nhc-variance") == 0) overrides.emplace_back("nhc_variance", argv[i + 1]);
+            else if (std::strcmp(argv[i], "--nhc-R-cv") == 0) overrides.emplace_back("nhc_R_cv", argv[i + 1]);
             else if (std::strcmp(argv[i], "--distortion-model") == 0) overrides.emplace_back("distortion_model", argv[i + 1]);
             else if (std::strcmp(argv[i], "--rectified-camera") == 0) {  // "fx fy cx cy": the four rectified_* parameters
                 std::istringstream in(argv[i + 1]);

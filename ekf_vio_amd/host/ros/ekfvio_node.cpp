@@ -117,7 +117,11 @@ class EkfvioNode {
         // ekfvio_set_imu_extrinsics, so that imu_update models the IMU in its own frame; gravity_align_samples, default 0 = off: that many IMU
         // records at the start are averaged, not applied, and set the gravity vector, ekfvio_set_gravity -- the rig has to stand still;
         // replenish_grid_x and replenish_grid_y, default 0 0 = off: new landmarks are the strongest free corner of every cell of that grid over
-        // the resized frame, emptier cells first, instead of the detector's raster order, ekfvio_set_replenish_grid -- at most 256 cells)
+        // the resized frame, emptier cells first, instead of the detector's raster order, ekfvio_set_replenish_grid -- at most 256 cells;
+        // nhc_variance, default 0 = off, in (m/s)^2: the nonholonomic constraint of a wheeled vehicle -- no velocity along the vehicle's y and z
+        // axes -- as a standing aiding measurement in every frame, ekfvio_set_frame_aid, told at start-up likewise; nhc_R_cv, nine numbers
+        // row-major as ONE STRING, vehicle -> camera axes, default a forward-looking camera in its optical frame.  There is no wheel-odometry
+        // subscription: measured speed reaches the filter through ekfvio::EKFVIO::aid from the integrator's own callback)
         for (const std::string& name : ekfvio::Params::names()) {
             XmlRpc::XmlRpcValue v;
             if (ros::param::get("~" + name, v)) params_.set(name, to_text(v));

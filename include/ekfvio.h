@@ -873,6 +873,83 @@ EKFVIO_API int ekfvio_get_zupt(ekfvio_filter* f, float* flow2N, int32_t* n_landm
 EKFVIO_API int ekfvio_zupt_decide(const float* prev_px, const float* cur_px, const uint8_t* pass, int32_t count, float max_flow_px,
                                   int32_t min_tracks, float min_ratio, float* flow2, int32_t* n_pass, int32_t* n_still, int32_t* stationary);
 
+/* ---- linear aiding measurements of the base state (not in the reference, whose monocular filter has no metric input: with cfg.use_imu = 0 its
+ * scale is set by default_point_depth and nothing else) ----------------------------------------------------------------------------------
+ * z = H x[0:22] + v, v ~ N(0, R): k = 1..6 rows, H dense k x 22 row-major over the base state (pos 0..2, q 3..6, vel 7..9, omega 10..12,
+ * a 13..15, b_acc 16..18, b_gyr 19..21), R full symmetric k x k row-major of which the LOWER triangle alone is read, Joseph form, on the
+ * device.  Wheel speed, a position or altitude fix, a nonholonomic constraint.  The lines below are the specification: everything in fp32,
+ * without fused multiply-add, division and square root correctly rounded, every sum over an ascending index, associated to the left and
+ * starting from its first written term; a NumPy restatement of them (tests/_aid.py: kernel_order_fp32) is what the device is held to, bit
+ * for bit.  P(i,j) is Sigma's element in row i, column j AS STORED; r, s run over 0..k-1, c over 0..21; R(r,s) with r < s reads R(s,r).
+ *
+ *     w_r(i) = H(r,0)*P(0,i) + ... + H(r,21)*P(21,i)          x_r(i) = P(i,0)*H(r,0) + ... + P(i,21)*H(r,21)      (all 22 terms, zeros of H included)
+ *     A(r,s) = w_r(0)*H(s,0) + ... + w_r(21)*H(s,21)          (all k x k elements: t below reads both triangles)
+ *     S(r,s) = A(r,s) + R(r,s)                                r >= s: the lower triangle alone is factored
+ *     y_r    = z_r - (H(r,0)*mu_0 + ... + H(r,21)*mu_21)
+ *     L: left-looking Cholesky, for j = 0..k-1:   d_j = S(j,j) - L(j,0)*L(j,0) - ... - L(j,j-1)*L(j,j-1)    L(j,j) = sqrt(d_j)
+ *                                    for r > j:   v = S(r,j) - L(r,0)*L(j,0) - ... - L(r,j-1)*L(j,j-1)      L(r,j) = v / L(j,j)
+ *        (it stops at the first pivot d_j that is not finite and > 0; d2 is then a NaN)
+ *     e_r = (y_r - e_0*L(r,0) - ... - e_{r-1}*L(r,r-1)) / L(r,r)          d2 = e_0*e_0 + ... + e_{k-1}*e_{k-1}
+ *     accepted  <=>  every pivot d_j finite and > 0   and   (chi2 == 0  or  d2 <= chi2)       (a NaN among the pivots, or a NaN d2 under a gate, rejects)
+ *     accepted, per state row i = 0 .. n-1 (x_r = x_r(i), w_r = w_r(i)):
+ *         forward,  r = 0..k-1:    k_r = (x_r - k_0*L(r,0) - ... - k_{r-1}*L(r,r-1)) / L(r,r)
+ *         backward, r = k-1..0:    k_r = (k_r - k_{r+1}*L(r+1,r) - ... - k_{k-1}*L(k-1,r)) / L(r,r)
+ *         t_c = x_c - k_0*A(0,c) - ... - k_{k-1}*A(k-1,c)
+ *         g_r = (k_0*R(0,r) + ... + k_{k-1}*R(k-1,r)) - t_r
+ *         dm  = 0 + k_0*y_0 + ... + k_{k-1}*y_{k-1}
+ *         mu'_i = mu_i + dm
+ *     quaternion: qn = sqrt(mu'_3*mu'_3 + mu'_4*mu'_4 + mu'_5*mu'_5 + mu'_6*mu'_6), mu'_3..6 divided by qn
+ *     Sigma'(i,j) = flush((P(i,j) - k_0(i)*w_0(j) - ... - k_{k-1}(i)*w_{k-1}(j)) + g_0(i)*k_0(j) + ... + g_{k-1}(i)*k_{k-1}(j))
+ *     flush(v) = v where |v| > 1e-8f * 1e-5f, else 0 (the reference's prune)
+ *
+ * Not accepted: Sigma is untouched and the mean keeps every bit (the mean is updated in place: nothing is copied or swapped).  The landmarks'
+ * last KLT results, delete flags, ids and birth stamps are never touched either way.  With H the selection of state rows 7..12, z = 0 and a
+ * diagonal R these lines are the zero-velocity update's (ekfvio_zupt_update), bit for bit.
+ *
+ * What it does not do.  H has no landmark columns and the measurement is linear: no range, no bearing, no attitude given as a quaternion.
+ * Stamps must not run backwards.  A position fix is taken in the filter's own world frame (the camera's first pose): aligning a geodetic
+ * frame with it is the caller's.  An altitude-only row makes nothing observable on a trajectory without vertical motion.
+ *
+ * Two launches per update, instantiated per k (a one-row update does not pay for six); H, z, R and chi2 travel as kernel arguments; both
+ * kernels return at once on "not accepted".  The first aiding call of a handle takes 32 bytes of device and 32 bytes of pinned host memory.
+ * Every entry point validates on the host and returns EKFVIO_EINVAL with nothing changed for: k outside 1..6, a NULL pointer, a non-finite
+ * entry, chi2 < 0 or not finite, R not positive definite (fp64 Cholesky of the lower triangle).  All are asynchronous, as ekfvio_imu_update.
+ *
+ * ekfvio_aid_update: the update alone on the state as it stands. */
+EKFVIO_API int ekfvio_aid_update(ekfvio_filter* f, int32_t k, const float* H, const float* z, const float* R, float chi2);
+/* Propagates to `stamp` first, exactly as ekfvio_imu does with cfg.use_imu = 1 and whatever cfg.use_imu says: process(dt = stamp - t), then
+ * the update.  The first stamp a handle sees only sets its time (nothing is applied); a stamp before the filter's time: EKFVIO_EINVAL. */
+EKFVIO_API int ekfvio_aid(ekfvio_filter* f, double stamp, int32_t k, const float* H, const float* z, const float* R, float chi2);
+/* A standing measurement, applied in every frame of ekfvio_step_image behind the first: behind the tracker, in front of the zero-velocity
+ * update, the innovation gate and the camera update (which read the state it leaves), and outside what an aborted persistent sweep runs
+ * again.  For constraints that need no sensor: the nonholonomic v_x = v_y = 0 of a forward-looking camera on a car, a planar robot's
+ * v_y = 0.  k = 0: off (default; then no launch differs, nothing is allocated and every output keeps its bits; the other arguments are not
+ * looked at).  A property of the handle: it holds from the next frame, survives ekfvio_reset (the counts start over) and drops no captured
+ * graph (ekfvio_run_uploaded carries none).  A refused call leaves the setting what it was. */
+EKFVIO_API int ekfvio_set_frame_aid(ekfvio_filter* f, int32_t k, const float* H, const float* z, const float* R, float chi2);
+/* The most recent aiding update of the handle, standing or called (any pointer may be NULL): d2, the normalised innovation squared -- the
+ * consistency figure R is tuned by: over many updates its mean should be near k; a NaN where a pivot failed --, *accepted_last, and how many
+ * were applied and rejected since create / reset.  The gain kernel's first workgroup writes them into pinned host memory: behind
+ * ekfvio_step_image this is a memcpy; behind a bare ekfvio_aid / ekfvio_aid_update it waits for the handle's stream.  Zeros on a handle
+ * that never ran one. */
+EKFVIO_API int ekfvio_get_aid(ekfvio_filter* f, float* d2_last, int32_t* accepted_last, int64_t* applied_total, int64_t* rejected_total);
+/* The residual y[k], S[k*k] (row-major, S = A + R in full), d2 and *pd (1: every pivot finite and > 0; else 0 and d2 a NaN) of the lines
+ * above, from base_mu[22] and Sigma's 22 x 22 base block (row-major, element (i,j) at 22 i + j), which is all of Sigma that enters them.
+ * A pure host function (no handle, no device) that compiles the very inline functions the kernels compile (csrc/aid.h), as
+ * ekfvio_zupt_decide and ekfvio_imu_model do.  y, S, d2, pd may be NULL.  What the entry points above refuse, a NULL base_mu or Sigma_bb, or
+ * a non-finite entry of either: EKFVIO_EINVAL. */
+EKFVIO_API int ekfvio_aid_innovation(const float base_mu[22], const float* Sigma_bb, int32_t k, const float* H, const float* z, const float* R,
+                                     float* y, float* S, float* d2, int32_t* pd);
+/* The three rows of a velocity v measured in a vehicle frame whose axes map to the camera's by R_cv (row-major, v_cam = R_cv v_vehicle) and
+ * whose origin sits at p_cv in the camera frame: z = M (vel + omega x p_cv), M = R_cv^T, linear in state rows 7..12 (the angular-acceleration
+ * term is neglected, as in the IMU model):
+ *     H(r, 7+j) = M[r][j]        H(r, 10+j) = (M[r][0]*C[0][j] + M[r][1]*C[1][j]) + M[r][2]*C[2][j]        zero elsewhere
+ *     M[r][j] = R_cv[3 j + r]    C = [[0, p_2, -p_1], [-p_2, 0, p_0], [p_1, -p_0, 0]]
+ * H[66], z[3] = v, R[9] = cov with its lower triangle mirrored.  R_cv, p_cv NULL: the identity, zero.  A pure host function.  A NULL among
+ * the others, a non-finite entry, an R_cv that ekfvio_set_imu_extrinsics would refuse, or a cov that is not positive definite: EKFVIO_EINVAL. */
+EKFVIO_API int ekfvio_aid_rows_body_velocity(const float R_cv[9], const float p_cv[3], const float v[3], const float cov[9], float* H, float* z,
+                                             float* R);
+
 /* ---- device-resident measurement sequences (benchmark / replay) ---------------------- */
 /* Copies `frames` consecutive (z, R, pass) triples for the current landmark count to HBM. */
 EKFVIO_API int ekfvio_upload_measurements(ekfvio_filter* f, int32_t frames, const float* z, const float* R, const uint8_t* pass);
